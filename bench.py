@@ -15,7 +15,21 @@ Inputs are resident in HBM before the timed region.  Strong scaling: the same `-
 over the ranks by contiguous camera ranges cut on the observation prefix sum (BASELINE.json configs[3]); at
 N = 1 one GPU holds all of it.
 
-Only the `cpu_baseline` leg touches oracle/ (rank 0, N = 1, bounded sample).
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, the outputs
+(--dump-outputs DIR) and the result line.  Everything else the line can carry -- the kernel in the first allocation,
+the launch after a cache sweep, same-run calibration, live PMC traffic, the CPU baseline, the other configurations and
+passes, and at N > 1 the other arrangement and the per-rank kernel / collective split -- runs with --full
+(--no-cpu-baseline, --no-extras and --no-live-traffic narrow it there):
+
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
+
+--dump-outputs DIR writes what the last timed step computed, a fixed seeded sample of observations of the whole
+list (rank order at N > 1): DIR/residual.npy [k, 2], jacobian_camera.npy [k, 18], jacobian_point.npy [k, 6],
+observation_index.npy [k] (the sampled indices), error_sum.npy [1] (the folded sum of squared residuals, all-reduced)
+and total_l2_error.npy [1], all float64, under 64 MB together.  The inputs are seeded: the same arguments give the same
+inputs on every run and every build.
+
+Only the `cpu_baseline` leg touches oracle/ (rank 0, N = 1, bounded sample, --full).
 """
 import argparse
 import json
@@ -72,8 +86,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--blocks", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (see the module docstring); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write a seeded sample of what the last step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip calibration, live traffic and the other configurations")
     ap.add_argument("--assume-store-GBs", type=float, default=0.0,
                     help="diagnostic: tell the placed launch that its output set streams at this rate instead of the measured one "
                          "(c2b_jacobian_outputs_set_store_rate) -- how the counter passes of live_traffic make their child run the "
@@ -113,7 +131,10 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="take the multi-rank code path (process group, balanced split, all-reduce) even with one rank: "
                          "how tests exercise the RCCL backend on a 1-GPU box")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def build_shard(args, rank, world, dev, balanced=True):
@@ -604,6 +625,49 @@ def same_run_calibration(n, r, Jc, Jp, dev, alg):
             "same_run_algorithmic_floor_us": round(alg / store_rate * 1e6, 2)}
 
 
+DUMP_SEED = 20245
+DUMP_ROWS = 1 << 18          # sampled observations: 26 float64 outputs + the index each, 56.6 MB (the cap is 64 MB)
+
+
+def output_sample(sh, r, Jc, Jp, e, dist_on, world):
+    """--dump-outputs: the rows of r / Jc / Jp of a fixed, seeded sample of observations of the WHOLE list (indices drawn
+    from the global observation count, so the sample does not depend on N), and the step's error scalar `e` (a 0-d device
+    tensor, all-reduced when N > 1).  Every rank takes the rows of its own range; rank 0 gets them all, in rank order
+    (= observation order: the ranks hold contiguous camera ranges).  Returns {name: float64 array} on rank 0, None on the
+    others."""
+    import numpy as np
+    import torch
+    n_total, lo, n = sh["n_obs_total"], int(sh["obs_base"]), sh["n_obs"]
+    k = min(n_total, DUMP_ROWS)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_total, size=k, replace=False)).astype(np.int64)
+    mine = idx[(idx >= lo) & (idx < lo + n)]
+    loc = torch.from_numpy(mine - lo).to(r.device)
+    part = {"observation_index": mine.astype(np.float64),
+            "residual": r.index_select(0, loc).cpu().numpy(),
+            "jacobian_camera": Jc.index_select(0, loc).cpu().numpy(),
+            "jacobian_point": Jp.index_select(0, loc).cpu().numpy()}
+    error_sum = float(e.item())
+    if dist_on:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, part)
+        if dist.get_rank() != 0:
+            return None
+        part = {name: np.concatenate([p[name] for p in parts]) for name in part}
+    import city2ba_amd.dist as Dist
+    part["error_sum"] = np.array([error_sum], dtype=np.float64)
+    part["total_l2_error"] = np.array([Dist.finish_error(error_sum, 2.0)], dtype=np.float64)
+    return part
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy, float64, C order"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     import torch
@@ -665,10 +729,11 @@ def main():
     # The output arrays.  Where they are allocated changes the kernel's time by up to 20 %, so the
     # line reports BOTH: the kernel in the first allocation the library hands out (what a caller that does not search
     # gets), measured here before anything else, and the timed region in the set c2b_jacobian_outputs_alloc keeps after
-    # its bounded search -- the same entry point every caller of the C ABI has.  Untimed set-up.
+    # its bounded search -- the same entry point every caller of the C ABI has.  Untimed set-up; the first allocation is
+    # measured with --full only.
     torch.cuda.empty_cache()
     first_us, first_GBs = None, None
-    if rank == 0 and n >= 1_000_000:
+    if args.full and rank == 0 and n >= 1_000_000:
         first = D.JacobianOutputs(n, dev, max_attempts=1)
         first_us, first_GBs = kernel_us_in(first), first.store_GBs
         del first
@@ -898,15 +963,24 @@ def main():
         elapsed = float(t.item())
 
     # ---- after the region --------------------------------------------------------------------------------------------
-    # (1) the OTHER arrangement, the same number of un-instrumented steps, bracketed the same way
+    # (0) what the last timed step computed, before anything else launches: its error scalar is the ring's last slot
+    # when the collective overlapped, `err` otherwise
+    if args.dump_outputs:
+        dog.beat("--dump-outputs: gathering the sample of the last step's outputs")
+        last_e = err_ring[(slot[0] - 1) % n_slots] if shipped == "overlapped" else err[0]
+        sample = output_sample(sh, r, Jc, Jp, last_e, dist_on, world)
+        if rank == 0:
+            write_outputs(args.dump_outputs, sample)
+    # (1) the OTHER arrangement, the same number of un-instrumented steps, bracketed the same way (--full)
     other = {}
-    if dist_on and graph is None:
+    if args.full and dist_on and graph is None:
         other["in_line"] = elapsed if shipped == "in_line" else timed_loop(step_in_line, args.steps, "in-line loop after the region")
         if can_overlap:
             other["overlapped"] = elapsed if shipped == "overlapped" else timed_loop(step_overlapped, args.steps, "overlapped loop after the region")
-    # (2) the kernel / collective split on EVERY rank: instrumented in-line steps (events would distort the timed loops)
+    # (2) the kernel / collective split on EVERY rank: instrumented in-line steps (events would distort the timed loops;
+    # --full).  Without it the kernel figures come from the events inside the region (N = 1 in line) or are not measured.
     kernel_us_mine, allreduce_us_mine, graph_step_us = None, None, None
-    if dist_on or graph is not None:
+    if args.full and (dist_on or graph is not None):
         post = min(args.steps, 20)
         dog.beat("instrumented pass: %d in-line steps with HIP events on every rank" % post)
         pev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(post)]
@@ -921,11 +995,13 @@ def main():
         if rank == 0:
             events = pev
     else:
-        step_in_line()                                            # N = 1: leave the scalar of one more launch in `err`
+        step_in_line()                                            # leave the (all-reduced) scalar of one more in-line launch in `err`
         torch.cuda.synchronize()
+        if shipped != "in_line":
+            events = None                                         # nothing recorded them
     total_err = Dist.finish_error(err.item(), 2.0)          # every arrangement reduced the same data: `err` holds the in-line sum
-    # every overlapped step's slot must hold exactly that sum, bit for bit
-    ring_ok = bool((err_ring[:min(slot[0], n_slots)] == err).all().item()) if (can_overlap and slot[0]) else None
+    # every overlapped step's slot must hold exactly that sum, bit for bit (--full)
+    ring_ok = bool((err_ring[:min(slot[0], n_slots)] == err).all().item()) if (args.full and can_overlap and slot[0]) else None
     per_rank = [{"n_obs": n, "kernel_us": kernel_us_mine, "allreduce_us": allreduce_us_mine,
                  "store_GBs_kept": (placement_log[placement_chosen] if placement_log and 0 <= placement_chosen < len(placement_log) else None),
                  "ring_ok": ring_ok}]
@@ -938,16 +1014,18 @@ def main():
     dog.stop()
 
     if rank == 0:
-        kern_ms = sorted(ev[0].elapsed_time(ev[1]) for ev in events)
+        # kernel times: HIP events inside the region (N = 1 in line) or of the instrumented pass (--full); else not measured
+        kern_ms = sorted(ev[0].elapsed_time(ev[1]) for ev in events) if events is not None else None
         step_us = elapsed / args.steps * 1e6
-        step_breakdown = {"kernel_us_rank0": round(sum(kern_ms) / len(kern_ms) * 1e3, 2)}
+        step_breakdown = {"kernel_us_rank0": round(sum(kern_ms) / len(kern_ms) * 1e3, 2) if kern_ms else None}
         if dist_on:
-            ar_us = per_rank[0]["allreduce_us"]
-            step_breakdown["allreduce_us"] = round(ar_us, 2)
-            # every rank's own figures (instrumented in-line steps right after the region): a slow device among the N --
-            # one whose outputs stream at 5.7 instead of 7 TB/s paces every step -- is named here
-            step_breakdown["kernel_us_per_rank"] = [round(q["kernel_us"], 2) for q in per_rank]
-            step_breakdown["allreduce_us_per_rank"] = [round(q["allreduce_us"], 2) for q in per_rank]
+            if kernel_us_mine is not None:
+                ar_us = per_rank[0]["allreduce_us"]
+                step_breakdown["allreduce_us"] = round(ar_us, 2)
+                # every rank's own figures (instrumented in-line steps right after the region): a slow device among the N --
+                # one whose outputs stream at 5.7 instead of 7 TB/s paces every step -- is named here
+                step_breakdown["kernel_us_per_rank"] = [round(q["kernel_us"], 2) for q in per_rank]
+                step_breakdown["allreduce_us_per_rank"] = [round(q["allreduce_us"], 2) for q in per_rank]
             step_breakdown["store_GBs_kept_per_rank"] = [q["store_GBs_kept"] for q in per_rank]
             step_breakdown["rccl_ranks"] = rccl_ranks
             step_breakdown["comm_init_ms"] = round(comm_init_ms, 1) if comm_init_ms is not None else None
@@ -960,20 +1038,21 @@ def main():
                 step_breakdown["ms_per_step_" + name] = round(secs / args.steps * 1e3, 5)
             # overlapped: the collective is off the kernel stream's critical path, so what a step costs beyond its kernel
             # is launch gaps, the hand-off and waiting for the slowest rank; in line: kernel + collective + the rest
-            slowest = max(q["kernel_us"] for q in per_rank)
-            step_breakdown["step_overhead_us"] = round(step_us - slowest - (0.0 if shipped == "overlapped" else ar_us), 2)
+            if kernel_us_mine is not None:
+                slowest = max(q["kernel_us"] for q in per_rank)
+                step_breakdown["step_overhead_us"] = round(step_us - slowest - (0.0 if shipped == "overlapped" else ar_us), 2)
             step_breakdown["allreduce_overlaps_next_kernel"] = shipped == "overlapped"
-            if can_overlap:
+            if can_overlap and args.full:
                 oks = [q["ring_ok"] for q in per_rank]
                 step_breakdown["overlapped_sums_equal_the_in_line_sum"] = (all(o for o in oks if o is not None) if any(o is not None for o in oks) else None)
             step_breakdown["watchdog_seconds"] = args.watchdog_seconds
-        else:
+        elif kern_ms:
             step_breakdown["step_overhead_us"] = round(step_us - step_breakdown["kernel_us_rank0"], 2)
-        kern_avg_s = sum(kern_ms) / len(kern_ms) / 1e3
+        kern_avg_s = sum(kern_ms) / len(kern_ms) / 1e3 if kern_ms else None
         n_total = sh["n_obs_total"]
         value = n_total * args.steps / elapsed / 1e6
         alg = algorithmic_bytes(n, sh["n_cam_local"], sh["n_pts"])
-        achieved = alg / kern_avg_s / 1e9
+        achieved = alg / kern_avg_s / 1e9 if kern_avg_s else None
         policy = D.jacobian_stream_policy(n, sh["n_cam_local"], sh["n_pts"])
         shape = D.jacobian_launch_shape(n, outs.store_GBs)
         kernel_name = KERNEL_FMT % (shape[0], shape[1], 4 if shape[1] == 2 else 1, policy)     # (MINW: 4 with two tiles per wave, capi.hip: launch_jac_l)
@@ -1002,7 +1081,8 @@ def main():
                 "hip_graph": ("one graph launch per step (%s captured)" % ("kernel + all-reduce" if collective_in_graph else "kernel")
                               + ("; step on the GPU %.2f us" % graph_step_us if graph_step_us else ""))
                 if graph is not None else (graph_note or False),
-                "kernel_time_source": "HIP events around the launch inside the timed region" if not dist_on else
+                "kernel_time_source": "not measured (--full measures it)" if not kern_ms else
+                                      "HIP events around the launch inside the timed region" if (not dist_on and shipped == "in_line") else
                                       "HIP events around %d instrumented in-line steps right after the timed region, on every "
                                       "rank (event records inside a ~90 us step would cost ~13 us of it)" % min(args.steps, 20),
                 # where rank 0's step goes (HIP events around the kernel and around the collective; the rest of the
@@ -1010,14 +1090,14 @@ def main():
                 **step_breakdown,
             },
             "roofline": {
-                "bound": "hbm", "kernel": kernel_name, "achieved": round(achieved, 1),
+                "bound": "hbm", "kernel": kernel_name, "achieved": round(achieved, 1) if achieved else None,
                 "launch_shape": "%d threads per workgroup, %d tile%s of 64 observations per wave (c2b_jacobian_launch_shape: by the "
                                 "launch's size and the %s GB/s the output set takes streaming stores at; below 6 300 GB/s 256 x 1, below 6 850 GB/s 1 024 x 1: the finer "
                                 "grain is 1.6-4.4 %% faster, profiles/r05_ab_slow_store.txt, r05p_ab_step_three_classes.txt)" % (
                                     shape[0] * 64, shape[1], "" if shape[1] == 1 else "s", ("%.0f" % outs.store_GBs) if outs.store_GBs else "unmeasured"),
                 "stream_policy": {0: "every load cached", 2: "observed uv non-temporal", 3: "observed uv and point index non-temporal"}[policy]
                 + " (c2b_jacobian_stream_policy: tables and streams of this launch against the 256 MB Infinity Cache)",
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
                 # HBM bytes per launch from the PMC counters (2 x FETCH_SIZE + WRITE_SIZE, the guide's gfx950 correction).
                 # Counters cannot be collected inside a timed run: this is the figure of a SEPARATE rocprofv3 --pmc pass of
                 # this very command (tools/profile_bench.sh), recorded in profiles/ -- NOT measured in this run
@@ -1028,7 +1108,8 @@ def main():
                 if traffic is not None else None,
                 "algorithmic_bytes_per_launch": alg, "observations_per_launch": n,
                 "bytes_per_observation": round(alg / max(n, 1), 2),
-                "kernel_avg_us": round(kern_avg_s * 1e6, 2), "kernel_min_us": round(kern_ms[0] * 1e3, 2),
+                "kernel_avg_us": round(kern_avg_s * 1e6, 2) if kern_ms else None,
+                "kernel_min_us": round(kern_ms[0] * 1e3, 2) if kern_ms else None,
                 # MI355X devices differ in how fast they take streaming stores (5.6-5.9 TB/s on some,
                 # 7.0-7.1 on others, both inside one process on a third kind) and this launch is 85 % stores: the class of
                 # the device this line was measured on, from the store rates of the output sets the placement search tried
@@ -1048,7 +1129,8 @@ def main():
                 "input_placement": input_placement,
             },
         }
-        if not dist_on:
+        # ---- --full: everything beyond the headline ----------------------------------------------------------------------
+        if args.full and not dist_on:
             # The honest triple.  `value` is the timed region: steps back to back on one problem (the camera and point
             # records, 232 MB at --blocks 128, are found in the 256 MB Infinity Cache) writing into the output set the
             # placement search kept.  Beside it: the same launch (a) in the FIRST allocation the library hands out -- what
@@ -1074,7 +1156,7 @@ def main():
                                  "value_first_allocation: the same launch in the first allocation handed out (no search); "
                                  "value_caches_swept: the same launch after a 1-GiB read swept the caches; the last two = "
                                  "observations / (that kernel's time + this run's per-step overhead of %.1f us)" % over_us)
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             cal = same_run_calibration(n, r, Jc, Jp, dev, alg)
             out["roofline"].update(cal)
             # THE device-independent figure of merit: this kernel against the launch's algorithmic bytes at the store rate
@@ -1085,9 +1167,9 @@ def main():
             out["roofline"]["kernel_over_same_run_copy"] = round(kern_avg_s * 1e6 / cal["same_run_copy_us"], 4)
         #  under a profiler the child rocprofv3 runs would nest: skipped, the recorded figure stays
         under_profiler = any(k.startswith("ROCPROF") for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-        if under_profiler:
+        if args.full and under_profiler:
             out["roofline"]["traffic_live_unavailable"] = "this run is itself under a profiler"
-        if world == 1 and args.blocks == 128 and not args.no_extras and not args.no_live_traffic and not under_profiler:
+        if args.full and world == 1 and args.blocks == 128 and not args.no_extras and not args.no_live_traffic and not under_profiler:
             # the counters cannot be collected inside the timed run, but they can be collected on THIS box right after it
             t_live, how = live_traffic(kernel_name, args.blocks, outs.store_GBs)
             out["roofline"]["traffic_recorded"] = traffic
@@ -1099,11 +1181,11 @@ def main():
                                                           "instance; (2 x FETCH_SIZE + WRITE_SIZE) x 1024)" % how)
             else:
                 out["roofline"]["traffic_live_unavailable"] = how
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sh, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and args.blocks == 128 and not args.no_extras:
+        if args.full and world == 1 and args.blocks == 128 and not args.no_extras:
             out["other_configs"] = other_configs(dev)
             out["other_configs"]["blocks128_uniform_random_point_gather"] = adversarial_gather(sh, r, Jc, Jp, ws)
             out["other_configs"]["blocks128_other_passes"] = light_kernels(sh, dev, ws)

@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMON = ["--blocks", "32", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras"]
+FULL = COMMON + ["--full"]           # the per-rank kernel / collective split and the other arrangement: --full only
 
 
 def _free_port():
@@ -52,7 +53,7 @@ def test_rccl_world_size_one_reproduces_the_plain_run(plain, collective, graph, 
     many ranks the communicator spans, both arrangements timed in the same run"""
     env = {"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port())}
     rc, out, err = _run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--collective", collective,
-                         "--graph", graph, "--overlap", overlap] + COMMON, env)
+                         "--graph", graph, "--overlap", overlap] + FULL, env)
     assert rc == 0 and out is not None, err[-2000:]
     assert "Traceback" not in err, err[-2000:]
     cfg = out["config"]
@@ -102,7 +103,7 @@ def test_rccl_world_size_one_reproduces_the_plain_run(plain, collective, graph, 
 def test_two_ranks_on_one_gpu_exit_cleanly_and_agree(plain):
     env = {"C2B_DIST_BACKEND": "gloo", "C2B_SHARE_GPU": "1"}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + COMMON
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + FULL
     rc, out, err = _run(cmd, env)
     assert rc == 0, err[-3000:]                                  # every rank, not only the one that prints
     assert "Traceback" not in err and "ChildFailedError" not in err, err[-3000:]
@@ -120,6 +121,35 @@ def test_two_ranks_on_one_gpu_exit_cleanly_and_agree(plain):
     assert cfg["rccl_ranks"] == [2, 2] and cfg["arrangement"] == "in_line"          # gloo stages the scalar through the host
     assert len(cfg["kernel_us_per_rank"]) == 2 and min(cfg["kernel_us_per_rank"]) > 0 and min(cfg["allreduce_us_per_rank"]) > 0
     assert out["ms_per_step"] == cfg["ms_per_step_in_line"] and "ms_per_step_overlapped" not in cfg
+
+
+def test_plain_multi_rank_runs_dump_what_one_rank_dumps(tmp_path):
+    """without --full the N-rank line is the headline alone (no per-rank kernel split, no other arrangement), and
+    --dump-outputs gathers every rank's rows of the sample: RCCL at world size one (the arrangement chosen by the A/B) and
+    two ranks over gloo dump the rows the single-rank run dumps"""
+    import numpy as np
+    names = ("residual", "jacobian_camera", "jacobian_point", "observation_index")
+    d1 = tmp_path / "one"
+    rc, _, err = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(d1)] + COMMON)
+    assert rc == 0, err[-2000:]
+    ref = {k: np.load(str(d1 / (k + ".npy"))) for k in names + ("error_sum",)}
+    runs = {"rccl": ([sys.executable, "bench.py", "--gpus", "1", "--force-dist"],
+                     {"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port())}),
+            "gloo2": ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+                       "--master-port", str(_free_port()), "bench.py", "--gpus", "2"], {"C2B_DIST_BACKEND": "gloo", "C2B_SHARE_GPU": "1"})}
+    for name, (cmd, env) in runs.items():
+        d = tmp_path / name
+        rc, out, err = _run(cmd + ["--dump-outputs", str(d)] + COMMON, env)
+        assert rc == 0 and out is not None, (name, err[-3000:])
+        assert "Traceback" not in err, (name, err[-3000:])
+        cfg = out["config"]
+        assert out["ms_per_step"] > 0 and out["steps"] == 5
+        assert cfg["kernel_time_source"].startswith("not measured") and cfg["kernel_us_rank0"] is None
+        assert "kernel_us_per_rank" not in cfg and not any(k.startswith("ms_per_step_") for k in cfg), (name, sorted(cfg))
+        for k in names:
+            assert np.array_equal(np.load(str(d / (k + ".npy"))), ref[k]), (name, k)
+        e = np.load(str(d / "error_sum.npy"))[0]
+        assert abs(e - ref["error_sum"][0]) <= 1e-12 * ref["error_sum"][0], (name, e, ref["error_sum"][0])
 
 
 def test_comm_through_the_c_abi_at_world_size_one():

@@ -6,7 +6,7 @@ N=${1:-4}; B=${2:-32}; G=${3:-on}; O=${4:-auto}
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 set -o pipefail
 C2B_DIST_BACKEND=gloo C2B_SHARE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-  --master-port $((29700 + N)) bench.py --gpus $N --blocks $B --steps 5 --warmup 2 --graph $G --overlap $O --no-cpu-baseline --no-extras 2> /tmp/rehearse_$N.err \
+  --master-port $((29700 + N)) bench.py --gpus $N --blocks $B --steps 5 --warmup 2 --graph $G --overlap $O --full --no-cpu-baseline --no-extras 2> /tmp/rehearse_$N.err \
   | python -c "
 import json,sys
 for l in sys.stdin:
