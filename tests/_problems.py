@@ -196,3 +196,64 @@ def np_candidate_pairs(centers, pts, max_dist, cam_lo=0, cam_hi=None, chunk=100_
     if not out_c:
         return np.zeros(0, np.int32), np.zeros(0, np.int32)
     return np.concatenate(out_c), np.concatenate(out_p)
+
+
+# ---- cameras whose radial term k2 differs from camera to camera (some 0, some not) ----
+K2_PATTERNS = ("half", "alternate", "lone", "signs", "first_differs")
+
+
+def wave_first_cameras(cam_of, wave_obs):
+    """Cameras of the observations that open a wave, for waves of each length in `wave_obs` observations, read off the
+    observation list in launch order (cam_of[i] = camera of observation i)."""
+    cam_of = np.asarray(cam_of)
+    firsts = set()
+    for w in wave_obs:
+        firsts.update(int(c) for c in cam_of[::int(w)])
+    return np.array(sorted(firsts), dtype=np.int64)
+
+
+def mixed_k2_cameras(cams15, pattern, seed, firsts=None):
+    """A copy of cams15 with k2 (column 14) rewritten camera by camera, so that waves mix cameras with k2 == 0 and
+    k2 != 0:
+      half           nonzero with probability 1/2;
+      alternate      odd cameras nonzero, even ones zero;
+      lone           first half of the cameras: one in 13 nonzero; second half: one in 13 zero;
+      signs          in turn 0.0, -0.0, the smallest subnormal 5e-324 (either sign), |k2| around 1 and around 1e-2, both
+                     signs;
+      first_differs  the cameras in `firsts` (wave_first_cameras) nonzero, every other camera zero."""
+    rng = np.random.default_rng(seed)
+    n = len(cams15)
+    c = np.arange(n)
+    small = rng.uniform(-1e-2, 1e-2, n)
+    if pattern == "half":
+        k2 = np.where(rng.random(n) < 0.5, small, 0.0)
+    elif pattern == "alternate":
+        k2 = np.where(c % 2 == 1, small, 0.0)
+    elif pattern == "lone":
+        k2 = np.where((c < n // 2) == (c % 13 == 0), small, 0.0)
+    elif pattern == "signs":
+        choices = np.array([0.0, -0.0, 5e-324, -5e-324, 1.0, -1.0, 1e-2, -1e-2])
+        k2 = choices[c % len(choices)]
+        k2 = np.where(np.abs(k2) >= 1e-2, k2 * rng.uniform(0.5, 1.5, n), k2)
+    elif pattern == "first_differs":
+        assert firsts is not None
+        k2 = np.zeros(n)
+        k2[firsts] = np.where(small[firsts] != 0.0, small[firsts], 1e-3)
+    else:
+        raise AssertionError(pattern)
+    out = np.array(cams15, dtype=np.float64, copy=True)
+    out[:, 14] = k2
+    return out
+
+
+def points_in_front(cams15, cam_of, seed):
+    """One world point per observation, in front of that observation's camera: camera-frame q with q.z in [-10, -1]
+    and |q.x|, |q.y| <= 0.9 |q.z| (so |p| <= 1.3 and every projection and Jacobian stays of order one)."""
+    rng = np.random.default_rng(seed)
+    cam_of = np.asarray(cam_of, dtype=np.int64)
+    m = len(cam_of)
+    z = -rng.uniform(1.0, 10.0, m)
+    q = np.stack([rng.uniform(-0.9, 0.9, m) * -z, rng.uniform(-0.9, 0.9, m) * -z, z], axis=1)
+    M = cams15[cam_of, :9].reshape(m, 3, 3).transpose(0, 2, 1)       # R is column-major: q = R X + t
+    X = np.linalg.solve(M, (q - cams15[cam_of, 9:12])[:, :, None])[:, :, 0]
+    return np.ascontiguousarray(X)

@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 
 import oracle as O
-from _problems import grid_cameras_points, grid_candidate_pairs, random_problem
+from _problems import (K2_PATTERNS, grid_cameras_points, grid_candidate_pairs, mixed_k2_cameras, random_problem,
+                       wave_first_cameras)
 
 IDENT_CAM = [0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
 
@@ -130,6 +131,32 @@ def test_zero_error_by_construction():
     P = random_problem(40, 400, 8, seed=5, empty_every=7)
     assert O.total_reprojection_error(P["cams15"], P["pts"], P["row_ptr"], P["pt_idx"], P["uv"], 2.0) == 0.0
     assert O.total_reprojection_error(P["cams15"], P["pts"], P["row_ptr"], P["pt_idx"], P["uv"], 1.0) == 0.0
+
+
+@pytest.mark.parametrize("pattern", K2_PATTERNS)
+def test_mixed_k2_residual_and_visibility_carry_the_projections_bits(pattern):
+    """The premise of the GPU's bit-exact mixed-k2 tests (tests/test_gpu_k2_mix.py), with cameras of k2 = 0, -0.0,
+    subnormal and nonzero side by side: the oracle's residual is project_observations - uv bit for bit, and its
+    visibility predicate's uv is project_observations' wherever the pair is kept."""
+    P = random_problem(200, 3000, 9, seed=17, noise=1e-3)
+    counts = np.diff(P["row_ptr"].astype(np.int64))
+    cam_of = np.repeat(np.arange(len(counts)), counts)
+    cams = mixed_k2_cameras(P["cams15"], pattern, seed=3, firsts=wave_first_cameras(cam_of, (64, 128, 192)))
+    k2 = cams[:, 14]
+    assert (k2 == 0.0).any() and (k2 != 0.0).any()
+    if pattern == "signs":
+        assert (np.signbit(k2) & (k2 == 0.0)).any() and (~np.signbit(k2) & (k2 == 0.0)).any() and (k2 == 5e-324).any()
+    proj = O.project_observations(cams, P["pts"], P["row_ptr"], P["pt_idx"])
+    uv = proj + np.random.default_rng(4).normal(scale=1e-3, size=proj.shape)
+    r, _, _ = O.residual_jacobian(cams, P["pts"], P["row_ptr"], P["pt_idx"], uv)
+    assert np.array_equal(r.view(np.uint64), (proj - uv).view(np.uint64))
+    # visibility over the same cameras with the points shuffled among them: kept, in front but outside, behind, too far
+    pt = np.random.default_rng(5).permutation(P["pt_idx"].astype(np.int64))
+    vis_uv, keep = O.visibility_pairs(cams, P["pts"], cam_of, pt, 12.0)
+    want = O.project_observations(cams, P["pts"], P["row_ptr"], pt)
+    k = keep.astype(bool)
+    assert 0 < k.sum() < len(k) // 2
+    assert np.array_equal(vis_uv[k].view(np.uint64), want[k].view(np.uint64))
 
 
 def test_transform_uses_old_rotation():
