@@ -17,7 +17,7 @@ ERR_OOM = -4
 ERR_NO_DEVICE = -5
 ERR_RCCL = -6
 COMM_ID_BYTES = 128
-ABI_VERSION = 6            # include/city2ba_hip.h: C2B_ABI_VERSION
+ABI_VERSION = 7            # include/city2ba_hip.h: C2B_ABI_VERSION
 CAMBLK_DOUBLES = 32
 STATS_DOUBLES = 20
 
@@ -76,6 +76,10 @@ SIGNATURES = {
     "c2b_jacobian_outputs_free": (None, [_vp]),
     "c2b_calib_store_pattern": (_int, [_i64, _vp, _vp, _vp, _vp]),
     "c2b_calib_copy": (_int, [_vp, _vp, _i64, _vp]),
+    "c2b_normal_transpose_temp_bytes": (_i64, [_i64, _i64]),
+    "c2b_normal_transpose": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_normal_cameras_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_normal_points_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_visibility_pairs": (_int, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_visibility_dense_tiles": (_i64, [_i64]),
     "c2b_visibility_dense_count": (_int, [_vp, _i64, _vp, _i64, _d, _vp, _vp, _vp, _vp]),
@@ -179,6 +183,7 @@ SIGNATURES = {
     "c2b_problem_add_noise_errors_l1_l2_sharded": (_int, [_vp, _vp, _d, _d, _d, _d, _u64, C.POINTER(_d), C.POINTER(_d)]),
     "c2b_problem_residual_jacobian": (_int, [_vp, _vp, _vp, _vp]),
     "c2b_problem_residual_jacobian_device": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_d)]),
+    "c2b_problem_normal_equations": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_d)]),
     "c2b_problem_stats": (_int, [_vp, _vp]),
     "c2b_problem_visibility_pairs": (_int, [_vp, _i64, _vp, _vp, _d, _vp, _vp]),
     "c2b_problem_cull": (_int, [_vp, _int]),

@@ -246,6 +246,40 @@ class BAProblem:
             outputs = D.JacobianOutputs(self.num_observations(), self._device, max_attempts, _handle=h)
         return outputs, s.value
 
+    def normal_equations(self, out=None):
+        """The Gauss-Newton diagonal blocks and gradient, reduced on the device from the Jacobian residual_jacobian
+        returns (c2b_problem_normal_equations): (U [n_cam,9,9], gc [n_cam,9], V [n_pts,3,3], gp [n_pts,3], sum_sq) --
+        U = sum Jc^T Jc and gc = sum Jc^T r per camera, V = sum Jp^T Jp and gp = sum Jp^T r per point, sum_sq = sum |r|^2.
+        The four arrays are float64 torch tensors on the problem's device; out = (U, gc, V, gp) fills the caller's
+        (contiguous float64 on that device, of those shapes; an entry of None skips its pass together with its partner,
+        which must be None too).  Deterministic: the same problem gives the same bits on every call.  On a shard U / gc
+        are the shard's cameras and V / gp its partial sums over its own observations (they add up over the ranks)."""
+        import torch
+        nc, npt = self.num_cameras(), self.num_points()
+        dev = torch.device("cuda", self._device)
+        shapes = ((nc, 9, 9), (nc, 9), (npt, 3, 3), (npt, 3))
+        if out is None:
+            arrs = [torch.empty(sh, dtype=torch.float64, device=dev) for sh in shapes]
+        else:
+            arrs = list(out)
+            if len(arrs) != 4:
+                raise ValueError("normal_equations: out must be (U, gc, V, gp)")
+            for a, sh, name in zip(arrs, shapes, ("U", "gc", "V", "gp")):
+                if a is None:
+                    continue
+                if not isinstance(a, torch.Tensor) or a.dtype != torch.float64 or a.device != dev or tuple(a.shape) != sh \
+                        or not a.is_contiguous():
+                    raise ValueError("normal_equations: out %s must be a contiguous float64 tensor of shape %s on %s" % (name, sh, dev))
+            if (arrs[0] is None) != (arrs[1] is None) or (arrs[2] is None) != (arrs[3] is None):
+                raise ValueError("normal_equations: U / gc and V / gp are given or skipped in pairs")
+        s = C.c_double()
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None     # empty: no pass to run
+        U, gc, V, gp = arrs
+        # the library's stream is its own: work queued on torch's stream for these tensors must be done first
+        torch.cuda.current_stream(dev).synchronize()
+        L.check(L.lib().c2b_problem_normal_equations(self._h, ptr(U), ptr(gc), ptr(V), ptr(gp), C.byref(s)))
+        return U, gc, V, gp, s.value
+
     def _stats(self):
         s = np.empty(L.STATS_DOUBLES)
         L.check(L.lib().c2b_problem_stats(self._h, _ptr(s)))

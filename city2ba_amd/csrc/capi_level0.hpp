@@ -1253,3 +1253,97 @@ int c2b_visibility_dense_fill(const double *camblk, int64_t n_cam, const double 
     C2B_API_END("visibility_dense_fill")
 }
 
+
+// ---- Gauss-Newton diagonal blocks (normal_kernels.hpp) -----------------------------------------------------------
+// temp of c2b_normal_transpose: [cursor: n_pts u32, padded to 16 B] [slots: n_obs u32]
+int64_t c2b_normal_transpose_temp_bytes(int64_t n_obs, int64_t n_pts) {
+    if (n_obs < 0) n_obs = 0;
+    if (n_pts < 0) n_pts = 0;
+    return ((n_pts + 3) / 4 * 4 + n_obs + 4) * (int64_t)sizeof(uint32_t);
+}
+
+int c2b_normal_transpose(const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx, int64_t n_obs, int64_t n_pts,
+                         uint64_t *pt_row_ptr, uint32_t *obs_of, uint32_t *cam_of, void *temp, void *stream) {
+    C2B_API_BEGIN
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_pts < 0 || n_pts > (int64_t)0xffffffff)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_transpose: count out of range");
+    if (n_cam < 0 || n_cam >= (int64_t)1 << 31) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_transpose: n_cam out of range");
+    if (!pt_row_ptr || (n_obs && (!row_ptr || !pt_idx || !obs_of || !cam_of || !temp || n_cam == 0)))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_transpose: NULL argument, or observations without cameras");
+    if ((reinterpret_cast<uintptr_t>(pt_row_ptr) & 7) || (reinterpret_cast<uintptr_t>(row_ptr) & 7) || (reinterpret_cast<uintptr_t>(pt_idx) & 3) ||
+        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3) || !aligned16(temp))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_transpose: misaligned pointer (row pointers 8 bytes, indices 4, temp 16)");
+    hipStream_t st = S(stream);
+    if (!n_obs || !n_pts) {
+        HIP_TRY(hipMemsetAsync(pt_row_ptr, 0, sizeof(uint64_t) * (size_t)(n_pts + 1), st));
+        return C2B_OK;
+    }
+    uint32_t *cursor = reinterpret_cast<uint32_t *>(temp);
+    uint32_t *slots = cursor + (n_pts + 3) / 4 * 4;
+    HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(uint32_t) * (size_t)n_pts, st));
+    const unsigned go = (unsigned)((n_obs + 255) / 256);
+    hipLaunchKernelGGL(k_nt_count, dim3(go), dim3(256), 0, st, pt_idx, n_obs, n_pts, cursor);
+    hipLaunchKernelGGL(k_nt_scan, dim3(1), dim3(kNtScanThreads), 0, st, cursor, n_pts, pt_row_ptr);
+    hipLaunchKernelGGL(k_nt_fill, dim3(go), dim3(256), 0, st, pt_idx, n_obs, n_pts, cursor, slots);
+    hipLaunchKernelGGL(k_nt_rank, dim3(go), dim3(256), 0, st, pt_idx, (const uint64_t *)pt_row_ptr, n_pts, (const uint32_t *)slots,
+                       row_ptr, (int)n_cam, obs_of, cam_of);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("normal_transpose")
+}
+
+static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+int c2b_normal_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                            const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
+                            void *workspace, double *sum_sq, void *stream) {
+    C2B_API_BEGIN
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: count out of range");
+    if (sum_sq && !workspace) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: sum_sq needs a workspace");
+    if (n_cam && (!camblk || !row_ptr || !U || !gc)) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: NULL argument");
+    if (n_obs && (!pts4 || !pt_idx || !uv_obs)) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: NULL observation input");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(row_ptr) || !aligned8(U) || !aligned8(gc) ||
+        (reinterpret_cast<uintptr_t>(pt_idx) & 3) || !aligned8(sum_sq))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    if (!n_cam) {
+        if (sum_sq) HIP_TRY(hipMemsetAsync(sum_sq, 0, sizeof(double), st));
+        return C2B_OK;
+    }
+    const int64_t quads = (n_cam + kNormCamsPerWave - 1) / kNormCamsPerWave, waves = kNormBlock / 64;
+    const unsigned grid = (unsigned)((quads + waves - 1) / waves < kNormMaxGrid ? (quads + waves - 1) / waves : kNormMaxGrid);
+    const double4 *p4 = reinterpret_cast<const double4 *>(pts4);
+    const double2 *uv = reinterpret_cast<const double2 *>(uv_obs);
+    if (sum_sq) {
+        double *block_part = reinterpret_cast<double *>(workspace) + kWsBlockPart;
+        hipLaunchKernelGGL(k_normal_cameras<true>, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv,
+                           U, gc, block_part);
+        hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)block_part, (int)(grid * waves), sum_sq);
+    } else {
+        hipLaunchKernelGGL(k_normal_cameras<false>, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv,
+                           U, gc, nullptr);
+    }
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("normal_cameras_rows")
+}
+
+int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
+                           void *stream) {
+    C2B_API_BEGIN
+    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: n_pts out of range");
+    if (n_pts && (!camblk || !pts4 || !pt_row_ptr || !obs_of || !cam_of || !uv_obs || !V || !gp))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: NULL argument");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(V) || !aligned8(gp) ||
+        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: misaligned pointer");
+    if (!n_pts) return C2B_OK;
+    hipLaunchKernelGGL(k_normal_points, dim3((unsigned)((n_pts + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0, S(stream), camblk,
+                       reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of, reinterpret_cast<const double2 *>(uv_obs),
+                       V, gp);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("normal_points_rows")
+}

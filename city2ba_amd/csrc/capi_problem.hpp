@@ -25,6 +25,9 @@ struct c2b_problem {
     uint64_t *rows_ptr = nullptr;
     void *rows_tiles = nullptr;
     bool rows_valid = false;
+    // its point-major transpose for c2b_problem_normal_equations (pt_row_ptr [n_pts + 1], obs_of / cam_of [n_obs]), dropped with it
+    uint64_t *nt_ptr = nullptr;
+    uint32_t *nt_obs = nullptr, *nt_cam = nullptr;
     uint32_t *dense_pt = nullptr;   // survivors of the last dense visibility sweep
     double *dense_uv = nullptr;
     uint64_t *dense_row = nullptr;  // its CSR row pointer [n_cam + 1], kept for the occlusion filter
@@ -49,6 +52,10 @@ static void drop_rows(c2b_problem *p) {
     if (p->rows_ptr) (void)hipFree(p->rows_ptr);
     if (p->rows_tiles) (void)hipFree(p->rows_tiles);
     p->rows_ptr = nullptr; p->rows_tiles = nullptr; p->rows_valid = false;
+    if (p->nt_ptr) (void)hipFree(p->nt_ptr);
+    if (p->nt_obs) (void)hipFree(p->nt_obs);
+    if (p->nt_cam) (void)hipFree(p->nt_cam);
+    p->nt_ptr = nullptr; p->nt_obs = p->nt_cam = nullptr;
 }
 
 static void free_buffers(c2b_problem *p) {
@@ -490,6 +497,82 @@ int c2b_problem_total_reprojection_errors_l1_l2_sharded(c2b_problem *p, c2b_comm
     if (comm->device != p->device) return fail(C2B_ERR_INVALID_ARGUMENT, "total_reprojection_errors_l1_l2_sharded: communicator and problem live on different devices");
     return errors_l1_l2_impl(p, comm, l1, l2);
     C2B_API_END("problem_total_reprojection_errors_l1_l2_sharded")
+}
+
+// the point-major transpose of the current observation list (after ensure_rows; pt_idx does not change without drop_rows)
+static int ensure_transpose(c2b_problem *p) {
+    if (p->nt_ptr) return C2B_OK;
+    uint64_t *ptr = nullptr;
+    uint32_t *obs = nullptr, *cam = nullptr;
+    void *temp = nullptr;
+    auto release = [&]() {
+        if (ptr) (void)hipFree(ptr);
+        if (obs) (void)hipFree(obs);
+        if (cam) (void)hipFree(cam);
+        if (temp) (void)hipFree(temp);
+    };
+    const size_t n_obs = (size_t)p->n_obs;
+    hipError_t e = hipMalloc((void **)&ptr, sizeof(uint64_t) * (size_t)(p->n_pts + 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&obs, sizeof(uint32_t) * (n_obs ? n_obs : 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&cam, sizeof(uint32_t) * (n_obs ? n_obs : 1));
+    if (e == hipSuccess) e = hipMalloc(&temp, (size_t)c2b_normal_transpose_temp_bytes(p->n_obs, p->n_pts));
+    if (e != hipSuccess) {
+        release();
+        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "normal_equations: transpose allocation: %s", hipGetErrorString(e));
+    }
+    int rc = c2b_normal_transpose(p->rows_ptr, p->n_cam, p->pt_idx, p->n_obs, p->n_pts, ptr, obs, cam, temp, p->stream);
+    if (!rc) {
+        e = hipStreamSynchronize(p->stream);                 // temp is freed below
+        if (e != hipSuccess) rc = fail(C2B_ERR_HIP, "normal_equations: transpose: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(temp);
+    temp = nullptr;
+    if (rc) { release(); return rc; }
+    p->nt_ptr = ptr; p->nt_obs = obs; p->nt_cam = cam;
+    return C2B_OK;
+}
+
+int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *V, double *gp, double *sum_sq) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: problem is NULL");
+    if (!U != !gc || !V != !gp) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: U / gc and V / gp go in pairs (both or neither)");
+    for (const void *q : {(const void *)U, (const void *)gc, (const void *)V, (const void *)gp, (const void *)sum_sq})
+        if (reinterpret_cast<uintptr_t>(q) & 7) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: misaligned pointer");
+    NEED_UPLOADED(p, "problem_normal_equations");
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (rc) return rc;
+    const bool want_sum = sum_sq != nullptr;
+    if (U) {
+        rc = c2b_normal_cameras_rows(p->camblk, p->pts4, p->n_obs ? p->rows_ptr : nullptr, p->n_obs ? p->n_cam : 0, p->pt_idx, p->uv,
+                                     p->n_obs, U, gc, want_sum ? p->ws : nullptr, want_sum ? p->scalar : nullptr, p->stream);
+        if (!rc && !p->n_obs && p->n_cam) {                   // no list: every camera's block is empty
+            HIP_TRY(hipMemsetAsync(U, 0, sizeof(double) * 81 * (size_t)p->n_cam, p->stream));
+            HIP_TRY(hipMemsetAsync(gc, 0, sizeof(double) * 9 * (size_t)p->n_cam, p->stream));
+        }
+    } else if (want_sum) {
+        rc = p->n_obs ? c2b_reprojection_error_sum_rows(p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->rows_tiles, p->pt_idx, p->uv,
+                                                        p->n_obs, 2.0, p->ws, p->scalar, p->stream)
+                      : (hipMemsetAsync(p->scalar, 0, sizeof(double), p->stream) == hipSuccess ? C2B_OK
+                                                                                             : fail(C2B_ERR_HIP, "problem_normal_equations: memset"));
+    }
+    if (rc) return rc;
+    if (V && p->n_pts) {
+        if (p->n_obs) {
+            rc = ensure_transpose(p);
+            if (!rc) rc = c2b_normal_points_rows(p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, V, gp, p->stream);
+            if (rc) return rc;
+        } else {
+            HIP_TRY(hipMemsetAsync(V, 0, sizeof(double) * 9 * (size_t)p->n_pts, p->stream));
+            HIP_TRY(hipMemsetAsync(gp, 0, sizeof(double) * 3 * (size_t)p->n_pts, p->stream));
+        }
+    }
+    double s = 0.0;
+    if (want_sum) HIP_TRY(hipMemcpyAsync(&s, p->scalar, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (want_sum) *sum_sq = s;
+    return C2B_OK;
+    C2B_API_END("problem_normal_equations")
 }
 
 // Results leave in chunks of kJacChunk observations through a ring of kJacSlots device buffers: the kernel of chunk

@@ -314,6 +314,39 @@ def residual_jacobian_rows_placed(camblk, pts4, rows, pt_idx, uv, outputs, norm=
     return out_sum
 
 
+class PointRows:
+    """The point-major transpose of a camera-major list (c2b_normal_transpose): pt_row_ptr [n_pts + 1] (int64 holding
+    u64), obs_of [n_obs] -- each point's observations in ascending order, a stable argsort of pt_idx -- and cam_of [n_obs],
+    the camera of obs_of[j] (int32 tensors holding u32).  What normal_points_rows walks."""
+
+    def __init__(self, rows, pt_idx, n_pts):
+        _chk(pt_idx, torch.int32, "pt_idx")
+        dev = rows.row_ptr.device
+        self.n_pts, self.n_obs = int(n_pts), rows.n_obs
+        self.pt_row_ptr = torch.empty(self.n_pts + 1, dtype=torch.int64, device=dev)
+        self.obs_of = torch.empty(max(self.n_obs, 1), dtype=torch.int32, device=dev)[:self.n_obs]
+        self.cam_of = torch.empty(max(self.n_obs, 1), dtype=torch.int32, device=dev)[:self.n_obs]
+        temp = torch.empty((L.lib().c2b_normal_transpose_temp_bytes(self.n_obs, self.n_pts) + 7) // 8, dtype=torch.float64, device=dev)
+        L.check(L.lib().c2b_normal_transpose(_p(rows.row_ptr), rows.n_cam, _p(pt_idx), self.n_obs, self.n_pts, _p(self.pt_row_ptr),
+                                             _p(self.obs_of), _p(self.cam_of), _p(temp), _stream()))
+        temp.record_stream(torch.cuda.current_stream(dev))
+
+
+def normal_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, gc, ws=None, sum_sq=None):
+    """camera pass of the Gauss-Newton blocks: U [n_cam,9,9] = sum Jc^T Jc, gc [n_cam,9] = sum Jc^T r over each camera's
+    observations (+ sum |r|^2 into sum_sq[0] when ws and sum_sq are given), the Jacobian never stored"""
+    L.check(L.lib().c2b_normal_cameras_rows(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs,
+                                            _p(U), _p(gc), _p(ws), _p(sum_sq), _stream()))
+    return U, gc
+
+
+def normal_points_rows(camblk, pts4, prows, uv, V, gp):
+    """point pass: V [n_pts,3,3] = sum Jp^T Jp, gp [n_pts,3] = sum Jp^T r over each point's observations (PointRows)"""
+    L.check(L.lib().c2b_normal_points_rows(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of),
+                                           _p(uv), _p(V), _p(gp), _stream()))
+    return V, gp
+
+
 def residual_jacobian(camblk, pts4, cam_idx, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None):
     """ws != None -> the same launch also folds sum |r|^norm into ws (see error_sum_finish)."""
     L.check(L.lib().c2b_residual_jacobian(_p(camblk), _p(pts4), _p(cam_idx), _p(pt_idx), _p(uv), cam_idx.shape[0],

@@ -69,24 +69,24 @@
  *     add_drift, add_drift_normalized, add_noise_entities, add_noise_observations, add_sin_noise
  *   the shard map (1):
  *     partition_cameras
- *   Level 1: a resident BAProblem (46):
+ *   Level 1: a resident BAProblem (47):
  *     problem_create, problem_destroy, problem_options_init, problem_set_options, problem_get_options,
  *     host_set_io_threads, problem_upload, problem_upload_bal, problem_synthetic_grid_layout,
  *     problem_synthetic_line_layout, problem_sizes, problem_download, problem_download_bal, problem_write,
  *     problem_read, problem_from_position_direction, problem_centers, problem_project,
  *     problem_total_reprojection_error, problem_total_reprojection_error_sharded,
  *     problem_total_reprojection_errors_l1_l2, problem_total_reprojection_errors_l1_l2_sharded,
- *     problem_residual_jacobian, problem_residual_jacobian_device, host_alloc, host_free, problem_stats, problem_cull,
- *     problem_largest_connected_component, problem_remove_singletons, problem_adopt_visibility,
- *     problem_download_graph, problem_export_device, problem_visibility_pairs, problem_visibility_pairs_compact,
- *     problem_visibility_within_distance, problem_generate_world_points, problem_visibility_dense,
- *     problem_visibility_dense_fetch, problem_visibility_dense_occlude, problem_visibility_dense_occlude_bvh,
- *     problem_add_drift, problem_add_drift_normalized, problem_add_noise, problem_add_sin_noise,
- *     problem_add_noise_errors_l1_l2
+ *     problem_residual_jacobian, problem_residual_jacobian_device, problem_normal_equations, host_alloc, host_free,
+ *     problem_stats, problem_cull, problem_largest_connected_component, problem_remove_singletons,
+ *     problem_adopt_visibility, problem_download_graph, problem_export_device, problem_visibility_pairs,
+ *     problem_visibility_pairs_compact, problem_visibility_within_distance, problem_generate_world_points,
+ *     problem_visibility_dense, problem_visibility_dense_fetch, problem_visibility_dense_occlude,
+ *     problem_visibility_dense_occlude_bvh, problem_add_drift, problem_add_drift_normalized, problem_add_noise,
+ *     problem_add_sin_noise, problem_add_noise_errors_l1_l2
  *   Level 1: one shard of a larger problem (6):
  *     problem_set_shard, problem_stats_sharded, problem_add_drift_sharded, problem_add_noise_sharded,
  *     problem_add_sin_noise_sharded, problem_add_noise_errors_l1_l2_sharded
- *   -- city2ba_hip.h: 119 entry points --
+ *   -- city2ba_hip.h: 120 entry points --
  *   city2ba_hip_host.h: host-side rows (CPU; never touch the GPU) (42):
  *     synthetic_grid_sizes, synthetic_grid_layout, synthetic_line_layout, candidate_pairs, pairs_count, pairs_cam_idx,
  *     pairs_pt_idx, pairs_free, obj_load, obj_model_count, obj_model_name, obj_model_sizes, obj_model_copy,
@@ -95,11 +95,12 @@
  *     remove_singletons, add_incorrect_correspondences, drop_features, split_landmarks, join_landmarks, bal_read,
  *     bal_sizes, bal_copy, bal_close, bal_write, bal_read_as, bal_write_as, format_f64, parse_f64, ply_write,
  *     bvh_build, bvh_sizes, bvh_copy, bvh_free
- *   city2ba_hip_experimental.h: diagnostics, calibration, f32 extension (15):
+ *   city2ba_hip_experimental.h: diagnostics, calibration, f32 extension (19):
  *     workspace_selfcheck, comm_backend, jacobian_tiles_per_wave, jacobian_launch_shape, jacobian_outputs_log,
- *     jacobian_outputs_set_store_rate, calib_store_pattern, calib_copy, convert_f64_to_f32, convert_f32_to_f64,
- *     stats_f32, add_drift_f32, add_drift_normalized_f32, add_noise_entities_f32, add_sin_noise_f32
- *   (176 entry points in all; names above without their c2b_ prefix)
+ *     jacobian_outputs_set_store_rate, calib_store_pattern, calib_copy, normal_transpose_temp_bytes, normal_transpose,
+ *     normal_cameras_rows, normal_points_rows, convert_f64_to_f32, convert_f32_to_f64, stats_f32, add_drift_f32,
+ *     add_drift_normalized_f32, add_noise_entities_f32, add_sin_noise_f32
+ *   (181 entry points in all; names above without their c2b_ prefix)
  * ---- end of index ----
  *
  * Every function returns C2B_OK or a negative status; c2b_last_error() gives the text.
@@ -130,7 +131,7 @@ const char *c2b_version(void);
 /* The ABI's number: bumped whenever an existing entry's argument list or a buffer's layout changes (r05 did both without a number:
  * camblk became a blocked table, c2b_stats* and the camera-table writers gained a pointer in the middle of their lists).  A host
  * compares c2b_abi_version() with the C2B_ABI_VERSION it was compiled against, once, before its first call. */
-#define C2B_ABI_VERSION 6
+#define C2B_ABI_VERSION 7
 int c2b_abi_version(void);
 const char *c2b_last_error(void);
 int c2b_device_count(int *count);
@@ -550,6 +551,20 @@ int c2b_problem_residual_jacobian(c2b_problem *p, double *r, double *Jc, double 
  * it (the observation count must still match), read it through c2b_jacobian_outputs_pointers, release it with
  * c2b_jacobian_outputs_free.  Bits equal to c2b_problem_residual_jacobian's. */
 int c2b_problem_residual_jacobian_device(c2b_problem *p, int max_attempts, c2b_jacobian_outputs **outputs, double *sum_sq);
+/* The Gauss-Newton diagonal blocks and gradient, reduced on the device from the per-observation Jacobian of
+ * c2b_problem_residual_jacobian (same bits, bal- or state-mode columns as there; r = projected - observed), never
+ * written out:  U [n_cam][9][9] = sum Jc^T Jc and gc [n_cam][9] = sum Jc^T r over each camera's observations,
+ * V [n_pts][3][3] = sum Jp^T Jp and gp [n_pts][3] = sum Jp^T r over each point's, *sum_sq = sum |r|^2.  All f64, row-major,
+ * both triangles stored (U[a][b] and U[b][a] are the same bits); an empty camera or an unobserved point gets exact zeros.
+ * U, gc, V, gp are DEVICE arrays on the problem's device (8-byte aligned); a NULL pair (U and gc, or V and gp) skips
+ * that pass, one NULL of a pair is an error.  sum_sq is a host pointer and may be NULL (with U NULL it comes from the
+ * error-sum launch of c2b_problem_total_reprojection_error instead of the camera pass: the same sum, rounded in another order).  Deterministic: no float
+ * atomics; a camera's block is summed in an order fixed by its own observation list, a point's in ascending observation
+ * index, so the same problem gives the same bits every run.  The point pass reads a point-major transpose of the list
+ * that the problem builds on first use and keeps until the list changes.  On a shard (c2b_problem_set_shard) U / gc are
+ * the rows of the shard's cameras -- bit-equal to the whole problem's -- and V / gp are the shard's PARTIAL sums over
+ * its own observations, which add up over the ranks to the whole problem's (the caller reduces them).  Synchronous. */
+int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *V, double *gp, double *sum_sq);
 /* page-locked host memory for buffers that cross PCIe often (hipHostMalloc / hipHostFree) */
 int c2b_host_alloc(void **ptr, int64_t bytes);
 void c2b_host_free(void *ptr);

@@ -44,6 +44,28 @@ int c2b_jacobian_outputs_set_store_rate(c2b_jacobian_outputs *h, double store_GB
 int c2b_calib_store_pattern(int64_t n_obs, double *r, double *Jc, double *Jp, void *stream);
 int c2b_calib_copy(const void *src, void *dst, int64_t bytes, void *stream);
 
+/* ---- Gauss-Newton diagonal blocks, Level 0 (c2b_problem_normal_equations is the stable entry) ----
+ * The whole observation list in the row-structure form (row_ptr [n_cam + 1] over the camera-major list; pt_idx, uv_obs
+ * its observations; camblk, pts4 as for c2b_residual_jacobian_rows, whose Jacobian these passes reduce without storing it).
+ * The passes need no tile records: the camera pass walks row_ptr, the point pass the transpose.
+ * _transpose: the point-major order of the list -- pt_row_ptr [n_pts + 1] (u64), obs_of [n_obs] the observations of
+ * each point in ascending order (= a stable argsort of pt_idx), cam_of [n_obs] the camera of obs_of[j]; temp is
+ * c2b_normal_transpose_temp_bytes(n_obs, n_pts) bytes of device memory (16-byte aligned), free once the stream passed
+ * the call.  Every pt_idx must be < n_pts.
+ * _cameras_rows: U [n_cam][9][9], gc [n_cam][9] (both required); with a workspace and sum_sq != NULL (device pointer)
+ * the same launch folds sum |r|^2 into sum_sq[0].
+ * _points_rows: V [n_pts][3][3], gp [n_pts][3] from the transpose.
+ * Asynchronous on `stream`; results as c2b_problem_normal_equations describes. */
+int64_t c2b_normal_transpose_temp_bytes(int64_t n_obs, int64_t n_pts);
+int c2b_normal_transpose(const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx, int64_t n_obs, int64_t n_pts,
+                         uint64_t *pt_row_ptr, uint32_t *obs_of, uint32_t *cam_of, void *temp, void *stream);
+int c2b_normal_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                            const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
+                            void *workspace, double *sum_sq, void *stream);
+int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
+                           void *stream);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
