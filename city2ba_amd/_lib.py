@@ -27,6 +27,13 @@ _u64 = C.c_uint64
 _d = C.c_double
 _int = C.c_int
 
+
+class StepInfo(C.Structure):
+    """c2b_step_info (include/city2ba_hip_experimental.h)"""
+    _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("rel_residual", C.c_double), ("sum_sq", C.c_double),
+                ("model_decrease", C.c_double)]
+
+
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
 SIGNATURES = {
     "c2b_version": (C.c_char_p, []),
@@ -80,6 +87,10 @@ SIGNATURES = {
     "c2b_normal_transpose": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "c2b_normal_cameras_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "c2b_normal_points_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_schur_points_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "c2b_schur_cameras_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _d, _vp, _vp, _vp, _vp]),
+    "c2b_problem_solve_step": (_int, [_vp, _d, _int, _d, _vp, _vp, _vp]),
+    "c2b_problem_apply_step": (_int, [_vp, _vp, _vp]),
     "c2b_visibility_pairs": (_int, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_visibility_dense_tiles": (_i64, [_i64]),
     "c2b_visibility_dense_count": (_int, [_vp, _i64, _vp, _i64, _d, _vp, _vp, _vp, _vp]),

@@ -280,6 +280,48 @@ class BAProblem:
         L.check(L.lib().c2b_problem_normal_equations(self._h, ptr(U), ptr(gc), ptr(V), ptr(gp), C.byref(s)))
         return U, gc, V, gp, s.value
 
+    def solve_step(self, lam, max_iters=100, rel_tol=1e-6, out=None):
+        """One damped Gauss-Newton (Levenberg-Marquardt) step on the device (c2b_problem_solve_step): the solution of
+        (J^T J + lam D) delta = -g, D = diag(min(max(diag(J^T J), 1e-6), 1e32)), by PCG on the Schur complement of the
+        cameras.  Returns (dc [n_cam,9], dp [n_pts,3], info): float64 torch tensors on the problem's device (out = (dc, dp)
+        fills the caller's, contiguous float64 of those shapes) and info = dict(iterations, status -- 0 converged,
+        1 max_iters, 2 breakdown --, rel_residual, sum_sq = |r|^2 now, model_decrease = |r|^2 - |r + J delta|^2).
+        The columns of dc are those of residual_jacobian (the ω of this mode); apply_step adds the step."""
+        import torch
+        nc, npt = self.num_cameras(), self.num_points()
+        dev = torch.device("cuda", self._device)
+        shapes = ((nc, 9), (npt, 3))
+        if out is None:
+            arrs = [torch.empty(sh, dtype=torch.float64, device=dev) for sh in shapes]
+        else:
+            arrs = list(out)
+            if len(arrs) != 2:
+                raise ValueError("solve_step: out must be (dc, dp)")
+            for a, sh, name in zip(arrs, shapes, ("dc", "dp")):
+                if not isinstance(a, torch.Tensor) or a.dtype != torch.float64 or a.device != dev or tuple(a.shape) != sh \
+                        or not a.is_contiguous():
+                    raise ValueError("solve_step: out %s must be a contiguous float64 tensor of shape %s on %s" % (name, sh, dev))
+        info = L.StepInfo()
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a.numel() else None
+        torch.cuda.current_stream(dev).synchronize()
+        L.check(L.lib().c2b_problem_solve_step(self._h, float(lam), int(max_iters), float(rel_tol), ptr(arrs[0]), ptr(arrs[1]),
+                                               C.byref(info)))
+        d = {k: getattr(info, k) for k, _ in L.StepInfo._fields_}
+        return arrs[0], arrs[1], d
+
+    def apply_step(self, dc, dp):
+        """cameras and points += a step of solve_step (c2b_problem_apply_step): bal9 = to_vec of the cameras + dc, the
+        cameras rebuilt from it, points + dp; either may be None (no change).  The problem is in bal mode afterwards."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        for a, sh, name in ((dc, (self.num_cameras(), 9), "dc"), (dp, (self.num_points(), 3), "dp")):
+            if a is not None and (not isinstance(a, torch.Tensor) or a.dtype != torch.float64 or a.device != dev
+                                  or tuple(a.shape) != sh or not a.is_contiguous()):
+                raise ValueError("apply_step: %s must be a contiguous float64 tensor of shape %s on %s" % (name, sh, dev))
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
+        torch.cuda.current_stream(dev).synchronize()
+        L.check(L.lib().c2b_problem_apply_step(self._h, ptr(dc), ptr(dp)))
+
     def _stats(self):
         s = np.empty(L.STATS_DOUBLES)
         L.check(L.lib().c2b_problem_stats(self._h, _ptr(s)))

@@ -33,6 +33,7 @@
 #include "host_synthetic.hpp"
 #include "kernels.hpp"
 #include "normal_kernels.hpp"
+#include "schur_kernels.hpp"
 #include "cull_kernels.hpp"
 #include "cell_kernels.hpp"
 #include "text_kernels.hpp"

@@ -1347,3 +1347,58 @@ int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_p
     return C2B_OK;
     C2B_API_END("normal_points_rows")
 }
+
+// ---- damped Gauss-Newton step: the implicit Schur complement's passes (schur_kernels.hpp) -----------------------
+static bool good_lambda(double lam) { return std::isfinite(lam) && lam > 0.0; }
+
+int c2b_schur_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                          const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
+                          const double *x_cam, const double *h_pts, double *t_pts, void *stream) {
+    C2B_API_BEGIN
+    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: n_pts out of range");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: lambda must be finite and > 0");
+    if (n_pts && (!V || !t_pts || (x_cam && (!camblk || !pts4 || !pt_row_ptr || !obs_of || !cam_of || !uv_obs))))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: NULL argument");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(V) || !aligned8(x_cam) ||
+        !aligned8(h_pts) || !aligned8(t_pts) || (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: misaligned pointer");
+    if (!n_pts) return C2B_OK;
+    hipLaunchKernelGGL(k_schur_points<false>, dim3(blocks_for(n_pts, kSchurBlock)), dim3(kSchurBlock), 0, S(stream), camblk,
+                       reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of, reinterpret_cast<const double2 *>(uv_obs),
+                       V, lambda, x_cam, h_pts, t_pts);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("schur_points_rows")
+}
+
+// grid of k_schur_cameras: one wave per kNormCamsPerWave cameras
+static unsigned schur_cameras_grid(int64_t n_cam) {
+    const int64_t quads = (n_cam + kNormCamsPerWave - 1) / kNormCamsPerWave, waves = kNormBlock / 64;
+    return (unsigned)((quads + waves - 1) / waves);
+}
+
+int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                           const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
+                           const double *t_pts, double *y_cam, void *stream) {
+    C2B_API_BEGIN
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: count out of range");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: lambda must be finite and > 0");
+    if (n_cam && (!camblk || !row_ptr || !U || !y_cam)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: NULL argument");
+    if (n_obs && (!pts4 || !pt_idx || !uv_obs || !t_pts)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: NULL observation input");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(row_ptr) || !aligned8(U) || !aligned8(x_cam) ||
+        !aligned8(t_pts) || !aligned8(y_cam) || (reinterpret_cast<uintptr_t>(pt_idx) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: misaligned pointer");
+    if (!n_cam) return C2B_OK;
+    if (x_cam)
+        hipLaunchKernelGGL(k_schur_cameras<kSchurApply>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
+                           reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
+                           U, lambda, x_cam, nullptr, t_pts, y_cam, nullptr);
+    else
+        hipLaunchKernelGGL(k_schur_cameras<kSchurNoX>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
+                           reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
+                           U, lambda, nullptr, nullptr, t_pts, y_cam, nullptr);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("schur_cameras_rows")
+}

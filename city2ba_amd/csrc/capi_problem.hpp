@@ -28,6 +28,10 @@ struct c2b_problem {
     // its point-major transpose for c2b_problem_normal_equations (pt_row_ptr [n_pts + 1], obs_of / cam_of [n_obs]), dropped with it
     uint64_t *nt_ptr = nullptr;
     uint32_t *nt_obs = nullptr, *nt_cam = nullptr;
+    // c2b_problem_solve_step's buffers (U, gc, V, gp, the preconditioner's factors, the PCG vectors, partials, scalars):
+    // one allocation, sized by the list, dropped with it
+    double *sv = nullptr;
+    int64_t sv_doubles = 0;
     uint32_t *dense_pt = nullptr;   // survivors of the last dense visibility sweep
     double *dense_uv = nullptr;
     uint64_t *dense_row = nullptr;  // its CSR row pointer [n_cam + 1], kept for the occlusion filter
@@ -39,6 +43,8 @@ struct c2b_problem {
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_done[kJacSlots] = {nullptr, nullptr, nullptr}, ev_free[kJacSlots] = {nullptr, nullptr, nullptr};
 };
+
+static void cameras_mutated(c2b_problem *p);
 
 static void free_dense(c2b_problem *p) {
     if (p->dense_pt) (void)hipFree(p->dense_pt);
@@ -56,6 +62,8 @@ static void drop_rows(c2b_problem *p) {
     if (p->nt_obs) (void)hipFree(p->nt_obs);
     if (p->nt_cam) (void)hipFree(p->nt_cam);
     p->nt_ptr = nullptr; p->nt_obs = p->nt_cam = nullptr;
+    if (p->sv) (void)hipFree(p->sv);
+    p->sv = nullptr; p->sv_doubles = 0;
 }
 
 static void free_buffers(c2b_problem *p) {
@@ -573,6 +581,188 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
     if (want_sum) *sum_sq = s;
     return C2B_OK;
     C2B_API_END("problem_normal_equations")
+}
+
+// ---- damped Gauss-Newton step (schur_kernels.hpp) ------------------------------------------------------------------
+// c2b_problem::sv, carved: U [n_cam][81], gc [n_cam][9], V [n_pts][9], gp [n_pts][3], Lf [n_cam][45], t [n_pts][3],
+// r / z / p / q [n_cam][9], two partial arrays [n_part], the device scalars [kScSlots]
+struct SolveBufs {
+    double *U, *gc, *V, *gp, *Lf, *t, *r, *z, *pv, *q, *pa, *pb, *sc;
+    int64_t n_part;
+};
+
+static int64_t solve_parts(const c2b_problem *p) {
+    const int64_t a = (int64_t)schur_cameras_grid(p->n_cam) * (kNormBlock / 64);
+    return std::max<int64_t>({a, (int64_t)blocks_for(p->n_cam, kSchurBlock), (int64_t)blocks_for(p->n_obs, kSchurBlock), 1});
+}
+
+static int64_t solve_doubles(const c2b_problem *p) {
+    return p->n_cam * (81 + 9 + kCholPacked + 4 * 9) + p->n_pts * (9 + 3 + 3) + 2 * solve_parts(p) + kScSlots;
+}
+
+static SolveBufs solve_bufs(c2b_problem *p) {
+    SolveBufs b;
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    double *q = p->sv;
+    auto take = [&](int64_t n) { double *r = q; q += n; return r; };
+    b.U = take(81 * nc); b.gc = take(9 * nc); b.V = take(9 * np); b.gp = take(3 * np); b.Lf = take(kCholPacked * nc);
+    b.t = take(3 * np); b.r = take(9 * nc); b.z = take(9 * nc); b.pv = take(9 * nc); b.q = take(9 * nc);
+    b.n_part = solve_parts(p);
+    b.pa = take(b.n_part); b.pb = take(b.n_part); b.sc = take(kScSlots);
+    return b;
+}
+
+static int ensure_solver(c2b_problem *p) {
+    const int64_t n = solve_doubles(p);
+    if (p->sv && p->sv_doubles >= n) return C2B_OK;
+    if (p->sv) (void)hipFree(p->sv);
+    p->sv_doubles = 0;
+    const hipError_t e = hipMalloc((void **)&p->sv, sizeof(double) * (size_t)n);
+    if (e == hipSuccess) p->sv_doubles = n;
+    if (e != hipSuccess) {
+        p->sv = nullptr;
+        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_solve_step: allocation: %s", hipGetErrorString(e));
+    }
+    return C2B_OK;
+}
+
+int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double rel_tol, double *dc, double *dp, c2b_step_info *info) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: problem is NULL");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: lambda must be finite and > 0");
+    if (max_iters < 0 || !(rel_tol >= 0.0) || !std::isfinite(rel_tol))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: max_iters must be >= 0 and rel_tol finite and >= 0");
+    NEED_UPLOADED(p, "problem_solve_step");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: a shard cannot be solved alone (the point-side sums span every rank)");
+    const int64_t nc = p->n_cam, np = p->n_pts, no = p->n_obs;
+    if ((nc && !dc) || (np && !dp)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: dc / dp is NULL");
+    if (!aligned8(dc) || !aligned8(dp)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: misaligned pointer");
+    hipStream_t st = p->stream;
+    c2b_step_info out{0, 0, 0.0, 0.0, 0.0};
+    if (!no) {                                               // no observation: g = 0, the step is 0
+        if (nc) HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
+        if (np) HIP_TRY(hipMemsetAsync(dp, 0, sizeof(double) * 3 * (size_t)np, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (info) *info = out;
+        return C2B_OK;
+    }
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (!rc) rc = ensure_transpose(p);
+    if (!rc) rc = ensure_solver(p);
+    if (rc) return rc;
+    const SolveBufs B = solve_bufs(p);
+    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4);
+    const double2 *uv = reinterpret_cast<const double2 *>(p->uv);
+    const unsigned cgrid = schur_cameras_grid(nc), nbc = blocks_for(nc, kSchurBlock), nbo = blocks_for(no, kSchurBlock);
+    const int n_cpart = (int)(cgrid * (kNormBlock / 64));
+    auto points = [&](const double *x, const double *h, double *t, bool neg) {
+        if (neg)
+            hipLaunchKernelGGL(k_schur_points<true>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
+                               p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t);
+        else
+            hipLaunchKernelGGL(k_schur_points<false>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
+                               p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t);
+    };
+    double h[kScSlots];
+    auto fetch = [&](int slots) -> int {                     // the first `slots` scalars to the host, after all queued work
+        HIP_TRY(launch_error());
+        HIP_TRY(hipMemcpyAsync(h, B.sc, sizeof(double) * slots, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return C2B_OK;
+    };
+
+    // U, gc, V, gp; the preconditioner; b = -gc + W V_l^-1 gp into r
+    rc = c2b_normal_cameras_rows(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.gc, nullptr, nullptr, st);
+    if (!rc) rc = c2b_normal_points_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, B.gp, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
+    points(nullptr, B.gp, B.t, false);
+    hipLaunchKernelGGL(k_schur_cameras<kSchurRhs>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc, p->pt_idx,
+                       uv, (const double *)B.U, lambda, nullptr, (const double *)B.gc, (const double *)B.t, B.r, nullptr);
+    hipLaunchKernelGGL(k_pcg_update<true>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc, 0, dc,
+                       B.r, B.pv, (const double *)nullptr, B.z, B.pa, B.pb);
+    hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbc, B.sc + kScRr);
+    hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pb, (int)nbc, B.sc + kScRz0);
+    if ((rc = fetch(kScRz1 + 1))) return rc;
+
+    // PCG from x = 0 (x is dc)
+    const double bb = h[kScRr], bnorm = std::sqrt(bb);
+    double rnorm = bnorm;
+    int it = 0, status = 1;
+    if (!std::isfinite(bb) || !std::isfinite(h[kScRz0])) {
+        status = 2;
+    } else if (rnorm <= rel_tol * bnorm) {                   // b = 0 (or rel_tol >= 1)
+        status = 0;
+    } else {
+        while (it < max_iters) {
+            const int cur = (it & 1) ? kScRz1 : kScRz0, nxt = (it & 1) ? kScRz0 : kScRz1;
+            points(B.pv, nullptr, B.t, false);
+            hipLaunchKernelGGL(k_schur_cameras<kSchurDot>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
+                               p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv, (const double *)nullptr,
+                               (const double *)B.t, B.q, B.pa);
+            hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, n_cpart, B.sc + kScPq);
+            hipLaunchKernelGGL(k_pcg_update<false>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc,
+                               cur, dc, B.r, B.pv, (const double *)B.q, B.z, B.pa, B.pb);
+            hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbc, B.sc + kScRr);
+            hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pb, (int)nbc, B.sc + nxt);
+            if ((rc = fetch(kScRz1 + 1))) return rc;
+            const double pq = h[kScPq], rz = h[cur], alpha = rz / pq;
+            if (!(pq > 0.0) || !std::isfinite(alpha)) { status = 2; break; }     // k_pcg_update left x as it was
+            ++it;
+            const double rr = h[kScRr], rzn = h[nxt];
+            if (!std::isfinite(rr) || !std::isfinite(rzn)) { status = 2; break; }
+            rnorm = std::sqrt(rr);
+            if (rnorm <= rel_tol * bnorm) { status = 0; break; }
+            if (it == max_iters) break;
+            hipLaunchKernelGGL(k_pcg_direction, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, rzn / rz,
+                               (const double *)B.z, B.pv);
+        }
+    }
+
+    // dp = -V_l^-1 (gp + W^T dc); then |r|^2 and the model decrease from J, per observation
+    points(dc, B.gp, dp, true);
+    hipLaunchKernelGGL(k_schur_model, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                       (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb);
+    hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbo, B.sc + kScSumSq);
+    hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pb, (int)nbo, B.sc + kScModel);
+    if ((rc = fetch(kScModel + 1))) return rc;
+    out.iterations = it;
+    out.status = status;
+    out.rel_residual = bb == 0.0 ? 0.0 : rnorm / bnorm;
+    out.sum_sq = h[kScSumSq];
+    out.model_decrease = h[kScModel];
+    if (info) *info = out;
+    return C2B_OK;
+    C2B_API_END("problem_solve_step")
+}
+
+int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_apply_step");
+    if (!aligned8(dc) || !aligned8(dp)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_apply_step: misaligned pointer");
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    hipStream_t st = p->stream;
+    if (nc) {
+        if (!p->bal_valid && !p->bal9_fresh) {               // state mode: the columns of dc refer to to_vec(cam15)
+            const int rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st);
+            if (rc) return rc;
+        }
+        if (dc) hipLaunchKernelGGL(k_add_f64, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc, p->bal9);
+        LAUNCH_CHECK();
+        const int rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
+        if (rc) return rc;
+    }
+    if (dp && np) {
+        hipLaunchKernelGGL(k_points_add, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp, reinterpret_cast<double4 *>(p->pts4));
+        LAUNCH_CHECK();
+    }
+    cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
+    p->bal_valid = true;
+    HIP_TRY(hipStreamSynchronize(st));
+    return C2B_OK;
+    C2B_API_END("problem_apply_step")
 }
 
 // Results leave in chunks of kJacChunk observations through a ring of kJacSlots device buffers: the kernel of chunk

@@ -1,0 +1,309 @@
+// schur_kernels.hpp -- gfx950 kernels of the damped Gauss-Newton step (included by capi.hip only, after normal_kernels.hpp).
+//
+// The step solves (J^T J + lambda D) delta = -g through the Schur complement on the cameras, S = U_l - W V_l^-1 W^T,
+// by block-Jacobi preconditioned conjugate gradients, never forming W (= sum Jc^T Jp) or S: every product with them is
+// a pass over the observations that recomputes J through jacobian_obs, as the normal_kernels.hpp passes do.
+//   * k_schur_points: point-major through the transpose, one lane per point walking its observations in ascending
+//     index: t_p = V_l,p^-1 (h_p + sum Jp^T (Jc x_c)), the 3x3 solve in registers.
+//   * k_schur_cameras: camera-major, kNormG lanes per camera (the k_normal_cameras layout and xor tree), one wave per
+//     four cameras: y_c = U_l,c x_c - sum Jc^T (Jp t_p), optionally with the wave's x.y as one partial.
+//   * k_schur_factor / k_pcg_update / k_pcg_direction: the 9x9 Cholesky preconditioner, the PCG vector updates with
+//     r.r and r.z as one partial per workgroup, p = z + beta p.
+//   * k_schur_model: ||r||^2 and ||r||^2 - ||r + Jc dc + Jp dp||^2 per observation, one partial per workgroup.
+// Damping (Marquardt with Ceres' clamps): A_l = A + lambda diag(d), d_i = min(max(A_ii, 1e-6), 1e32).
+// Every partial is summed by k_normal_sum in a fixed order; no float atomics, so the same inputs give the same bits.
+#pragma once
+#include "normal_kernels.hpp"
+
+namespace c2b {
+
+constexpr int kSchurBlock = 256;
+constexpr int kCholPacked = 45;                   // lower triangle of a 9x9, row by row
+enum { kSchurApply = 0, kSchurDot = 1, kSchurRhs = 2, kSchurNoX = 3 };
+// device scalars of a solve (c2b_problem::sv_sc): p.q, r.r, r.z ping-pong, sum |r|^2, model decrease
+enum { kScPq = 0, kScRr = 1, kScRz0 = 2, kScRz1 = 3, kScSumSq = 4, kScModel = 5, kScSlots = 8 };
+
+C2B_DEV double damped(double a, double lam) { return a + lam * fmin(fmax(a, 1e-6), 1e32); }
+
+// index of (i, j), j <= i, in the packed lower triangle
+C2B_DEV constexpr int tri9(int i, int j) { return i * (i + 1) / 2 + j; }
+
+// the workgroup's sum of one value per thread, in a fixed order, written by thread 0
+C2B_DEV void block_sum_to(double v, double *sRed, double *__restrict__ out) {
+    const double w = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
+}
+
+// ---- point pass ----------------------------------------------------------------------------------------------
+// t_p = (NEG ? -1 : 1) V_l,p^-1 (h_p + sum_o Jp_o^T (Jc_o x_c(o))); h == NULL is 0, x == NULL is 0 (no observation read)
+template <bool NEG>
+__global__ __launch_bounds__(kSchurBlock) void k_schur_points(
+    const double *__restrict__ camblk, const double4 *__restrict__ pts4, int64_t n_pts, const uint64_t *__restrict__ pt_row_ptr,
+    const uint32_t *__restrict__ obs_of, const uint32_t *__restrict__ cam_of, const double2 *__restrict__ uv_obs,
+    const double *__restrict__ V, double lam, const double *__restrict__ x, const double *__restrict__ h, double *__restrict__ t) {
+    const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (p >= n_pts) return;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    if (h) { a0 = h[3 * p]; a1 = h[3 * p + 1]; a2 = h[3 * p + 2]; }
+    if (x) {
+        const uint64_t b = pt_row_ptr[p], e = pt_row_ptr[p + 1];
+        if (e > b) {
+            const double4 X = pts4[p];
+            for (uint64_t j = b; j < e; ++j) {
+                const uint32_t o = obs_of[j], c = cam_of[j];
+                double r0, r1, jc[18], jp[6];
+                jacobian_obs(cam_ref(camblk, c), X, uv_obs[o], r0, r1, jc, jp);
+                const double *xc = x + (int64_t)c * 9;
+                double z0 = 0.0, z1 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    const double xk = xc[k];
+                    z0 += jc[k] * xk;
+                    z1 += jc[9 + k] * xk;
+                }
+                a0 += jp[0] * z0 + jp[3] * z1;
+                a1 += jp[1] * z0 + jp[4] * z1;
+                a2 += jp[2] * z0 + jp[5] * z1;
+            }
+        }
+    }
+    // V_l = L L^T, L in registers (the reciprocals of its diagonal)
+    const double *Vp = V + p * 9;
+    const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
+    const double i0 = 1.0 / sqrt(v00);
+    const double l10 = v10 * i0, l20 = v20 * i0;
+    const double i1 = 1.0 / sqrt(v11 - l10 * l10);
+    const double l21 = (v21 - l20 * l10) * i1;
+    const double i2 = 1.0 / sqrt((v22 - l20 * l20) - l21 * l21);
+    const double y0 = a0 * i0, y1 = (a1 - l10 * y0) * i1, y2 = ((a2 - l20 * y0) - l21 * y1) * i2;
+    const double t2 = y2 * i2, t1 = (y1 - l21 * t2) * i1, t0 = ((y0 - l10 * t1) - l20 * t2) * i0;
+    t[3 * p] = NEG ? -t0 : t0;
+    t[3 * p + 1] = NEG ? -t1 : t1;
+    t[3 * p + 2] = NEG ? -t2 : t2;
+}
+
+// ---- camera pass ---------------------------------------------------------------------------------------------
+// s_c = sum_o Jc_o^T (Jp_o t_p(o)) over the camera's list, then
+//   kSchurApply: y_c = U_l,c x_c - s_c;  kSchurNoX: y_c = -s_c (x unused);  kSchurDot: as kSchurApply, and sum_c x_c . y_c
+//   leaves as one partial per wave in block_part;  kSchurRhs: y_c = s_c - h_c (the reduced right-hand side when
+//   t = V_l^-1 gp, h = gc).  One instance per mode: a pointer its mode does not read costs it no scalar registers.
+template <int MODE>
+__global__ __launch_bounds__(kNormBlock) void k_schur_cameras(
+    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
+    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const double *__restrict__ U, double lam,
+    const double *__restrict__ x, const double *__restrict__ h, const double *__restrict__ t, double *__restrict__ y,
+    double *__restrict__ block_part) {
+    constexpr int kWaves = kNormBlock / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
+    const int q = (int)blockIdx.x * kWaves + wave;                   // one wave per kNormCamsPerWave cameras, no grid-stride loop
+    const int c = q * kNormCamsPerWave + grp;
+    const bool cam_ok = c < n_cam;
+    const uint64_t b = cam_ok ? row_ptr[c] : 0, e = cam_ok ? row_ptr[c + 1] : 0;
+    const CamRef cam = cam_ref(camblk, cam_ok ? (uint32_t)c : 0u);
+    double s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = 0.0;
+#pragma unroll 1
+    for (uint64_t o = b + gl; o < e; o += kNormG) {
+        const uint32_t pi = pt_idx[o];
+        double r0, r1, jc[18], jp[6];
+        jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
+        const double *tp = t + (int64_t)pi * 3;
+        const double t0 = tp[0], t1 = tp[1], t2 = tp[2];
+        const double z0 = (jp[0] * t0 + jp[1] * t1) + jp[2] * t2;
+        const double z1 = (jp[3] * t0 + jp[4] * t1) + jp[5] * t2;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s[k] += jc[k] * z0 + jc[9 + k] * z1;
+    }
+    // fixed xor tree over the group's 16 lanes (every lane ends with the same bits)
+#pragma unroll
+    for (int off = kNormG / 2; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s[k] += __shfl_xor(s[k], off, 64);
+    }
+    double sg = 0.0;                                                 // s[gl] without a dynamically indexed register array
+#pragma unroll
+    for (int k = 0; k < 9; ++k) sg = gl == k ? s[k] : sg;
+    double yg = 0.0, xg = 0.0;
+    if (cam_ok && gl < 9) {
+        if (MODE == kSchurRhs) {
+            yg = sg - h[(int64_t)c * 9 + gl];
+        } else {
+            double ux = 0.0;
+            if (MODE != kSchurNoX) {
+                const double *Ur = U + (int64_t)c * 81 + gl * 9, *xc = x + (int64_t)c * 9;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    const double u = Ur[k];
+                    ux += (k == gl ? damped(u, lam) : u) * xc[k];
+                }
+                xg = xc[gl];
+            }
+            yg = ux - sg;
+        }
+        y[(int64_t)c * 9 + gl] = yg;
+    }
+    if (MODE == kSchurDot) {                                         // the wave's x.y: its four cameras, in a fixed tree
+        const double w = wave_sum(xg * yg);                          // 0 on lanes gl >= 9 and past n_cam
+        if (lane == 0) block_part[q] = w;
+    }
+}
+
+// ---- preconditioner and PCG vectors ----------------------------------------------------------------------------------
+// Lf[c] = the Cholesky factor of U_l,c, packed lower rows with the reciprocal of each diagonal entry in its place
+__global__ __launch_bounds__(kSchurBlock) void k_schur_factor(int64_t n_cam, const double *__restrict__ U, double lam,
+                                                              double *__restrict__ Lf) {
+    const int64_t c = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (c >= n_cam) return;
+    const double *Uc = U + c * 81;
+    double a[kCholPacked];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) a[tri9(i, j)] = i == j ? damped(Uc[i * 9 + j], lam) : Uc[i * 9 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        double d = a[tri9(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= a[tri9(j, k)] * a[tri9(j, k)];
+        const double inv = 1.0 / sqrt(d);
+        a[tri9(j, j)] = inv;
+#pragma unroll
+        for (int i = j + 1; i < 9; ++i) {
+            double v = a[tri9(i, j)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= a[tri9(i, k)] * a[tri9(j, k)];
+            a[tri9(i, j)] = v * inv;
+        }
+    }
+    double *Lc = Lf + c * kCholPacked;
+#pragma unroll
+    for (int k = 0; k < kCholPacked; ++k) Lc[k] = a[k];
+}
+
+// z = (L L^T)^-1 r with a factor of k_schur_factor
+C2B_DEV void chol9_solve(const double *__restrict__ Lc, const double (&r)[9], double (&z)[9]) {
+    double l[kCholPacked];
+#pragma unroll
+    for (int k = 0; k < kCholPacked; ++k) l[k] = Lc[k];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        double v = r[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v -= l[tri9(i, k)] * z[k];
+        z[i] = v * l[tri9(i, i)];
+    }
+#pragma unroll
+    for (int i = 8; i >= 0; --i) {
+        double v = z[i];
+#pragma unroll
+        for (int k = i + 1; k < 9; ++k) v -= l[tri9(k, i)] * z[k];
+        z[i] = v * l[tri9(i, i)];
+    }
+}
+
+// FIRST: r holds b; x = 0, z = M^-1 r, p = z.  Otherwise alpha = sc[rz] / sc[pq] (no update at all unless pq > 0 and
+// alpha is finite: the host then reports a breakdown with x the last good iterate): x += alpha p, r -= alpha q,
+// z = M^-1 r.  Both: r.r and r.z leave as one partial per workgroup (part_rr, part_rz).
+template <bool FIRST>
+__global__ __launch_bounds__(kSchurBlock) void k_pcg_update(
+    int64_t n_cam, const double *__restrict__ Lf, const double *__restrict__ sc, int rz_slot, double *__restrict__ x,
+    double *__restrict__ r, double *__restrict__ p, const double *__restrict__ q, double *__restrict__ z,
+    double *__restrict__ part_rr, double *__restrict__ part_rz) {
+    __shared__ double sRed[2][4];
+    const int64_t c = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    double rr = 0.0, rz = 0.0;
+    if (c < n_cam) {
+        double rc[9], zc[9];
+        bool go = true;
+        double alpha = 0.0;
+        if (!FIRST) {
+            const double pq = sc[kScPq];
+            alpha = sc[rz_slot] / pq;
+            go = pq > 0.0 && isfinite(alpha);
+        }
+        if (go) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) rc[k] = r[c * 9 + k];
+            if (FIRST) {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) x[c * 9 + k] = 0.0;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    const double pk = p[c * 9 + k];
+                    x[c * 9 + k] += alpha * pk;
+                    rc[k] -= alpha * q[c * 9 + k];
+                    r[c * 9 + k] = rc[k];
+                }
+            }
+            chol9_solve(Lf + c * kCholPacked, rc, zc);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                if (FIRST) p[c * 9 + k] = zc[k];
+                else z[c * 9 + k] = zc[k];
+                rr += rc[k] * rc[k];
+                rz += rc[k] * zc[k];
+            }
+        }
+    }
+    block_sum_to(rr, sRed[0], part_rr + blockIdx.x);
+    block_sum_to(rz, sRed[1], part_rz + blockIdx.x);
+}
+
+// p = z + beta p over n doubles
+__global__ __launch_bounds__(kSchurBlock) void k_pcg_direction(int64_t n, double beta, const double *__restrict__ z, double *__restrict__ p) {
+    const int64_t i = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (i < n) p[i] = z[i] + beta * p[i];
+}
+
+// ---- model decrease ---------------------------------------------------------------------------------------------
+// per observation e = Jc dc + Jp dp: |r|^2 and |r|^2 - |r + e|^2 = -(2r + e).e, one partial of each per workgroup
+__global__ __launch_bounds__(kSchurBlock) void k_schur_model(
+    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint32_t *__restrict__ cam_idx,
+    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, int64_t n_obs, const double *__restrict__ dc,
+    const double *__restrict__ dp, double *__restrict__ part_sq, double *__restrict__ part_md) {
+    __shared__ double sRed[2][4];
+    const int64_t o = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    double sq = 0.0, md = 0.0;
+    if (o < n_obs) {
+        const uint32_t c = cam_idx[o], pi = pt_idx[o];
+        double r0, r1, jc[18], jp[6];
+        jacobian_obs(cam_ref(camblk, c), pts4[pi], uv_obs[o], r0, r1, jc, jp);
+        const double *dcc = dc + (int64_t)c * 9, *dpp = dp + (int64_t)pi * 3;
+        double e0 = 0.0, e1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            e0 += jc[k] * dcc[k];
+            e1 += jc[9 + k] * dcc[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            e0 += jp[k] * dpp[k];
+            e1 += jp[3 + k] * dpp[k];
+        }
+        sq = r0 * r0 + r1 * r1;
+        md = -((2.0 * r0 + e0) * e0 + (2.0 * r1 + e1) * e1);
+    }
+    block_sum_to(sq, sRed[0], part_sq + blockIdx.x);
+    block_sum_to(md, sRed[1], part_md + blockIdx.x);
+}
+
+// ---- apply -----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kSchurBlock) void k_add_f64(int64_t n, const double *__restrict__ d, double *__restrict__ a) {
+    const int64_t i = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (i < n) a[i] += d[i];
+}
+
+__global__ __launch_bounds__(kSchurBlock) void k_points_add(int64_t n_pts, const double *__restrict__ dp, double4 *__restrict__ pts4) {
+    const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (p >= n_pts) return;
+    double4 X = pts4[p];
+    X.x += dp[3 * p]; X.y += dp[3 * p + 1]; X.z += dp[3 * p + 2];
+    pts4[p] = X;
+}
+
+}  // namespace c2b

@@ -347,6 +347,22 @@ def normal_points_rows(camblk, pts4, prows, uv, V, gp):
     return V, gp
 
 
+def schur_points_rows(camblk, pts4, prows, uv, V, lam, x, h, t):
+    """point pass of the damped step's Schur complement: t [n_pts,3] = V_l^-1 (h + sum Jp^T (Jc x)) per point (PointRows),
+    V_l = V damped by lam (c2b_schur_points_rows); x [n_cam,9] None means 0, h [n_pts,3] None means 0"""
+    L.check(L.lib().c2b_schur_points_rows(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of),
+                                          _p(uv), _p(V), float(lam), _p(x), _p(h), _p(t), _stream()))
+    return t
+
+
+def schur_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, lam, x, t, y):
+    """camera pass: y [n_cam,9] = U_l x - sum Jc^T (Jp t) per camera, U_l = U damped by lam (c2b_schur_cameras_rows);
+    x None drops the U term.  S x = schur_cameras_rows(.., x, schur_points_rows(.., x, None, t), y)"""
+    L.check(L.lib().c2b_schur_cameras_rows(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs,
+                                           _p(U), float(lam), _p(x), _p(t), _p(y), _stream()))
+    return y
+
+
 def residual_jacobian(camblk, pts4, cam_idx, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None):
     """ws != None -> the same launch also folds sum |r|^norm into ws (see error_sum_finish)."""
     L.check(L.lib().c2b_residual_jacobian(_p(camblk), _p(pts4), _p(cam_idx), _p(pt_idx), _p(uv), cam_idx.shape[0],

@@ -1,0 +1,36 @@
+"""Levenberg-Marquardt on a resident BAProblem: BAProblem.solve_step (the damped Gauss-Newton step by PCG on the
+cameras' Schur complement, on the device) and apply_step, with Nielsen's update of the damping."""
+
+
+def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6):
+    """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
+    sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
+    and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit).  Returns the
+    history: one dict per iteration -- error (sum |r|^2 before it), lam (the damping it used), accepted, pcg_iterations,
+    status (the solve's) -- and the final sum |r|^2 as the last entry's 'error_after'."""
+    ba.apply_step(None, None)                       # bal mode: bal9 is then what the problem holds exactly
+    bal9, pts = ba.cameras_bal(), ba.points()
+    row_ptr, pt_idx, uv = ba.row_ptr.copy(), ba.pt_idx.copy(), ba.observations()
+    nu = 2.0
+    history = []
+    e0 = ba.total_reprojection_error(2.0) ** 2
+    for _ in range(int(iterations)):
+        dc, dp, info = ba.solve_step(lam, max_iters=max_iters, rel_tol=rel_tol)
+        ba.apply_step(dc, dp)
+        e1 = ba.total_reprojection_error(2.0) ** 2
+        md = info["model_decrease"]
+        rho = (e0 - e1) / md if md > 0.0 else -1.0
+        accepted = rho > 0.0 and e1 < e0
+        history.append(dict(error=e0, lam=lam, accepted=accepted, pcg_iterations=info["iterations"], status=info["status"]))
+        if accepted:
+            lam *= max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3)
+            nu = 2.0
+            bal9, pts = ba.cameras_bal(), ba.points()
+            e0 = e1
+        else:
+            ba._upload(bal9, True, pts, row_ptr, pt_idx, uv)
+            lam *= nu
+            nu *= 2.0
+    if history:
+        history[-1]["error_after"] = e0
+    return history

@@ -66,6 +66,44 @@ int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_p
                            const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
                            void *stream);
 
+/* ---- damped Gauss-Newton (Levenberg-Marquardt) step: implicit Schur complement + PCG ----
+ * The damped normal equations (J^T J + lambda D) delta = -g of the Jacobian c2b_problem_residual_jacobian gives (same
+ * bal- or state-mode columns, r = projected - observed), solved on the device without storing J, W or S.  H = J^T J has
+ * the diagonal blocks U_c (9x9), V_p (3x3) of c2b_problem_normal_equations and W_cp = sum Jc^T Jp; g = (gc, gp).
+ * Damping: A_l = A + lambda diag(d) for every diagonal block A, d_i = min(max(A_ii, 1e-6), 1e32); lambda finite and > 0.
+ * Reduced camera system S dc = b, S = U_l - W V_l^-1 W^T, b = -gc + W V_l^-1 gp; dp = -V_l^-1 (gp + W^T dc).
+ *
+ * Level 0, asynchronous on `stream`, the inputs of c2b_normal_points_rows / _cameras_rows plus U or V as those fill them:
+ * _points_rows: t_pts [n_pts][3] = V_l,p^-1 (h_p + sum_o Jp_o^T (Jc_o x_c(o))), each point's observations in ascending
+ *   index through the transpose; x_cam [n_cam][9] NULL means 0 (no observation is read), h_pts [n_pts][3] NULL means 0.
+ * _cameras_rows: y_cam [n_cam][9] = U_l,c x_c - sum_o Jc_o^T (Jp_o t_p(o)) over each camera's list; x_cam NULL drops
+ *   the U term.  So S x = cameras(x, points(x, NULL)) and b = -gc - cameras(NULL, points(NULL, gp)).
+ * Deterministic: no float atomics; every sum runs in an order fixed by the problem. */
+int c2b_schur_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                          const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
+                          const double *x_cam, const double *h_pts, double *t_pts, void *stream);
+int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                           const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
+                           const double *t_pts, double *y_cam, void *stream);
+/* Level 1, synchronous; dc [n_cam][9] and dp [n_pts][3] are DEVICE arrays on the problem's device (8-byte aligned).
+ * _solve_step: forms U, gc, V, gp (the passes of c2b_problem_normal_equations) into buffers the problem keeps until its
+ *   observation list changes, then PCG on S from dc = 0 with the block-Jacobi preconditioner U_l,c (9x9 Cholesky): it
+ *   stops when the recurrence residual |b - S x_k| <= rel_tol |b| (status 0), after max_iters iterations (status 1), or
+ *   on a breakdown -- p.Sp <= 0 or a non-finite value -- with dc the last good iterate (status 2).  b = 0: a zero step
+ *   after 0 iterations.  Then dp by back-substitution.  info (may be NULL): iterations, status, rel_residual |r_k| / |b|,
+ *   sum_sq = |r|^2 at the current state and model_decrease = |r|^2 - |r + Jc dc + Jp dp|^2, both summed per observation
+ *   from J.  An empty camera or an unobserved point gets an exact zero.  A problem with a shard set is refused: the
+ *   point-side sums span every rank.  Deterministic: the same problem and arguments give the same bits.
+ * _apply_step: bal9 = (bal mode ? bal9 : to_vec(cam15)) + dc, cam15 rebuilt from it, points += dp (NULL: no change);
+ *   the problem is in bal mode afterwards (apply_step(p, NULL, NULL) takes a state-mode problem there), and every
+ *   cache of the cameras and points is dropped. */
+typedef struct {
+    int32_t iterations, status;
+    double rel_residual, sum_sq, model_decrease;
+} c2b_step_info;
+int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double rel_tol, double *dc, double *dp, c2b_step_info *info);
+int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */

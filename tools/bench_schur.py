@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Time the damped Gauss-Newton step on `synthetic --blocks B` (default 128, the flagship size; observation noise 1e-3)
+and print one JSON line:
+  * the two Schur passes at Level 0 (HIP events), with their algorithmic bytes and fraction of 8 TB/s;
+  * solve_step with 0 iterations -- the set-up (the normal-equation passes, the 9x9 factorisations, b) plus the
+    back-substitution and the model-decrease pass, i.e. everything but PCG;
+  * solve_step with 25 iterations and rel_tol = 0 (a fixed-count solve), and one PCG iteration as the difference / 25;
+  * apply_step.
+The Level-1 calls are synchronous and timed on the host clock; each figure is the median of --reps after --warmup.
+
+    python tools/bench_schur.py [--blocks 128] [--reps 5] [--warmup 1]
+
+Algorithmic bytes (each input read once, each output written once):
+  point pass:  n_obs x (4 obs_of + 4 cam_of + 16 uv) + n_pts x (8 pt_row_ptr + 32 point + 72 V + 24 t) + n_cam x (192 record + 72 x)
+  camera pass: n_obs x (4 pt_idx + 16 uv) + n_pts x (32 point + 24 t) + n_cam x (8 row_ptr + 192 record + 648 U + 72 x + 72 y)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=128)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    a = ap.parse_args()
+    import __graft_entry__ as entry
+    entry.build()
+    import torch
+    from city2ba_amd import device as D
+    from city2ba_amd import noise as N
+    from city2ba_amd import synthetic as S
+    dev = torch.device("cuda", 0)
+    lam = 1e-4
+
+    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, cull=False, mirror=False)   # bench.py's instance
+    N.add_noise(ba, 0.0, 0.0, 0.0, 1e-3, seed=20243)
+    n_cam, n_pts, n = ba._sizes()
+
+    # Level 0 over the same state
+    ex = ba.export_device()
+    camblk = D.cameras_prepare_state(ex["cam15"])
+    pts4, pi, uv = ex["pts4"], ex["pt_idx"], ex["uv"]
+    rows = D.Rows(ex["row_ptr"], n)
+    prows = D.PointRows(rows, pi, n_pts)
+    f64 = dict(dtype=torch.float64, device=dev)
+    U, gc = torch.empty((n_cam, 9, 9), **f64), torch.empty((n_cam, 9), **f64)
+    V, gp = torch.empty((n_pts, 3, 3), **f64), torch.empty((n_pts, 3), **f64)
+    D.normal_cameras_rows(camblk, pts4, rows, pi, uv, U, gc)
+    D.normal_points_rows(camblk, pts4, prows, uv, V, gp)
+    x = torch.randn((n_cam, 9), **f64) * 1e-3
+    t, y = torch.empty((n_pts, 3), **f64), torch.empty((n_cam, 9), **f64)
+
+    def events(fn):
+        for _ in range(a.warmup + 2):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(max(a.reps, 10)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            times.append(e0.elapsed_time(e1) * 1e3)
+        return {"median_us": round(_median(times), 1), "min_us": round(min(times), 1)}
+
+    def wall(fn):
+        for _ in range(a.warmup):
+            fn()
+        times = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fn()
+            times.append((time.perf_counter() - t0) * 1e3)
+        return {"median_ms": round(_median(times), 3), "min_ms": round(min(times), 3)}
+
+    us_p = events(lambda: D.schur_points_rows(camblk, pts4, prows, uv, V, lam, x, None, t))
+    us_c = events(lambda: D.schur_cameras_rows(camblk, pts4, rows, pi, uv, U, lam, x, t, y))
+    bytes_p = n * 24 + n_pts * (8 + 32 + 72 + 24) + n_cam * (192 + 72)
+    bytes_c = n * 20 + n_pts * (32 + 24) + n_cam * (8 + 192 + 648 + 72 + 72)
+    frac = lambda b, us: round(b / (us * 1e-6) / 8e12, 4)
+    del U, gc, V, gp, t, y, x, prows, rows, camblk, ex
+    torch.cuda.empty_cache()
+
+    dc, dp = torch.empty((n_cam, 9), **f64), torch.empty((n_pts, 3), **f64)
+    info = {}
+
+    def solve(k):
+        info[k] = ba.solve_step(lam, max_iters=k, rel_tol=0.0, out=(dc, dp))[2]
+
+    s0 = wall(lambda: solve(0))
+    s25 = wall(lambda: solve(25))
+    zc, zp = torch.zeros_like(dc), torch.zeros_like(dp)
+    ap_ms = wall(lambda: ba.apply_step(zc, zp))
+    out = {
+        "blocks": a.blocks, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts, "lambda": lam,
+        "points_pass": dict(us_p, algorithmic_bytes=bytes_p, frac_of_8TBs=frac(bytes_p, us_p["median_us"])),
+        "cameras_pass": dict(us_c, algorithmic_bytes=bytes_c, frac_of_8TBs=frac(bytes_c, us_c["median_us"])),
+        "both_passes_us": round(us_p["median_us"] + us_c["median_us"], 1),
+        "solve_0_iterations": s0,
+        "solve_25_iterations": s25,
+        "pcg_iteration_ms": round((s25["median_ms"] - s0["median_ms"]) / 25.0, 3),
+        "apply_step": ap_ms,
+        "info_25": info[25],
+    }
+    ba.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
