@@ -1349,14 +1349,15 @@ int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_p
 }
 
 // ---- damped Gauss-Newton step: the implicit Schur complement's passes (schur_kernels.hpp) -----------------------
-static bool good_lambda(double lam) { return std::isfinite(lam) && lam > 0.0; }
+// the damping range: inside it lambda * 1e-6 and lambda * 1e32 (the clamp's ends) stay normal doubles
+static bool good_lambda(double lam) { return lam >= C2B_STEP_LAMBDA_MIN && lam <= C2B_STEP_LAMBDA_MAX; }
 
 int c2b_schur_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
                           const double *x_cam, const double *h_pts, double *t_pts, void *stream) {
     C2B_API_BEGIN
     if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: n_pts out of range");
-    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: lambda must be finite and > 0");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: lambda must lie in [1e-20, 1e32]");
     if (n_pts && (!V || !t_pts || (x_cam && (!camblk || !pts4 || !pt_row_ptr || !obs_of || !cam_of || !uv_obs))))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: NULL argument");
     if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(V) || !aligned8(x_cam) ||
@@ -1383,7 +1384,7 @@ int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint6
     C2B_API_BEGIN
     if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: count out of range");
-    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: lambda must be finite and > 0");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: lambda must lie in [1e-20, 1e32]");
     if (n_cam && (!camblk || !row_ptr || !U || !y_cam)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: NULL argument");
     if (n_obs && (!pts4 || !pt_idx || !uv_obs || !t_pts)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: NULL observation input");
     if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(row_ptr) || !aligned8(U) || !aligned8(x_cam) ||

@@ -629,7 +629,7 @@ static int ensure_solver(c2b_problem *p) {
 int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double rel_tol, double *dc, double *dp, c2b_step_info *info) {
     C2B_API_BEGIN
     if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: problem is NULL");
-    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: lambda must be finite and > 0");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: lambda must lie in [1e-20, 1e32]");
     if (max_iters < 0 || !(rel_tol >= 0.0) || !std::isfinite(rel_tol))
         return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: max_iters must be >= 0 and rel_tol finite and >= 0");
     NEED_UPLOADED(p, "problem_solve_step");
@@ -733,6 +733,15 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     out.rel_residual = bb == 0.0 ? 0.0 : rnorm / bnorm;
     out.sum_sq = h[kScSumSq];
     out.model_decrease = h[kScModel];
+    if (!std::isfinite(out.sum_sq) || !std::isfinite(out.model_decrease) || !std::isfinite(out.rel_residual)) {
+        // a factorisation failed (a pivot <= 0 at the damping's low end) and a NaN reached the step: no step at all
+        HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
+        if (np) HIP_TRY(hipMemsetAsync(dp, 0, sizeof(double) * 3 * (size_t)np, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        out.status = 2;
+        out.rel_residual = 1.0;
+        out.model_decrease = 0.0;
+    }
     if (info) *info = out;
     return C2B_OK;
     C2B_API_END("problem_solve_step")

@@ -1,17 +1,25 @@
 """Levenberg-Marquardt on a resident BAProblem: BAProblem.solve_step (the damped Gauss-Newton step by PCG on the
 cameras' Schur complement, on the device) and apply_step, with Nielsen's update of the damping."""
 
+LAMBDA_MIN, LAMBDA_MAX = 1e-20, 1e32                # the damping c2b_problem_solve_step accepts (C2B_STEP_LAMBDA_MIN / _MAX)
+
+
+def _clamp(lam):
+    return min(max(lam, LAMBDA_MIN), LAMBDA_MAX)
+
 
 def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6):
     """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
     sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
-    and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit).  Returns the
-    history: one dict per iteration -- error (sum |r|^2 before it), lam (the damping it used), accepted, pcg_iterations,
-    status (the solve's) -- and the final sum |r|^2 as the last entry's 'error_after'."""
+    and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit); lam is held
+    in [LAMBDA_MIN, LAMBDA_MAX] throughout.  Returns the history: one dict per iteration -- error (sum |r|^2 before it),
+    lam (the damping it used), accepted, pcg_iterations, status (the solve's) -- and the final sum |r|^2 as the last
+    entry's 'error_after'."""
     ba.apply_step(None, None)                       # bal mode: bal9 is then what the problem holds exactly
     bal9, pts = ba.cameras_bal(), ba.points()
     row_ptr, pt_idx, uv = ba.row_ptr.copy(), ba.pt_idx.copy(), ba.observations()
     nu = 2.0
+    lam = _clamp(lam)
     history = []
     e0 = ba.total_reprojection_error(2.0) ** 2
     for _ in range(int(iterations)):
@@ -23,13 +31,13 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
         accepted = rho > 0.0 and e1 < e0
         history.append(dict(error=e0, lam=lam, accepted=accepted, pcg_iterations=info["iterations"], status=info["status"]))
         if accepted:
-            lam *= max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3)
+            lam = _clamp(lam * max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
             nu = 2.0
             bal9, pts = ba.cameras_bal(), ba.points()
             e0 = e1
         else:
             ba._upload(bal9, True, pts, row_ptr, pt_idx, uv)
-            lam *= nu
+            lam = _clamp(lam * nu)
             nu *= 2.0
     if history:
         history[-1]["error_after"] = e0

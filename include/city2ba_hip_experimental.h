@@ -70,7 +70,9 @@ int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_p
  * The damped normal equations (J^T J + lambda D) delta = -g of the Jacobian c2b_problem_residual_jacobian gives (same
  * bal- or state-mode columns, r = projected - observed), solved on the device without storing J, W or S.  H = J^T J has
  * the diagonal blocks U_c (9x9), V_p (3x3) of c2b_problem_normal_equations and W_cp = sum Jc^T Jp; g = (gc, gp).
- * Damping: A_l = A + lambda diag(d) for every diagonal block A, d_i = min(max(A_ii, 1e-6), 1e32); lambda finite and > 0.
+ * Damping: A_l = A + lambda diag(d) for every diagonal block A, d_i = min(max(A_ii, 1e-6), 1e32); lambda in
+ * [C2B_STEP_LAMBDA_MIN, C2B_STEP_LAMBDA_MAX] (inside it lambda * 1e-6 and lambda * 1e32 stay normal doubles), else
+ * C2B_ERR_INVALID_ARGUMENT.
  * Reduced camera system S dc = b, S = U_l - W V_l^-1 W^T, b = -gc + W V_l^-1 gp; dp = -V_l^-1 (gp + W^T dc).
  *
  * Level 0, asynchronous on `stream`, the inputs of c2b_normal_points_rows / _cameras_rows plus U or V as those fill them:
@@ -79,6 +81,8 @@ int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_p
  * _cameras_rows: y_cam [n_cam][9] = U_l,c x_c - sum_o Jc_o^T (Jp_o t_p(o)) over each camera's list; x_cam NULL drops
  *   the U term.  So S x = cameras(x, points(x, NULL)) and b = -gc - cameras(NULL, points(NULL, gp)).
  * Deterministic: no float atomics; every sum runs in an order fixed by the problem. */
+#define C2B_STEP_LAMBDA_MIN 1e-20
+#define C2B_STEP_LAMBDA_MAX 1e32
 int c2b_schur_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
                           const double *x_cam, const double *h_pts, double *t_pts, void *stream);
@@ -90,7 +94,9 @@ int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint6
  *   observation list changes, then PCG on S from dc = 0 with the block-Jacobi preconditioner U_l,c (9x9 Cholesky): it
  *   stops when the recurrence residual |b - S x_k| <= rel_tol |b| (status 0), after max_iters iterations (status 1), or
  *   on a breakdown -- p.Sp <= 0 or a non-finite value -- with dc the last good iterate (status 2).  b = 0: a zero step
- *   after 0 iterations.  Then dp by back-substitution.  info (may be NULL): iterations, status, rel_residual |r_k| / |b|,
+ *   after 0 iterations.  Then dp by back-substitution.  A step whose model pass is not finite (near the low end of the
+ *   damping range a 3x3 factorisation of a point seen once can fail) is returned as dc = dp = 0 with status 2,
+ *   rel_residual 1 and model_decrease 0.  info (may be NULL): iterations, status, rel_residual |r_k| / |b|,
  *   sum_sq = |r|^2 at the current state and model_decrease = |r|^2 - |r + Jc dc + Jp dp|^2, both summed per observation
  *   from J.  An empty camera or an unobserved point gets an exact zero.  A problem with a shard set is refused: the
  *   point-side sums span every rank.  Deterministic: the same problem and arguments give the same bits.

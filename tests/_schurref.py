@@ -74,10 +74,10 @@ class Problem:
         a = np.zeros((self.n_pts, 3), dtype=self.dtype)
         s = np.zeros((self.n_pts, 3), dtype=self.dtype)
         if h is not None:
-            a += np.asarray(h, dtype=np.float64).astype(self.dtype)
+            a += np.asarray(h).astype(self.dtype)
             s += self.Sgp
         if x is not None:
-            x = np.asarray(x, dtype=np.float64).reshape(self.n_cam, 9).astype(self.dtype)
+            x = np.asarray(x).reshape(self.n_cam, 9).astype(self.dtype)
             xo = x[self.cam]
             np.add.at(a, self.pt, np.einsum("nab,na->nb", self.W, xo))
             np.add.at(s, self.pt, np.einsum("nib,ni->nb", self.aJp, np.einsum("nia,na->ni", self.aJc, np.abs(xo))))
@@ -95,8 +95,8 @@ class Problem:
         s = np.zeros((self.n_cam, 9), dtype=self.dtype)
         np.add.at(s, self.cam, np.einsum("nia,ni->na", self.aJc, np.einsum("nib,nb->ni", self.aJp, np.abs(to) + tscale[self.pt])))
         if h is not None:
-            return wt - np.asarray(h, dtype=np.float64).astype(self.dtype), s + self.Sgc
-        x = np.asarray(x, dtype=np.float64).reshape(self.n_cam, 9).astype(self.dtype)
+            return wt - np.asarray(h).astype(self.dtype), s + self.Sgc
+        x = np.asarray(x).reshape(self.n_cam, 9).astype(self.dtype)
         Ul = self.Ul(lam)
         SUl = self.SU + (Ul - self.U)                                       # the damping adds its own (exact) diagonal
         return np.einsum("cab,cb->ca", Ul, x) - wt, s + np.einsum("cab,cb->ca", SUl, np.abs(x))
@@ -178,3 +178,180 @@ class Problem:
         e = np.einsum("nia,na->ni", self.Jc.astype(LD), dc[self.cam]) + np.einsum("nia,na->ni", self.Jp.astype(LD), dp[self.pt])
         r = self.r.astype(LD)
         return np.sum(r * r) - np.sum((r + e) * (r + e))
+
+
+# ---- PCG, iterate by iterate ----------------------------------------------------------------------------------------
+EPS = 2.0 ** -52
+
+
+def chol_blocks(A):
+    """lower Cholesky factors of a stack of SPD blocks [m, k, k], in A's dtype (longdouble works)"""
+    k = A.shape[1]
+    L = np.zeros_like(A)
+    for j in range(k):
+        L[:, j, j] = np.sqrt(A[:, j, j] - np.sum(L[:, j, :j] * L[:, j, :j], axis=-1))
+        for i in range(j + 1, k):
+            L[:, i, j] = (A[:, i, j] - np.sum(L[:, i, :j] * L[:, j, :j], axis=-1)) / L[:, j, j]
+    return L
+
+
+def chol_inverse(L):
+    """(L L^T)^-1 for a stack of lower factors"""
+    k = L.shape[1]
+    Li = np.zeros_like(L)                                                 # L^-1 by forward substitution
+    for i in range(k):
+        Li[:, i, i] = 1 / L[:, i, i]
+        for j in range(i):
+            Li[:, i, j] = -np.sum(L[:, i, j:i] * Li[:, j:i, j], axis=-1) / L[:, i, i]
+    return np.einsum("mki,mkj->mij", Li, Li)
+
+
+def pcg_loop(ops, max_iters, rel_tol, beta_scale=1.0):
+    """c2b_problem_solve_step's loop over the operations `ops` provides: x0 = 0, r0 = b, z = M^-1 r, p0 = z0,
+    alpha = rz / pq (no update unless pq > 0 and alpha is finite: breakdown, status 2, x the last good iterate),
+    x += alpha p, r -= alpha q, z = M^-1 r, stop when |r_k| <= rel_tol |b| (status 0) or after max_iters (1), else
+    beta = rz_new / rz, p = z + beta p.  Returns dict(xs, rs (the recurrence residual vectors), rel (|r_k| / |b|),
+    status, iterations, rel_residual); xs[k] is the k-th iterate."""
+    b = ops.rhs()
+    x = ops.zeros_like(b)
+    r = b
+    z = ops.precond(r)
+    p = z
+    rr, rz = ops.dot_rr(r, r), ops.dot_rr(r, z)
+    bb = rr
+    bnorm = ops.sqrt(bb)
+    rnorm = bnorm
+    xs, rs, rel = [x], [r], [0.0 if bb == 0 else 1.0]
+    it, status = 0, 1
+    if not (np.isfinite(float(bb)) and np.isfinite(float(rz))):
+        status = 2
+    elif rnorm <= rel_tol * bnorm:
+        status = 0
+    else:
+        while it < max_iters:
+            q = ops.S(p)
+            pq = ops.dot_pq(p, q)
+            alpha = ops.div(rz, pq)
+            if not (pq > 0) or not np.isfinite(float(alpha)):
+                status = 2
+                break
+            x = ops.axpy(x, alpha, p)
+            r = ops.axpy(r, -alpha, q)
+            z = ops.precond(r)
+            it += 1
+            rr, rzn = ops.dot_rr(r, r, loop=True), ops.dot_rr(r, z)
+            if not (np.isfinite(float(rr)) and np.isfinite(float(rzn))):
+                status = 2
+                break
+            rnorm = ops.sqrt(rr)
+            xs.append(x)
+            rs.append(r)
+            rel.append(rnorm / bnorm)
+            if rnorm <= rel_tol * bnorm:
+                status = 0
+                break
+            if it == max_iters:
+                break
+            p = ops.axpy(z, ops.div(rzn, rz) * beta_scale, p)
+            rz = rzn
+    return dict(xs=xs, rs=rs, rel=rel, status=status, iterations=it, rel_residual=0.0 if bb == 0 else rnorm / bnorm)
+
+
+class _LDOps:
+    """the loop's operations in longdouble through the implicit S_times / rhs; with rng, every operator output, vector
+    update and dot product is moved by a random +-(its first-order scale) * 2^-52: one plausible f64 evaluation"""
+
+    def __init__(self, P, lam, Minv, MScale, rng=None):
+        self.P, self.lam, self.Minv, self.MScale, self.rng = P, lam, Minv, MScale, rng
+
+    def _jig(self, v, scale):
+        if self.rng is None:
+            return v
+        s = self.rng.choice(np.array([-1.0, 1.0]), size=np.shape(v)).astype(LD)
+        return v + s * np.asarray(scale, dtype=LD) * LD(EPS)
+
+    def zeros_like(self, v):
+        return np.zeros_like(v)
+
+    def sqrt(self, v):
+        return np.sqrt(v)
+
+    def div(self, a, b):
+        return self._jig(a / b, abs(a / b))
+
+    def rhs(self):
+        b, s = self.P.rhs(self.lam)
+        return self._jig(b, s)
+
+    def S(self, p):
+        y, s = self.P.S_times(self.lam, p)
+        return self._jig(y, s)
+
+    def precond(self, r):
+        z = np.einsum("cab,cb->ca", self.Minv, r)
+        return self._jig(z, np.einsum("cab,cb->ca", self.MScale, np.abs(z)))
+
+    def _dot(self, a, b, loop=False):
+        return self._jig(np.sum(a * b), np.sum(np.abs(a * b)))
+
+    dot_pq = dot_rr = _dot
+
+    def axpy(self, y, a, x):
+        v = y + a * x
+        return self._jig(v, np.abs(y) + np.abs(a * x))
+
+
+def _pcg_ops(P, lam, rng=None):
+    Ul = P.Ul(lam).astype(LD)
+    L = chol_blocks(Ul)
+    Minv = chol_inverse(L)
+    # the first-order scale of a Cholesky solve: (M + dM) z = r with |dM| <= c u |L| |L^T|
+    MScale = np.einsum("cij,cjk->cik", np.abs(Minv), np.einsum("cij,ckj->cik", np.abs(L), np.abs(L)))
+    return _LDOps(P, lam, Minv, MScale, rng)
+
+
+def energy(P, lam, x):
+    """1/2 x^T S x - b^T x (longdouble), the quantity PCG lowers at every iterate"""
+    x = np.asarray(x).reshape(P.n_cam, 9).astype(LD)
+    Sx, _ = P.S_times(lam, x)
+    b, _ = P.rhs(lam)
+    return LD(0.5) * np.sum(x * Sx) - np.sum(b * x)
+
+
+def pcg(P, lam, max_iters, rel_tol, runs=8, seed=0, mult=16.0, floor=1e-13):
+    """The reference PCG on a longdouble Problem: c2b_problem_solve_step restated (pcg_loop) with M = the Cholesky factor
+    of U_l,c per camera.  For every iterate k: x[k], dp[k] (back-substitution of x[k]), rel[k] = |r_k| / |b| and
+    energy[k] = 1/2 x^T S x - b^T x (from the recurrence, -1/2 x^T (b + r)).  `runs` seeded reruns move every operator
+    output and dot product by +-(first-order scale) * 2^-52; the bounds are `mult` x the largest deviation of each
+    quantity from the unperturbed run, with a floor of `floor` x its size (x, dp, energy) or of 4 eps (rel)."""
+    assert P.dtype == LD
+    b, bscale = P.rhs(lam)
+    base = pcg_loop(_pcg_ops(P, lam), max_iters, rel_tol)
+
+    def derived(res, rng=None):
+        xs = res["xs"]
+        dps = [P.back_substitute(lam, x) for x in xs]
+        dps = [d if rng is None else _LDOps(P, lam, None, None, rng)._jig(d, s) for d, s in dps]
+        en = [-LD(0.5) * np.sum(x * (b + r)) for x, r in zip(xs, res["rs"])]
+        return xs, dps, [LD(v) for v in res["rel"]], en
+
+    xs, dps, rel, en = derived(base)
+    n = len(xs)
+    dev = dict(x=np.zeros(n), dp=np.zeros(n), rel=np.zeros(n), energy=np.zeros(n))
+    rng = np.random.default_rng(seed)
+    for _ in range(runs):
+        res = pcg_loop(_pcg_ops(P, lam, rng), max_iters, rel_tol)
+        pxs, pdps, prel, pen = derived(res, rng)
+        m = min(n, len(pxs))
+        for k in range(m):
+            dev["x"][k] = max(dev["x"][k], float(np.linalg.norm((pxs[k] - xs[k]).astype(np.float64))))
+            dev["dp"][k] = max(dev["dp"][k], float(np.linalg.norm((pdps[k] - dps[k]).astype(np.float64))))
+            dev["rel"][k] = max(dev["rel"][k], abs(float(prel[k] - rel[k])))
+            dev["energy"][k] = max(dev["energy"][k], abs(float(pen[k] - en[k])))
+    nx = np.array([float(np.linalg.norm(x.astype(np.float64))) for x in xs])
+    ndp = np.array([float(np.linalg.norm(d.astype(np.float64))) for d in dps])
+    escale = np.array([float(abs(e)) for e in en])
+    bound = dict(x=np.maximum(mult * dev["x"], floor * nx), dp=np.maximum(mult * dev["dp"], floor * ndp),
+                 rel=np.maximum(mult * dev["rel"], 4 * EPS), energy=np.maximum(mult * dev["energy"], floor * escale))
+    return dict(x=xs, dp=dps, rel=rel, energy=en, bound=bound, deviation=dev, status=base["status"],
+                iterations=base["iterations"], rel_residual=base["rel_residual"])

@@ -93,11 +93,23 @@ def _problems():
             return ba, True
         return make
 
+    def mid_grid():                                              # n_cam = 2879: several k_pcg_update workgroups, a
+        from city2ba_amd import synthetic as S                   # partly empty last wave, > 256 p.q and model partials
+        g = S.synthetic_grid(10, 10, 8, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=False)
+        nc = g.num_cameras() - 1
+        rp = g.row_ptr[:nc + 1].copy()
+        no = int(rp[-1])
+        uv = g.observations()[:no] + np.random.default_rng(6).normal(scale=1e-3, size=(no, 2))
+        ba = c2b.BAProblem.from_bal(g.cameras_bal()[:nc], g.points(), rp, g.pt_idx[:no].copy(), uv)
+        g.close()
+        return ba, True
+
     return [("random bal", rand_bal), ("random state", rand_state), ("mixed k2", k2), ("grid culled", grid(True)),
-            ("grid", grid(False)), ("small grid culled", small_grid(True)), ("small grid", small_grid(False))]
+            ("grid", grid(False)), ("small grid culled", small_grid(True)), ("small grid", small_grid(False)),
+            ("mid grid", mid_grid)]
 
 
-PROBLEMS = ["random bal", "random state", "mixed k2", "grid culled", "grid"]
+PROBLEMS = ["random bal", "random state", "mixed k2", "grid culled", "grid", "mid grid"]
 
 
 
