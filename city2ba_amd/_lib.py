@@ -28,6 +28,21 @@ _d = C.c_double
 _int = C.c_int
 
 
+# robust losses of the step (c2b_problem_set_loss): name -> kind; None and "squared" are the squared loss
+LOSS_KINDS = {None: 0, "squared": 0, "huber": 1, "cauchy": 2, "soft_l1": 3}
+LOSS_NAMES = {0: None, 1: "huber", 2: "cauchy", 3: "soft_l1"}
+
+
+def loss_kind(loss):
+    """the C ABI's kind of a loss given by name (or None, or the kind itself)"""
+    if isinstance(loss, int) and not isinstance(loss, bool):
+        return loss
+    try:
+        return LOSS_KINDS[loss]
+    except (KeyError, TypeError):
+        raise ValueError("loss must be None, 'huber', 'cauchy' or 'soft_l1', not %r" % (loss,))
+
+
 class StepInfo(C.Structure):
     """c2b_step_info (include/city2ba_hip_experimental.h)"""
     _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("rel_residual", C.c_double), ("sum_sq", C.c_double),
@@ -91,6 +106,13 @@ SIGNATURES = {
     "c2b_schur_cameras_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _d, _vp, _vp, _vp, _vp]),
     "c2b_problem_solve_step": (_int, [_vp, _d, _int, _d, _vp, _vp, _vp]),
     "c2b_problem_apply_step": (_int, [_vp, _vp, _vp]),
+    "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
+    "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
+    "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),
+    "c2b_normal_cameras_rows_loss": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _d, _vp]),
+    "c2b_normal_points_rows_loss": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _d, _vp]),
+    "c2b_schur_points_rows_loss": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _int, _d, _vp]),
+    "c2b_schur_cameras_rows_loss": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _d, _vp, _vp, _vp, _int, _d, _vp]),
     "c2b_visibility_pairs": (_int, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_visibility_dense_tiles": (_i64, [_i64]),
     "c2b_visibility_dense_count": (_int, [_vp, _i64, _vp, _i64, _d, _vp, _vp, _vp, _vp]),

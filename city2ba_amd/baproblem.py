@@ -280,6 +280,28 @@ class BAProblem:
         L.check(L.lib().c2b_problem_normal_equations(self._h, ptr(U), ptr(gc), ptr(V), ptr(gp), C.byref(s)))
         return U, gc, V, gp, s.value
 
+    def set_loss(self, kind, scale=1.0):
+        """The robust loss of normal_equations / solve_step / robust_cost (c2b_problem_set_loss): "huber", "cauchy" or
+        "soft_l1" with its scale a > 0 (Ceres' definitions, in the units of the residuals), or None for the squared loss.
+        Under a loss the step is one of iteratively reweighted least squares: every observation's (r, Jc, Jp) is scaled by
+        sqrt(w), w = rho'(|r|^2) at the current state; sum_sq and model_decrease are then the weighted quantities, and
+        robust_cost() is what a loop minimises.  The loss belongs to the handle: uploads and culls keep it."""
+        L.check(L.lib().c2b_problem_set_loss(self._h, L.loss_kind(kind), float(scale)))
+
+    @property
+    def loss(self):
+        """(name, scale) of the loss in force; (None, 1.0) is the squared loss"""
+        k, a = C.c_int(), C.c_double()
+        L.check(L.lib().c2b_problem_get_loss(self._h, C.byref(k), C.byref(a)))
+        return L.LOSS_NAMES[k.value], a.value
+
+    def robust_cost(self):
+        """sum rho(|r|^2) over the observations under the problem's loss, on the device (c2b_problem_robust_cost); with
+        the squared loss, sum |r|^2"""
+        s = C.c_double()
+        L.check(L.lib().c2b_problem_robust_cost(self._h, C.byref(s)))
+        return s.value
+
     def solve_step(self, lam, max_iters=100, rel_tol=1e-6, out=None):
         """One damped Gauss-Newton (Levenberg-Marquardt) step on the device (c2b_problem_solve_step): the solution of
         (J^T J + lam D) delta = -g, D = diag(min(max(diag(J^T J), 1e-6), 1e32)), by PCG on the Schur complement of the

@@ -1294,10 +1294,15 @@ int c2b_normal_transpose(const uint64_t *row_ptr, int64_t n_cam, const uint32_t 
 
 static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
-int c2b_normal_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
-                            const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
-                            void *workspace, double *sum_sq, void *stream) {
-    C2B_API_BEGIN
+// a robust loss's arguments: kind 0 squared (scale ignored), 1 Huber, 2 Cauchy, 3 soft-L1; scale a > 0
+static bool good_loss(int kind, double scale) { return kind == 0 || (kind >= 1 && kind <= 3 && std::isfinite(scale) && scale > 0.0); }
+#define NEED_LOSS(kind, scale, who) \
+    if (!good_loss(kind, scale)) return fail(C2B_ERR_INVALID_ARGUMENT, who ": loss kind must be 0..3 and its scale finite and > 0")
+
+// the *_rows entries and their *_loss twins: kind 0 launches the squared-loss kernels, any other kind the weighted ones
+static int normal_cameras_rows_impl(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                                    const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
+                                    void *workspace, double *sum_sq, int kind, double scale, void *stream) {
     if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
         return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: count out of range");
     if (sum_sq && !workspace) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: sum_sq needs a workspace");
@@ -1315,7 +1320,18 @@ int c2b_normal_cameras_rows(const double *camblk, const double *pts4, const uint
     const unsigned grid = (unsigned)((quads + waves - 1) / waves < kNormMaxGrid ? (quads + waves - 1) / waves : kNormMaxGrid);
     const double4 *p4 = reinterpret_cast<const double4 *>(pts4);
     const double2 *uv = reinterpret_cast<const double2 *>(uv_obs);
-    if (sum_sq) {
+    if (kind != kLossSquared) {
+        const double a2 = scale * scale;
+        hipLaunchKernelGGL(k_normal_cameras_loss, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv, U, gc,
+                           kind, a2);
+        if (sum_sq) {                                        // the weighted sum of squares: a pass of its own (see k_robust_cost)
+            double *block_part = reinterpret_cast<double *>(workspace) + kWsBlockPart;
+            const unsigned nb = blocks_for(n_obs, kNormBlock);   // <= block_part_slots(n_obs): one partial per 4 tiles of 64
+            if (nb) hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, st, camblk, p4, (const uint32_t *)nullptr, row_ptr,
+                                       (int)n_cam, pt_idx, uv, n_obs, kind, a2, block_part);
+            hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)block_part, (int)nb, sum_sq);
+        }
+    } else if (sum_sq) {
         double *block_part = reinterpret_cast<double *>(workspace) + kWsBlockPart;
         hipLaunchKernelGGL(k_normal_cameras<true>, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv,
                            U, gc, block_part);
@@ -1326,13 +1342,28 @@ int c2b_normal_cameras_rows(const double *camblk, const double *pts4, const uint
     }
     LAUNCH_CHECK();
     return C2B_OK;
+}
+
+int c2b_normal_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                            const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
+                            void *workspace, double *sum_sq, void *stream) {
+    C2B_API_BEGIN
+    return normal_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, gc, workspace, sum_sq, 0, 1.0, stream);
     C2B_API_END("normal_cameras_rows")
 }
 
-int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
-                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
-                           void *stream) {
+int c2b_normal_cameras_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                                 const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
+                                 void *workspace, double *sum_sq, int kind, double scale, void *stream) {
     C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "normal_cameras_rows_loss");
+    return normal_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, gc, workspace, sum_sq, kind, scale, stream);
+    C2B_API_END("normal_cameras_rows_loss")
+}
+
+static int normal_points_rows_impl(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                                   const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
+                                   int kind, double scale, void *stream) {
     if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: n_pts out of range");
     if (n_pts && (!camblk || !pts4 || !pt_row_ptr || !obs_of || !cam_of || !uv_obs || !V || !gp))
         return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: NULL argument");
@@ -1340,22 +1371,42 @@ int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_p
         (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: misaligned pointer");
     if (!n_pts) return C2B_OK;
-    hipLaunchKernelGGL(k_normal_points, dim3((unsigned)((n_pts + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0, S(stream), camblk,
-                       reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of, reinterpret_cast<const double2 *>(uv_obs),
-                       V, gp);
+    if (kind != kLossSquared)
+        hipLaunchKernelGGL(k_normal_points_loss, dim3((unsigned)((n_pts + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0, S(stream),
+                           camblk, reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
+                           reinterpret_cast<const double2 *>(uv_obs), V, gp, kind, scale * scale);
+    else
+        hipLaunchKernelGGL(k_normal_points, dim3((unsigned)((n_pts + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0, S(stream), camblk,
+                           reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
+                           reinterpret_cast<const double2 *>(uv_obs), V, gp);
     LAUNCH_CHECK();
     return C2B_OK;
+}
+
+int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
+                           void *stream) {
+    C2B_API_BEGIN
+    return normal_points_rows_impl(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, gp, 0, 1.0, stream);
     C2B_API_END("normal_points_rows")
+}
+
+int c2b_normal_points_rows_loss(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                                const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
+                                int kind, double scale, void *stream) {
+    C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "normal_points_rows_loss");
+    return normal_points_rows_impl(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, gp, kind, scale, stream);
+    C2B_API_END("normal_points_rows_loss")
 }
 
 // ---- damped Gauss-Newton step: the implicit Schur complement's passes (schur_kernels.hpp) -----------------------
 // the damping range: inside it lambda * 1e-6 and lambda * 1e32 (the clamp's ends) stay normal doubles
 static bool good_lambda(double lam) { return lam >= C2B_STEP_LAMBDA_MIN && lam <= C2B_STEP_LAMBDA_MAX; }
 
-int c2b_schur_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
-                          const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
-                          const double *x_cam, const double *h_pts, double *t_pts, void *stream) {
-    C2B_API_BEGIN
+static int schur_points_rows_impl(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                                  const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
+                                  const double *x_cam, const double *h_pts, double *t_pts, int kind, double scale, void *stream) {
     if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: n_pts out of range");
     if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: lambda must lie in [1e-20, 1e32]");
     if (n_pts && (!V || !t_pts || (x_cam && (!camblk || !pts4 || !pt_row_ptr || !obs_of || !cam_of || !uv_obs))))
@@ -1364,12 +1415,34 @@ int c2b_schur_points_rows(const double *camblk, const double *pts4, int64_t n_pt
         !aligned8(h_pts) || !aligned8(t_pts) || (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: misaligned pointer");
     if (!n_pts) return C2B_OK;
-    hipLaunchKernelGGL(k_schur_points<false>, dim3(blocks_for(n_pts, kSchurBlock)), dim3(kSchurBlock), 0, S(stream), camblk,
-                       reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of, reinterpret_cast<const double2 *>(uv_obs),
-                       V, lambda, x_cam, h_pts, t_pts);
+    if (kind != kLossSquared)
+        hipLaunchKernelGGL(k_schur_points_loss<false>, dim3(blocks_for(n_pts, kSchurBlock)), dim3(kSchurBlock), 0, S(stream), camblk,
+                           reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
+                           reinterpret_cast<const double2 *>(uv_obs), V, lambda, x_cam, h_pts, t_pts, kind, scale * scale);
+    else
+        hipLaunchKernelGGL(k_schur_points<false>, dim3(blocks_for(n_pts, kSchurBlock)), dim3(kSchurBlock), 0, S(stream), camblk,
+                           reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
+                           reinterpret_cast<const double2 *>(uv_obs), V, lambda, x_cam, h_pts, t_pts);
     LAUNCH_CHECK();
     return C2B_OK;
+}
+
+int c2b_schur_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                          const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
+                          const double *x_cam, const double *h_pts, double *t_pts, void *stream) {
+    C2B_API_BEGIN
+    return schur_points_rows_impl(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, lambda, x_cam, h_pts, t_pts, 0, 1.0, stream);
     C2B_API_END("schur_points_rows")
+}
+
+int c2b_schur_points_rows_loss(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                               const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
+                               const double *x_cam, const double *h_pts, double *t_pts, int kind, double scale, void *stream) {
+    C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "schur_points_rows_loss");
+    return schur_points_rows_impl(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, lambda, x_cam, h_pts, t_pts, kind, scale,
+                                  stream);
+    C2B_API_END("schur_points_rows_loss")
 }
 
 // grid of k_schur_cameras: one wave per kNormCamsPerWave cameras
@@ -1378,10 +1451,9 @@ static unsigned schur_cameras_grid(int64_t n_cam) {
     return (unsigned)((quads + waves - 1) / waves);
 }
 
-int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
-                           const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
-                           const double *t_pts, double *y_cam, void *stream) {
-    C2B_API_BEGIN
+static int schur_cameras_rows_impl(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                                   const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
+                                   const double *t_pts, double *y_cam, int kind, double scale, void *stream) {
     if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: count out of range");
     if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: lambda must lie in [1e-20, 1e32]");
@@ -1391,7 +1463,17 @@ int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint6
         !aligned8(t_pts) || !aligned8(y_cam) || (reinterpret_cast<uintptr_t>(pt_idx) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: misaligned pointer");
     if (!n_cam) return C2B_OK;
-    if (x_cam)
+    if (kind != kLossSquared) {
+        const double a2 = scale * scale;
+        if (x_cam)
+            hipLaunchKernelGGL(k_schur_cameras_loss<kSchurApply>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
+                               reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
+                               U, lambda, x_cam, (const double *)nullptr, t_pts, y_cam, (double *)nullptr, kind, a2);
+        else
+            hipLaunchKernelGGL(k_schur_cameras_loss<kSchurNoX>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
+                               reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
+                               U, lambda, (const double *)nullptr, (const double *)nullptr, t_pts, y_cam, (double *)nullptr, kind, a2);
+    } else if (x_cam)
         hipLaunchKernelGGL(k_schur_cameras<kSchurApply>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
                            reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
                            U, lambda, x_cam, nullptr, t_pts, y_cam, nullptr);
@@ -1401,5 +1483,21 @@ int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint6
                            U, lambda, nullptr, nullptr, t_pts, y_cam, nullptr);
     LAUNCH_CHECK();
     return C2B_OK;
+}
+
+int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                           const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
+                           const double *t_pts, double *y_cam, void *stream) {
+    C2B_API_BEGIN
+    return schur_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, lambda, x_cam, t_pts, y_cam, 0, 1.0, stream);
     C2B_API_END("schur_cameras_rows")
+}
+
+int c2b_schur_cameras_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                                const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
+                                const double *t_pts, double *y_cam, int kind, double scale, void *stream) {
+    C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "schur_cameras_rows_loss");
+    return schur_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, lambda, x_cam, t_pts, y_cam, kind, scale, stream);
+    C2B_API_END("schur_cameras_rows_loss")
 }

@@ -18,6 +18,10 @@ struct c2b_problem {
     // shard_n_cam_global (< 0: not a shard), its first observation is observation shard_obs_base of the whole list
     int64_t shard_cam_base = 0, shard_n_cam_global = -1, shard_obs_base = 0;
     c2b_problem_options opt{0, 0, 0, 0, 0, 0, -1};   // c2b_problem_set_options; survives uploads / reads (it is the handle's, not the data's)
+    // c2b_problem_set_loss: the robust loss of normal_equations / solve_step / robust_cost (0 squared, 1 Huber, 2 Cauchy,
+    // 3 soft-L1) and its scale; the handle's too
+    int loss_kind = 0;
+    double loss_scale = 1.0;
     bool bal_valid = false;     // bal9 still describes the cameras (no mutation since upload_bal)
     bool blk_valid = false;     // camblk matches cam15 (and bal_valid mode)
     bool bal9_fresh = false;    // !bal_valid, but bal9 holds to_vec of the current cameras (the last write / download_bal computed it)
@@ -540,6 +544,64 @@ static int ensure_transpose(c2b_problem *p) {
     return C2B_OK;
 }
 
+// ---- robust loss -----------------------------------------------------------------------------------------
+int c2b_problem_set_loss(c2b_problem *p, int kind, double scale) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_loss: problem is NULL");
+    NEED_LOSS(kind, scale, "problem_set_loss");
+    p->loss_kind = kind;
+    p->loss_scale = kind == kLossSquared ? 1.0 : scale;
+    return C2B_OK;
+    C2B_API_END("problem_set_loss")
+}
+
+int c2b_problem_get_loss(const c2b_problem *p, int *kind, double *scale) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_loss: problem is NULL");
+    if (kind) *kind = p->loss_kind;
+    if (scale) *scale = p->loss_scale;
+    return C2B_OK;
+    C2B_API_END("problem_get_loss")
+}
+
+// sum over the observations of rho(s) (weighted_sq: of w s) under the problem's loss into out[0] (device), asynchronous;
+// one partial per workgroup of 256 observations: the workspace holds one per 4 tiles of 64 (block_part_slots)
+static int robust_sum(c2b_problem *p, bool weighted_sq, double *out) {
+    const int rc = ensure_camblk(p);
+    if (rc) return rc;
+    static_assert(kNormBlock == 256, "k_robust_cost's partials are sized by block_part_slots");
+    const unsigned nb = blocks_for(p->n_obs, kNormBlock);
+    double *part = reinterpret_cast<double *>(p->ws) + kWsBlockPart;
+    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4);
+    const double2 *uv = reinterpret_cast<const double2 *>(p->uv);
+    const double a2 = p->loss_scale * p->loss_scale;
+    if (weighted_sq)
+        hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, p->stream, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                           (const uint64_t *)nullptr, 0, (const uint32_t *)p->pt_idx, uv, p->n_obs, p->loss_kind, a2, part);
+    else
+        hipLaunchKernelGGL(k_robust_cost<false>, dim3(nb), dim3(kNormBlock), 0, p->stream, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                           (const uint64_t *)nullptr, 0, (const uint32_t *)p->pt_idx, uv, p->n_obs, p->loss_kind, a2, part);
+    hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, p->stream, (const double *)part, (int)nb, out);
+    HIP_TRY(launch_error());
+    return C2B_OK;
+}
+
+int c2b_problem_robust_cost(c2b_problem *p, double *cost) {
+    C2B_API_BEGIN
+    if (!p || !cost) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_robust_cost: NULL argument");
+    NEED_UPLOADED(p, "problem_robust_cost");
+    double s = 0.0;
+    if (p->n_obs) {
+        const int rc = robust_sum(p, false, p->scalar);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(&s, p->scalar, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    *cost = s;
+    return C2B_OK;
+    C2B_API_END("problem_robust_cost")
+}
+
 int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *V, double *gp, double *sum_sq) {
     C2B_API_BEGIN
     if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: problem is NULL");
@@ -552,12 +614,15 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
     if (rc) return rc;
     const bool want_sum = sum_sq != nullptr;
     if (U) {
-        rc = c2b_normal_cameras_rows(p->camblk, p->pts4, p->n_obs ? p->rows_ptr : nullptr, p->n_obs ? p->n_cam : 0, p->pt_idx, p->uv,
-                                     p->n_obs, U, gc, want_sum ? p->ws : nullptr, want_sum ? p->scalar : nullptr, p->stream);
+        rc = normal_cameras_rows_impl(p->camblk, p->pts4, p->n_obs ? p->rows_ptr : nullptr, p->n_obs ? p->n_cam : 0, p->pt_idx, p->uv,
+                                      p->n_obs, U, gc, want_sum ? p->ws : nullptr, want_sum ? p->scalar : nullptr, p->loss_kind,
+                                      p->loss_scale, p->stream);
         if (!rc && !p->n_obs && p->n_cam) {                   // no list: every camera's block is empty
             HIP_TRY(hipMemsetAsync(U, 0, sizeof(double) * 81 * (size_t)p->n_cam, p->stream));
             HIP_TRY(hipMemsetAsync(gc, 0, sizeof(double) * 9 * (size_t)p->n_cam, p->stream));
         }
+    } else if (want_sum && p->loss_kind != kLossSquared && p->n_obs) {
+        rc = robust_sum(p, true, p->scalar);                 // the weighted sum of squares without the blocks
     } else if (want_sum) {
         rc = p->n_obs ? c2b_reprojection_error_sum_rows(p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->rows_tiles, p->pt_idx, p->uv,
                                                         p->n_obs, 2.0, p->ws, p->scalar, p->stream)
@@ -568,7 +633,8 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
     if (V && p->n_pts) {
         if (p->n_obs) {
             rc = ensure_transpose(p);
-            if (!rc) rc = c2b_normal_points_rows(p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, V, gp, p->stream);
+            if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, V, gp, p->loss_kind,
+                                                  p->loss_scale, p->stream);
             if (rc) return rc;
         } else {
             HIP_TRY(hipMemsetAsync(V, 0, sizeof(double) * 9 * (size_t)p->n_pts, p->stream));
@@ -657,8 +723,16 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     const double2 *uv = reinterpret_cast<const double2 *>(p->uv);
     const unsigned cgrid = schur_cameras_grid(nc), nbc = blocks_for(nc, kSchurBlock), nbo = blocks_for(no, kSchurBlock);
     const int n_cpart = (int)(cgrid * (kNormBlock / 64));
+    const int kind = p->loss_kind;                           // 0: every launch below is the squared-loss kernel it always was
+    const double a2 = p->loss_scale * p->loss_scale;
     auto points = [&](const double *x, const double *h, double *t, bool neg) {
-        if (neg)
+        if (kind != kLossSquared && neg)
+            hipLaunchKernelGGL(k_schur_points_loss<true>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
+                               p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, kind, a2);
+        else if (kind != kLossSquared)
+            hipLaunchKernelGGL(k_schur_points_loss<false>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
+                               p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, kind, a2);
+        else if (neg)
             hipLaunchKernelGGL(k_schur_points<true>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
                                p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t);
         else
@@ -674,13 +748,19 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     };
 
     // U, gc, V, gp; the preconditioner; b = -gc + W V_l^-1 gp into r
-    rc = c2b_normal_cameras_rows(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.gc, nullptr, nullptr, st);
-    if (!rc) rc = c2b_normal_points_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, B.gp, st);
+    rc = normal_cameras_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.gc, nullptr, nullptr, kind,
+                                  p->loss_scale, st);
+    if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, B.gp, kind, p->loss_scale, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
     points(nullptr, B.gp, B.t, false);
-    hipLaunchKernelGGL(k_schur_cameras<kSchurRhs>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc, p->pt_idx,
-                       uv, (const double *)B.U, lambda, nullptr, (const double *)B.gc, (const double *)B.t, B.r, nullptr);
+    if (kind != kLossSquared)
+        hipLaunchKernelGGL(k_schur_cameras_loss<kSchurRhs>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
+                           p->pt_idx, uv, (const double *)B.U, lambda, (const double *)nullptr, (const double *)B.gc, (const double *)B.t,
+                           B.r, (double *)nullptr, kind, a2);
+    else
+        hipLaunchKernelGGL(k_schur_cameras<kSchurRhs>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc, p->pt_idx,
+                           uv, (const double *)B.U, lambda, nullptr, (const double *)B.gc, (const double *)B.t, B.r, nullptr);
     hipLaunchKernelGGL(k_pcg_update<true>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc, 0, dc,
                        B.r, B.pv, (const double *)nullptr, B.z, B.pa, B.pb);
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbc, B.sc + kScRr);
@@ -699,9 +779,14 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
         while (it < max_iters) {
             const int cur = (it & 1) ? kScRz1 : kScRz0, nxt = (it & 1) ? kScRz0 : kScRz1;
             points(B.pv, nullptr, B.t, false);
-            hipLaunchKernelGGL(k_schur_cameras<kSchurDot>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
-                               p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv, (const double *)nullptr,
-                               (const double *)B.t, B.q, B.pa);
+            if (kind != kLossSquared)
+                hipLaunchKernelGGL(k_schur_cameras_loss<kSchurDot>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
+                                   p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv, (const double *)nullptr,
+                                   (const double *)B.t, B.q, B.pa, kind, a2);
+            else
+                hipLaunchKernelGGL(k_schur_cameras<kSchurDot>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
+                                   p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv, (const double *)nullptr,
+                                   (const double *)B.t, B.q, B.pa);
             hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, n_cpart, B.sc + kScPq);
             hipLaunchKernelGGL(k_pcg_update<false>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc,
                                cur, dc, B.r, B.pv, (const double *)B.q, B.z, B.pa, B.pb);
@@ -723,8 +808,12 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
 
     // dp = -V_l^-1 (gp + W^T dc); then |r|^2 and the model decrease from J, per observation
     points(dc, B.gp, dp, true);
-    hipLaunchKernelGGL(k_schur_model, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
-                       (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb);
+    if (kind != kLossSquared)
+        hipLaunchKernelGGL(k_schur_model_loss, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                           (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb, kind, a2);
+    else
+        hipLaunchKernelGGL(k_schur_model, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                           (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb);
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbo, B.sc + kScSumSq);
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pb, (int)nbo, B.sc + kScModel);
     if ((rc = fetch(kScModel + 1))) return rc;

@@ -12,6 +12,8 @@
 //   * k_schur_model: ||r||^2 and ||r||^2 - ||r + Jc dc + Jp dp||^2 per observation, one partial per workgroup.
 // Damping (Marquardt with Ceres' clamps): A_l = A + lambda diag(d), d_i = min(max(A_ii, 1e-6), 1e32).
 // Every partial is summed by k_normal_sum in a fixed order; no float atomics, so the same inputs give the same bits.
+// Robust losses (k_*_loss): the passes over the observations scale (r, Jc, Jp) by sqrt(w) right after jacobian_obs
+// (loss_scale_obs, normal_kernels.hpp); each is a copy of its squared-loss kernel's text with that line added.
 #pragma once
 #include "normal_kernels.hpp"
 
@@ -84,6 +86,55 @@ __global__ __launch_bounds__(kSchurBlock) void k_schur_points(
     t[3 * p + 2] = NEG ? -t2 : t2;
 }
 
+// its weighted twin (a copy: see k_normal_cameras_loss in normal_kernels.hpp)
+template <bool NEG>
+__global__ __launch_bounds__(kSchurBlock) void k_schur_points_loss(
+    const double *__restrict__ camblk, const double4 *__restrict__ pts4, int64_t n_pts, const uint64_t *__restrict__ pt_row_ptr,
+    const uint32_t *__restrict__ obs_of, const uint32_t *__restrict__ cam_of, const double2 *__restrict__ uv_obs,
+    const double *__restrict__ V, double lam, const double *__restrict__ x, const double *__restrict__ h, double *__restrict__ t,
+    int kind, double la2) {
+    const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (p >= n_pts) return;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    if (h) { a0 = h[3 * p]; a1 = h[3 * p + 1]; a2 = h[3 * p + 2]; }
+    if (x) {
+        const uint64_t b = pt_row_ptr[p], e = pt_row_ptr[p + 1];
+        if (e > b) {
+            const double4 X = pts4[p];
+            for (uint64_t j = b; j < e; ++j) {
+                const uint32_t o = obs_of[j], c = cam_of[j];
+                double r0, r1, jc[18], jp[6];
+                jacobian_obs(cam_ref(camblk, c), X, uv_obs[o], r0, r1, jc, jp);
+                loss_scale_obs(kind, la2, r0, r1, jc, jp);
+                const double *xc = x + (int64_t)c * 9;
+                double z0 = 0.0, z1 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    const double xk = xc[k];
+                    z0 += jc[k] * xk;
+                    z1 += jc[9 + k] * xk;
+                }
+                a0 += jp[0] * z0 + jp[3] * z1;
+                a1 += jp[1] * z0 + jp[4] * z1;
+                a2 += jp[2] * z0 + jp[5] * z1;
+            }
+        }
+    }
+    // V_l = L L^T, L in registers (the reciprocals of its diagonal)
+    const double *Vp = V + p * 9;
+    const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
+    const double i0 = 1.0 / sqrt(v00);
+    const double l10 = v10 * i0, l20 = v20 * i0;
+    const double i1 = 1.0 / sqrt(v11 - l10 * l10);
+    const double l21 = (v21 - l20 * l10) * i1;
+    const double i2 = 1.0 / sqrt((v22 - l20 * l20) - l21 * l21);
+    const double y0 = a0 * i0, y1 = (a1 - l10 * y0) * i1, y2 = ((a2 - l20 * y0) - l21 * y1) * i2;
+    const double t2 = y2 * i2, t1 = (y1 - l21 * t2) * i1, t0 = ((y0 - l10 * t1) - l20 * t2) * i0;
+    t[3 * p] = NEG ? -t0 : t0;
+    t[3 * p + 1] = NEG ? -t1 : t1;
+    t[3 * p + 2] = NEG ? -t2 : t2;
+}
+
 // ---- camera pass ---------------------------------------------------------------------------------------------
 // s_c = sum_o Jc_o^T (Jp_o t_p(o)) over the camera's list, then
 //   kSchurApply: y_c = U_l,c x_c - s_c;  kSchurNoX: y_c = -s_c (x unused);  kSchurDot: as kSchurApply, and sum_c x_c . y_c
@@ -110,6 +161,71 @@ __global__ __launch_bounds__(kNormBlock) void k_schur_cameras(
         const uint32_t pi = pt_idx[o];
         double r0, r1, jc[18], jp[6];
         jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
+        const double *tp = t + (int64_t)pi * 3;
+        const double t0 = tp[0], t1 = tp[1], t2 = tp[2];
+        const double z0 = (jp[0] * t0 + jp[1] * t1) + jp[2] * t2;
+        const double z1 = (jp[3] * t0 + jp[4] * t1) + jp[5] * t2;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s[k] += jc[k] * z0 + jc[9 + k] * z1;
+    }
+    // fixed xor tree over the group's 16 lanes (every lane ends with the same bits)
+#pragma unroll
+    for (int off = kNormG / 2; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s[k] += __shfl_xor(s[k], off, 64);
+    }
+    double sg = 0.0;                                                 // s[gl] without a dynamically indexed register array
+#pragma unroll
+    for (int k = 0; k < 9; ++k) sg = gl == k ? s[k] : sg;
+    double yg = 0.0, xg = 0.0;
+    if (cam_ok && gl < 9) {
+        if (MODE == kSchurRhs) {
+            yg = sg - h[(int64_t)c * 9 + gl];
+        } else {
+            double ux = 0.0;
+            if (MODE != kSchurNoX) {
+                const double *Ur = U + (int64_t)c * 81 + gl * 9, *xc = x + (int64_t)c * 9;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    const double u = Ur[k];
+                    ux += (k == gl ? damped(u, lam) : u) * xc[k];
+                }
+                xg = xc[gl];
+            }
+            yg = ux - sg;
+        }
+        y[(int64_t)c * 9 + gl] = yg;
+    }
+    if (MODE == kSchurDot) {                                         // the wave's x.y: its four cameras, in a fixed tree
+        const double w = wave_sum(xg * yg);                          // 0 on lanes gl >= 9 and past n_cam
+        if (lane == 0) block_part[q] = w;
+    }
+}
+
+// its weighted twin, one instance per mode (a copy: see k_normal_cameras_loss; shared through a C2B_DEV body the
+// squared-loss instances changed registers, 110 -> 128 VGPRs in kSchurApply)
+template <int MODE>
+__global__ __launch_bounds__(kNormBlock) void k_schur_cameras_loss(
+    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
+    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const double *__restrict__ U, double lam,
+    const double *__restrict__ x, const double *__restrict__ h, const double *__restrict__ t, double *__restrict__ y,
+    double *__restrict__ block_part, int kind, double la2) {
+    constexpr int kWaves = kNormBlock / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
+    const int q = (int)blockIdx.x * kWaves + wave;                   // one wave per kNormCamsPerWave cameras, no grid-stride loop
+    const int c = q * kNormCamsPerWave + grp;
+    const bool cam_ok = c < n_cam;
+    const uint64_t b = cam_ok ? row_ptr[c] : 0, e = cam_ok ? row_ptr[c + 1] : 0;
+    const CamRef cam = cam_ref(camblk, cam_ok ? (uint32_t)c : 0u);
+    double s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = 0.0;
+#pragma unroll 1
+    for (uint64_t o = b + gl; o < e; o += kNormG) {
+        const uint32_t pi = pt_idx[o];
+        double r0, r1, jc[18], jp[6];
+        jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
+        loss_scale_obs(kind, la2, r0, r1, jc, jp);
         const double *tp = t + (int64_t)pi * 3;
         const double t0 = tp[0], t1 = tp[1], t2 = tp[2];
         const double z0 = (jp[0] * t0 + jp[1] * t1) + jp[2] * t2;
@@ -273,6 +389,38 @@ __global__ __launch_bounds__(kSchurBlock) void k_schur_model(
         const uint32_t c = cam_idx[o], pi = pt_idx[o];
         double r0, r1, jc[18], jp[6];
         jacobian_obs(cam_ref(camblk, c), pts4[pi], uv_obs[o], r0, r1, jc, jp);
+        const double *dcc = dc + (int64_t)c * 9, *dpp = dp + (int64_t)pi * 3;
+        double e0 = 0.0, e1 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            e0 += jc[k] * dcc[k];
+            e1 += jc[9 + k] * dcc[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            e0 += jp[k] * dpp[k];
+            e1 += jp[3 + k] * dpp[k];
+        }
+        sq = r0 * r0 + r1 * r1;
+        md = -((2.0 * r0 + e0) * e0 + (2.0 * r1 + e1) * e1);
+    }
+    block_sum_to(sq, sRed[0], part_sq + blockIdx.x);
+    block_sum_to(md, sRed[1], part_md + blockIdx.x);
+}
+
+// its weighted twin (a copy): of the reweighted r and e, so w |r|^2 and -w (2r + e).e -- what the step modelled
+__global__ __launch_bounds__(kSchurBlock) void k_schur_model_loss(
+    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint32_t *__restrict__ cam_idx,
+    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, int64_t n_obs, const double *__restrict__ dc,
+    const double *__restrict__ dp, double *__restrict__ part_sq, double *__restrict__ part_md, int kind, double la2) {
+    __shared__ double sRed[2][4];
+    const int64_t o = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    double sq = 0.0, md = 0.0;
+    if (o < n_obs) {
+        const uint32_t c = cam_idx[o], pi = pt_idx[o];
+        double r0, r1, jc[18], jp[6];
+        jacobian_obs(cam_ref(camblk, c), pts4[pi], uv_obs[o], r0, r1, jc, jp);
+        loss_scale_obs(kind, la2, r0, r1, jc, jp);
         const double *dcc = dc + (int64_t)c * 9, *dpp = dp + (int64_t)pi * 3;
         double e0 = 0.0, e1 = 0.0;
 #pragma unroll

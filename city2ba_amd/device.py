@@ -332,32 +332,59 @@ class PointRows:
         temp.record_stream(torch.cuda.current_stream(dev))
 
 
-def normal_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, gc, ws=None, sum_sq=None):
+def _loss_args(loss):
+    """loss= of the *_rows passes: None, or (name, scale) -- the (kind, scale) of the *_rows_loss entries"""
+    if isinstance(loss, str) or not hasattr(loss, "__len__") or len(loss) != 2:
+        raise ValueError("loss must be None or (name, scale), e.g. ('cauchy', 0.01), not %r" % (loss,))
+    return L.loss_kind(loss[0]), float(loss[1])
+
+
+def normal_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, gc, ws=None, sum_sq=None, loss=None):
     """camera pass of the Gauss-Newton blocks: U [n_cam,9,9] = sum Jc^T Jc, gc [n_cam,9] = sum Jc^T r over each camera's
-    observations (+ sum |r|^2 into sum_sq[0] when ws and sum_sq are given), the Jacobian never stored"""
+    observations (+ sum |r|^2 into sum_sq[0] when ws and sum_sq are given), the Jacobian never stored.  loss = (name,
+    scale): every observation reweighted by the robust loss's sqrt(w) first (c2b_normal_cameras_rows_loss)"""
+    if loss is not None:
+        L.check(L.lib().c2b_normal_cameras_rows_loss(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs,
+                                                     _p(U), _p(gc), _p(ws), _p(sum_sq), *_loss_args(loss), _stream()))
+        return U, gc
     L.check(L.lib().c2b_normal_cameras_rows(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs,
                                             _p(U), _p(gc), _p(ws), _p(sum_sq), _stream()))
     return U, gc
 
 
-def normal_points_rows(camblk, pts4, prows, uv, V, gp):
-    """point pass: V [n_pts,3,3] = sum Jp^T Jp, gp [n_pts,3] = sum Jp^T r over each point's observations (PointRows)"""
+def normal_points_rows(camblk, pts4, prows, uv, V, gp, loss=None):
+    """point pass: V [n_pts,3,3] = sum Jp^T Jp, gp [n_pts,3] = sum Jp^T r over each point's observations (PointRows);
+    loss = (name, scale) as in normal_cameras_rows"""
+    if loss is not None:
+        L.check(L.lib().c2b_normal_points_rows_loss(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of),
+                                                    _p(prows.cam_of), _p(uv), _p(V), _p(gp), *_loss_args(loss), _stream()))
+        return V, gp
     L.check(L.lib().c2b_normal_points_rows(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of),
                                            _p(uv), _p(V), _p(gp), _stream()))
     return V, gp
 
 
-def schur_points_rows(camblk, pts4, prows, uv, V, lam, x, h, t):
+def schur_points_rows(camblk, pts4, prows, uv, V, lam, x, h, t, loss=None):
     """point pass of the damped step's Schur complement: t [n_pts,3] = V_l^-1 (h + sum Jp^T (Jc x)) per point (PointRows),
-    V_l = V damped by lam (c2b_schur_points_rows); x [n_cam,9] None means 0, h [n_pts,3] None means 0"""
+    V_l = V damped by lam (c2b_schur_points_rows); x [n_cam,9] None means 0, h [n_pts,3] None means 0; loss = (name,
+    scale): Jc, Jp of the reweighted system (V must be its V)"""
+    if loss is not None:
+        L.check(L.lib().c2b_schur_points_rows_loss(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of),
+                                                   _p(prows.cam_of), _p(uv), _p(V), float(lam), _p(x), _p(h), _p(t), *_loss_args(loss),
+                                                   _stream()))
+        return t
     L.check(L.lib().c2b_schur_points_rows(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of),
                                           _p(uv), _p(V), float(lam), _p(x), _p(h), _p(t), _stream()))
     return t
 
 
-def schur_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, lam, x, t, y):
+def schur_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, lam, x, t, y, loss=None):
     """camera pass: y [n_cam,9] = U_l x - sum Jc^T (Jp t) per camera, U_l = U damped by lam (c2b_schur_cameras_rows);
-    x None drops the U term.  S x = schur_cameras_rows(.., x, schur_points_rows(.., x, None, t), y)"""
+    x None drops the U term.  S x = schur_cameras_rows(.., x, schur_points_rows(.., x, None, t), y); loss as there"""
+    if loss is not None:
+        L.check(L.lib().c2b_schur_cameras_rows_loss(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs,
+                                                    _p(U), float(lam), _p(x), _p(t), _p(y), *_loss_args(loss), _stream()))
+        return y
     L.check(L.lib().c2b_schur_cameras_rows(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs,
                                            _p(U), float(lam), _p(x), _p(t), _p(y), _stream()))
     return y

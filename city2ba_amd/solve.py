@@ -1,5 +1,6 @@
 """Levenberg-Marquardt on a resident BAProblem: BAProblem.solve_step (the damped Gauss-Newton step by PCG on the
-cameras' Schur complement, on the device) and apply_step, with Nielsen's update of the damping."""
+cameras' Schur complement, on the device) and apply_step, with Nielsen's update of the damping; optionally under a
+robust loss (BAProblem.set_loss), by iteratively reweighted least squares."""
 
 LAMBDA_MIN, LAMBDA_MAX = 1e-20, 1e32                # the damping c2b_problem_solve_step accepts (C2B_STEP_LAMBDA_MIN / _MAX)
 
@@ -8,28 +9,37 @@ def _clamp(lam):
     return min(max(lam, LAMBDA_MIN), LAMBDA_MAX)
 
 
-def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6):
+def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0):
     """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
     sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
     and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit); lam is held
     in [LAMBDA_MIN, LAMBDA_MAX] throughout.  Returns the history: one dict per iteration -- error (sum |r|^2 before it),
     lam (the damping it used), accepted, pcg_iterations, status (the solve's) -- and the final sum |r|^2 as the last
-    entry's 'error_after'."""
+    entry's 'error_after'.
+    loss = "huber" | "cauchy" | "soft_l1" with loss_scale (BAProblem.set_loss, which this calls: the loss stays on ba): the
+    steps are those of iteratively reweighted least squares, the quantity compared before and after a step is
+    ba.robust_cost() = sum rho(|r|^2) -- 'error', 'error_after' and the entry 'cost' hold it -- and the gain ratio
+    divides by the weighted model decrease the step reports.  loss = None leaves ba's loss as it is: a loss the caller
+    set with ba.set_loss is in force all the same (the step is the reweighted one, so the cost must be the robust one);
+    with none in force the loop runs as it always did and 'cost' repeats 'error'."""
+    if loss is not None:
+        ba.set_loss(loss, loss_scale)
+    robust = ba.loss[0] is not None
     ba.apply_step(None, None)                       # bal mode: bal9 is then what the problem holds exactly
     bal9, pts = ba.cameras_bal(), ba.points()
     row_ptr, pt_idx, uv = ba.row_ptr.copy(), ba.pt_idx.copy(), ba.observations()
     nu = 2.0
     lam = _clamp(lam)
     history = []
-    e0 = ba.total_reprojection_error(2.0) ** 2
+    e0 = ba.robust_cost() if robust else ba.total_reprojection_error(2.0) ** 2
     for _ in range(int(iterations)):
         dc, dp, info = ba.solve_step(lam, max_iters=max_iters, rel_tol=rel_tol)
         ba.apply_step(dc, dp)
-        e1 = ba.total_reprojection_error(2.0) ** 2
+        e1 = ba.robust_cost() if robust else ba.total_reprojection_error(2.0) ** 2
         md = info["model_decrease"]
         rho = (e0 - e1) / md if md > 0.0 else -1.0
         accepted = rho > 0.0 and e1 < e0
-        history.append(dict(error=e0, lam=lam, accepted=accepted, pcg_iterations=info["iterations"], status=info["status"]))
+        history.append(dict(error=e0, cost=e0, lam=lam, accepted=accepted, pcg_iterations=info["iterations"], status=info["status"]))
         if accepted:
             lam = _clamp(lam * max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
             nu = 2.0

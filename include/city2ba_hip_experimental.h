@@ -110,6 +110,41 @@ typedef struct {
 int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double rel_tol, double *dc, double *dp, c2b_step_info *info);
 int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp);
 
+/* ---- robust losses in the step: iteratively reweighted least squares ----
+ * Per observation s = r0^2 + r1^2, a loss rho(s) with scale a > 0 (Ceres' definitions) and the weight w = rho'(s):
+ *   kind 0 squared:  rho = s                                              w = 1
+ *   kind 1 Huber:    rho = s (s <= a^2), else 2 a sqrt(s) - a^2           w = 1 (s <= a^2), else a / sqrt(s)
+ *   kind 2 Cauchy:   rho = a^2 log1p(s / a^2)                             w = 1 / (1 + s / a^2)
+ *   kind 3 soft-L1:  rho = 2 a^2 (sqrt(1 + s / a^2) - 1)                  w = 1 / sqrt(1 + s / a^2)
+ * Every pass that uses (r, Jc, Jp) of an observation uses sqrt(w) (r, Jc, Jp) instead, w taken at the current state and
+ * held for the whole solve: U = sum w Jc^T Jc, gc = sum w Jc^T r, V, gp, W, the damping diagonal, the preconditioner, b,
+ * the back-substitution and the model decrease all follow from that one substitution.  No second-order (Triggs) term: H
+ * stays positive semi-definite.  w is recomputed per observation from r: there is no weight array.  0 < w <= 1, and
+ * s = 0 gives w = 1 in every kind.
+ * _set_loss / _get_loss: the loss is the handle's state (default kind 0); it survives uploads, reads and culls.  kind
+ *   outside 0..3, or (kind != 0) a scale that is not finite or <= 0: C2B_ERR_INVALID_ARGUMENT; kind 0 ignores the scale.
+ *   c2b_problem_normal_equations and c2b_problem_solve_step honour it: under a loss U, gc, V, gp are the reweighted
+ *   blocks, and sum_sq (both entries) and c2b_step_info.model_decrease are the weighted sum w |r|^2 and
+ *   sum -w (2r + e).e the step modelled.  With kind 0 both entries launch the squared-loss kernels, bit for bit.
+ * _robust_cost: sum rho(s) at the current state under the problem's loss (kind 0: sum |r|^2), one projection per
+ *   observation, summed in a fixed order -- what a loop under a loss minimises (not sum w s).  Synchronous.
+ * The *_rows_loss entries are the Level-0 passes above with (kind, scale) before the stream; kind 0 is the plain entry. */
+int c2b_problem_set_loss(c2b_problem *p, int kind, double scale);
+int c2b_problem_get_loss(const c2b_problem *p, int *kind, double *scale);
+int c2b_problem_robust_cost(c2b_problem *p, double *cost);
+int c2b_normal_cameras_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                                 const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
+                                 void *workspace, double *sum_sq, int kind, double scale, void *stream);
+int c2b_normal_points_rows_loss(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                                const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
+                                int kind, double scale, void *stream);
+int c2b_schur_points_rows_loss(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                               const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
+                               const double *x_cam, const double *h_pts, double *t_pts, int kind, double scale, void *stream);
+int c2b_schur_cameras_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                                const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
+                                const double *t_pts, double *y_cam, int kind, double scale, void *stream);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */

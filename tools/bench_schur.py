@@ -5,10 +5,13 @@ and print one JSON line:
   * solve_step with 0 iterations -- the set-up (the normal-equation passes, the 9x9 factorisations, b) plus the
     back-substitution and the model-decrease pass, i.e. everything but PCG;
   * solve_step with 25 iterations and rel_tol = 0 (a fixed-count solve), and one PCG iteration as the difference / 25;
-  * apply_step.
+  * apply_step, and under --loss robust_cost() (the LM loop's accept test: one projection per observation).
 The Level-1 calls are synchronous and timed on the host clock; each figure is the median of --reps after --warmup.
 
-    python tools/bench_schur.py [--blocks 128] [--reps 5] [--warmup 1]
+    python tools/bench_schur.py [--blocks 128] [--reps 5] [--warmup 1] [--loss huber|cauchy|soft_l1 --loss-scale A]
+
+--loss times the same figures under a robust loss (the weighted kernels); without it every launch is a
+squared-loss kernel.
 
 Algorithmic bytes (each input read once, each output written once):
   point pass:  n_obs x (4 obs_of + 4 cam_of + 16 uv) + n_pts x (8 pt_row_ptr + 32 point + 72 V + 24 t) + n_cam x (192 record + 72 x)
@@ -34,7 +37,10 @@ def main():
     ap.add_argument("--blocks", type=int, default=128)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--loss", choices=["huber", "cauchy", "soft_l1"], default=None, help="robust loss (default: squared)")
+    ap.add_argument("--loss-scale", type=float, default=3e-3, help="its scale a, in the residuals' units (noise is 1e-3)")
     a = ap.parse_args()
+    loss = (a.loss, a.loss_scale) if a.loss else None
     import __graft_entry__ as entry
     entry.build()
     import torch
@@ -57,8 +63,8 @@ def main():
     f64 = dict(dtype=torch.float64, device=dev)
     U, gc = torch.empty((n_cam, 9, 9), **f64), torch.empty((n_cam, 9), **f64)
     V, gp = torch.empty((n_pts, 3, 3), **f64), torch.empty((n_pts, 3), **f64)
-    D.normal_cameras_rows(camblk, pts4, rows, pi, uv, U, gc)
-    D.normal_points_rows(camblk, pts4, prows, uv, V, gp)
+    D.normal_cameras_rows(camblk, pts4, rows, pi, uv, U, gc, loss=loss)
+    D.normal_points_rows(camblk, pts4, prows, uv, V, gp, loss=loss)
     x = torch.randn((n_cam, 9), **f64) * 1e-3
     t, y = torch.empty((n_pts, 3), **f64), torch.empty((n_cam, 9), **f64)
 
@@ -86,8 +92,8 @@ def main():
             times.append((time.perf_counter() - t0) * 1e3)
         return {"median_ms": round(_median(times), 3), "min_ms": round(min(times), 3)}
 
-    us_p = events(lambda: D.schur_points_rows(camblk, pts4, prows, uv, V, lam, x, None, t))
-    us_c = events(lambda: D.schur_cameras_rows(camblk, pts4, rows, pi, uv, U, lam, x, t, y))
+    us_p = events(lambda: D.schur_points_rows(camblk, pts4, prows, uv, V, lam, x, None, t, loss=loss))
+    us_c = events(lambda: D.schur_cameras_rows(camblk, pts4, rows, pi, uv, U, lam, x, t, y, loss=loss))
     bytes_p = n * 24 + n_pts * (8 + 32 + 72 + 24) + n_cam * (192 + 72)
     bytes_c = n * 20 + n_pts * (32 + 24) + n_cam * (8 + 192 + 648 + 72 + 72)
     frac = lambda b, us: round(b / (us * 1e-6) / 8e12, 4)
@@ -96,6 +102,8 @@ def main():
 
     dc, dp = torch.empty((n_cam, 9), **f64), torch.empty((n_pts, 3), **f64)
     info = {}
+    if loss:
+        ba.set_loss(*loss)
 
     def solve(k):
         info[k] = ba.solve_step(lam, max_iters=k, rel_tol=0.0, out=(dc, dp))[2]
@@ -104,8 +112,9 @@ def main():
     s25 = wall(lambda: solve(25))
     zc, zp = torch.zeros_like(dc), torch.zeros_like(dp)
     ap_ms = wall(lambda: ba.apply_step(zc, zp))
+    rc_ms = wall(ba.robust_cost) if loss else None           # what an LM iteration under a loss pays for its accept test
     out = {
-        "blocks": a.blocks, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts, "lambda": lam,
+        "blocks": a.blocks, "loss": a.loss, "loss_scale": a.loss_scale if a.loss else None, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts, "lambda": lam,
         "points_pass": dict(us_p, algorithmic_bytes=bytes_p, frac_of_8TBs=frac(bytes_p, us_p["median_us"])),
         "cameras_pass": dict(us_c, algorithmic_bytes=bytes_c, frac_of_8TBs=frac(bytes_c, us_c["median_us"])),
         "both_passes_us": round(us_p["median_us"] + us_c["median_us"], 1),
@@ -113,6 +122,7 @@ def main():
         "solve_25_iterations": s25,
         "pcg_iteration_ms": round((s25["median_ms"] - s0["median_ms"]) / 25.0, 3),
         "apply_step": ap_ms,
+        **({"robust_cost": rc_ms} if loss else {}),
         "info_25": info[25],
     }
     ba.close()
