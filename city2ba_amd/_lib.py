@@ -17,7 +17,7 @@ ERR_OOM = -4
 ERR_NO_DEVICE = -5
 ERR_RCCL = -6
 COMM_ID_BYTES = 128
-ABI_VERSION = 7            # include/city2ba_hip.h: C2B_ABI_VERSION
+ABI_VERSION = 8            # include/city2ba_hip.h: C2B_ABI_VERSION
 CAMBLK_DOUBLES = 32
 STATS_DOUBLES = 20
 
@@ -41,6 +41,21 @@ def loss_kind(loss):
         return LOSS_KINDS[loss]
     except (KeyError, TypeError):
         raise ValueError("loss must be None, 'huber', 'cauchy' or 'soft_l1', not %r" % (loss,))
+
+
+# preconditioners of the step's PCG (c2b_problem_set_preconditioner): name -> kind
+PRECOND_KINDS = {"block_jacobi": 0, "schur_jacobi": 1}
+PRECOND_NAMES = {0: "block_jacobi", 1: "schur_jacobi"}
+
+
+def precond_kind(name):
+    """the C ABI's kind of a preconditioner given by name (or the kind itself)"""
+    if isinstance(name, int) and not isinstance(name, bool):
+        return name
+    try:
+        return PRECOND_KINDS[name]
+    except (KeyError, TypeError):
+        raise ValueError("preconditioner must be 'block_jacobi' or 'schur_jacobi', not %r" % (name,))
 
 
 class StepInfo(C.Structure):
@@ -113,6 +128,11 @@ SIGNATURES = {
     "c2b_normal_points_rows_loss": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _d, _vp]),
     "c2b_schur_points_rows_loss": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _int, _d, _vp]),
     "c2b_schur_cameras_rows_loss": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _d, _vp, _vp, _vp, _int, _d, _vp]),
+    "c2b_problem_set_preconditioner": (_int, [_vp, _int]),
+    "c2b_problem_get_preconditioner": (_int, [_vp, C.POINTER(_int)]),
+    "c2b_problem_preconditioner_fallbacks": (_int, [_vp, C.POINTER(_i64)]),
+    "c2b_schur_jacobi_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _d, _vp, _vp]),
+    "c2b_schur_jacobi_rows_loss": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _d, _vp, _int, _d, _vp]),
     "c2b_visibility_pairs": (_int, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_visibility_dense_tiles": (_i64, [_i64]),
     "c2b_visibility_dense_count": (_int, [_vp, _i64, _vp, _i64, _d, _vp, _vp, _vp, _vp]),

@@ -302,6 +302,27 @@ class BAProblem:
         L.check(L.lib().c2b_problem_robust_cost(self._h, C.byref(s)))
         return s.value
 
+    def set_preconditioner(self, kind):
+        """What solve_step's PCG is preconditioned with (c2b_problem_set_preconditioner): "block_jacobi", the 9x9 blocks
+        of the damped U (the default), or "schur_jacobi", the 9x9 diagonal blocks of the Schur complement itself -- one
+        more pass over the observations in the set-up and the same kernels per iteration; it changes the iteration
+        count, not the solution (measurements: DESIGN 4.4).  The setting belongs to the handle: uploads and culls keep it."""
+        L.check(L.lib().c2b_problem_set_preconditioner(self._h, L.precond_kind(kind)))
+
+    @property
+    def preconditioner(self):
+        """the name of the preconditioner in force"""
+        k = C.c_int()
+        L.check(L.lib().c2b_problem_get_preconditioner(self._h, C.byref(k)))
+        return L.PRECOND_NAMES[k.value]
+
+    def preconditioner_fallbacks(self):
+        """cameras whose Schur-Jacobi block could not be factored in the last solve_step and took the block-Jacobi
+        factor instead (c2b_problem_preconditioner_fallbacks); 0 after a block-Jacobi solve"""
+        n = C.c_int64()
+        L.check(L.lib().c2b_problem_preconditioner_fallbacks(self._h, C.byref(n)))
+        return n.value
+
     def solve_step(self, lam, max_iters=100, rel_tol=1e-6, out=None):
         """One damped Gauss-Newton (Levenberg-Marquardt) step on the device (c2b_problem_solve_step): the solution of
         (J^T J + lam D) delta = -g, D = diag(min(max(diag(J^T J), 1e-6), 1e32)), by PCG on the Schur complement of the

@@ -1501,3 +1501,45 @@ int c2b_schur_cameras_rows_loss(const double *camblk, const double *pts4, const 
     return schur_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, lambda, x_cam, t_pts, y_cam, kind, scale, stream);
     C2B_API_END("schur_cameras_rows_loss")
 }
+
+// the Schur-Jacobi blocks M (k_schur_jacobi, on the grid of k_schur_cameras)
+static int schur_jacobi_rows_impl(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                                  const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
+                                  int kind, double scale, void *stream) {
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: count out of range");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: lambda must lie in [1e-20, 1e32]");
+    if (n_cam && (!camblk || !row_ptr || !U || !M)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: NULL argument");
+    if (n_obs && (!pts4 || !pt_idx || !uv_obs || !V)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: NULL observation input");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(row_ptr) || !aligned8(U) || !aligned8(V) ||
+        !aligned8(M) || (reinterpret_cast<uintptr_t>(pt_idx) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: misaligned pointer");
+    if (!n_cam) return C2B_OK;
+    if (kind != kLossSquared)
+        hipLaunchKernelGGL(k_schur_jacobi_loss, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
+                           reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
+                           U, V, lambda, M, kind, scale * scale);
+    else
+        hipLaunchKernelGGL(k_schur_jacobi, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
+                           reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
+                           U, V, lambda, M);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
+int c2b_schur_jacobi_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                          const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
+                          void *stream) {
+    C2B_API_BEGIN
+    return schur_jacobi_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, V, lambda, M, 0, 1.0, stream);
+    C2B_API_END("schur_jacobi_rows")
+}
+
+int c2b_schur_jacobi_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                               const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
+                               int kind, double scale, void *stream) {
+    C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "schur_jacobi_rows_loss");
+    return schur_jacobi_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, V, lambda, M, kind, scale, stream);
+    C2B_API_END("schur_jacobi_rows_loss")
+}

@@ -22,6 +22,10 @@ struct c2b_problem {
     // 3 soft-L1) and its scale; the handle's too
     int loss_kind = 0;
     double loss_scale = 1.0;
+    // c2b_problem_set_preconditioner: what c2b_problem_solve_step's PCG is preconditioned with (0 block-Jacobi on U,
+    // 1 Schur-Jacobi), the handle's too; and how many cameras' Schur-Jacobi factors fell back in the last solve
+    int precond_kind = 0;
+    int64_t precond_fallbacks = 0;
     bool bal_valid = false;     // bal9 still describes the cameras (no mutation since upload_bal)
     bool blk_valid = false;     // camblk matches cam15 (and bal_valid mode)
     bool bal9_fresh = false;    // !bal_valid, but bal9 holds to_vec of the current cameras (the last write / download_bal computed it)
@@ -564,6 +568,33 @@ int c2b_problem_get_loss(const c2b_problem *p, int *kind, double *scale) {
     C2B_API_END("problem_get_loss")
 }
 
+// ---- preconditioner of the step ----------------------------------------------------------------------------
+int c2b_problem_set_preconditioner(c2b_problem *p, int kind) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_preconditioner: problem is NULL");
+    if (kind != C2B_PRECOND_BLOCK_JACOBI && kind != C2B_PRECOND_SCHUR_JACOBI)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_preconditioner: kind must be 0 (block-Jacobi) or 1 (Schur-Jacobi), not %d", kind);
+    p->precond_kind = kind;
+    return C2B_OK;
+    C2B_API_END("problem_set_preconditioner")
+}
+
+int c2b_problem_get_preconditioner(const c2b_problem *p, int *kind) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_preconditioner: problem is NULL");
+    if (kind) *kind = p->precond_kind;
+    return C2B_OK;
+    C2B_API_END("problem_get_preconditioner")
+}
+
+int c2b_problem_preconditioner_fallbacks(const c2b_problem *p, int64_t *n) {
+    C2B_API_BEGIN
+    if (!p || !n) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_preconditioner_fallbacks: NULL argument");
+    *n = p->precond_fallbacks;
+    return C2B_OK;
+    C2B_API_END("problem_preconditioner_fallbacks")
+}
+
 // sum over the observations of rho(s) (weighted_sq: of w s) under the problem's loss into out[0] (device), asynchronous;
 // one partial per workgroup of 256 observations: the workspace holds one per 4 tiles of 64 (block_part_slots)
 static int robust_sum(c2b_problem *p, bool weighted_sq, double *out) {
@@ -651,9 +682,10 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
 
 // ---- damped Gauss-Newton step (schur_kernels.hpp) ------------------------------------------------------------------
 // c2b_problem::sv, carved: U [n_cam][81], gc [n_cam][9], V [n_pts][9], gp [n_pts][3], Lf [n_cam][45], t [n_pts][3],
-// r / z / p / q [n_cam][9], two partial arrays [n_part], the device scalars [kScSlots]
+// r / z / p / q [n_cam][9], two partial arrays [n_part], the device scalars [kScSlots]; under the Schur-Jacobi
+// preconditioner its blocks M [n_cam][81] after them (the rest lies where it lies without)
 struct SolveBufs {
-    double *U, *gc, *V, *gp, *Lf, *t, *r, *z, *pv, *q, *pa, *pb, *sc;
+    double *U, *gc, *V, *gp, *Lf, *t, *r, *z, *pv, *q, *pa, *pb, *sc, *M;
     int64_t n_part;
 };
 
@@ -663,7 +695,8 @@ static int64_t solve_parts(const c2b_problem *p) {
 }
 
 static int64_t solve_doubles(const c2b_problem *p) {
-    return p->n_cam * (81 + 9 + kCholPacked + 4 * 9) + p->n_pts * (9 + 3 + 3) + 2 * solve_parts(p) + kScSlots;
+    return p->n_cam * (81 + 9 + kCholPacked + 4 * 9) + p->n_pts * (9 + 3 + 3) + 2 * solve_parts(p) + kScSlots +
+           (p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? 81 * p->n_cam : 0);
 }
 
 static SolveBufs solve_bufs(c2b_problem *p) {
@@ -675,6 +708,7 @@ static SolveBufs solve_bufs(c2b_problem *p) {
     b.t = take(3 * np); b.r = take(9 * nc); b.z = take(9 * nc); b.pv = take(9 * nc); b.q = take(9 * nc);
     b.n_part = solve_parts(p);
     b.pa = take(b.n_part); b.pb = take(b.n_part); b.sc = take(kScSlots);
+    b.M = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? take(81 * nc) : nullptr;
     return b;
 }
 
@@ -706,6 +740,7 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     if (!aligned8(dc) || !aligned8(dp)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: misaligned pointer");
     hipStream_t st = p->stream;
     c2b_step_info out{0, 0, 0.0, 0.0, 0.0};
+    p->precond_fallbacks = 0;
     if (!no) {                                               // no observation: g = 0, the step is 0
         if (nc) HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
         if (np) HIP_TRY(hipMemsetAsync(dp, 0, sizeof(double) * 3 * (size_t)np, st));
@@ -752,7 +787,16 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
                                   p->loss_scale, st);
     if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, B.gp, kind, p->loss_scale, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
+    const bool schur_jacobi = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI;
+    if (schur_jacobi) {                                      // M from U's diagonal and V, its factors, the fallbacks' count
+        rc = schur_jacobi_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.V, lambda, B.M, kind, p->loss_scale, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_schur_factor_blocks, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.M, (const double *)B.U,
+                           lambda, B.Lf, B.pa);
+        hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbc, B.sc + kScFallback);
+    } else {
+        hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
+    }
     points(nullptr, B.gp, B.t, false);
     if (kind != kLossSquared)
         hipLaunchKernelGGL(k_schur_cameras_loss<kSchurRhs>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
@@ -816,7 +860,8 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
                            (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb);
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbo, B.sc + kScSumSq);
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pb, (int)nbo, B.sc + kScModel);
-    if ((rc = fetch(kScModel + 1))) return rc;
+    if ((rc = fetch(schur_jacobi ? kScFallback + 1 : kScModel + 1))) return rc;
+    if (schur_jacobi) p->precond_fallbacks = (int64_t)h[kScFallback];
     out.iterations = it;
     out.status = status;
     out.rel_residual = bb == 0.0 ? 0.0 : rnorm / bnorm;

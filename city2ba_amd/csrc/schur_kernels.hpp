@@ -9,6 +9,8 @@
 //     four cameras: y_c = U_l,c x_c - sum Jc^T (Jp t_p), optionally with the wave's x.y as one partial.
 //   * k_schur_factor / k_pcg_update / k_pcg_direction: the 9x9 Cholesky preconditioner, the PCG vector updates with
 //     r.r and r.z as one partial per workgroup, p = z + beta p.
+//   * k_schur_jacobi / k_schur_factor_blocks: the Schur-Jacobi preconditioner, S's own 9x9 diagonal blocks in place of
+//     U_l's, factored into k_schur_factor's format (an option of the solve).
 //   * k_schur_model: ||r||^2 and ||r||^2 - ||r + Jc dc + Jp dp||^2 per observation, one partial per workgroup.
 // Damping (Marquardt with Ceres' clamps): A_l = A + lambda diag(d), d_i = min(max(A_ii, 1e-6), 1e32).
 // Every partial is summed by k_normal_sum in a fixed order; no float atomics, so the same inputs give the same bits.
@@ -374,6 +376,214 @@ __global__ __launch_bounds__(kSchurBlock) void k_pcg_update(
 __global__ __launch_bounds__(kSchurBlock) void k_pcg_direction(int64_t n, double beta, const double *__restrict__ z, double *__restrict__ p) {
     const int64_t i = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
     if (i < n) p[i] = z[i] + beta * p[i];
+}
+
+// ---- Schur-Jacobi preconditioner ----------------------------------------------------------------------
+// M_c = lam diag(d_c) + sum_o Jc_o^T (I2 - Jp_o V_l,p(o)^-1 Jp_o^T) Jc_o over the camera's list: the 9x9 diagonal block of
+// S when no camera sees a point twice.  Every term is positive semi-definite (V_l >= Jp_o^T Jp_o) and is accumulated as
+// such: nothing is subtracted from U_l, so nothing cancels at small lam.  The layout of k_normal_cameras (16 lanes per
+// camera, the xor tree, the packed sums staged in LDS for the 81 stores) on the grid of k_schur_cameras (one wave per four
+// cameras).  Per observation: V_l,p = L L^T in registers as in k_schur_points, y_a = L^-1 Jp_a^T for the two rows a of
+// Jp, F = I2 - [y_a . y_b].  d_c is read from U's diagonal when the block is written.
+constexpr int kScFallback = 6;                    // device scalar of a solve: cameras whose Schur-Jacobi factor fell back
+static_assert(kScFallback > kScModel && kScFallback < kScSlots, "kScFallback must be a free slot of c2b_problem::sv_sc");
+
+__global__ __launch_bounds__(kNormBlock) void k_schur_jacobi(
+    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
+    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const double *__restrict__ U,
+    const double *__restrict__ V, double lam, double *__restrict__ M) {
+    constexpr int kWaves = kNormBlock / 64;
+    __shared__ double sAcc[kWaves * kNormCamsPerWave * kNormSym];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
+    double *mine = sAcc + (wave * kNormCamsPerWave + grp) * kNormSym;
+    const int q = (int)blockIdx.x * kWaves + wave;                   // one wave per kNormCamsPerWave cameras, no grid-stride loop
+    const int c = q * kNormCamsPerWave + grp;
+    const bool cam_ok = c < n_cam;
+    const uint64_t b = cam_ok ? row_ptr[c] : 0, e = cam_ok ? row_ptr[c + 1] : 0;
+    const CamRef cam = cam_ref(camblk, cam_ok ? (uint32_t)c : 0u);
+    double acc[kNormSym];
+#pragma unroll
+    for (int k = 0; k < kNormSym; ++k) acc[k] = 0.0;
+#pragma unroll 1
+    for (uint64_t o = b + gl; o < e; o += kNormG) {
+        const uint32_t pi = pt_idx[o];
+        double r0, r1, jc[18], jp[6];
+        jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
+        // V_l = L L^T, L in registers (the reciprocals of its diagonal)
+        const double *Vp = V + (int64_t)pi * 9;
+        const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
+        const double i0 = 1.0 / sqrt(v00);
+        const double l10 = v10 * i0, l20 = v20 * i0;
+        const double i1 = 1.0 / sqrt(v11 - l10 * l10);
+        const double l21 = (v21 - l20 * l10) * i1;
+        const double i2 = 1.0 / sqrt((v22 - l20 * l20) - l21 * l21);
+        const double ya0 = jp[0] * i0, ya1 = (jp[1] - l10 * ya0) * i1, ya2 = ((jp[2] - l20 * ya0) - l21 * ya1) * i2;
+        const double yb0 = jp[3] * i0, yb1 = (jp[4] - l10 * yb0) * i1, yb2 = ((jp[5] - l20 * yb0) - l21 * yb1) * i2;
+        const double f00 = 1.0 - ((ya0 * ya0 + ya1 * ya1) + ya2 * ya2);
+        const double f01 = -((ya0 * yb0 + ya1 * yb1) + ya2 * yb2);
+        const double f11 = 1.0 - ((yb0 * yb0 + yb1 * yb1) + yb2 * yb2);
+#pragma unroll
+        for (int a = 0; a < 9; ++a) {
+            const double g0 = f00 * jc[a] + f01 * jc[9 + a], g1 = f01 * jc[a] + f11 * jc[9 + a];
+#pragma unroll
+            for (int d = a; d < 9; ++d) acc[sym9(a, d)] += g0 * jc[d] + g1 * jc[9 + d];
+        }
+    }
+    // fixed tree over the group's 16 lanes (xor: every lane ends with the same bits)
+#pragma unroll
+    for (int off = kNormG / 2; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < kNormSym; ++k) acc[k] += __shfl_xor(acc[k], off, 64);
+    }
+    if (gl == 0) {
+#pragma unroll
+        for (int k = 0; k < kNormSym; ++k) mine[k] = acc[k];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (cam_ok) {
+        // both triangles from one packed entry: M[a][d] and M[d][a] are the same bits; 16 lanes write a block of 81
+        const double *Uc = U + (int64_t)c * 81;
+        double *Mc = M + (int64_t)c * 81;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {
+            const int i = gl + t * kNormG;
+            if (i < 81) {
+                const int a = i / 9, d = i % 9;
+                const double s = mine[a <= d ? sym9(a, d) : sym9(d, a)];
+                Mc[i] = a == d ? s + lam * fmin(fmax(Uc[i], 1e-6), 1e32) : s;
+            }
+        }
+    }
+}
+
+// its weighted twin (a copy: see k_normal_cameras_loss): Jc, Jp of the reweighted system, V its V
+__global__ __launch_bounds__(kNormBlock) void k_schur_jacobi_loss(
+    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
+    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const double *__restrict__ U,
+    const double *__restrict__ V, double lam, double *__restrict__ M, int kind, double la2) {
+    constexpr int kWaves = kNormBlock / 64;
+    __shared__ double sAcc[kWaves * kNormCamsPerWave * kNormSym];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
+    double *mine = sAcc + (wave * kNormCamsPerWave + grp) * kNormSym;
+    const int q = (int)blockIdx.x * kWaves + wave;                   // one wave per kNormCamsPerWave cameras, no grid-stride loop
+    const int c = q * kNormCamsPerWave + grp;
+    const bool cam_ok = c < n_cam;
+    const uint64_t b = cam_ok ? row_ptr[c] : 0, e = cam_ok ? row_ptr[c + 1] : 0;
+    const CamRef cam = cam_ref(camblk, cam_ok ? (uint32_t)c : 0u);
+    double acc[kNormSym];
+#pragma unroll
+    for (int k = 0; k < kNormSym; ++k) acc[k] = 0.0;
+#pragma unroll 1
+    for (uint64_t o = b + gl; o < e; o += kNormG) {
+        const uint32_t pi = pt_idx[o];
+        double r0, r1, jc[18], jp[6];
+        jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
+        loss_scale_obs(kind, la2, r0, r1, jc, jp);
+        // V_l = L L^T, L in registers (the reciprocals of its diagonal)
+        const double *Vp = V + (int64_t)pi * 9;
+        const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
+        const double i0 = 1.0 / sqrt(v00);
+        const double l10 = v10 * i0, l20 = v20 * i0;
+        const double i1 = 1.0 / sqrt(v11 - l10 * l10);
+        const double l21 = (v21 - l20 * l10) * i1;
+        const double i2 = 1.0 / sqrt((v22 - l20 * l20) - l21 * l21);
+        const double ya0 = jp[0] * i0, ya1 = (jp[1] - l10 * ya0) * i1, ya2 = ((jp[2] - l20 * ya0) - l21 * ya1) * i2;
+        const double yb0 = jp[3] * i0, yb1 = (jp[4] - l10 * yb0) * i1, yb2 = ((jp[5] - l20 * yb0) - l21 * yb1) * i2;
+        const double f00 = 1.0 - ((ya0 * ya0 + ya1 * ya1) + ya2 * ya2);
+        const double f01 = -((ya0 * yb0 + ya1 * yb1) + ya2 * yb2);
+        const double f11 = 1.0 - ((yb0 * yb0 + yb1 * yb1) + yb2 * yb2);
+#pragma unroll
+        for (int a = 0; a < 9; ++a) {
+            const double g0 = f00 * jc[a] + f01 * jc[9 + a], g1 = f01 * jc[a] + f11 * jc[9 + a];
+#pragma unroll
+            for (int d = a; d < 9; ++d) acc[sym9(a, d)] += g0 * jc[d] + g1 * jc[9 + d];
+        }
+    }
+    // fixed tree over the group's 16 lanes (xor: every lane ends with the same bits)
+#pragma unroll
+    for (int off = kNormG / 2; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < kNormSym; ++k) acc[k] += __shfl_xor(acc[k], off, 64);
+    }
+    if (gl == 0) {
+#pragma unroll
+        for (int k = 0; k < kNormSym; ++k) mine[k] = acc[k];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (cam_ok) {
+        // both triangles from one packed entry: M[a][d] and M[d][a] are the same bits; 16 lanes write a block of 81
+        const double *Uc = U + (int64_t)c * 81;
+        double *Mc = M + (int64_t)c * 81;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {
+            const int i = gl + t * kNormG;
+            if (i < 81) {
+                const int a = i / 9, d = i % 9;
+                const double s = mine[a <= d ? sym9(a, d) : sym9(d, a)];
+                Mc[i] = a == d ? s + lam * fmin(fmax(Uc[i], 1e-6), 1e32) : s;
+            }
+        }
+    }
+}
+
+// a (packed lower rows) to its Cholesky factor in place, the reciprocal of each diagonal entry in its place: the
+// arithmetic of k_schur_factor.  False when a pivot is not finite or not > 0 (a then holds no factor): an entry that is
+// not finite reaches a later pivot, so the pivots alone decide.
+C2B_DEV bool chol9_packed(double (&a)[kCholPacked]) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        double d = a[tri9(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= a[tri9(j, k)] * a[tri9(j, k)];
+        ok = ok && isfinite(d) && d > 0.0;
+        const double inv = 1.0 / sqrt(d);
+        a[tri9(j, j)] = inv;
+#pragma unroll
+        for (int i = j + 1; i < 9; ++i) {
+            double v = a[tri9(i, j)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= a[tri9(i, k)] * a[tri9(j, k)];
+            a[tri9(i, j)] = v * inv;
+        }
+    }
+    return ok;
+}
+
+// Lf[c] = the factor of M_c in k_schur_factor's format, so k_pcg_update and chol9_solve apply it unchanged.  A camera
+// whose M_c has a pivot that is not finite or not > 0 gets the factor of U_l,c instead (the block-Jacobi one, by the same
+// arithmetic); how many did leaves as one count per workgroup (a double holding an integer: k_normal_sum adds them exactly)
+__global__ __launch_bounds__(kSchurBlock) void k_schur_factor_blocks(int64_t n_cam, const double *__restrict__ M,
+                                                                     const double *__restrict__ U, double lam,
+                                                                     double *__restrict__ Lf, double *__restrict__ part_fb) {
+    __shared__ double sRed[4];
+    const int64_t c = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    double fell = 0.0;
+    if (c < n_cam) {
+        const double *Mc = M + c * 81;
+        double a[kCholPacked];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+#pragma unroll
+            for (int j = 0; j <= i; ++j) a[tri9(i, j)] = Mc[i * 9 + j];
+        }
+        if (!chol9_packed(a)) {
+            const double *Uc = U + c * 81;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+#pragma unroll
+                for (int j = 0; j <= i; ++j) a[tri9(i, j)] = i == j ? damped(Uc[i * 9 + j], lam) : Uc[i * 9 + j];
+            }
+            (void)chol9_packed(a);
+            fell = 1.0;
+        }
+        double *Lc = Lf + c * kCholPacked;
+#pragma unroll
+        for (int k = 0; k < kCholPacked; ++k) Lc[k] = a[k];
+    }
+    block_sum_to(fell, sRed, part_fb + blockIdx.x);
 }
 
 // ---- model decrease ---------------------------------------------------------------------------------------------

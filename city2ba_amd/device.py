@@ -378,6 +378,19 @@ def schur_points_rows(camblk, pts4, prows, uv, V, lam, x, h, t, loss=None):
     return t
 
 
+def schur_jacobi_blocks(camblk, pts4, rows, pt_idx, uv, U, V, lam, M, loss=None):
+    """the Schur-Jacobi preconditioner's blocks: M [n_cam,9,9] = lam diag(d_c) + sum Jc^T (I - Jp V_l^-1 Jp^T) Jc per camera,
+    d_c the damping diagonal of U's block (c2b_schur_jacobi_rows) -- the diagonal blocks of the Schur complement when no
+    camera sees a point twice.  U, V as normal_cameras_rows / normal_points_rows filled them; loss as there"""
+    if loss is not None:
+        L.check(L.lib().c2b_schur_jacobi_rows_loss(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs,
+                                                   _p(U), _p(V), float(lam), _p(M), *_loss_args(loss), _stream()))
+        return M
+    L.check(L.lib().c2b_schur_jacobi_rows(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs,
+                                          _p(U), _p(V), float(lam), _p(M), _stream()))
+    return M
+
+
 def schur_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, lam, x, t, y, loss=None):
     """camera pass: y [n_cam,9] = U_l x - sum Jc^T (Jp t) per camera, U_l = U damped by lam (c2b_schur_cameras_rows);
     x None drops the U term.  S x = schur_cameras_rows(.., x, schur_points_rows(.., x, None, t), y); loss as there"""

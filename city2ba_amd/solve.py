@@ -9,7 +9,7 @@ def _clamp(lam):
     return min(max(lam, LAMBDA_MIN), LAMBDA_MAX)
 
 
-def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0):
+def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0, preconditioner=None):
     """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
     sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
     and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit); lam is held
@@ -21,7 +21,11 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     ba.robust_cost() = sum rho(|r|^2) -- 'error', 'error_after' and the entry 'cost' hold it -- and the gain ratio
     divides by the weighted model decrease the step reports.  loss = None leaves ba's loss as it is: a loss the caller
     set with ba.set_loss is in force all the same (the step is the reweighted one, so the cost must be the robust one);
-    with none in force the loop runs as it always did and 'cost' repeats 'error'."""
+    with none in force the loop runs as it always did and 'cost' repeats 'error'.
+    preconditioner = "block_jacobi" | "schur_jacobi" (BAProblem.set_preconditioner, which this calls: it stays on ba);
+    None leaves ba's as it is.  It changes how many PCG iterations a step takes, not what the step converges to."""
+    if preconditioner is not None:
+        ba.set_preconditioner(preconditioner)
     if loss is not None:
         ba.set_loss(loss, loss_scale)
     robust = ba.loss[0] is not None

@@ -145,6 +145,34 @@ int c2b_schur_cameras_rows_loss(const double *camblk, const double *pts4, const 
                                 const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
                                 const double *t_pts, double *y_cam, int kind, double scale, void *stream);
 
+/* ---- the preconditioner of the step: block-Jacobi on U (default) or Schur-Jacobi ----
+ * Schur-Jacobi: per camera, with d_c the damping diagonal of U_c (the clamp rule above) and w_o the loss's weight,
+ *   M_c = lambda diag(d_c) + sum_o w_o Jc_o^T (I2 - Jp_o V_l,p(o)^-1 Jp_o^T) Jc_o       over the camera's list,
+ * the 9x9 diagonal block of S = U_l - W V_l^-1 W^T whenever no camera sees a point twice.  With a duplicated (camera,
+ * point) pair it is not that block, but every term is positive semi-definite, so M_c stays symmetric positive definite;
+ * the sum is accumulated in that form (nothing is subtracted from U_l).  M_c replaces U_l,c as the 9x9 block the PCG
+ * factors and applies: the iterations are the same kernels, and the solution of S dc = b is the same.
+ * _set_preconditioner / _get_preconditioner: the handle's state like the loss (default C2B_PRECOND_BLOCK_JACOBI); it
+ *   survives uploads, reads and culls.  Another kind: C2B_ERR_INVALID_ARGUMENT.  c2b_problem_solve_step honours it: with
+ *   kind 0 it launches exactly what it launched before this entry existed, bit for bit; with kind 1 the set-up runs one
+ *   more pass over the observations (M, in a buffer of n_cam x 81 doubles the problem then keeps with the others) and
+ *   factors M_c.  A camera whose M_c has a pivot that is not finite or not > 0 falls back to U_l,c's factor.
+ * _preconditioner_fallbacks: how many cameras fell back in the last c2b_problem_solve_step; 0 after a block-Jacobi solve.
+ * _schur_jacobi_rows(_loss): the Level-0 pass, asynchronous on `stream`: the inputs of c2b_schur_cameras_rows that it
+ *   needs plus V [n_pts][3][3]; U and V are those c2b_normal_*_rows filled (under the same loss).  Output M [n_cam][9][9],
+ *   both triangles the same bits.  Deterministic. */
+#define C2B_PRECOND_BLOCK_JACOBI 0
+#define C2B_PRECOND_SCHUR_JACOBI 1
+int c2b_problem_set_preconditioner(c2b_problem *p, int kind);
+int c2b_problem_get_preconditioner(const c2b_problem *p, int *kind);
+int c2b_problem_preconditioner_fallbacks(const c2b_problem *p, int64_t *n);
+int c2b_schur_jacobi_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                          const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
+                          void *stream);
+int c2b_schur_jacobi_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                               const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
+                               int kind, double scale, void *stream);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */

@@ -9,6 +9,12 @@ and print one JSON line:
 The Level-1 calls are synchronous and timed on the host clock; each figure is the median of --reps after --warmup.
 
     python tools/bench_schur.py [--blocks 128] [--reps 5] [--warmup 1] [--loss huber|cauchy|soft_l1 --loss-scale A]
+                                [--preconditioner block_jacobi|schur_jacobi] [--to-tol]
+
+--preconditioner schur_jacobi (combinable with --loss) solves with the Schur-Jacobi blocks and also reports
+the pass that forms them alone (k_schur_jacobi: us, algorithmic bytes, fraction of 8 TB/s).  --to-tol adds, for either
+preconditioner, the iterations and wall time of a solve to rel_tol 1e-2 and to 1e-4 (max_iters --tol-max-iters; a
+solve that ends with status 1 is reported as such).
 
 --loss times the same figures under a robust loss (the weighted kernels); without it every launch is a
 squared-loss kernel.
@@ -39,6 +45,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--loss", choices=["huber", "cauchy", "soft_l1"], default=None, help="robust loss (default: squared)")
     ap.add_argument("--loss-scale", type=float, default=3e-3, help="its scale a, in the residuals' units (noise is 1e-3)")
+    ap.add_argument("--preconditioner", choices=["block_jacobi", "schur_jacobi"], default="block_jacobi")
+    ap.add_argument("--to-tol", action="store_true", help="also time solves to rel_tol 1e-2 and 1e-4")
+    ap.add_argument("--tol-max-iters", type=int, default=1000)
     a = ap.parse_args()
     loss = (a.loss, a.loss_scale) if a.loss else None
     import __graft_entry__ as entry
@@ -97,11 +106,18 @@ def main():
     bytes_p = n * 24 + n_pts * (8 + 32 + 72 + 24) + n_cam * (192 + 72)
     bytes_c = n * 20 + n_pts * (32 + 24) + n_cam * (8 + 192 + 648 + 72 + 72)
     frac = lambda b, us: round(b / (us * 1e-6) / 8e12, 4)
+    sj = a.preconditioner == "schur_jacobi"
+    if sj:                                                   # the pass that forms M, alone
+        M = torch.empty((n_cam, 9, 9), **f64)
+        us_m = events(lambda: D.schur_jacobi_blocks(camblk, pts4, rows, pi, uv, U, V, lam, M, loss=loss))
+        bytes_m = n * 20 + n_pts * (32 + 72) + n_cam * (8 + 192 + 72 + 648)      # + U's diagonal (its lines), M written once
+        del M
     del U, gc, V, gp, t, y, x, prows, rows, camblk, ex
     torch.cuda.empty_cache()
 
     dc, dp = torch.empty((n_cam, 9), **f64), torch.empty((n_pts, 3), **f64)
     info = {}
+    ba.set_preconditioner(a.preconditioner)
     if loss:
         ba.set_loss(*loss)
 
@@ -113,8 +129,19 @@ def main():
     zc, zp = torch.zeros_like(dc), torch.zeros_like(dp)
     ap_ms = wall(lambda: ba.apply_step(zc, zp))
     rc_ms = wall(ba.robust_cost) if loss else None           # what an LM iteration under a loss pays for its accept test
+    to_tol = {}
+    if a.to_tol:
+        for tol in (1e-2, 1e-4):
+            res = {}
+
+            def solve_tol():
+                res["info"] = ba.solve_step(lam, max_iters=a.tol_max_iters, rel_tol=tol, out=(dc, dp))[2]
+
+            w = wall(solve_tol)
+            to_tol["to_rel_tol_%g" % tol] = dict(w, iterations=res["info"]["iterations"], status=res["info"]["status"],
+                                                 rel_residual=res["info"]["rel_residual"])
     out = {
-        "blocks": a.blocks, "loss": a.loss, "loss_scale": a.loss_scale if a.loss else None, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts, "lambda": lam,
+        "blocks": a.blocks, "preconditioner": a.preconditioner, "loss": a.loss, "loss_scale": a.loss_scale if a.loss else None, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts, "lambda": lam,
         "points_pass": dict(us_p, algorithmic_bytes=bytes_p, frac_of_8TBs=frac(bytes_p, us_p["median_us"])),
         "cameras_pass": dict(us_c, algorithmic_bytes=bytes_c, frac_of_8TBs=frac(bytes_c, us_c["median_us"])),
         "both_passes_us": round(us_p["median_us"] + us_c["median_us"], 1),
@@ -123,6 +150,9 @@ def main():
         "pcg_iteration_ms": round((s25["median_ms"] - s0["median_ms"]) / 25.0, 3),
         "apply_step": ap_ms,
         **({"robust_cost": rc_ms} if loss else {}),
+        **({"schur_jacobi_pass": dict(us_m, algorithmic_bytes=bytes_m, frac_of_8TBs=frac(bytes_m, us_m["median_us"])),
+            "fallbacks": ba.preconditioner_fallbacks()} if sj else {}),
+        **to_tol,
         "info_25": info[25],
     }
     ba.close()
