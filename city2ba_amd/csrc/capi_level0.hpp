@@ -1299,7 +1299,8 @@ static bool good_loss(int kind, double scale) { return kind == 0 || (kind >= 1 &
 #define NEED_LOSS(kind, scale, who) \
     if (!good_loss(kind, scale)) return fail(C2B_ERR_INVALID_ARGUMENT, who ": loss kind must be 0..3 and its scale finite and > 0")
 
-// the *_rows entries and their *_loss twins: kind 0 launches the squared-loss kernels, any other kind the weighted ones
+// the *_rows entries and their *_loss forms: kind 0 launches the squared-loss instance of a pass (the empty pack), any
+// other kind the weighted one (with_loss, normal_kernels.hpp)
 static int normal_cameras_rows_impl(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
                                     const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
                                     void *workspace, double *sum_sq, int kind, double scale, void *stream) {
@@ -1320,25 +1321,23 @@ static int normal_cameras_rows_impl(const double *camblk, const double *pts4, co
     const unsigned grid = (unsigned)((quads + waves - 1) / waves < kNormMaxGrid ? (quads + waves - 1) / waves : kNormMaxGrid);
     const double4 *p4 = reinterpret_cast<const double4 *>(pts4);
     const double2 *uv = reinterpret_cast<const double2 *>(uv_obs);
-    if (kind != kLossSquared) {
-        const double a2 = scale * scale;
-        hipLaunchKernelGGL(k_normal_cameras_loss, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv, U, gc,
-                           kind, a2);
-        if (sum_sq) {                                        // the weighted sum of squares: a pass of its own (see k_robust_cost)
-            double *block_part = reinterpret_cast<double *>(workspace) + kWsBlockPart;
+    const double a2 = scale * scale;
+    double *block_part = sum_sq ? reinterpret_cast<double *>(workspace) + kWsBlockPart : nullptr;
+    if (sum_sq && kind == kLossSquared) {
+        hipLaunchKernelGGL(k_normal_cameras<true>, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv,
+                           U, gc, block_part);
+        hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)block_part, (int)(grid * waves), sum_sq);
+    } else {
+        with_loss(kind, a2, [&](auto... loss) {
+            hipLaunchKernelGGL((k_normal_cameras<false, decltype(loss)...>), dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr,
+                               (int)n_cam, pt_idx, uv, U, gc, (double *)nullptr, loss...);
+        });
+        if (sum_sq) {                                        // under a loss: the weighted sum of squares, a pass of its own (k_robust_cost)
             const unsigned nb = blocks_for(n_obs, kNormBlock);   // <= block_part_slots(n_obs): one partial per 4 tiles of 64
             if (nb) hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, st, camblk, p4, (const uint32_t *)nullptr, row_ptr,
                                        (int)n_cam, pt_idx, uv, n_obs, kind, a2, block_part);
             hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)block_part, (int)nb, sum_sq);
         }
-    } else if (sum_sq) {
-        double *block_part = reinterpret_cast<double *>(workspace) + kWsBlockPart;
-        hipLaunchKernelGGL(k_normal_cameras<true>, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv,
-                           U, gc, block_part);
-        hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)block_part, (int)(grid * waves), sum_sq);
-    } else {
-        hipLaunchKernelGGL(k_normal_cameras<false>, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv,
-                           U, gc, nullptr);
     }
     LAUNCH_CHECK();
     return C2B_OK;
@@ -1371,14 +1370,11 @@ static int normal_points_rows_impl(const double *camblk, const double *pts4, int
         (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: misaligned pointer");
     if (!n_pts) return C2B_OK;
-    if (kind != kLossSquared)
-        hipLaunchKernelGGL(k_normal_points_loss, dim3((unsigned)((n_pts + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0, S(stream),
-                           camblk, reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
-                           reinterpret_cast<const double2 *>(uv_obs), V, gp, kind, scale * scale);
-    else
-        hipLaunchKernelGGL(k_normal_points, dim3((unsigned)((n_pts + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0, S(stream), camblk,
-                           reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
-                           reinterpret_cast<const double2 *>(uv_obs), V, gp);
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        hipLaunchKernelGGL(k_normal_points<decltype(loss)...>, dim3((unsigned)((n_pts + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0,
+                           S(stream), camblk, reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
+                           reinterpret_cast<const double2 *>(uv_obs), V, gp, loss...);
+    });
     LAUNCH_CHECK();
     return C2B_OK;
 }
@@ -1415,14 +1411,11 @@ static int schur_points_rows_impl(const double *camblk, const double *pts4, int6
         !aligned8(h_pts) || !aligned8(t_pts) || (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: misaligned pointer");
     if (!n_pts) return C2B_OK;
-    if (kind != kLossSquared)
-        hipLaunchKernelGGL(k_schur_points_loss<false>, dim3(blocks_for(n_pts, kSchurBlock)), dim3(kSchurBlock), 0, S(stream), camblk,
-                           reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
-                           reinterpret_cast<const double2 *>(uv_obs), V, lambda, x_cam, h_pts, t_pts, kind, scale * scale);
-    else
-        hipLaunchKernelGGL(k_schur_points<false>, dim3(blocks_for(n_pts, kSchurBlock)), dim3(kSchurBlock), 0, S(stream), camblk,
-                           reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
-                           reinterpret_cast<const double2 *>(uv_obs), V, lambda, x_cam, h_pts, t_pts);
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        hipLaunchKernelGGL((k_schur_points<false, decltype(loss)...>), dim3(blocks_for(n_pts, kSchurBlock)), dim3(kSchurBlock), 0, S(stream),
+                           camblk, reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
+                           reinterpret_cast<const double2 *>(uv_obs), V, lambda, x_cam, h_pts, t_pts, loss...);
+    });
     LAUNCH_CHECK();
     return C2B_OK;
 }
@@ -1463,24 +1456,18 @@ static int schur_cameras_rows_impl(const double *camblk, const double *pts4, con
         !aligned8(t_pts) || !aligned8(y_cam) || (reinterpret_cast<uintptr_t>(pt_idx) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: misaligned pointer");
     if (!n_cam) return C2B_OK;
-    if (kind != kLossSquared) {
-        const double a2 = scale * scale;
+    with_loss(kind, scale * scale, [&](auto... loss) {
         if (x_cam)
-            hipLaunchKernelGGL(k_schur_cameras_loss<kSchurApply>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
-                               reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
-                               U, lambda, x_cam, (const double *)nullptr, t_pts, y_cam, (double *)nullptr, kind, a2);
+            hipLaunchKernelGGL((k_schur_cameras<kSchurApply, decltype(loss)...>), dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0,
+                               S(stream), camblk, reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx,
+                               reinterpret_cast<const double2 *>(uv_obs), U, lambda, x_cam, (const double *)nullptr, t_pts, y_cam,
+                               (double *)nullptr, loss...);
         else
-            hipLaunchKernelGGL(k_schur_cameras_loss<kSchurNoX>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
-                               reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
-                               U, lambda, (const double *)nullptr, (const double *)nullptr, t_pts, y_cam, (double *)nullptr, kind, a2);
-    } else if (x_cam)
-        hipLaunchKernelGGL(k_schur_cameras<kSchurApply>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
-                           reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
-                           U, lambda, x_cam, nullptr, t_pts, y_cam, nullptr);
-    else
-        hipLaunchKernelGGL(k_schur_cameras<kSchurNoX>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
-                           reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
-                           U, lambda, nullptr, nullptr, t_pts, y_cam, nullptr);
+            hipLaunchKernelGGL((k_schur_cameras<kSchurNoX, decltype(loss)...>), dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0,
+                               S(stream), camblk, reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx,
+                               reinterpret_cast<const double2 *>(uv_obs), U, lambda, (const double *)nullptr, (const double *)nullptr, t_pts,
+                               y_cam, (double *)nullptr, loss...);
+    });
     LAUNCH_CHECK();
     return C2B_OK;
 }
@@ -1515,14 +1502,11 @@ static int schur_jacobi_rows_impl(const double *camblk, const double *pts4, cons
         !aligned8(M) || (reinterpret_cast<uintptr_t>(pt_idx) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: misaligned pointer");
     if (!n_cam) return C2B_OK;
-    if (kind != kLossSquared)
-        hipLaunchKernelGGL(k_schur_jacobi_loss, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        hipLaunchKernelGGL(k_schur_jacobi<decltype(loss)...>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
                            reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
-                           U, V, lambda, M, kind, scale * scale);
-    else
-        hipLaunchKernelGGL(k_schur_jacobi, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
-                           reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
-                           U, V, lambda, M);
+                           U, V, lambda, M, loss...);
+    });
     LAUNCH_CHECK();
     return C2B_OK;
 }

@@ -761,18 +761,14 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     const int kind = p->loss_kind;                           // 0: every launch below is the squared-loss kernel it always was
     const double a2 = p->loss_scale * p->loss_scale;
     auto points = [&](const double *x, const double *h, double *t, bool neg) {
-        if (kind != kLossSquared && neg)
-            hipLaunchKernelGGL(k_schur_points_loss<true>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
-                               p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, kind, a2);
-        else if (kind != kLossSquared)
-            hipLaunchKernelGGL(k_schur_points_loss<false>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
-                               p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, kind, a2);
-        else if (neg)
-            hipLaunchKernelGGL(k_schur_points<true>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
-                               p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t);
-        else
-            hipLaunchKernelGGL(k_schur_points<false>, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, p->camblk, p4, np,
-                               p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t);
+        with_loss(kind, a2, [&](auto... loss) {
+            if (neg)
+                hipLaunchKernelGGL((k_schur_points<true, decltype(loss)...>), dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st,
+                                   p->camblk, p4, np, p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, loss...);
+            else
+                hipLaunchKernelGGL((k_schur_points<false, decltype(loss)...>), dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st,
+                                   p->camblk, p4, np, p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, loss...);
+        });
     };
     double h[kScSlots];
     auto fetch = [&](int slots) -> int {                     // the first `slots` scalars to the host, after all queued work
@@ -798,13 +794,11 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
         hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
     }
     points(nullptr, B.gp, B.t, false);
-    if (kind != kLossSquared)
-        hipLaunchKernelGGL(k_schur_cameras_loss<kSchurRhs>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
-                           p->pt_idx, uv, (const double *)B.U, lambda, (const double *)nullptr, (const double *)B.gc, (const double *)B.t,
-                           B.r, (double *)nullptr, kind, a2);
-    else
-        hipLaunchKernelGGL(k_schur_cameras<kSchurRhs>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc, p->pt_idx,
-                           uv, (const double *)B.U, lambda, nullptr, (const double *)B.gc, (const double *)B.t, B.r, nullptr);
+    with_loss(kind, a2, [&](auto... loss) {
+        hipLaunchKernelGGL((k_schur_cameras<kSchurRhs, decltype(loss)...>), dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr,
+                           (int)nc, p->pt_idx, uv, (const double *)B.U, lambda, (const double *)nullptr, (const double *)B.gc,
+                           (const double *)B.t, B.r, (double *)nullptr, loss...);
+    });
     hipLaunchKernelGGL(k_pcg_update<true>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc, 0, dc,
                        B.r, B.pv, (const double *)nullptr, B.z, B.pa, B.pb);
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbc, B.sc + kScRr);
@@ -823,14 +817,11 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
         while (it < max_iters) {
             const int cur = (it & 1) ? kScRz1 : kScRz0, nxt = (it & 1) ? kScRz0 : kScRz1;
             points(B.pv, nullptr, B.t, false);
-            if (kind != kLossSquared)
-                hipLaunchKernelGGL(k_schur_cameras_loss<kSchurDot>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
-                                   p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv, (const double *)nullptr,
-                                   (const double *)B.t, B.q, B.pa, kind, a2);
-            else
-                hipLaunchKernelGGL(k_schur_cameras<kSchurDot>, dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr, (int)nc,
-                                   p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv, (const double *)nullptr,
-                                   (const double *)B.t, B.q, B.pa);
+            with_loss(kind, a2, [&](auto... loss) {
+                hipLaunchKernelGGL((k_schur_cameras<kSchurDot, decltype(loss)...>), dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4,
+                                   p->rows_ptr, (int)nc, p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv,
+                                   (const double *)nullptr, (const double *)B.t, B.q, B.pa, loss...);
+            });
             hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, n_cpart, B.sc + kScPq);
             hipLaunchKernelGGL(k_pcg_update<false>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc,
                                cur, dc, B.r, B.pv, (const double *)B.q, B.z, B.pa, B.pb);
@@ -852,12 +843,10 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
 
     // dp = -V_l^-1 (gp + W^T dc); then |r|^2 and the model decrease from J, per observation
     points(dc, B.gp, dp, true);
-    if (kind != kLossSquared)
-        hipLaunchKernelGGL(k_schur_model_loss, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
-                           (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb, kind, a2);
-    else
-        hipLaunchKernelGGL(k_schur_model, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
-                           (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb);
+    with_loss(kind, a2, [&](auto... loss) {
+        hipLaunchKernelGGL(k_schur_model<decltype(loss)...>, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                           (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb, loss...);
+    });
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbo, B.sc + kScSumSq);
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pb, (int)nbo, B.sc + kScModel);
     if ((rc = fetch(schur_jacobi ? kScFallback + 1 : kScModel + 1))) return rc;

@@ -16,10 +16,12 @@
 //     scan, a fill through integer atomic cursors (arbitrary order), then each slot's final place by rank within its
 //     point's list (observation indices are unique, so the rank is a permutation): the result is exactly the stable
 //     argsort of pt_idx.  The rank step costs k^2 loads for a point of k observations (cached; k is tens here).
-//   * robust losses (k_*_loss): iteratively reweighted least squares.  An observation's weight w = rho'(s),
+//   * robust losses: iteratively reweighted least squares.  An observation's weight w = rho'(s),
 //     s = |r|^2, is recomputed from the r jacobian_obs returns and (r, Jc, Jp) are scaled by sqrt(w) before anything is
-//     accumulated: no weight array, no extra memory traffic.  The squared-loss kernels are untouched text; each weighted
-//     kernel is a copy of its original with that one line added (k_normal_cameras_loss explains why).
+//     accumulated: no weight array, no extra memory traffic.  Every pass over the observations is one kernel template
+//     with a trailing parameter pack `class... Loss`: empty, the instance is the squared-loss kernel, its arguments and
+//     its code what they were before losses existed; <..., int, double> takes (kind, a2) last and makes that one call
+//     (loss_scale_obs explains why a pack).
 #pragma once
 #include "kernels.hpp"
 
@@ -67,7 +69,14 @@ C2B_DEV double loss_rho(int kind, double a2, double s) {
     return s;
 }
 
-// (r, Jc, Jp) *= sqrt(w): the one substitution every weighted pass makes, right after jacobian_obs
+// (r, Jc, Jp) *= sqrt(w): the one substitution every weighted pass makes, right after jacobian_obs, as
+//     if constexpr (sizeof...(Loss) > 0) loss_scale_obs(loss..., r0, r1, jc, jp);
+// with (kind, a2) the kernel's own trailing pack `Loss... loss`.  The pack is the mechanism because it leaves the
+// empty instance exactly the kernel it was, signature and body: the squared-loss kernels are pinned to the code they
+// compiled to before losses existed.  The other way of sharing the text did not: as instances of a common C2B_DEV body
+// with a LOSS flag, k_schur_cameras<kSchurApply> went from 110 to 128 VGPRs and k_normal_cameras from 252 to 248, and
+// the rest kept their registers but not their code.  A run-time flag would put the weighting's code and registers into
+// the squared-loss kernel itself.  tests/test_isa_pins.py holds both instances of every pass to their registers.
 C2B_DEV void loss_scale_obs(int kind, double a2, double &r0, double &r1, double jc[18], double jp[6]) {
     const double sw = sqrt(loss_weight(kind, a2, r0 * r0 + r1 * r1));
     r0 *= sw; r1 *= sw;
@@ -75,6 +84,14 @@ C2B_DEV void loss_scale_obs(int kind, double a2, double &r0, double &r1, double 
     for (int k = 0; k < 18; ++k) jc[k] *= sw;
 #pragma unroll
     for (int k = 0; k < 6; ++k) jp[k] *= sw;
+}
+
+// host side of the pack: launch(kind, a2) under a loss, launch() without, so a pass is launched from one place as
+//     with_loss(kind, a2, [&](auto... loss) { hipLaunchKernelGGL((k_x<..., decltype(loss)...>), ..., loss...); });
+template <class Launch>
+inline void with_loss(int kind, double a2, Launch &&launch) {
+    if (kind != kLossSquared) launch(kind, a2);
+    else launch();
 }
 
 // ---- point-major transpose ----------------------------------------------------------------------------------
@@ -134,11 +151,14 @@ __global__ __launch_bounds__(256) void k_nt_rank(const uint32_t *__restrict__ pt
 }
 
 // ---- camera pass ---------------------------------------------------------------------------------------------
-template <bool WITH_SUM>
+// The weighted camera pass is k_normal_cameras<false, int, double>: it has no sum of squares.  With the fold of
+// k_normal_cameras<true> it needs two scalar registers more than there are, so the weighted sum is k_robust_cost<true>'s.
+template <bool WITH_SUM, class... Loss>
 __global__ __launch_bounds__(kNormBlock) void k_normal_cameras(
     const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
     const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, double *__restrict__ U, double *__restrict__ gc,
-    double *__restrict__ block_part) {
+    double *__restrict__ block_part, Loss... loss) {
+    static_assert(!(WITH_SUM && sizeof...(Loss) > 0), "the weighted camera pass has no scalar registers left for the sum's fold");
     constexpr int kWaves = kNormBlock / 64;
     __shared__ double sAcc[kWaves * kNormCamsPerWave * kNormAcc];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
@@ -159,6 +179,7 @@ __global__ __launch_bounds__(kNormBlock) void k_normal_cameras(
         for (uint64_t o = b + gl; o < e; o += kNormG) {
             double r0, r1, jc[18], jp[6];
             jacobian_obs(cam, pts4[pt_idx[o]], uv_obs[o], r0, r1, jc, jp);
+            if constexpr (sizeof...(Loss) > 0) loss_scale_obs(loss..., r0, r1, jc, jp);
 #pragma unroll
             for (int a = 0; a < 9; ++a) {
 #pragma unroll
@@ -203,73 +224,6 @@ __global__ __launch_bounds__(kNormBlock) void k_normal_cameras(
     }
 }
 
-// Its weighted twin: k_normal_cameras<false> with (r, Jc, Jp) scaled by sqrt(w), so U and gc are the reweighted system's.
-// A copy of the text, not an instance of a shared body or of a flag on the kernel: the squared-loss kernels are pinned to
-// the code they compiled to before losses existed, and routed through a shared C2B_DEV body they came out changed
-// (252 -> 248 VGPRs here).  tests/test_robust_kernel_twins.py holds every twin to its original's text.  It has no sum
-// of squares: with the fold of k_normal_cameras<true> it needs two scalar registers more than there are, so the
-// weighted sum is k_robust_cost<true>'s.
-__global__ __launch_bounds__(kNormBlock) void k_normal_cameras_loss(
-    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
-    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, double *__restrict__ U, double *__restrict__ gc,
-    int kind, double a2) {
-    constexpr int kWaves = kNormBlock / 64;
-    __shared__ double sAcc[kWaves * kNormCamsPerWave * kNormAcc];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
-    double *mine = sAcc + (wave * kNormCamsPerWave + grp) * kNormAcc;
-    const int n_quads = (n_cam + kNormCamsPerWave - 1) / kNormCamsPerWave;          // 32-bit: this kernel has no scalar
-    const int wave_step = (int)gridDim.x * kWaves;                                  // registers to spare (n_cam < 2^31)
-#pragma unroll 1
-    for (int q = (int)blockIdx.x * kWaves + wave; q < n_quads; q += wave_step) {   // wave-uniform
-        const int c = q * kNormCamsPerWave + grp;
-        const bool cam_ok = c < n_cam;
-        const uint64_t b = cam_ok ? row_ptr[c] : 0, e = cam_ok ? row_ptr[c + 1] : 0;
-        const CamRef cam = cam_ref(camblk, cam_ok ? (uint32_t)c : 0u);
-        double acc[kNormAcc];
-#pragma unroll
-        for (int k = 0; k < kNormAcc; ++k) acc[k] = 0.0;
-#pragma unroll 1
-        for (uint64_t o = b + gl; o < e; o += kNormG) {
-            double r0, r1, jc[18], jp[6];
-            jacobian_obs(cam, pts4[pt_idx[o]], uv_obs[o], r0, r1, jc, jp);
-            loss_scale_obs(kind, a2, r0, r1, jc, jp);
-#pragma unroll
-            for (int a = 0; a < 9; ++a) {
-#pragma unroll
-                for (int d = a; d < 9; ++d) acc[sym9(a, d)] += jc[a] * jc[d] + jc[9 + a] * jc[9 + d];
-                acc[kNormSym + a] += jc[a] * r0 + jc[9 + a] * r1;
-            }
-        }
-        // fixed tree over the group's 16 lanes (xor: every lane ends with the same bits)
-#pragma unroll
-        for (int off = kNormG / 2; off > 0; off >>= 1) {
-#pragma unroll
-            for (int k = 0; k < kNormAcc; ++k) acc[k] += __shfl_xor(acc[k], off, 64);
-        }
-        if (gl == 0) {
-#pragma unroll
-            for (int k = 0; k < kNormAcc; ++k) mine[k] = acc[k];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (cam_ok) {
-            // both triangles from one packed entry: U[a][d] and U[d][a] are the same bits; 16 lanes write a row of 81 + 9
-            double *Uc = U + (int64_t)c * 81;
-#pragma unroll
-            for (int t = 0; t < 6; ++t) {
-                const int i = gl + t * kNormG;
-                if (i < 81) {
-                    const int a = i / 9, d = i % 9;
-                    Uc[i] = mine[a <= d ? sym9(a, d) : sym9(d, a)];
-                }
-            }
-            if (gl < 9) gc[(int64_t)c * 9 + gl] = mine[kNormSym + gl];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
 // the wave partials of k_normal_cameras in a fixed order (one workgroup): thread t sums partials t, t + 256, ...
 __global__ __launch_bounds__(256) void k_normal_sum(const double *__restrict__ block_part, int n, double *__restrict__ out_sum) {
     __shared__ double sRed[4];
@@ -282,10 +236,11 @@ __global__ __launch_bounds__(256) void k_normal_sum(const double *__restrict__ b
 }
 
 // ---- point pass ------------------------------------------------------------------------------------------------
+template <class... Loss>
 __global__ __launch_bounds__(kNormBlock) void k_normal_points(
     const double *__restrict__ camblk, const double4 *__restrict__ pts4, int64_t n_pts, const uint64_t *__restrict__ pt_row_ptr,
     const uint32_t *__restrict__ obs_of, const uint32_t *__restrict__ cam_of, const double2 *__restrict__ uv_obs,
-    double *__restrict__ V, double *__restrict__ gp) {
+    double *__restrict__ V, double *__restrict__ gp, Loss... loss) {
     const int64_t p = (int64_t)blockIdx.x * kNormBlock + threadIdx.x;
     if (p >= n_pts) return;
     const uint64_t b = pt_row_ptr[p], e = pt_row_ptr[p + 1];
@@ -296,40 +251,7 @@ __global__ __launch_bounds__(kNormBlock) void k_normal_points(
             const uint32_t o = obs_of[j];
             double r0, r1, jc[18], jp[6];
             jacobian_obs(cam_ref(camblk, cam_of[j]), X, uv_obs[o], r0, r1, jc, jp);
-            v00 += jp[0] * jp[0] + jp[3] * jp[3];
-            v01 += jp[0] * jp[1] + jp[3] * jp[4];
-            v02 += jp[0] * jp[2] + jp[3] * jp[5];
-            v11 += jp[1] * jp[1] + jp[4] * jp[4];
-            v12 += jp[1] * jp[2] + jp[4] * jp[5];
-            v22 += jp[2] * jp[2] + jp[5] * jp[5];
-            g0 += jp[0] * r0 + jp[3] * r1;
-            g1 += jp[1] * r0 + jp[4] * r1;
-            g2 += jp[2] * r0 + jp[5] * r1;
-        }
-    }
-    double *Vp = V + p * 9;
-    Vp[0] = v00; Vp[1] = v01; Vp[2] = v02;
-    Vp[3] = v01; Vp[4] = v11; Vp[5] = v12;
-    Vp[6] = v02; Vp[7] = v12; Vp[8] = v22;
-    gp[3 * p] = g0; gp[3 * p + 1] = g1; gp[3 * p + 2] = g2;
-}
-
-// its weighted twin (a copy: see k_normal_cameras_loss)
-__global__ __launch_bounds__(kNormBlock) void k_normal_points_loss(
-    const double *__restrict__ camblk, const double4 *__restrict__ pts4, int64_t n_pts, const uint64_t *__restrict__ pt_row_ptr,
-    const uint32_t *__restrict__ obs_of, const uint32_t *__restrict__ cam_of, const double2 *__restrict__ uv_obs,
-    double *__restrict__ V, double *__restrict__ gp, int kind, double a2) {
-    const int64_t p = (int64_t)blockIdx.x * kNormBlock + threadIdx.x;
-    if (p >= n_pts) return;
-    const uint64_t b = pt_row_ptr[p], e = pt_row_ptr[p + 1];
-    double v00 = 0.0, v01 = 0.0, v02 = 0.0, v11 = 0.0, v12 = 0.0, v22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
-    if (e > b) {
-        const double4 X = pts4[p];
-        for (uint64_t j = b; j < e; ++j) {
-            const uint32_t o = obs_of[j];
-            double r0, r1, jc[18], jp[6];
-            jacobian_obs(cam_ref(camblk, cam_of[j]), X, uv_obs[o], r0, r1, jc, jp);
-            loss_scale_obs(kind, a2, r0, r1, jc, jp);
+            if constexpr (sizeof...(Loss) > 0) loss_scale_obs(loss..., r0, r1, jc, jp);
             v00 += jp[0] * jp[0] + jp[3] * jp[3];
             v01 += jp[0] * jp[1] + jp[3] * jp[4];
             v02 += jp[0] * jp[2] + jp[3] * jp[5];
@@ -350,7 +272,7 @@ __global__ __launch_bounds__(kNormBlock) void k_normal_points_loss(
 
 // ---- robust cost -----------------------------------------------------------------------------------------------
 // one projection per observation, one partial per workgroup (k_normal_sum adds them): sum rho(s), what a loop under a loss
-// minimises; WEIGHTED_SQ: sum w s instead, the weighted sum of squares (k_normal_cameras_loss with the fold of
+// minimises; WEIGHTED_SQ: sum w s instead, the weighted sum of squares (the weighted k_normal_cameras with the fold of
 // k_normal_cameras<true> needs two scalar registers more than there are, so under a loss the sum is this pass).
 // cam_idx == NULL: the observation's camera is searched in row_ptr
 template <bool WEIGHTED_SQ>

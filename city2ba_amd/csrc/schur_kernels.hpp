@@ -14,8 +14,10 @@
 //   * k_schur_model: ||r||^2 and ||r||^2 - ||r + Jc dc + Jp dp||^2 per observation, one partial per workgroup.
 // Damping (Marquardt with Ceres' clamps): A_l = A + lambda diag(d), d_i = min(max(A_ii, 1e-6), 1e32).
 // Every partial is summed by k_normal_sum in a fixed order; no float atomics, so the same inputs give the same bits.
-// Robust losses (k_*_loss): the passes over the observations scale (r, Jc, Jp) by sqrt(w) right after jacobian_obs
-// (loss_scale_obs, normal_kernels.hpp); each is a copy of its squared-loss kernel's text with that line added.
+// Robust losses: the passes over the observations scale (r, Jc, Jp) by sqrt(w) right after jacobian_obs.  Each is one
+// template with a trailing pack `class... Loss`: empty is the squared-loss kernel as it always was, <..., int, double>
+// takes (kind, a2) last and makes that one call (loss_scale_obs, normal_kernels.hpp, says why a pack and not a shared
+// device body or a flag).
 #pragma once
 #include "normal_kernels.hpp"
 
@@ -42,59 +44,12 @@ C2B_DEV void block_sum_to(double v, double *sRed, double *__restrict__ out) {
 
 // ---- point pass ----------------------------------------------------------------------------------------------
 // t_p = (NEG ? -1 : 1) V_l,p^-1 (h_p + sum_o Jp_o^T (Jc_o x_c(o))); h == NULL is 0, x == NULL is 0 (no observation read)
-template <bool NEG>
+template <bool NEG, class... Loss>
 __global__ __launch_bounds__(kSchurBlock) void k_schur_points(
     const double *__restrict__ camblk, const double4 *__restrict__ pts4, int64_t n_pts, const uint64_t *__restrict__ pt_row_ptr,
     const uint32_t *__restrict__ obs_of, const uint32_t *__restrict__ cam_of, const double2 *__restrict__ uv_obs,
-    const double *__restrict__ V, double lam, const double *__restrict__ x, const double *__restrict__ h, double *__restrict__ t) {
-    const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
-    if (p >= n_pts) return;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    if (h) { a0 = h[3 * p]; a1 = h[3 * p + 1]; a2 = h[3 * p + 2]; }
-    if (x) {
-        const uint64_t b = pt_row_ptr[p], e = pt_row_ptr[p + 1];
-        if (e > b) {
-            const double4 X = pts4[p];
-            for (uint64_t j = b; j < e; ++j) {
-                const uint32_t o = obs_of[j], c = cam_of[j];
-                double r0, r1, jc[18], jp[6];
-                jacobian_obs(cam_ref(camblk, c), X, uv_obs[o], r0, r1, jc, jp);
-                const double *xc = x + (int64_t)c * 9;
-                double z0 = 0.0, z1 = 0.0;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    const double xk = xc[k];
-                    z0 += jc[k] * xk;
-                    z1 += jc[9 + k] * xk;
-                }
-                a0 += jp[0] * z0 + jp[3] * z1;
-                a1 += jp[1] * z0 + jp[4] * z1;
-                a2 += jp[2] * z0 + jp[5] * z1;
-            }
-        }
-    }
-    // V_l = L L^T, L in registers (the reciprocals of its diagonal)
-    const double *Vp = V + p * 9;
-    const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
-    const double i0 = 1.0 / sqrt(v00);
-    const double l10 = v10 * i0, l20 = v20 * i0;
-    const double i1 = 1.0 / sqrt(v11 - l10 * l10);
-    const double l21 = (v21 - l20 * l10) * i1;
-    const double i2 = 1.0 / sqrt((v22 - l20 * l20) - l21 * l21);
-    const double y0 = a0 * i0, y1 = (a1 - l10 * y0) * i1, y2 = ((a2 - l20 * y0) - l21 * y1) * i2;
-    const double t2 = y2 * i2, t1 = (y1 - l21 * t2) * i1, t0 = ((y0 - l10 * t1) - l20 * t2) * i0;
-    t[3 * p] = NEG ? -t0 : t0;
-    t[3 * p + 1] = NEG ? -t1 : t1;
-    t[3 * p + 2] = NEG ? -t2 : t2;
-}
-
-// its weighted twin (a copy: see k_normal_cameras_loss in normal_kernels.hpp)
-template <bool NEG>
-__global__ __launch_bounds__(kSchurBlock) void k_schur_points_loss(
-    const double *__restrict__ camblk, const double4 *__restrict__ pts4, int64_t n_pts, const uint64_t *__restrict__ pt_row_ptr,
-    const uint32_t *__restrict__ obs_of, const uint32_t *__restrict__ cam_of, const double2 *__restrict__ uv_obs,
     const double *__restrict__ V, double lam, const double *__restrict__ x, const double *__restrict__ h, double *__restrict__ t,
-    int kind, double la2) {
+    Loss... loss) {
     const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
     if (p >= n_pts) return;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -107,7 +62,7 @@ __global__ __launch_bounds__(kSchurBlock) void k_schur_points_loss(
                 const uint32_t o = obs_of[j], c = cam_of[j];
                 double r0, r1, jc[18], jp[6];
                 jacobian_obs(cam_ref(camblk, c), X, uv_obs[o], r0, r1, jc, jp);
-                loss_scale_obs(kind, la2, r0, r1, jc, jp);
+                if constexpr (sizeof...(Loss) > 0) loss_scale_obs(loss..., r0, r1, jc, jp);
                 const double *xc = x + (int64_t)c * 9;
                 double z0 = 0.0, z1 = 0.0;
 #pragma unroll
@@ -142,12 +97,12 @@ __global__ __launch_bounds__(kSchurBlock) void k_schur_points_loss(
 //   kSchurApply: y_c = U_l,c x_c - s_c;  kSchurNoX: y_c = -s_c (x unused);  kSchurDot: as kSchurApply, and sum_c x_c . y_c
 //   leaves as one partial per wave in block_part;  kSchurRhs: y_c = s_c - h_c (the reduced right-hand side when
 //   t = V_l^-1 gp, h = gc).  One instance per mode: a pointer its mode does not read costs it no scalar registers.
-template <int MODE>
+template <int MODE, class... Loss>
 __global__ __launch_bounds__(kNormBlock) void k_schur_cameras(
     const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
     const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const double *__restrict__ U, double lam,
     const double *__restrict__ x, const double *__restrict__ h, const double *__restrict__ t, double *__restrict__ y,
-    double *__restrict__ block_part) {
+    double *__restrict__ block_part, Loss... loss) {
     constexpr int kWaves = kNormBlock / 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
     const int q = (int)blockIdx.x * kWaves + wave;                   // one wave per kNormCamsPerWave cameras, no grid-stride loop
@@ -163,71 +118,7 @@ __global__ __launch_bounds__(kNormBlock) void k_schur_cameras(
         const uint32_t pi = pt_idx[o];
         double r0, r1, jc[18], jp[6];
         jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
-        const double *tp = t + (int64_t)pi * 3;
-        const double t0 = tp[0], t1 = tp[1], t2 = tp[2];
-        const double z0 = (jp[0] * t0 + jp[1] * t1) + jp[2] * t2;
-        const double z1 = (jp[3] * t0 + jp[4] * t1) + jp[5] * t2;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) s[k] += jc[k] * z0 + jc[9 + k] * z1;
-    }
-    // fixed xor tree over the group's 16 lanes (every lane ends with the same bits)
-#pragma unroll
-    for (int off = kNormG / 2; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) s[k] += __shfl_xor(s[k], off, 64);
-    }
-    double sg = 0.0;                                                 // s[gl] without a dynamically indexed register array
-#pragma unroll
-    for (int k = 0; k < 9; ++k) sg = gl == k ? s[k] : sg;
-    double yg = 0.0, xg = 0.0;
-    if (cam_ok && gl < 9) {
-        if (MODE == kSchurRhs) {
-            yg = sg - h[(int64_t)c * 9 + gl];
-        } else {
-            double ux = 0.0;
-            if (MODE != kSchurNoX) {
-                const double *Ur = U + (int64_t)c * 81 + gl * 9, *xc = x + (int64_t)c * 9;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    const double u = Ur[k];
-                    ux += (k == gl ? damped(u, lam) : u) * xc[k];
-                }
-                xg = xc[gl];
-            }
-            yg = ux - sg;
-        }
-        y[(int64_t)c * 9 + gl] = yg;
-    }
-    if (MODE == kSchurDot) {                                         // the wave's x.y: its four cameras, in a fixed tree
-        const double w = wave_sum(xg * yg);                          // 0 on lanes gl >= 9 and past n_cam
-        if (lane == 0) block_part[q] = w;
-    }
-}
-
-// its weighted twin, one instance per mode (a copy: see k_normal_cameras_loss; shared through a C2B_DEV body the
-// squared-loss instances changed registers, 110 -> 128 VGPRs in kSchurApply)
-template <int MODE>
-__global__ __launch_bounds__(kNormBlock) void k_schur_cameras_loss(
-    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
-    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const double *__restrict__ U, double lam,
-    const double *__restrict__ x, const double *__restrict__ h, const double *__restrict__ t, double *__restrict__ y,
-    double *__restrict__ block_part, int kind, double la2) {
-    constexpr int kWaves = kNormBlock / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
-    const int q = (int)blockIdx.x * kWaves + wave;                   // one wave per kNormCamsPerWave cameras, no grid-stride loop
-    const int c = q * kNormCamsPerWave + grp;
-    const bool cam_ok = c < n_cam;
-    const uint64_t b = cam_ok ? row_ptr[c] : 0, e = cam_ok ? row_ptr[c + 1] : 0;
-    const CamRef cam = cam_ref(camblk, cam_ok ? (uint32_t)c : 0u);
-    double s[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s[k] = 0.0;
-#pragma unroll 1
-    for (uint64_t o = b + gl; o < e; o += kNormG) {
-        const uint32_t pi = pt_idx[o];
-        double r0, r1, jc[18], jp[6];
-        jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
-        loss_scale_obs(kind, la2, r0, r1, jc, jp);
+        if constexpr (sizeof...(Loss) > 0) loss_scale_obs(loss..., r0, r1, jc, jp);
         const double *tp = t + (int64_t)pi * 3;
         const double t0 = tp[0], t1 = tp[1], t2 = tp[2];
         const double z0 = (jp[0] * t0 + jp[1] * t1) + jp[2] * t2;
@@ -388,10 +279,11 @@ __global__ __launch_bounds__(kSchurBlock) void k_pcg_direction(int64_t n, double
 constexpr int kScFallback = 6;                    // device scalar of a solve: cameras whose Schur-Jacobi factor fell back
 static_assert(kScFallback > kScModel && kScFallback < kScSlots, "kScFallback must be a free slot of c2b_problem::sv_sc");
 
+template <class... Loss>
 __global__ __launch_bounds__(kNormBlock) void k_schur_jacobi(
     const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
     const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const double *__restrict__ U,
-    const double *__restrict__ V, double lam, double *__restrict__ M) {
+    const double *__restrict__ V, double lam, double *__restrict__ M, Loss... loss) {
     constexpr int kWaves = kNormBlock / 64;
     __shared__ double sAcc[kWaves * kNormCamsPerWave * kNormSym];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
@@ -409,77 +301,7 @@ __global__ __launch_bounds__(kNormBlock) void k_schur_jacobi(
         const uint32_t pi = pt_idx[o];
         double r0, r1, jc[18], jp[6];
         jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
-        // V_l = L L^T, L in registers (the reciprocals of its diagonal)
-        const double *Vp = V + (int64_t)pi * 9;
-        const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
-        const double i0 = 1.0 / sqrt(v00);
-        const double l10 = v10 * i0, l20 = v20 * i0;
-        const double i1 = 1.0 / sqrt(v11 - l10 * l10);
-        const double l21 = (v21 - l20 * l10) * i1;
-        const double i2 = 1.0 / sqrt((v22 - l20 * l20) - l21 * l21);
-        const double ya0 = jp[0] * i0, ya1 = (jp[1] - l10 * ya0) * i1, ya2 = ((jp[2] - l20 * ya0) - l21 * ya1) * i2;
-        const double yb0 = jp[3] * i0, yb1 = (jp[4] - l10 * yb0) * i1, yb2 = ((jp[5] - l20 * yb0) - l21 * yb1) * i2;
-        const double f00 = 1.0 - ((ya0 * ya0 + ya1 * ya1) + ya2 * ya2);
-        const double f01 = -((ya0 * yb0 + ya1 * yb1) + ya2 * yb2);
-        const double f11 = 1.0 - ((yb0 * yb0 + yb1 * yb1) + yb2 * yb2);
-#pragma unroll
-        for (int a = 0; a < 9; ++a) {
-            const double g0 = f00 * jc[a] + f01 * jc[9 + a], g1 = f01 * jc[a] + f11 * jc[9 + a];
-#pragma unroll
-            for (int d = a; d < 9; ++d) acc[sym9(a, d)] += g0 * jc[d] + g1 * jc[9 + d];
-        }
-    }
-    // fixed tree over the group's 16 lanes (xor: every lane ends with the same bits)
-#pragma unroll
-    for (int off = kNormG / 2; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < kNormSym; ++k) acc[k] += __shfl_xor(acc[k], off, 64);
-    }
-    if (gl == 0) {
-#pragma unroll
-        for (int k = 0; k < kNormSym; ++k) mine[k] = acc[k];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (cam_ok) {
-        // both triangles from one packed entry: M[a][d] and M[d][a] are the same bits; 16 lanes write a block of 81
-        const double *Uc = U + (int64_t)c * 81;
-        double *Mc = M + (int64_t)c * 81;
-#pragma unroll
-        for (int t = 0; t < 6; ++t) {
-            const int i = gl + t * kNormG;
-            if (i < 81) {
-                const int a = i / 9, d = i % 9;
-                const double s = mine[a <= d ? sym9(a, d) : sym9(d, a)];
-                Mc[i] = a == d ? s + lam * fmin(fmax(Uc[i], 1e-6), 1e32) : s;
-            }
-        }
-    }
-}
-
-// its weighted twin (a copy: see k_normal_cameras_loss): Jc, Jp of the reweighted system, V its V
-__global__ __launch_bounds__(kNormBlock) void k_schur_jacobi_loss(
-    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint64_t *__restrict__ row_ptr, int n_cam,
-    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const double *__restrict__ U,
-    const double *__restrict__ V, double lam, double *__restrict__ M, int kind, double la2) {
-    constexpr int kWaves = kNormBlock / 64;
-    __shared__ double sAcc[kWaves * kNormCamsPerWave * kNormSym];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / kNormG, gl = lane % kNormG;
-    double *mine = sAcc + (wave * kNormCamsPerWave + grp) * kNormSym;
-    const int q = (int)blockIdx.x * kWaves + wave;                   // one wave per kNormCamsPerWave cameras, no grid-stride loop
-    const int c = q * kNormCamsPerWave + grp;
-    const bool cam_ok = c < n_cam;
-    const uint64_t b = cam_ok ? row_ptr[c] : 0, e = cam_ok ? row_ptr[c + 1] : 0;
-    const CamRef cam = cam_ref(camblk, cam_ok ? (uint32_t)c : 0u);
-    double acc[kNormSym];
-#pragma unroll
-    for (int k = 0; k < kNormSym; ++k) acc[k] = 0.0;
-#pragma unroll 1
-    for (uint64_t o = b + gl; o < e; o += kNormG) {
-        const uint32_t pi = pt_idx[o];
-        double r0, r1, jc[18], jp[6];
-        jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
-        loss_scale_obs(kind, la2, r0, r1, jc, jp);
+        if constexpr (sizeof...(Loss) > 0) loss_scale_obs(loss..., r0, r1, jc, jp);
         // V_l = L L^T, L in registers (the reciprocals of its diagonal)
         const double *Vp = V + (int64_t)pi * 9;
         const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
@@ -588,10 +410,11 @@ __global__ __launch_bounds__(kSchurBlock) void k_schur_factor_blocks(int64_t n_c
 
 // ---- model decrease ---------------------------------------------------------------------------------------------
 // per observation e = Jc dc + Jp dp: |r|^2 and |r|^2 - |r + e|^2 = -(2r + e).e, one partial of each per workgroup
+template <class... Loss>
 __global__ __launch_bounds__(kSchurBlock) void k_schur_model(
     const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint32_t *__restrict__ cam_idx,
     const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, int64_t n_obs, const double *__restrict__ dc,
-    const double *__restrict__ dp, double *__restrict__ part_sq, double *__restrict__ part_md) {
+    const double *__restrict__ dp, double *__restrict__ part_sq, double *__restrict__ part_md, Loss... loss) {
     __shared__ double sRed[2][4];
     const int64_t o = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
     double sq = 0.0, md = 0.0;
@@ -599,38 +422,7 @@ __global__ __launch_bounds__(kSchurBlock) void k_schur_model(
         const uint32_t c = cam_idx[o], pi = pt_idx[o];
         double r0, r1, jc[18], jp[6];
         jacobian_obs(cam_ref(camblk, c), pts4[pi], uv_obs[o], r0, r1, jc, jp);
-        const double *dcc = dc + (int64_t)c * 9, *dpp = dp + (int64_t)pi * 3;
-        double e0 = 0.0, e1 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            e0 += jc[k] * dcc[k];
-            e1 += jc[9 + k] * dcc[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            e0 += jp[k] * dpp[k];
-            e1 += jp[3 + k] * dpp[k];
-        }
-        sq = r0 * r0 + r1 * r1;
-        md = -((2.0 * r0 + e0) * e0 + (2.0 * r1 + e1) * e1);
-    }
-    block_sum_to(sq, sRed[0], part_sq + blockIdx.x);
-    block_sum_to(md, sRed[1], part_md + blockIdx.x);
-}
-
-// its weighted twin (a copy): of the reweighted r and e, so w |r|^2 and -w (2r + e).e -- what the step modelled
-__global__ __launch_bounds__(kSchurBlock) void k_schur_model_loss(
-    const double *__restrict__ camblk, const double4 *__restrict__ pts4, const uint32_t *__restrict__ cam_idx,
-    const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, int64_t n_obs, const double *__restrict__ dc,
-    const double *__restrict__ dp, double *__restrict__ part_sq, double *__restrict__ part_md, int kind, double la2) {
-    __shared__ double sRed[2][4];
-    const int64_t o = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
-    double sq = 0.0, md = 0.0;
-    if (o < n_obs) {
-        const uint32_t c = cam_idx[o], pi = pt_idx[o];
-        double r0, r1, jc[18], jp[6];
-        jacobian_obs(cam_ref(camblk, c), pts4[pi], uv_obs[o], r0, r1, jc, jp);
-        loss_scale_obs(kind, la2, r0, r1, jc, jp);
+        if constexpr (sizeof...(Loss) > 0) loss_scale_obs(loss..., r0, r1, jc, jp);
         const double *dcc = dc + (int64_t)c * 9, *dpp = dp + (int64_t)pi * 3;
         double e0 = 0.0, e1 = 0.0;
 #pragma unroll

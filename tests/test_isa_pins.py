@@ -52,6 +52,32 @@ def test_headline_kernel_resources(isa):
     assert jac[0]["vgpr"] <= 128 and jac[0]["lds"] <= 80 * 1024       # 4 waves per SIMD, two workgroups per CU
 
 
+# Both instances of every pass over the observations that carries the robust losses' parameter pack (DESIGN 4.1-4.4's
+# tables): the empty pack is the squared-loss kernel with the resources it had before losses existed, <..., int, double>
+# the weighted one with those it had as a kernel of its own.  (vgpr, sgpr, lds, scratch)
+LOSS_FOLDED = {
+    "k_normal_cameras<true>": (252, 106, 6912, 0),
+    "k_normal_cameras<false>": (244, 102, 6912, 0), "k_normal_cameras<false, int, double>": (244, 105, 6912, 0),
+    "k_normal_points<>": (93, 81, 0, 0), "k_normal_points<int, double>": (94, 86, 0, 0),
+    "k_schur_points<false>": (126, 84, 0, 0), "k_schur_points<false, int, double>": (114, 91, 0, 0),
+    "k_schur_points<true>": (126, 84, 0, 0), "k_schur_points<true, int, double>": (114, 91, 0, 0),
+    "k_schur_cameras<0>": (110, 89, 0, 0), "k_schur_cameras<0, int, double>": (128, 96, 0, 0),       # kSchurApply
+    "k_schur_cameras<1>": (148, 91, 0, 0), "k_schur_cameras<1, int, double>": (134, 98, 0, 0),       # kSchurDot
+    "k_schur_cameras<2>": (112, 83, 0, 0), "k_schur_cameras<2, int, double>": (130, 90, 0, 0),       # kSchurRhs
+    "k_schur_cameras<3>": (110, 83, 0, 0), "k_schur_cameras<3, int, double>": (128, 90, 0, 0),       # kSchurNoX
+    "k_schur_jacobi<>": (228, 92, 5760, 0), "k_schur_jacobi<int, double>": (220, 99, 5760, 0),
+    "k_schur_model<>": (76, 38, 64, 0), "k_schur_model<int, double>": (88, 36, 64, 0),
+}
+
+
+def test_both_instances_of_every_loss_folded_pass_keep_their_resources(isa):
+    _, _, rows = isa
+    folded = {r["name"]: (r["vgpr"], r["sgpr"], r["lds"], r["scratch"]) for r in rows
+              if r["name"].split("<")[0] in {n.split("<")[0] for n in LOSS_FOLDED}}
+    assert len(folded) == len([r for r in rows if r["name"] in folded]), "an instance is compiled twice"
+    assert folded == LOSS_FOLDED        # these instances and no other (k_normal_cameras<true, int, double> must not exist)
+
+
 def test_fold_publish_and_acquire_instruction_order(isa):
     I, asm, rows = isa
     folding = [r for r in rows if r["name"].startswith(FOLDING)]

@@ -1,7 +1,8 @@
 """The Schur-Jacobi preconditioner's host reference (tests/_precondref.py) checked on the CPU: its blocks are the diagonal
 blocks of S when no camera sees a point twice and stay positive definite when one does; on the grid the two
 preconditioners were compared on it at least halves the reference's iteration count; the built library exports the new
-entries under a new ABI number; and the weighted pass is its original plus one line."""
+entries under a new ABI number.  (That the weighted pass is the one text of k_schur_jacobi plus one line is
+tests/test_robust_loss_fold.py's, with the other five passes.)"""
 import ctypes as C
 import os
 import re
@@ -143,11 +144,3 @@ def test_library_exports_the_preconditioner_entries_under_a_new_abi_number():
     # without a device the handle cannot exist; the argument checks that need none still answer
     assert raw.c2b_problem_set_preconditioner(None, 1) == _lib.ERR_INVALID_ARGUMENT
     assert raw.c2b_problem_preconditioner_fallbacks(None, None) == _lib.ERR_INVALID_ARGUMENT
-
-
-def test_weighted_schur_jacobi_pass_is_its_original_plus_one_line():
-    from test_robust_kernel_twins import CSRC, _kernel, _strip_twin
-    text = open(os.path.join(CSRC, "schur_kernels.hpp")).read()
-    want = _kernel(text, "k_schur_jacobi")
-    got = _strip_twin(_kernel(text, "k_schur_jacobi_loss"), "k_schur_jacobi", "la2")
-    assert "jacobian_obs(" in want and re.sub(r"\s+", " ", got) == re.sub(r"\s+", " ", want)
