@@ -17,7 +17,7 @@ ERR_OOM = -4
 ERR_NO_DEVICE = -5
 ERR_RCCL = -6
 COMM_ID_BYTES = 128
-ABI_VERSION = 8            # include/city2ba_hip.h: C2B_ABI_VERSION
+ABI_VERSION = 9            # include/city2ba_hip.h: C2B_ABI_VERSION
 CAMBLK_DOUBLES = 32
 STATS_DOUBLES = 20
 
@@ -131,6 +131,8 @@ SIGNATURES = {
     "c2b_problem_set_preconditioner": (_int, [_vp, _int]),
     "c2b_problem_get_preconditioner": (_int, [_vp, C.POINTER(_int)]),
     "c2b_problem_preconditioner_fallbacks": (_int, [_vp, C.POINTER(_i64)]),
+    "c2b_problem_set_constant": (_int, [_vp, _vp, _vp]),
+    "c2b_problem_get_constant": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "c2b_schur_jacobi_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _d, _vp, _vp]),
     "c2b_schur_jacobi_rows_loss": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _d, _vp, _int, _d, _vp]),
     "c2b_visibility_pairs": (_int, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp]),

@@ -323,6 +323,41 @@ class BAProblem:
         L.check(L.lib().c2b_problem_preconditioner_fallbacks(self._h, C.byref(n)))
         return n.value
 
+    def set_constant(self, cameras=None, points=None):
+        """Hold camera parameters and points constant in normal_equations / solve_step / apply_step
+        (c2b_problem_set_constant).  cameras: uint16 [n_cam], bit k set = parameter k constant, k in to_vec order
+        (ω0 ω1 ω2 t0 t1 t2 f k1 k2; solve.ROTATION ... solve.ALL name the groups), or bool [n_cam, 9]; points: bool [n_pts].
+        None: none of that kind; both None clears the masks.  The step is that of the problem in which the constant
+        parameters cannot move, their entries of dc / dp are exactly 0, and apply_step leaves them bit for bit.  The
+        masks belong to the handle: they survive apply_step, noise and an upload of the same counts, and are dropped by
+        whatever changes a count or renumbers the entities (cull, read, the generators)."""
+        nc, npt = self.num_cameras(), self.num_points()
+        cm = pm = None
+        if cameras is not None:
+            a = np.asarray(cameras)
+            if a.dtype == np.bool_:
+                if a.shape != (nc, 9):
+                    raise ValueError("set_constant: a bool cameras mask must have shape (%d, 9)" % nc)
+                cm = np.ascontiguousarray((a.astype(np.uint16) << np.arange(9, dtype=np.uint16)).sum(axis=1, dtype=np.uint16))
+            else:
+                if a.shape != (nc,) or not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < 0 or a.max() > 0xffff)):
+                    raise ValueError("set_constant: cameras must be uint16 [%d] or bool [%d, 9]" % (nc, nc))
+                cm = np.ascontiguousarray(a, dtype=np.uint16)
+        if points is not None:
+            a = np.asarray(points)
+            if a.shape != (npt,) or not (a.dtype == np.bool_ or np.issubdtype(a.dtype, np.integer)) or \
+                    (a.size and (a.min() < 0 or a.max() > 0xff)):
+                raise ValueError("set_constant: points must be bool [%d]" % npt)
+            pm = np.ascontiguousarray(a, dtype=np.uint8)
+        L.check(L.lib().c2b_problem_set_constant(self._h, _ptr(cm), _ptr(pm)))
+
+    def constant(self):
+        """the masks in force (c2b_problem_get_constant): (bool [n_cam, 9], bool [n_pts]); all False when none is set"""
+        cm = np.zeros(self.num_cameras(), dtype=np.uint16)
+        pm = np.zeros(self.num_points(), dtype=np.uint8)
+        L.check(L.lib().c2b_problem_get_constant(self._h, _ptr(cm), _ptr(pm), None, None))
+        return ((cm[:, None] >> np.arange(9, dtype=np.uint16)) & 1).astype(bool), pm.astype(bool)
+
     def solve_step(self, lam, max_iters=100, rel_tol=1e-6, out=None):
         """One damped Gauss-Newton (Levenberg-Marquardt) step on the device (c2b_problem_solve_step): the solution of
         (J^T J + lam D) delta = -g, D = diag(min(max(diag(J^T J), 1e-6), 1e32)), by PCG on the Schur complement of the

@@ -26,6 +26,14 @@ struct c2b_problem {
     // 1 Schur-Jacobi), the handle's too; and how many cameras' Schur-Jacobi factors fell back in the last solve
     int precond_kind = 0;
     int64_t precond_fallbacks = 0;
+    // c2b_problem_set_constant: the camera parameters (bit k of a camera's word, to_vec order) and the points
+    // (0 / 1) that normal_equations / solve_step / apply_step hold constant; the handle's, kept while both counts stay
+    // what they were set for (const_n_cam, const_n_pts).  A kind with nothing set has no array: no launch changes for it.
+    uint16_t *cmask = nullptr;
+    uint8_t *pmask = nullptr;
+    std::vector<uint16_t> h_cmask;
+    std::vector<uint8_t> h_pmask;
+    int64_t const_n_cam = -1, const_n_pts = -1, const_params = 0, const_pts = 0;
     bool bal_valid = false;     // bal9 still describes the cameras (no mutation since upload_bal)
     bool blk_valid = false;     // camblk matches cam15 (and bal_valid mode)
     bool bal9_fresh = false;    // !bal_valid, but bal9 holds to_vec of the current cameras (the last write / download_bal computed it)
@@ -72,6 +80,16 @@ static void drop_rows(c2b_problem *p) {
     p->nt_ptr = nullptr; p->nt_obs = p->nt_cam = nullptr;
     if (p->sv) (void)hipFree(p->sv);
     p->sv = nullptr; p->sv_doubles = 0;
+}
+
+// the entities were renumbered or their counts changed: nothing is constant any more
+static void drop_constant(c2b_problem *p) {
+    if (p->cmask) (void)hipFree(p->cmask);
+    if (p->pmask) (void)hipFree(p->pmask);
+    p->cmask = nullptr; p->pmask = nullptr;
+    p->h_cmask.clear(); p->h_pmask.clear();
+    p->const_n_cam = p->const_n_pts = -1;
+    p->const_params = p->const_pts = 0;
 }
 
 static void free_buffers(c2b_problem *p) {
@@ -127,6 +145,7 @@ void c2b_problem_destroy(c2b_problem *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     free_buffers(p);
+    drop_constant(p);
     for (int k = 0; k < c2b_problem::kJacSlots; ++k) {
         if (p->ev_done[k]) (void)hipEventDestroy(p->ev_done[k]);
         if (p->ev_free[k]) (void)hipEventDestroy(p->ev_free[k]);
@@ -145,10 +164,12 @@ static int ensure_camblk(c2b_problem *p) {
     return C2B_OK;
 }
 
-// the resident arrays of a problem with these sizes (whatever it held before is freed); contents undefined
-static int alloc_problem(c2b_problem *p, int64_t n_cam, int64_t n_pts, int64_t n_obs) {
+// the resident arrays of a problem with these sizes (whatever it held before is freed); contents undefined.  The constant
+// masks go too, unless the caller brings the same entities back (an upload) and both counts are those they were set for.
+static int alloc_problem(c2b_problem *p, int64_t n_cam, int64_t n_pts, int64_t n_obs, bool same_entities = false) {
     HIP_TRY(hipSetDevice(p->device));
     free_buffers(p);
+    if (!same_entities || n_cam != p->const_n_cam || n_pts != p->const_n_pts) drop_constant(p);
     auto dalloc = [&](void **q, size_t bytes) -> hipError_t { return hipMalloc(q, bytes ? bytes : 16); };
     HIP_TRY(dalloc((void **)&p->cam15, sizeof(double) * 15 * n_cam));
     HIP_TRY(dalloc((void **)&p->bal9, sizeof(double) * 9 * n_cam));
@@ -187,7 +208,7 @@ static int upload_common(c2b_problem *p, int64_t n_cam, const double *cams, bool
                         (long long)o, (unsigned long long)pt_idx[o], (long long)n_pts);
         pi32[(size_t)o] = (uint32_t)pt_idx[o];
     }
-    if (int rc = alloc_problem(p, n_cam, n_pts, n_obs)) return rc;
+    if (int rc = alloc_problem(p, n_cam, n_pts, n_obs, true)) return rc;
     auto dalloc = [&](void **q, size_t bytes) -> hipError_t { return hipMalloc(q, bytes ? bytes : 16); };
 
     // staging through temporary device buffers (row_ptr, packed points)
@@ -548,6 +569,98 @@ static int ensure_transpose(c2b_problem *p) {
     return C2B_OK;
 }
 
+// ---- constant parameters -----------------------------------------------------------------------------------
+int c2b_problem_set_constant(c2b_problem *p, const uint16_t *cam_mask, const uint8_t *pt_mask) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_set_constant");
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    int64_t n_params = 0, n_const_pts = 0;
+    if (cam_mask)
+        for (int64_t c = 0; c < nc; ++c) {
+            if (cam_mask[c] & ~C2B_CONST_ALL)
+                return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_constant: camera %lld has a bit above bit 8 set (0x%x)", (long long)c,
+                            (unsigned)cam_mask[c]);
+            n_params += __builtin_popcount(cam_mask[c]);
+        }
+    if (pt_mask)
+        for (int64_t i = 0; i < np; ++i) {
+            if (pt_mask[i] > 1)
+                return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_constant: point %lld has mask %d, not 0 or 1", (long long)i, (int)pt_mask[i]);
+            n_const_pts += pt_mask[i];
+        }
+    // the new device arrays first: a failure leaves the masks in force as they were.  An all-zero mask is no mask.
+    std::vector<uint16_t> hc;
+    std::vector<uint8_t> hp;
+    uint16_t *dcm = nullptr;
+    uint8_t *dpm = nullptr;
+    hipError_t e = hipSuccess;
+    if (n_params) {
+        hc.assign(cam_mask, cam_mask + nc);
+        e = hipMalloc((void **)&dcm, sizeof(uint16_t) * (size_t)nc);
+        if (e == hipSuccess) e = hipMemcpyAsync(dcm, hc.data(), sizeof(uint16_t) * (size_t)nc, hipMemcpyHostToDevice, p->stream);
+    }
+    if (e == hipSuccess && n_const_pts) {
+        hp.assign(pt_mask, pt_mask + np);
+        e = hipMalloc((void **)&dpm, sizeof(uint8_t) * (size_t)np);
+        if (e == hipSuccess) e = hipMemcpyAsync(dpm, hp.data(), sizeof(uint8_t) * (size_t)np, hipMemcpyHostToDevice, p->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(p->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        if (dcm) (void)hipFree(dcm);
+        if (dpm) (void)hipFree(dpm);
+        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_set_constant: %s", hipGetErrorString(e));
+    }
+    drop_constant(p);
+    p->cmask = dcm; p->pmask = dpm;
+    p->h_cmask.swap(hc); p->h_pmask.swap(hp);
+    p->const_n_cam = nc; p->const_n_pts = np;
+    p->const_params = n_params; p->const_pts = n_const_pts;
+    return C2B_OK;
+    C2B_API_END("problem_set_constant")
+}
+
+int c2b_problem_get_constant(const c2b_problem *p, uint16_t *cam_mask, uint8_t *pt_mask, int64_t *n_const_cam_params, int64_t *n_const_pts) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_constant: problem is NULL");
+    if (!p->ws) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_constant: nothing uploaded");
+    if (cam_mask) {
+        if (p->cmask) std::copy(p->h_cmask.begin(), p->h_cmask.end(), cam_mask);
+        else std::fill(cam_mask, cam_mask + p->n_cam, (uint16_t)0);
+    }
+    if (pt_mask) {
+        if (p->pmask) std::copy(p->h_pmask.begin(), p->h_pmask.end(), pt_mask);
+        else std::fill(pt_mask, pt_mask + p->n_pts, (uint8_t)0);
+    }
+    if (n_const_cam_params) *n_const_cam_params = p->const_params;
+    if (n_const_pts) *n_const_pts = p->const_pts;
+    return C2B_OK;
+    C2B_API_END("problem_get_constant")
+}
+
+// the zeros of J~ into blocks the passes filled from J (asynchronous; nothing is launched for a kind with nothing constant):
+// rows and columns of A [n_cam][9][9] with `diag` on their diagonal, entries of y [n_cam][9] (either may be NULL) ...
+static int constant_cameras(c2b_problem *p, double *A, double diag, double *y) {
+    if (!p->cmask || !p->n_cam) return C2B_OK;
+    if (A) hipLaunchKernelGGL(k_const_blocks, dim3(blocks_for(9 * p->n_cam, kSchurBlock)), dim3(kSchurBlock), 0, p->stream, 9 * p->n_cam,
+                              (const uint16_t *)p->cmask, diag, A);
+    if (y) hipLaunchKernelGGL(k_const_cameras, dim3(blocks_for(p->n_cam, kSchurBlock)), dim3(kSchurBlock), 0, p->stream, p->n_cam,
+                              (const uint16_t *)p->cmask, y);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
+// ... V [n_pts][3][3] = diag I3 with gp [n_pts][3] = 0 (gp may be NULL), or t [n_pts][3] = 0 alone (V NULL), of the constant points
+static int constant_points(c2b_problem *p, double *V, double diag, double *t) {
+    if (!p->pmask || !p->n_pts) return C2B_OK;
+    if (V) hipLaunchKernelGGL(k_const_point_blocks, dim3(blocks_for(p->n_pts, kSchurBlock)), dim3(kSchurBlock), 0, p->stream, p->n_pts,
+                              (const uint8_t *)p->pmask, diag, V, t);
+    else hipLaunchKernelGGL(k_const_points, dim3(blocks_for(p->n_pts, kSchurBlock)), dim3(kSchurBlock), 0, p->stream, p->n_pts,
+                            (const uint8_t *)p->pmask, t);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
 // ---- robust loss -----------------------------------------------------------------------------------------
 int c2b_problem_set_loss(c2b_problem *p, int kind, double scale) {
     C2B_API_BEGIN
@@ -652,6 +765,7 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
             HIP_TRY(hipMemsetAsync(U, 0, sizeof(double) * 81 * (size_t)p->n_cam, p->stream));
             HIP_TRY(hipMemsetAsync(gc, 0, sizeof(double) * 9 * (size_t)p->n_cam, p->stream));
         }
+        if (!rc && p->n_obs) rc = constant_cameras(p, U, 0.0, gc);
     } else if (want_sum && p->loss_kind != kLossSquared && p->n_obs) {
         rc = robust_sum(p, true, p->scalar);                 // the weighted sum of squares without the blocks
     } else if (want_sum) {
@@ -666,6 +780,7 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
             rc = ensure_transpose(p);
             if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, V, gp, p->loss_kind,
                                                   p->loss_scale, p->stream);
+            if (!rc) rc = constant_points(p, V, 0.0, gp);
             if (rc) return rc;
         } else {
             HIP_TRY(hipMemsetAsync(V, 0, sizeof(double) * 9 * (size_t)p->n_pts, p->stream));
@@ -769,6 +884,10 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
                 hipLaunchKernelGGL((k_schur_points<false, decltype(loss)...>), dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st,
                                    p->camblk, p4, np, p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, loss...);
         });
+        if (p->pmask) (void)constant_points(p, nullptr, 0.0, t);        // t = 0 for the constant points (fetch sees a launch error)
+    };
+    auto mask_y = [&](double *y) {                           // after a camera pass: y's constant entries to 0
+        if (p->cmask) (void)constant_cameras(p, nullptr, 0.0, y);
     };
     double h[kScSlots];
     auto fetch = [&](int slots) -> int {                     // the first `slots` scalars to the host, after all queued work
@@ -784,8 +903,15 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, B.gp, kind, p->loss_scale, st);
     if (rc) return rc;
     const bool schur_jacobi = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI;
+    // constant parameters: from here on U, gc, V, gp are those of J~.  k_schur_jacobi first sees the constant
+    // points' V as kConstPointV, under which their observations add Jc^T Jc as they do with Jp = 0
+    rc = constant_cameras(p, B.U, 0.0, B.gc);
+    if (!rc) rc = constant_points(p, B.V, schur_jacobi ? kConstPointV : 0.0, B.gp);
+    if (rc) return rc;
     if (schur_jacobi) {                                      // M from U's diagonal and V, its factors, the fallbacks' count
         rc = schur_jacobi_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.V, lambda, B.M, kind, p->loss_scale, st);
+        if (!rc) rc = constant_cameras(p, B.M, lambda * 1e-6, nullptr);
+        if (!rc) rc = constant_points(p, B.V, 0.0, nullptr);
         if (rc) return rc;
         hipLaunchKernelGGL(k_schur_factor_blocks, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.M, (const double *)B.U,
                            lambda, B.Lf, B.pa);
@@ -799,6 +925,7 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
                            (int)nc, p->pt_idx, uv, (const double *)B.U, lambda, (const double *)nullptr, (const double *)B.gc,
                            (const double *)B.t, B.r, (double *)nullptr, loss...);
     });
+    mask_y(B.r);
     hipLaunchKernelGGL(k_pcg_update<true>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc, 0, dc,
                        B.r, B.pv, (const double *)nullptr, B.z, B.pa, B.pb);
     hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, (int)nbc, B.sc + kScRr);
@@ -822,6 +949,7 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
                                    p->rows_ptr, (int)nc, p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv,
                                    (const double *)nullptr, (const double *)B.t, B.q, B.pa, loss...);
             });
+            mask_y(B.q);                                     // p's constant entries are 0: the p.q partials need no correction
             hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)B.pa, n_cpart, B.sc + kScPq);
             hipLaunchKernelGGL(k_pcg_update<false>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc,
                                cur, dc, B.r, B.pv, (const double *)B.q, B.z, B.pa, B.pb);
@@ -881,13 +1009,20 @@ int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
             const int rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st);
             if (rc) return rc;
         }
-        if (dc) hipLaunchKernelGGL(k_add_f64, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc, p->bal9);
+        if (dc && p->cmask)                                  // a constant entry keeps its bits
+            hipLaunchKernelGGL(k_add_free, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc,
+                               (const uint16_t *)p->cmask, p->bal9);
+        else if (dc) hipLaunchKernelGGL(k_add_f64, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc, p->bal9);
         LAUNCH_CHECK();
         const int rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
         if (rc) return rc;
     }
     if (dp && np) {
-        hipLaunchKernelGGL(k_points_add, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp, reinterpret_cast<double4 *>(p->pts4));
+        if (p->pmask)
+            hipLaunchKernelGGL(k_points_add_free, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp,
+                               (const uint8_t *)p->pmask, reinterpret_cast<double4 *>(p->pts4));
+        else
+            hipLaunchKernelGGL(k_points_add, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp, reinterpret_cast<double4 *>(p->pts4));
         LAUNCH_CHECK();
     }
     cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
@@ -1267,6 +1402,7 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
     p->pts4 = (double *)n_pts4.release(); p->uv = (double *)n_uv.release(); p->ws = n_ws.release();
     p->cam_idx = (uint32_t *)cam[cur].release(); p->pt_idx = (uint32_t *)pt[cur].release();
     drop_rows(p);
+    drop_constant(p);                                         // the survivors are renumbered
     p->n_cam = nc; p->n_pts = np; p->n_obs = no;
     p->blk_valid = false;                                     // camblk is rebuilt on demand from the gathered cameras
     p->bal9_fresh = false;                                    // (bal9 was gathered only when it was the truth)
@@ -1761,6 +1897,7 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
     // the sampled points become the problem's
     free_dense(p);
     drop_rows(p);
+    drop_constant(p);
     if (p->pts4) (void)hipFree(p->pts4);
     p->pts4 = (double *)out.release();
     p->n_pts = accepted;

@@ -12,6 +12,9 @@
 //   * k_schur_jacobi / k_schur_factor_blocks: the Schur-Jacobi preconditioner, S's own 9x9 diagonal blocks in place of
 //     U_l's, factored into k_schur_factor's format (an option of the solve).
 //   * k_schur_model: ||r||^2 and ||r||^2 - ||r + Jc dc + Jp dp||^2 per observation, one partial per workgroup.
+//   * k_const_cameras / k_const_points / k_const_blocks / k_const_point_blocks: constant parameters, the
+//     projection onto the free ones applied around the passes above; k_add_free / k_points_add_free: the step added to
+//     the free entries alone.  None is launched while no mask is set.
 // Damping (Marquardt with Ceres' clamps): A_l = A + lambda diag(d), d_i = min(max(A_ii, 1e-6), 1e32).
 // Every partial is summed by k_normal_sum in a fixed order; no float atomics, so the same inputs give the same bits.
 // Robust losses: the passes over the observations scale (r, Jc, Jp) by sqrt(w) right after jacobian_obs.  Each is one
@@ -442,6 +445,63 @@ __global__ __launch_bounds__(kSchurBlock) void k_schur_model(
     block_sum_to(md, sRed[1], part_md + blockIdx.x);
 }
 
+// ---- constant parameters --------------------------------------------------------------------------------
+// A camera's mask has bit k set when its parameter k (to_vec order) is constant; a point's is 0 or 1.  The solve is that
+// of J~, J with those columns zero.  The passes above keep J: these kernels put the zeros where J~ has them, after the
+// pass.  They store and never load what they mask: an entity with nothing constant costs its mask word and no more.
+constexpr double kConstPointV = __builtin_huge_val();      // the diagonal of a constant point's V while k_schur_jacobi reads it
+
+// y[c][k] = 0 where bit k of cam_mask[c] is set: y = b or q after a camera pass, or gc.  One lane per camera.
+__global__ __launch_bounds__(kSchurBlock) void k_const_cameras(int64_t n_cam, const uint16_t *__restrict__ cam_mask,
+                                                               double *__restrict__ y) {
+    const int64_t c = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (c >= n_cam) return;
+    const unsigned m = cam_mask[c];
+    if (!m) return;
+    double *yc = y + c * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+        if ((m >> k) & 1u) yc[k] = 0.0;
+}
+
+// t[p] = 0 for a constant point: t after a point pass (V_l^-1 = 1e6 / lam would multiply W^T x into it), or dp.
+__global__ __launch_bounds__(kSchurBlock) void k_const_points(int64_t n_pts, const uint8_t *__restrict__ pt_mask,
+                                                              double *__restrict__ t) {
+    const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (p >= n_pts || !pt_mask[p]) return;
+    t[3 * p] = 0.0; t[3 * p + 1] = 0.0; t[3 * p + 2] = 0.0;
+}
+
+// A [n_cam][9][9] = U or M: row and column k of a camera's block to 0 where bit k is set, the diagonal entry to `diag`
+// (U: 0; M: lam 1e-6, the damping of a diagonal of 0, which is all J~ leaves there).  One lane per row of a block.
+__global__ __launch_bounds__(kSchurBlock) void k_const_blocks(int64_t n_rows, const uint16_t *__restrict__ cam_mask, double diag,
+                                                              double *__restrict__ A) {
+    const int64_t i = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (i >= n_rows) return;
+    const int64_t c = i / 9;
+    const int row = (int)(i - c * 9);
+    const unsigned m = cam_mask[c];
+    if (!m) return;
+    const bool whole = (m >> row) & 1u;
+    double *Ar = A + i * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+        if (whole || ((m >> k) & 1u)) Ar[k] = (whole && k == row) ? diag : 0.0;
+}
+
+// V [n_pts][3][3] (and gp [n_pts][3] unless NULL) of a constant point: V = diag I3, gp = 0.  diag = 0 is J~'s V; diag =
+// kConstPointV (+inf) is what k_schur_jacobi is given: the reciprocals of L's diagonal are then 0, L^-1 Jp^T is 0 and
+// I2 - Jp V_l^-1 Jp^T is I2 to the bit, which is the term of an observation whose Jp is 0.
+__global__ __launch_bounds__(kSchurBlock) void k_const_point_blocks(int64_t n_pts, const uint8_t *__restrict__ pt_mask, double diag,
+                                                                    double *__restrict__ V, double *__restrict__ gp) {
+    const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (p >= n_pts || !pt_mask[p]) return;
+    double *Vp = V + p * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Vp[k] = (k % 4 == 0) ? diag : 0.0;
+    if (gp) { gp[3 * p] = 0.0; gp[3 * p + 1] = 0.0; gp[3 * p + 2] = 0.0; }
+}
+
 // ---- apply -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSchurBlock) void k_add_f64(int64_t n, const double *__restrict__ d, double *__restrict__ a) {
     const int64_t i = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
@@ -451,6 +511,24 @@ __global__ __launch_bounds__(kSchurBlock) void k_add_f64(int64_t n, const double
 __global__ __launch_bounds__(kSchurBlock) void k_points_add(int64_t n_pts, const double *__restrict__ dp, double4 *__restrict__ pts4) {
     const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
     if (p >= n_pts) return;
+    double4 X = pts4[p];
+    X.x += dp[3 * p]; X.y += dp[3 * p + 1]; X.z += dp[3 * p + 2];
+    pts4[p] = X;
+}
+
+// the two above over the free entries only: a constant one keeps its bits whatever d holds there (-0 + 0 is +0)
+__global__ __launch_bounds__(kSchurBlock) void k_add_free(int64_t n, const double *__restrict__ d, const uint16_t *__restrict__ cam_mask,
+                                                          double *__restrict__ a) {
+    const int64_t i = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (i >= n) return;
+    const int64_t c = i / 9;
+    if (!((cam_mask[c] >> (int)(i - c * 9)) & 1u)) a[i] += d[i];
+}
+
+__global__ __launch_bounds__(kSchurBlock) void k_points_add_free(int64_t n_pts, const double *__restrict__ dp,
+                                                                 const uint8_t *__restrict__ pt_mask, double4 *__restrict__ pts4) {
+    const int64_t p = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x;
+    if (p >= n_pts || pt_mask[p]) return;
     double4 X = pts4[p];
     X.x += dp[3 * p]; X.y += dp[3 * p + 1]; X.z += dp[3 * p + 2];
     pts4[p] = X;

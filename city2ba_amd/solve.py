@@ -1,15 +1,20 @@
 """Levenberg-Marquardt on a resident BAProblem: BAProblem.solve_step (the damped Gauss-Newton step by PCG on the
 cameras' Schur complement, on the device) and apply_step, with Nielsen's update of the damping; optionally under a
-robust loss (BAProblem.set_loss), by iteratively reweighted least squares."""
+robust loss (BAProblem.set_loss), by iteratively reweighted least squares, and with chosen camera parameters and points
+held constant (BAProblem.set_constant)."""
 
 LAMBDA_MIN, LAMBDA_MAX = 1e-20, 1e32                # the damping c2b_problem_solve_step accepts (C2B_STEP_LAMBDA_MIN / _MAX)
+# bits of a camera's constant mask (BAProblem.set_constant; C2B_CONST_*): parameter k of to_vec order is bit k
+ROTATION, TRANSLATION, POSE = 0x007, 0x038, 0x03f
+FOCAL, K1, K2, INTRINSICS = 0x040, 0x080, 0x100, 0x1c0
+ALL = 0x1ff
 
 
 def _clamp(lam):
     return min(max(lam, LAMBDA_MIN), LAMBDA_MAX)
 
 
-def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0, preconditioner=None):
+def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0, preconditioner=None, constant=None):
     """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
     sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
     and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit); lam is held
@@ -23,7 +28,12 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     set with ba.set_loss is in force all the same (the step is the reweighted one, so the cost must be the robust one);
     with none in force the loop runs as it always did and 'cost' repeats 'error'.
     preconditioner = "block_jacobi" | "schur_jacobi" (BAProblem.set_preconditioner, which this calls: it stays on ba);
-    None leaves ba's as it is.  It changes how many PCG iterations a step takes, not what the step converges to."""
+    None leaves ba's as it is.  It changes how many PCG iterations a step takes, not what the step converges to.
+    constant = (cameras, points) as BAProblem.set_constant takes them (which this calls: the masks stay on ba); None leaves
+    ba's masks as they are.  Constant entries get a zero step and keep their bits through accepted and rejected iterations
+    (the restore after a rejected step is an upload of the same counts, which keeps the masks)."""
+    if constant is not None:
+        ba.set_constant(*constant)
     if preconditioner is not None:
         ba.set_preconditioner(preconditioner)
     if loss is not None:

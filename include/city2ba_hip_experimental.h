@@ -173,6 +173,42 @@ int c2b_schur_jacobi_rows_loss(const double *camblk, const double *pts4, const u
                                const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
                                int kind, double scale, void *stream);
 
+/* ---- constant camera parameters and points in the step ----
+ * A camera's mask has bit k set when its parameter k is held constant, k in to_vec order (the columns of Jc):
+ * w0 w1 w2 t0 t1 t2 f k1 k2; a point's mask is 1 when the whole point is.  With a mask in force c2b_problem_normal_equations
+ * and c2b_problem_solve_step return what they are specified to return, computed from J~ in place of J: J with column k of
+ * Jc_o zero for every observation o of a camera with bit k set, and Jp_o zero for every observation of a constant point.
+ * So the constant rows and columns of U, and those entries of gc, are 0, V and gp of a constant point are 0, their damped
+ * diagonals are lambda 1e-6 (the clamp rule), S, b and both preconditioners are those of J~, and every constant entry of
+ * dc and every row of dp of a constant point compares == 0.0 -- at every iterate, for every max_iters, under every
+ * status.  The free parameters get the step of the problem in which the constant ones cannot move, which is not the
+ * unmasked step with entries overwritten.  sum_sq does not change (the mask does not touch r, nor a loss's weights);
+ * model_decrease is summed from J, which equals the sum from J~ on a step with those zeros.  Every camera constant: b = 0,
+ * 0 iterations, status 0, dp = -V_l^-1 gp.  Every point constant: S = U_l.  c2b_problem_apply_step adds the step to the
+ * free entries only: constant entries of bal9 (state mode: of to_vec(cam15)) and constant points keep their bits.
+ * _set_constant: cam_mask [n_cam] (uint16_t words) and pt_mask [n_pts] are HOST arrays; either may be NULL (none of that
+ *   kind constant), both NULL clears the masks; an all-zero mask is no mask.  A bit above bit 8, or a pt_mask value other
+ *   than 0 or 1: C2B_ERR_INVALID_ARGUMENT, and the masks in force stay.  With none in force both entries launch exactly
+ *   what they launch without this entry, bit for bit.  Deterministic with a mask as without.
+ * _get_constant: the masks in force (zeros when none) and how many camera parameters / points they hold; any output may
+ *   be NULL.
+ * Lifetime: the masks are the handle's state.  They survive c2b_problem_apply_step, the noise functions, _set_loss,
+ *   _set_preconditioner, _adopt_visibility and an upload that keeps both n_cam and n_pts (the entities are then taken to
+ *   be the same ones).  Whatever changes a count or renumbers the entities drops them: a cull (_cull,
+ *   _largest_connected_component, _remove_singletons), a read, a generator, an upload of another size. */
+#define C2B_CONST_ROTATION 0x007
+#define C2B_CONST_TRANSLATION 0x038
+#define C2B_CONST_POSE 0x03f
+#define C2B_CONST_FOCAL 0x040
+#define C2B_CONST_K1 0x080
+#define C2B_CONST_K2 0x100
+#define C2B_CONST_INTRINSICS 0x1c0
+#define C2B_CONST_ALL 0x1ff
+typedef uint16_t c2b_camera_mask;      /* a camera's word: an OR of C2B_CONST_* bits */
+int c2b_problem_set_constant(c2b_problem *p, const c2b_camera_mask *cam_mask, const uint8_t *pt_mask);
+int c2b_problem_get_constant(const c2b_problem *p, c2b_camera_mask *cam_mask, uint8_t *pt_mask, int64_t *n_const_cam_params,
+                             int64_t *n_const_pts);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */

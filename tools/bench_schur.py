@@ -10,11 +10,16 @@ The Level-1 calls are synchronous and timed on the host clock; each figure is th
 
     python tools/bench_schur.py [--blocks 128] [--reps 5] [--warmup 1] [--loss huber|cauchy|soft_l1 --loss-scale A]
                                 [--preconditioner block_jacobi|schur_jacobi] [--to-tol]
+                                [--constant none|intrinsics|gauge|points]
 
 --preconditioner schur_jacobi (combinable with --loss) solves with the Schur-Jacobi blocks and also reports
 the pass that forms them alone (k_schur_jacobi: us, algorithmic bytes, fraction of 8 TB/s).  --to-tol adds, for either
 preconditioner, the iterations and wall time of a solve to rel_tol 1e-2 and to 1e-4 (max_iters --tol-max-iters; a
 solve that ends with status 1 is reported as such).
+
+--constant reports the same rows for a solve with constant parameters (BAProblem.set_constant): intrinsics
+= f, k1, k2 of every camera; gauge = camera 0 wholly and t0 of camera 1; points = every point.  none, the default, sets
+no mask: the run is the one it was before the option existed.  The Level-0 passes are timed without the mask.
 
 --loss times the same figures under a robust loss (the weighted kernels); without it every launch is a
 squared-loss kernel.
@@ -46,6 +51,8 @@ def main():
     ap.add_argument("--loss", choices=["huber", "cauchy", "soft_l1"], default=None, help="robust loss (default: squared)")
     ap.add_argument("--loss-scale", type=float, default=3e-3, help="its scale a, in the residuals' units (noise is 1e-3)")
     ap.add_argument("--preconditioner", choices=["block_jacobi", "schur_jacobi"], default="block_jacobi")
+    ap.add_argument("--constant", choices=["none", "intrinsics", "gauge", "points"], default="none",
+                    help="hold parameters constant in the solve (default: none)")
     ap.add_argument("--to-tol", action="store_true", help="also time solves to rel_tol 1e-2 and 1e-4")
     ap.add_argument("--tol-max-iters", type=int, default=1000)
     a = ap.parse_args()
@@ -120,6 +127,15 @@ def main():
     ba.set_preconditioner(a.preconditioner)
     if loss:
         ba.set_loss(*loss)
+    if a.constant != "none":
+        import numpy as np
+        from city2ba_amd import solve as LM
+        cm = np.zeros(n_cam, dtype=np.uint16)
+        if a.constant == "intrinsics":
+            cm[:] = LM.INTRINSICS
+        elif a.constant == "gauge":
+            cm[0], cm[1] = LM.ALL, 1 << 3
+        ba.set_constant(cm, np.ones(n_pts, dtype=bool) if a.constant == "points" else None)
 
     def solve(k):
         info[k] = ba.solve_step(lam, max_iters=k, rel_tol=0.0, out=(dc, dp))[2]
@@ -141,7 +157,7 @@ def main():
             to_tol["to_rel_tol_%g" % tol] = dict(w, iterations=res["info"]["iterations"], status=res["info"]["status"],
                                                  rel_residual=res["info"]["rel_residual"])
     out = {
-        "blocks": a.blocks, "preconditioner": a.preconditioner, "loss": a.loss, "loss_scale": a.loss_scale if a.loss else None, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts, "lambda": lam,
+        "blocks": a.blocks, "preconditioner": a.preconditioner, "constant": a.constant, "loss": a.loss, "loss_scale": a.loss_scale if a.loss else None, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts, "lambda": lam,
         "points_pass": dict(us_p, algorithmic_bytes=bytes_p, frac_of_8TBs=frac(bytes_p, us_p["median_us"])),
         "cameras_pass": dict(us_c, algorithmic_bytes=bytes_c, frac_of_8TBs=frac(bytes_c, us_c["median_us"])),
         "both_passes_us": round(us_p["median_us"] + us_c["median_us"], 1),
