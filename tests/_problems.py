@@ -257,3 +257,92 @@ def points_in_front(cams15, cam_of, seed):
     M = cams15[cam_of, :9].reshape(m, 3, 3).transpose(0, 2, 1)       # R is column-major: q = R X + t
     X = np.linalg.solve(M, (q - cams15[cam_of, 9:12])[:, :, None])[:, :, 0]
     return np.ascontiguousarray(X)
+
+
+# ---- a coupled general-position problem: shared points, general rotations, mixed distortion, chosen row lengths ----
+# camera rows of these lengths: around the 16 lanes a camera gets in k_normal_cameras / k_schur_cameras / k_schur_jacobi
+# and their multiples, an empty row, and rows of several hundred
+DOME_LENGTHS = (0, 1, 2, 3, 4, 5, 8, 9, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 127, 130, 257)
+DOME_N_CAM = 81                                                  # the 23 above + 58 drawn in 1..40; 81 % 4 == 1
+DOME_N_PTS = 400
+DOME_UNOBSERVED = 20                                             # the last points: no observation
+DOME_SINGLES = 40                                                # points 1 .. 40: seen exactly once
+DOME_CROWDED = 0                                                 # point 0: in every non-empty row
+
+
+def _dome_rows(rng, dup):
+    """(lengths, rows): the shuffled row lengths and each camera's point list.  Every non-empty row holds the crowded
+    point; the singles go one each to rows of length >= 3; the rest is drawn without repeats from the shared points.
+    Every third camera with at least 4 observations has one (camera, point) pair twice, at least two places apart -- the
+    crowded point's in every other such camera; with dup = False that place holds one more distinct shared point, so both
+    variants have the same lengths."""
+    lengths = np.array(list(DOME_LENGTHS) + [int(v) for v in rng.integers(1, 41, DOME_N_CAM - len(DOME_LENGTHS))])
+    rng.shuffle(lengths)
+    shared = np.arange(DOME_SINGLES + 1, DOME_N_PTS - DOME_UNOBSERVED)
+    takers = np.flatnonzero(lengths >= 3)
+    single_of = {}
+    for k, p in enumerate(range(1, DOME_SINGLES + 1)):
+        single_of.setdefault(int(takers[k % len(takers)]), []).append(p)
+    rows, n_dup_cams = [], 0
+    for c, n in enumerate(lengths):
+        n = int(n)
+        if n == 0:
+            rows.append(np.empty(0, dtype=np.int64))
+            continue
+        twice = n >= 4 and c % 3 == 0
+        own = single_of.get(c, [])[:max(0, n - 2)]
+        fill = rng.choice(shared, size=n - 1 - len(own) - (1 if twice else 0), replace=False)
+        row = np.concatenate([[DOME_CROWDED], own, fill]).astype(np.int64)
+        rng.shuffle(row)
+        if twice:
+            i = int(rng.integers(0, len(row)))
+            if n_dup_cams % 2 == 0:
+                i = int(np.flatnonzero(row == DOME_CROWDED)[0])
+            elif row[i] <= DOME_SINGLES:                         # a shared point, so that the singles stay seen once
+                i = int(np.flatnonzero(row > DOME_SINGLES)[0])
+            far = [j for j in range(len(row) + 1) if j < i - 1 or j > i + 2]       # insert position: >= 2 places from i
+            j = int(rng.choice(far))
+            extra = row[i] if dup else rng.choice(np.setdiff1d(shared, row))
+            row = np.insert(row, j, extra)
+            n_dup_cams += 1
+        assert len(row) == n
+        rows.append(row)
+    return lengths, rows
+
+
+def dome_problem(seed=0, dup=True, state=False, obs_noise=1e-3, start_noise=1e-3):
+    """DOME_N_CAM cameras on a shell of radius 8-14 around DOME_N_PTS points in the box [-2, 2]^3, each looking down its
+    -z axis at a target within 0.5 of the origin with a random roll (every point is in front of every camera, |uv| up to
+    about 0.5); the rotation vector is the oracle's to_rodrigues of the rotation matrix (angle 2 acos(q0): here 0.7 to 4.1); f in [0.8, 1.2], k1
+    and k2 in +-5e-2, k2 = 0 on every fifth camera.  Rows: _dome_rows.  Observations are the oracle's projection of that
+    state + obs_noise; the state returned is moved by start_noise in pose (w, t) and in the points.
+    Returns dict(bal9, cams15 (= camera_from_bal(bal9)), pts, row_ptr (u64), pt_idx (u64), uv, lengths, true_bal9,
+    true_pts, bal (= not state): load it with from_bal(bal9, ...) when bal, with from_visibility(cams15, ...) otherwise)."""
+    rng = np.random.default_rng(seed)
+    lengths, rows = _dome_rows(rng, dup)
+    pts = rng.uniform(-2.0, 2.0, size=(DOME_N_PTS, 3))
+    cams = np.empty((DOME_N_CAM, 15))
+    for c in range(DOME_N_CAM):
+        d = rng.normal(size=3)
+        ctr = d / np.linalg.norm(d) * rng.uniform(8.0, 14.0)
+        t = rng.normal(size=3)
+        target = t / np.linalg.norm(t) * rng.uniform(0.0, 0.5)
+        z = (ctr - target) / np.linalg.norm(ctr - target)        # the camera looks down -z
+        a = np.cross(z, rng.normal(size=3))
+        x = a / np.linalg.norm(a)                                # a random roll about z
+        Rm = np.stack([x, np.cross(z, x), z])                    # rows: the camera's axes in the world; q = Rm (X - ctr)
+        cams[c, :9] = Rm.T.ravel()                               # column-major
+        cams[c, 9:12] = -Rm @ ctr
+    cams[:, 12] = rng.uniform(0.8, 1.2, DOME_N_CAM)
+    cams[:, 13:15] = rng.uniform(-5e-2, 5e-2, size=(DOME_N_CAM, 2))
+    cams[::5, 14] = 0.0
+    true_bal9 = O.camera_to_bal(cams)
+    row_ptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
+    pt_idx = np.concatenate(rows).astype(np.uint64)
+    uv = O.project_observations(O.camera_from_bal(true_bal9), pts, row_ptr, pt_idx)
+    uv = uv + rng.normal(scale=obs_noise, size=uv.shape)
+    bal9 = true_bal9.copy()
+    bal9[:, :6] += rng.normal(scale=start_noise, size=(DOME_N_CAM, 6))
+    moved = pts + rng.normal(scale=start_noise, size=pts.shape)
+    return dict(bal9=bal9, cams15=O.camera_from_bal(bal9), pts=moved, row_ptr=row_ptr, pt_idx=pt_idx, uv=uv,
+                lengths=lengths, true_bal9=true_bal9, true_pts=pts, bal=not state)

@@ -13,6 +13,7 @@ import pytest
 import _precondref as PR
 import _robustref as B
 import _schurref as R
+import _solvecheck as SC
 import test_gpu_schur_jacobi as SJ
 from test_gpu_schur_pcg import KS
 from test_gpu_schur_step import EPS, _bits, _cam_of, _kappa, _make, _np, env  # noqa: F401  (env is the module fixture)
@@ -21,8 +22,7 @@ pytestmark = pytest.mark.gpu
 ROTATION, TRANSLATION, POSE, FOCAL, K1, K2, INTRINSICS, ALL = 0x007, 0x038, 0x03f, 0x040, 0x080, 0x100, 0x1c0, 0x1ff
 
 
-def _unpack(cm):
-    return ((np.asarray(cm, dtype=np.uint16)[:, None] >> np.arange(9, dtype=np.uint16)) & 1).astype(bool)
+_unpack = SC.unpack
 
 
 def _mask(ba, name):
@@ -50,8 +50,7 @@ def _lin(ba, cm, pm):
     """the arguments of _schurref.Problem / _robustref.problem for J~"""
     r, Jc, Jp = ba.residual_jacobian()
     cam, pt = _cam_of(ba.row_ptr), ba.pt_idx.astype(np.int64)
-    Jc = np.where(_unpack(cm)[cam][:, None, :], 0.0, Jc)
-    Jp = np.where(np.asarray(pm, dtype=bool)[pt][:, None, None], 0.0, Jp)
+    Jc, Jp = SC.masked_jacobian(Jc, Jp, cam, pt, cm, pm)
     return r, Jc, Jp, cam, pt, ba.num_cameras(), ba.num_points()
 
 
@@ -63,10 +62,7 @@ def _masked(name, kind="block_jacobi"):
     return ba, bal, cm, pm
 
 
-def _assert_zeros(dc, dp, cm, pm, tag):
-    dc, dp = np.asarray(dc), np.asarray(dp)
-    assert (dc[_unpack(cm)] == 0.0).all(), (tag, "a constant camera parameter moved")
-    assert (dp[np.asarray(pm, dtype=bool)] == 0.0).all(), (tag, "a constant point moved")
+_assert_zeros = SC.assert_zeros
 
 
 def _iterates(monkeypatch, ba, cm, pm, lam, ks, kind, tag, runs=8, loss=None):

@@ -9,6 +9,7 @@ import pytest
 import _precondref as PR
 import _robustref as B
 import _schurref as R
+import _solvecheck as SC
 from test_gpu_schur_pcg import KS, _crossing_tols, _model_tol, _over, _sparse_problem, _sum_sq
 from test_gpu_schur_step import _bits, _cam_of, _level0, _make, _np, _ref, env  # noqa: F401  (env is the module fixture)
 
@@ -38,13 +39,7 @@ def _device_blocks(env, ba, bal, lam, loss=None):
     return _np(M)
 
 
-def _check_blocks(M, P, lam, tag, runs):
-    ref, bound, _ = PR.blocks_bound(P, lam, runs=runs)
-    err = np.linalg.norm(M - ref.astype(np.float64), axis=(1, 2))
-    over = np.array([_over(e, b) for e, b in zip(err, bound)])
-    print("SJREF blocks %s lam=%g n_cam=%d worst |err|/bound %.3g" % (tag, lam, P.n_cam, float(over.max())))
-    assert np.isfinite(M).all() and float(over.max()) <= 1.0, (tag, lam, float(over.max()), int(over.argmax()))
-    assert _bits(M, M.transpose(0, 2, 1)), (tag, "the two triangles differ")
+_check_blocks = SC.check_blocks
 
 
 # ---- 1. the blocks ------------------------------------------------------------------------------------------------------
@@ -75,33 +70,7 @@ def _check_iterates(ba, lam, ks, runs=8, tag="", kind="schur_jacobi"):
     against _precondref.pcg for every k in ks (x, dp, recurrence residual, energy, model decrease, sum_sq)"""
     P = _ref(ba, R.LD)
     ref = PR.pcg(P, lam, max(ks), 0.0, kind=kind, runs=runs)
-    assert ref["status"] == 1 and ref["iterations"] == max(ks), (ref["status"], ref["iterations"])
-    b = ref["bound"]
-    worst = dict(x=0.0, dp=0.0, rel=0.0, energy=0.0, model=0.0)
-    e_prev = k_prev = None
-    for k in ks:
-        dc, dp, info = ba.solve_step(lam, max_iters=k, rel_tol=0.0)
-        dc, dp = _np(dc), _np(dp)
-        assert info["status"] == 1 and info["iterations"] == k, (tag, k, info)
-        ex = _over(float(np.linalg.norm(dc - ref["x"][k].astype(np.float64))), b["x"][k])
-        ed = _over(float(np.linalg.norm(dp - ref["dp"][k].astype(np.float64))), b["dp"][k])
-        er = _over(abs(info["rel_residual"] - float(ref["rel"][k])), b["rel"][k])
-        en = R.energy(P, lam, dc)
-        ee = _over(abs(float(en - ref["energy"][k])), b["energy"][k])
-        for key, v in (("x", ex), ("dp", ed), ("rel", er), ("energy", ee)):
-            worst[key] = max(worst[key], v)
-            assert v <= 1.0, (tag, lam, k, key, v, info)
-        if e_prev is not None and float(ref["energy"][k_prev] - ref["energy"][k]) > b["energy"][k] + b["energy"][k_prev]:
-            assert en < e_prev, (tag, lam, k, float(en), float(e_prev))
-        e_prev, k_prev = en, k
-        ss = float(_sum_sq(P))
-        assert abs(info["sum_sq"] - ss) <= 1e-13 * ss, (tag, k, info["sum_sq"], ss)
-        md = float(P.model_decrease(dc, dp))
-        em = _over(abs(info["model_decrease"] - md), _model_tol(P, dc, dp))
-        worst["model"] = max(worst["model"], em)
-        assert em <= 1.0, (tag, lam, k, info["model_decrease"], md)
-    print("SJREF iterates %s lam=%g worst |err|/bound %s" % (tag, lam, {k: "%.3g" % v for k, v in worst.items()}))
-    return ref
+    return SC.check_iterates(ba, P, ref, lam, ks, tag=tag, label="SJREF iterates")
 
 
 @pytest.mark.parametrize("name", RANDOM)

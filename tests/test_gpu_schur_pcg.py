@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import _schurref as R
+import _solvecheck as SC
 from test_gpu_schur_step import _make, _np, _ref, env  # noqa: F401  (env is the module fixture)
 
 pytestmark = pytest.mark.gpu
@@ -13,55 +14,14 @@ EPS = R.EPS
 KS = (0, 1, 2, 3, 5, 8, 13)
 
 
-def _over(err, bound):
-    return err / bound if bound > 0 else (0.0 if err == 0 else np.inf)
-
-
-def _sum_sq(P):
-    r = P.r.astype(R.LD)
-    return np.sum(r * r)
-
-
-def _model_tol(P, dc, dp):
-    """64 eps x the absolute-value scale of the per-observation model terms -(2r + e).e and their sum"""
-    dc, dp = np.abs(np.asarray(dc, dtype=np.float64)), np.abs(np.asarray(dp, dtype=np.float64))
-    ae = np.einsum("nia,na->ni", np.abs(P.Jc), dc[P.cam]) + np.einsum("nia,na->ni", np.abs(P.Jp), dp[P.pt])
-    ar = np.abs(P.r.astype(np.float64))
-    return 64 * EPS * float(np.sum((2 * ar + 2 * ae) * ae))
+_over, _sum_sq, _model_tol = SC.over, SC.sum_sq, SC.model_tol
 
 
 def _check_iterates(ba, lam, ks, runs=8, tag=""):
-    """solve_step(lam, k, 0) against pcg for every k in ks (the worst |err| / bound per quantity is printed); returns
-    the reference"""
+    """solve_step(lam, k, 0) against pcg for every k in ks (tests/_solvecheck.py's check_iterates: the worst |err| / bound
+    per quantity is printed); returns the reference"""
     P = _ref(ba, R.LD)
-    ref = R.pcg(P, lam, max(ks), 0.0, runs=runs)
-    assert ref["status"] == 1 and ref["iterations"] == max(ks), (ref["status"], ref["iterations"])
-    b = ref["bound"]
-    worst = dict(x=0.0, dp=0.0, rel=0.0, energy=0.0, model=0.0)
-    e_prev = k_prev = None
-    for k in ks:
-        dc, dp, info = ba.solve_step(lam, max_iters=k, rel_tol=0.0)
-        dc, dp = _np(dc), _np(dp)
-        assert info["status"] == 1 and info["iterations"] == k, (tag, k, info)
-        ex = _over(float(np.linalg.norm(dc - ref["x"][k].astype(np.float64))), b["x"][k])
-        ed = _over(float(np.linalg.norm(dp - ref["dp"][k].astype(np.float64))), b["dp"][k])
-        er = _over(abs(info["rel_residual"] - float(ref["rel"][k])), b["rel"][k])
-        en = R.energy(P, lam, dc)
-        ee = _over(abs(float(en - ref["energy"][k])), b["energy"][k])
-        for key, v in (("x", ex), ("dp", ed), ("rel", er), ("energy", ee)):
-            worst[key] = max(worst[key], v)
-            assert v <= 1.0, (tag, lam, k, key, v, info)
-        if e_prev is not None and float(ref["energy"][k_prev] - ref["energy"][k]) > b["energy"][k] + b["energy"][k_prev]:
-            assert en < e_prev, (tag, lam, k, float(en), float(e_prev))
-        e_prev, k_prev = en, k
-        ss = float(_sum_sq(P))
-        assert abs(info["sum_sq"] - ss) <= 1e-13 * ss, (tag, k, info["sum_sq"], ss)
-        md = float(P.model_decrease(dc, dp))
-        em = _over(abs(info["model_decrease"] - md), _model_tol(P, dc, dp))
-        worst["model"] = max(worst["model"], em)
-        assert em <= 1.0, (tag, lam, k, info["model_decrease"], md)
-    print("PCGREF %s lam=%g worst |err|/bound %s" % (tag, lam, {k: "%.3g" % v for k, v in worst.items()}))
-    return ref
+    return SC.check_iterates(ba, P, R.pcg(P, lam, max(ks), 0.0, runs=runs), lam, ks, tag=tag, label="PCGREF")
 
 
 # ---- 1. every iterate ----------------------------------------------------------------------------------------------
@@ -74,19 +34,7 @@ def test_iterates_follow_the_reference(env, name, lam):
 
 
 # ---- 2. stopping ------------------------------------------------------------------------------------------------------
-def _crossing_tols(ref, n):
-    """up to n thresholds, each between rel[K - 1] and rel[K] of a first crossing K >= 1 of the reference, and no rel[j],
-    j <= K, within 1e-6 of it or within the reference's bound of it"""
-    rel = np.array([float(v) for v in ref["rel"]])
-    margin = np.asarray(ref["bound"]["rel"])
-    out = []
-    for K in range(1, len(rel)):
-        if not rel[K] < rel[K - 1]:
-            continue
-        tol = np.sqrt(rel[K - 1] * rel[K])
-        if (rel[:K] > tol).all() and rel[K] <= tol and (np.abs(rel[:K + 1] - tol) > np.maximum(1e-6 * tol, margin[:K + 1])).all():
-            out.append((K, tol))
-    return out[::max(1, len(out) // n)][:n]
+_crossing_tols = SC.crossing_tols
 
 
 @pytest.mark.parametrize("name", ["random bal", "mixed k2"])
