@@ -53,12 +53,14 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+// the status code of a failed runtime call
+inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP; }
+
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
         if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "%s: %s (%s:%d)", #expr, \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                           \
+            return fail(hip_code(e_), "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
 // A launch is checked by what it ADDS to the thread's error state: S() notes the error (if any) that was already
@@ -71,8 +73,7 @@ thread_local hipError_t g_pending = hipSuccess;
         const hipError_t e_ = hipPeekAtLastError();                                                       \
         if (e_ != hipSuccess && e_ != g_pending) {                                                        \
             (void)hipGetLastError();                                                                      \
-            return fail(e_ == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "kernel launch: %s (%s:%d)",   \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                       \
+            return fail(hip_code(e_), "kernel launch: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
         }                                                                                                 \
     } while (0)
 
@@ -101,6 +102,47 @@ inline hipError_t launch_error() {
     return e;
 }
 inline unsigned blocks_for(int64_t n, int b = kBlock) { return (unsigned)((n + b - 1) / b); }
+
+// The owner of Level 1's device memory (capi_problem.hpp, capi_files.hpp): `count` elements of T that free themselves,
+// or a view into memory someone else owns (a DevArena block), which is never freed here.  It moves, never copies; it
+// passes for the pointer it holds, so a launch takes it as it would take a T *.  Untyped arrays are DevBuf<char>.
+template <class T>
+struct DevBuf {
+    T *ptr = nullptr;
+    bool owned = true;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); swap(o); } return *this; }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t count) {           // (what it held is freed first; nothing is ever 0 bytes long)
+        reset();
+        const hipError_t e = hipMalloc((void **)&ptr, count ? count * sizeof(T) : 16);
+        if (e != hipSuccess) ptr = nullptr;
+        return e;
+    }
+    void view(T *q) { reset(); ptr = q; owned = false; }
+    void reset() { if (ptr && owned) (void)hipFree(ptr); ptr = nullptr; owned = true; }
+    void swap(DevBuf &o) { std::swap(ptr, o.ptr); std::swap(owned, o.owned); }
+    operator T *() const { return ptr; }
+};
+
+// Temporaries of one call carved out of ONE allocation: a device malloc / free pair costs ~1 ms at these sizes (the free
+// synchronises), and cull used to make ~25 of each -- most of its 45 ms at --blocks 128 once its kernels took 10.
+// A call sums room() over its temporaries, reserves that once and carves them in the same order.
+struct DevArena {
+    DevBuf<char> block;
+    size_t used = 0, cap = 0;
+    template <class T> static size_t room(const DevBuf<T> &, size_t count) { return ((count ? count * sizeof(T) : 16) + 255) & ~(size_t)255; }
+    hipError_t reserve(size_t bytes) { cap = bytes; return block.alloc(bytes); }
+    template <class T> void carve(DevBuf<T> &b, size_t count) {
+        char *q = block.ptr + used;
+        used += room(b, count);
+        b.view(used <= cap ? reinterpret_cast<T *>(q) : nullptr);
+    }
+};
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // workspace layout (doubles): [stats records: kRedBlocks*kStatRec] [result slot of the fused error sum: 16]

@@ -135,37 +135,35 @@ int c2b_problem_write(c2b_problem *p, const char *path, int format) {
                       t_pts = (3 * n_pts + kTextTile - 1) / kTextTile, n_tiles = t_obs + t_cam + t_pts;
         char head[80];
         const int head_len = std::snprintf(head, sizeof head, "%lld %lld %lld\n", (long long)n_cam, (long long)n_pts, (long long)n_obs);
-        DevBuf tile_len, tile_base, total;
-        hipError_t e = tile_len.alloc(4 * (size_t)(n_tiles + 1));
-        if (e == hipSuccess) e = tile_base.alloc(8 * (size_t)(n_tiles + 1));
-        if (e == hipSuccess) e = total.alloc(8);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_write: %s", hipGetErrorString(e));
-        uint32_t *tl = tile_len.as<uint32_t>();
-        uint64_t *tb = tile_base.as<uint64_t>();
+        DevBuf<uint32_t> tl;                                 // the tiles' byte counts
+        DevBuf<uint64_t> tb, total;                          // their bases in the image; its size
+        hipError_t e = tl.alloc((size_t)(n_tiles + 1));
+        if (e == hipSuccess) e = tb.alloc((size_t)(n_tiles + 1));
+        if (e == hipSuccess) e = total.alloc(1);
+        if (e != hipSuccess) return fail(hip_code(e), "problem_write: %s", hipGetErrorString(e));
         const uint32_t *ci = (const uint32_t *)p->cam_idx, *pi = (const uint32_t *)p->pt_idx;
-        const double2 *uvd = reinterpret_cast<const double2 *>(p->uv);
+        const double2 *uvd = reinterpret_cast<const double2 *>(p->uv.ptr);
         if (t_obs) hipLaunchKernelGGL((k_text_obs<false>), dim3((unsigned)t_obs), dim3(kTextTile), 0, st, ci, pi, uvd, n_obs, T, tl,
                                       (const uint64_t *)nullptr, (char *)nullptr);
         if (t_cam) hipLaunchKernelGGL((k_text_vals<false>), dim3((unsigned)t_cam), dim3(kTextTile), 0, st, (const double *)p->bal9, n_cam, 9, 9, T,
                                       tl + t_obs, (const uint64_t *)nullptr, (char *)nullptr);
         if (t_pts) hipLaunchKernelGGL((k_text_vals<false>), dim3((unsigned)t_pts), dim3(kTextTile), 0, st, (const double *)p->pts4, n_pts, 3, 4, T,
                                       tl + t_obs + t_cam, (const uint64_t *)nullptr, (char *)nullptr);
-        hipLaunchKernelGGL(k_text_tile_bases, dim3(1), dim3(1024), 0, st, (const uint32_t *)tl, n_tiles, (uint64_t)head_len, tb, total.as<uint64_t>());
+        hipLaunchKernelGGL(k_text_tile_bases, dim3(1), dim3(1024), 0, st, (const uint32_t *)tl, n_tiles, (uint64_t)head_len, tb, total);
         e = launch_error();
         uint64_t bytes = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&bytes, total.ptr, 8, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        DevBuf img;
+        DevBuf<char> img;
         if (e == hipSuccess) e = img.alloc((size_t)bytes);
         if (e == hipSuccess) e = hipMemcpyAsync(img.ptr, head, (size_t)head_len, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_write: %s", hipGetErrorString(e));
-        char *im = img.as<char>();
+        if (e != hipSuccess) return fail(hip_code(e), "problem_write: %s", hipGetErrorString(e));
         if (t_obs) hipLaunchKernelGGL((k_text_obs<true>), dim3((unsigned)t_obs), dim3(kTextTile), 0, st, ci, pi, uvd, n_obs, T, (uint32_t *)nullptr,
-                                      (const uint64_t *)tb, im);
+                                      (const uint64_t *)tb, img);
         if (t_cam) hipLaunchKernelGGL((k_text_vals<true>), dim3((unsigned)t_cam), dim3(kTextTile), 0, st, (const double *)p->bal9, n_cam, 9, 9, T,
-                                      (uint32_t *)nullptr, (const uint64_t *)(tb + t_obs), im);
+                                      (uint32_t *)nullptr, (const uint64_t *)(tb + t_obs), img);
         if (t_pts) hipLaunchKernelGGL((k_text_vals<true>), dim3((unsigned)t_pts), dim3(kTextTile), 0, st, (const double *)p->pts4, n_pts, 3, 4, T,
-                                      (uint32_t *)nullptr, (const uint64_t *)(tb + t_obs + t_cam), im);
+                                      (uint32_t *)nullptr, (const uint64_t *)(tb + t_obs + t_cam), img);
         e = launch_error();
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return fail(C2B_ERR_HIP, "problem_write: %s", hipGetErrorString(e));
@@ -174,17 +172,16 @@ int c2b_problem_write(c2b_problem *p, const char *path, int format) {
     rc = ensure_rows(p);
     if (rc) return rc;
     const size_t words = 3 + (size_t)n_cam + 3 * (size_t)n_obs + 9 * (size_t)n_cam + 3 * (size_t)n_pts, bytes = words * 8;
-    DevBuf img;
-    hipError_t e = img.alloc(bytes);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_write: %s", hipGetErrorString(e));
-    uint64_t *w = img.as<uint64_t>();
+    DevBuf<uint64_t> img;
+    hipError_t e = img.alloc(words);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_write: %s", hipGetErrorString(e));
     hipStream_t st = p->stream;
     // (no observations: no row structure exists and every count is zero)
     hipLaunchKernelGGL(k_bbal_rows, dim3(blocks_of(n_cam, 256)), dim3(256), 0, st, (const uint64_t *)(n_obs ? p->rows_ptr : nullptr),
-                       n_cam, n_pts, n_obs, w);
+                       n_cam, n_pts, n_obs, img);
     if (n_obs) hipLaunchKernelGGL(k_bbal_observations, dim3(blocks_of(n_obs, 256)), dim3(256), 0, st, (const uint32_t *)p->cam_idx,
-                                  (const uint32_t *)p->pt_idx, reinterpret_cast<const double2 *>(p->uv), n_obs, w);
-    uint64_t *wc = w + 3 + n_cam + 3 * (size_t)n_obs, *wp = wc + 9 * (size_t)n_cam;
+                                  (const uint32_t *)p->pt_idx, reinterpret_cast<const double2 *>(p->uv.ptr), n_obs, img);
+    uint64_t *wc = img + 3 + n_cam + 3 * (size_t)n_obs, *wp = wc + 9 * (size_t)n_cam;
     if (n_cam) hipLaunchKernelGGL(k_bbal_rows_f64, dim3(blocks_of(9 * n_cam, 256)), dim3(256), 0, st, (const double *)p->bal9, n_cam, 9, 9, wc);
     if (n_pts) hipLaunchKernelGGL(k_bbal_rows_f64, dim3(blocks_of(3 * n_pts, 256)), dim3(256), 0, st, (const double *)p->pts4, n_pts, 3, 4, wp);
     e = launch_error();
@@ -329,84 +326,84 @@ static int read_text_device(c2b_problem *p, const char *path, bool *handled) {
     hipStream_t st = p->stream;
     const size_t padded = ((bytes + 15) & ~(size_t)15) + 16;
     const int64_t n_tiles = (int64_t)((bytes + kParseTile - 1) / kParseTile);
-    DevBuf raw, cnt, base, total, flags, t_cam, t_pt, t_uv, t_bal, t_pts;
+    DevBuf<char> raw;
+    DevBuf<uint32_t> cnt, flags, t_cam, t_pt;
+    DevBuf<uint64_t> base, total;
+    DevBuf<double> t_uv, t_bal, t_pts;
     hipError_t e = raw.alloc(padded);
-    if (e == hipSuccess) e = cnt.alloc(4 * (size_t)n_tiles);
-    if (e == hipSuccess) e = base.alloc(8 * (size_t)n_tiles);
-    if (e == hipSuccess) e = total.alloc(8);
-    if (e == hipSuccess) e = flags.alloc(16);
-    if (e == hipSuccess) e = t_cam.alloc(4 * (size_t)no);
-    if (e == hipSuccess) e = t_pt.alloc(4 * (size_t)no);
-    if (e == hipSuccess) e = t_uv.alloc(16 * (size_t)no);
-    if (e == hipSuccess) e = t_bal.alloc(72 * (size_t)nc);
-    if (e == hipSuccess) e = t_pts.alloc(32 * (size_t)np);
-    if (e == hipSuccess) e = hipMemsetAsync(raw.as<char>() + (padded - 32), 0, 32, st);
+    if (e == hipSuccess) e = cnt.alloc((size_t)n_tiles);
+    if (e == hipSuccess) e = base.alloc((size_t)n_tiles);
+    if (e == hipSuccess) e = total.alloc(1);
+    if (e == hipSuccess) e = flags.alloc(4);
+    if (e == hipSuccess) e = t_cam.alloc((size_t)no);
+    if (e == hipSuccess) e = t_pt.alloc((size_t)no);
+    if (e == hipSuccess) e = t_uv.alloc(2 * (size_t)no);
+    if (e == hipSuccess) e = t_bal.alloc(9 * (size_t)nc);
+    if (e == hipSuccess) e = t_pts.alloc(4 * (size_t)np);
+    if (e == hipSuccess) e = hipMemsetAsync(raw + (padded - 32), 0, 32, st);
     if (e == hipSuccess) e = hipMemsetAsync(flags.ptr, 0, 16, st);
     if (e == hipSuccess) e = hipMemsetAsync(t_pts.ptr, 0, np ? 32 * (size_t)np : 16, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_read: %s", hipGetErrorString(e));
-    const int io = file_to_device(fd, bytes, raw.as<char>(), p->opt.read_threads);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_read: %s", hipGetErrorString(e));
+    const int io = file_to_device(fd, bytes, raw, p->opt.read_threads);
     if (io == 1) return fail(C2B_ERR_HIP, "problem_read: host-to-device copy failed");
     if (io) return C2B_OK;                                   // unreadable: the host path says so
-    hipLaunchKernelGGL(k_text_count_tokens, dim3((unsigned)n_tiles), dim3(kTextTile), 0, st, (const char *)raw.as<char>(), (int64_t)bytes, cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_text_tile_bases, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt.as<uint32_t>(), n_tiles, (uint64_t)0, base.as<uint64_t>(),
-                       total.as<uint64_t>());
+    hipLaunchKernelGGL(k_text_count_tokens, dim3((unsigned)n_tiles), dim3(kTextTile), 0, st, raw, (int64_t)bytes, cnt);
+    hipLaunchKernelGGL(k_text_tile_bases, dim3(1), dim3(1024), 0, st, cnt, n_tiles, (uint64_t)0, base, total);
     e = launch_error();
     uint64_t n_tokens = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&n_tokens, total.ptr, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(C2B_ERR_HIP, "problem_read: %s", hipGetErrorString(e));
     if (n_tokens < 3 + 4 * no + 9 * nc + 3 * np) return C2B_OK;           // too short: the host parser says where
-    hipLaunchKernelGGL(k_text_parse, dim3((unsigned)n_tiles), dim3(kTextTile), 0, st, (const char *)raw.as<char>(), (int64_t)bytes,
-                       (const uint64_t *)base.as<uint64_t>(), T, nc, np, no, t_cam.as<uint32_t>(), t_pt.as<uint32_t>(), t_uv.as<double>(),
-                       t_bal.as<double>(), t_pts.as<double>(), flags.as<uint32_t>());
-    if (no > 1) hipLaunchKernelGGL(k_text_check_sorted, dim3(blocks_of((int64_t)no, 256)), dim3(256), 0, st, (const uint32_t *)t_cam.as<uint32_t>(), (int64_t)no,
-                                   flags.as<uint32_t>());
+    hipLaunchKernelGGL(k_text_parse, dim3((unsigned)n_tiles), dim3(kTextTile), 0, st, raw, (int64_t)bytes, base, T, nc, np, no, t_cam, t_pt,
+                       t_uv, t_bal, t_pts, flags);
+    if (no > 1) hipLaunchKernelGGL(k_text_check_sorted, dim3(blocks_of((int64_t)no, 256)), dim3(256), 0, st, t_cam, (int64_t)no, flags);
     e = launch_error();
     uint32_t fl[4] = {0, 0, 0, 0};
     if (e == hipSuccess) e = hipMemcpyAsync(fl, flags.ptr, 16, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(C2B_ERR_HIP, "problem_read: %s", hipGetErrorString(e));
     if (fl[0] || fl[1] || fl[2]) return C2B_OK;
-    DevBuf s_cam, s_pt, s_uv;                               // the camera-major lists when the file's are not
+    DevBuf<uint32_t> s_cam, s_pt;
+    DevBuf<double> s_uv;                                    // the camera-major lists when the file's are not
     if (fl[3]) {
         // BAProblem::new's per-camera push in file order = a stable sort by camera (text_kernels.hpp: k_sort_*): 8 bits
         // a pass over (camera, position in the file), then one gather of the point indices and the observations
         const int64_t n = (int64_t)no, n_st = (n + kSortTile - 1) / kSortTile, n_hist = 256 * n_st;
-        DevBuf k2, v1, v2, hist, offs, tiles, total32;
-        e = k2.alloc(4 * (size_t)n);
-        if (e == hipSuccess) e = v1.alloc(4 * (size_t)n);
-        if (e == hipSuccess) e = v2.alloc(4 * (size_t)n);
-        if (e == hipSuccess) e = hist.alloc(4 * (size_t)n_hist);
-        if (e == hipSuccess) e = offs.alloc(4 * (size_t)n_hist);
-        if (e == hipSuccess) e = tiles.alloc(4 * (size_t)(n_hist / kScanTile + 2));
-        if (e == hipSuccess) e = total32.alloc(4);
-        if (e == hipSuccess) e = s_cam.alloc(4 * (size_t)n);
-        if (e == hipSuccess) e = s_pt.alloc(4 * (size_t)n);
-        if (e == hipSuccess) e = s_uv.alloc(16 * (size_t)n);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_read: %s", hipGetErrorString(e));
+        DevBuf<uint32_t> k2, v1, v2, hist, offs, tiles, total32;
+        e = k2.alloc((size_t)n);
+        if (e == hipSuccess) e = v1.alloc((size_t)n);
+        if (e == hipSuccess) e = v2.alloc((size_t)n);
+        if (e == hipSuccess) e = hist.alloc((size_t)n_hist);
+        if (e == hipSuccess) e = offs.alloc((size_t)n_hist);
+        if (e == hipSuccess) e = tiles.alloc((size_t)(n_hist / kScanTile + 2));
+        if (e == hipSuccess) e = total32.alloc(1);
+        if (e == hipSuccess) e = s_cam.alloc((size_t)n);
+        if (e == hipSuccess) e = s_pt.alloc((size_t)n);
+        if (e == hipSuccess) e = s_uv.alloc(2 * (size_t)n);
+        if (e != hipSuccess) return fail(hip_code(e), "problem_read: %s", hipGetErrorString(e));
         int bits = 1;
         while (bits < 32 && (nc - 1) >> bits) ++bits;
         // keys ping-pong between t_cam / k2 so that the last pass lands in s_cam; values between v1 / v2
         const int passes = (bits + 7) / 8;
-        const uint32_t *k_in = t_cam.as<uint32_t>(), *v_in = nullptr;
+        const uint32_t *k_in = t_cam, *v_in = nullptr;
         for (int ps = 0; ps < passes; ++ps) {
-            uint32_t *k_out = ps == passes - 1 ? s_cam.as<uint32_t>() : (ps % 2 == 0 ? k2.as<uint32_t>() : t_cam.as<uint32_t>());
-            uint32_t *v_out = ps % 2 == 0 ? v1.as<uint32_t>() : v2.as<uint32_t>();
-            hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)n_st), dim3(64), 0, st, k_in, n, 8 * ps, n_st, hist.as<uint32_t>());
+            uint32_t *k_out = ps == passes - 1 ? s_cam : (ps % 2 == 0 ? k2 : t_cam);
+            uint32_t *v_out = ps % 2 == 0 ? v1 : v2;
+            hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)n_st), dim3(64), 0, st, k_in, n, 8 * ps, n_st, hist);
             uint32_t sum = 0;
-            e = scan_flags(st, hist.as<uint32_t>(), n_hist, offs.as<uint32_t>(), tiles.as<uint32_t>(), total32.as<uint32_t>(), &sum);
+            e = scan_flags(st, hist, n_hist, offs, tiles, total32, &sum);
             if (e == hipSuccess && (int64_t)sum != n) return fail(C2B_ERR_HIP, "problem_read: the sort's histogram does not add up");
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)n_st), dim3(64), 0, st, k_in, v_in, n, 8 * ps, n_st, (const uint32_t *)offs.as<uint32_t>(),
-                                   k_out, v_out);
+                hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)n_st), dim3(64), 0, st, k_in, v_in, n, 8 * ps, n_st, offs, k_out, v_out);
                 e = launch_error();
             }
             if (e != hipSuccess) return fail(C2B_ERR_HIP, "problem_read: %s", hipGetErrorString(e));
             k_in = k_out; v_in = v_out;
         }
-        hipLaunchKernelGGL(k_text_gather_obs, dim3(blocks_of(n, 256)), dim3(256), 0, st, v_in, n, (const uint32_t *)t_pt.as<uint32_t>(),
-                           (const double2 *)t_uv.as<double2>(), s_pt.as<uint32_t>(), s_uv.as<double2>());
+        hipLaunchKernelGGL(k_text_gather_obs, dim3(blocks_of(n, 256)), dim3(256), 0, st, v_in, n, t_pt,
+                           reinterpret_cast<const double2 *>(t_uv.ptr), s_pt, reinterpret_cast<double2 *>(s_uv.ptr));
         e = launch_error();
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return fail(C2B_ERR_HIP, "problem_read: %s", hipGetErrorString(e));
@@ -464,9 +461,9 @@ int c2b_problem_read(c2b_problem *p, const char *path, int format) {
     const off_t end = ::lseek(fd, 0, SEEK_END);
     if (end < 24) return fail(C2B_ERR_INVALID_ARGUMENT, "Binary parse error");
     const size_t bytes = (size_t)end & ~(size_t)7;                       // whole words (the format has nothing else)
-    DevBuf raw;
-    hipError_t e = raw.alloc(bytes);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_read: %s", hipGetErrorString(e));
+    DevBuf<uint64_t> raw;
+    hipError_t e = raw.alloc(bytes / 8);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_read: %s", hipGetErrorString(e));
     // A few reader threads fill a ring of pinned slots (reads of one file from the page cache run in parallel, unlike
     // buffered writes), chunk k into slot k % kSlots.  The per-camera counts can only be found in order -- each sits in
     // front of its records -- so the walk over them is a chain through the whole file: the reader that has just read
@@ -552,7 +549,7 @@ int c2b_problem_read(c2b_problem *p, const char *path, int format) {
             if (failed) break;
         }
         const size_t off = k * kChunk, len = std::min(kChunk, bytes - off);
-        const hipError_t ce = hipMemcpy(raw.as<char>() + off, pin + (k % kSlots) * kChunk, len, hipMemcpyHostToDevice);
+        const hipError_t ce = hipMemcpy(reinterpret_cast<char *>(raw.ptr) + off, pin + (k % kSlots) * kChunk, len, hipMemcpyHostToDevice);
         std::lock_guard<std::mutex> lk(mu);
         if (ce != hipSuccess) failed = 1;
         drained = k + 1;
@@ -576,17 +573,18 @@ int c2b_problem_read(c2b_problem *p, const char *path, int format) {
     // so that a failed read leaves "nothing uploaded" behind and never a problem that passes NEED_UPLOADED with garbage.
     struct DropUnlessDone { c2b_problem *q; bool done = false; ~DropUnlessDone() { if (!done) { (void)hipStreamSynchronize(q->stream); free_buffers(q); } } } guard{p};
     hipStream_t st = p->stream;
-    DevBuf d_row, d_bad;
-    e = d_row.alloc(sizeof(uint64_t) * (size_t)(n_cam + 1));
-    if (e == hipSuccess) e = d_bad.alloc(4);
+    DevBuf<uint64_t> d_row;
+    DevBuf<uint32_t> d_bad;
+    e = d_row.alloc((size_t)n_cam + 1);
+    if (e == hipSuccess) e = d_bad.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(d_bad.ptr, 0, 4, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_row.ptr, row_ptr.data(), sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_read: %s", hipGetErrorString(e));
-    rc = c2b_expand_rows(d_row.as<uint64_t>(), (int64_t)n_cam, 0, (int64_t)n_obs, p->cam_idx, st);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_read: %s", hipGetErrorString(e));
+    rc = c2b_expand_rows(d_row, (int64_t)n_cam, 0, (int64_t)n_obs, p->cam_idx, st);
     if (rc) return rc;
-    const uint64_t *w = raw.as<uint64_t>();
+    const uint64_t *w = raw;
     if (n_obs) hipLaunchKernelGGL(k_bbal_read_observations, dim3(blocks_of((int64_t)n_obs, 256)), dim3(256), 0, st, w, (const uint32_t *)p->cam_idx,
-                                  (int64_t)n_obs, n_pts, p->pt_idx, reinterpret_cast<double2 *>(p->uv), d_bad.as<uint32_t>());
+                                  (int64_t)n_obs, n_pts, p->pt_idx, reinterpret_cast<double2 *>(p->uv.ptr), d_bad);
     const uint64_t *wc = w + next_hdr / 8, *wp = wc + 9 * n_cam;
     if (n_cam) hipLaunchKernelGGL(k_bbal_read_rows_f64, dim3(blocks_of(9 * (int64_t)n_cam, 256)), dim3(256), 0, st, wc, (int64_t)n_cam, 9, 9, p->bal9);
     if (n_pts) hipLaunchKernelGGL(k_bbal_read_rows_f64, dim3(blocks_of(4 * (int64_t)n_pts, 256)), dim3(256), 0, st, wp, (int64_t)n_pts, 3, 4, p->pts4);

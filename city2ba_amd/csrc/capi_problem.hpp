@@ -8,12 +8,14 @@ struct c2b_problem {
     int device = 0;
     hipStream_t stream = nullptr;
     int64_t n_cam = 0, n_pts = 0, n_obs = 0;
-    double *cam15 = nullptr, *bal9 = nullptr, *camblk = nullptr, *cen4 = nullptr, *pts4 = nullptr, *uv = nullptr;
+    // every device array below is a DevBuf (capi.hip): the problem owns its memory through that one type, and the four
+    // functions under this struct say which group of them goes when
+    DevBuf<double> cam15, bal9, camblk, cen4, pts4, uv;
     // cen4[n_cam][4]: the cameras' centres as 32-byte rows (derived with camblk, valid when blk_valid): what the statistics
     // and the centre-keyed cell lists read -- a 128-byte line of camblk per camera otherwise
-    uint32_t *cam_idx = nullptr, *pt_idx = nullptr;
-    void *ws = nullptr;
-    double *stats = nullptr, *scalar = nullptr;
+    DevBuf<uint32_t> cam_idx, pt_idx;
+    DevBuf<char> ws;
+    DevBuf<double> stats, scalar;
     // this problem as ONE SHARD of a larger one (c2b_problem_set_shard): its cameras are [shard_cam_base, + n_cam) of
     // shard_n_cam_global (< 0: not a shard), its first observation is observation shard_obs_base of the whole list
     int64_t shard_cam_base = 0, shard_n_cam_global = -1, shard_obs_base = 0;
@@ -29,8 +31,8 @@ struct c2b_problem {
     // c2b_problem_set_constant: the camera parameters (bit k of a camera's word, to_vec order) and the points
     // (0 / 1) that normal_equations / solve_step / apply_step hold constant; the handle's, kept while both counts stay
     // what they were set for (const_n_cam, const_n_pts).  A kind with nothing set has no array: no launch changes for it.
-    uint16_t *cmask = nullptr;
-    uint8_t *pmask = nullptr;
+    DevBuf<uint16_t> cmask;
+    DevBuf<uint8_t> pmask;
     std::vector<uint16_t> h_cmask;
     std::vector<uint8_t> h_pmask;
     int64_t const_n_cam = -1, const_n_pts = -1, const_params = 0, const_pts = 0;
@@ -38,69 +40,60 @@ struct c2b_problem {
     bool blk_valid = false;     // camblk matches cam15 (and bal_valid mode)
     bool bal9_fresh = false;    // !bal_valid, but bal9 holds to_vec of the current cameras (the last write / download_bal computed it)
     // the row structure of the observation list for the *_rows launchers, rebuilt on demand after the list changed
-    uint64_t *rows_ptr = nullptr;
-    void *rows_tiles = nullptr;
+    DevBuf<uint64_t> rows_ptr;
+    DevBuf<char> rows_tiles;
     bool rows_valid = false;
     // its point-major transpose for c2b_problem_normal_equations (pt_row_ptr [n_pts + 1], obs_of / cam_of [n_obs]), dropped with it
-    uint64_t *nt_ptr = nullptr;
-    uint32_t *nt_obs = nullptr, *nt_cam = nullptr;
+    DevBuf<uint64_t> nt_ptr;
+    DevBuf<uint32_t> nt_obs, nt_cam;
     // c2b_problem_solve_step's buffers (U, gc, V, gp, the preconditioner's factors, the PCG vectors, partials, scalars):
     // one allocation, sized by the list, dropped with it
-    double *sv = nullptr;
+    DevBuf<double> sv;
     int64_t sv_doubles = 0;
-    uint32_t *dense_pt = nullptr;   // survivors of the last dense visibility sweep
-    double *dense_uv = nullptr;
-    uint64_t *dense_row = nullptr;  // its CSR row pointer [n_cam + 1], kept for the occlusion filter
+    DevBuf<uint32_t> dense_pt;      // survivors of the last dense visibility sweep
+    DevBuf<double> dense_uv;
+    DevBuf<uint64_t> dense_row;     // its CSR row pointer [n_cam + 1], kept for the occlusion filter
     int64_t dense_n = 0;
     // residual + Jacobian to host buffers: a ring of chunk-sized device buffers, a copy stream, per-slot events
     static constexpr int kJacSlots = 3;
     static constexpr int64_t kJacChunk = 256 * 1024;       // observations per chunk (53 MB of results)
-    double *jac_ring = nullptr;                            // kJacSlots x kJacChunk x 26 doubles
+    DevBuf<double> jac_ring;                               // kJacSlots x kJacChunk x 26 doubles
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_done[kJacSlots] = {nullptr, nullptr, nullptr}, ev_free[kJacSlots] = {nullptr, nullptr, nullptr};
 };
 
 static void cameras_mutated(c2b_problem *p);
 
+// the pending visibility result goes (a new sweep, a cull, new points)
 static void free_dense(c2b_problem *p) {
-    if (p->dense_pt) (void)hipFree(p->dense_pt);
-    if (p->dense_uv) (void)hipFree(p->dense_uv);
-    if (p->dense_row) (void)hipFree(p->dense_row);
-    p->dense_pt = nullptr; p->dense_uv = nullptr; p->dense_row = nullptr; p->dense_n = 0;
+    p->dense_pt.reset(); p->dense_uv.reset(); p->dense_row.reset();
+    p->dense_n = 0;
 }
 
 // the observation list changed (upload, cull, adopted visibility): its row structure is rebuilt by the next user
 static void drop_rows(c2b_problem *p) {
-    if (p->rows_ptr) (void)hipFree(p->rows_ptr);
-    if (p->rows_tiles) (void)hipFree(p->rows_tiles);
-    p->rows_ptr = nullptr; p->rows_tiles = nullptr; p->rows_valid = false;
-    if (p->nt_ptr) (void)hipFree(p->nt_ptr);
-    if (p->nt_obs) (void)hipFree(p->nt_obs);
-    if (p->nt_cam) (void)hipFree(p->nt_cam);
-    p->nt_ptr = nullptr; p->nt_obs = p->nt_cam = nullptr;
-    if (p->sv) (void)hipFree(p->sv);
-    p->sv = nullptr; p->sv_doubles = 0;
+    p->rows_ptr.reset(); p->rows_tiles.reset();
+    p->rows_valid = false;
+    p->nt_ptr.reset(); p->nt_obs.reset(); p->nt_cam.reset();
+    p->sv.reset();
+    p->sv_doubles = 0;
 }
 
 // the entities were renumbered or their counts changed: nothing is constant any more
 static void drop_constant(c2b_problem *p) {
-    if (p->cmask) (void)hipFree(p->cmask);
-    if (p->pmask) (void)hipFree(p->pmask);
-    p->cmask = nullptr; p->pmask = nullptr;
+    p->cmask.reset(); p->pmask.reset();
     p->h_cmask.clear(); p->h_pmask.clear();
     p->const_n_cam = p->const_n_pts = -1;
     p->const_params = p->const_pts = 0;
 }
 
+// everything but the constant masks goes: "nothing uploaded"
 static void free_buffers(c2b_problem *p) {
-    void *ptrs[] = {p->cam15, p->bal9, p->camblk, p->cen4, p->pts4, p->uv, p->cam_idx, p->pt_idx, p->ws, p->stats, p->scalar, p->jac_ring};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    p->jac_ring = nullptr;
+    p->cam15.reset(); p->bal9.reset(); p->camblk.reset(); p->cen4.reset(); p->pts4.reset(); p->uv.reset();
+    p->cam_idx.reset(); p->pt_idx.reset();
+    p->ws.reset(); p->stats.reset(); p->scalar.reset(); p->jac_ring.reset();
     free_dense(p);
     drop_rows(p);
-    p->cam15 = p->bal9 = p->camblk = p->cen4 = p->pts4 = p->uv = nullptr;
-    p->cam_idx = p->pt_idx = nullptr;
-    p->ws = nullptr; p->stats = p->scalar = nullptr;
     p->n_cam = p->n_pts = p->n_obs = 0;
     p->bal_valid = p->blk_valid = p->bal9_fresh = false;
 }
@@ -170,19 +163,18 @@ static int alloc_problem(c2b_problem *p, int64_t n_cam, int64_t n_pts, int64_t n
     HIP_TRY(hipSetDevice(p->device));
     free_buffers(p);
     if (!same_entities || n_cam != p->const_n_cam || n_pts != p->const_n_pts) drop_constant(p);
-    auto dalloc = [&](void **q, size_t bytes) -> hipError_t { return hipMalloc(q, bytes ? bytes : 16); };
-    HIP_TRY(dalloc((void **)&p->cam15, sizeof(double) * 15 * n_cam));
-    HIP_TRY(dalloc((void **)&p->bal9, sizeof(double) * 9 * n_cam));
-    HIP_TRY(dalloc((void **)&p->camblk, sizeof(double) * (size_t)cam_table_doubles(n_cam)));      // whole groups of 8 cameras
-    HIP_TRY(dalloc((void **)&p->cen4, sizeof(double) * 4 * n_cam));
-    HIP_TRY(dalloc((void **)&p->pts4, sizeof(double) * 4 * n_pts));
-    HIP_TRY(dalloc((void **)&p->uv, sizeof(double) * 2 * n_obs));
-    HIP_TRY(dalloc((void **)&p->cam_idx, sizeof(uint32_t) * n_obs));
-    HIP_TRY(dalloc((void **)&p->pt_idx, sizeof(uint32_t) * n_obs));
-    HIP_TRY(dalloc(&p->ws, (size_t)c2b_workspace_bytes(n_obs)));
+    HIP_TRY(p->cam15.alloc(15 * (size_t)n_cam));
+    HIP_TRY(p->bal9.alloc(9 * (size_t)n_cam));
+    HIP_TRY(p->camblk.alloc((size_t)cam_table_doubles(n_cam)));      // whole groups of 8 cameras
+    HIP_TRY(p->cen4.alloc(4 * (size_t)n_cam));
+    HIP_TRY(p->pts4.alloc(4 * (size_t)n_pts));
+    HIP_TRY(p->uv.alloc(2 * (size_t)n_obs));
+    HIP_TRY(p->cam_idx.alloc((size_t)n_obs));
+    HIP_TRY(p->pt_idx.alloc((size_t)n_obs));
+    HIP_TRY(p->ws.alloc((size_t)c2b_workspace_bytes(n_obs)));
     if (int rc = c2b_workspace_init(p->ws, p->stream)) return rc;
-    HIP_TRY(dalloc((void **)&p->stats, sizeof(double) * C2B_STATS_DOUBLES));
-    HIP_TRY(dalloc((void **)&p->scalar, sizeof(double) * 2));
+    HIP_TRY(p->stats.alloc(C2B_STATS_DOUBLES));
+    HIP_TRY(p->scalar.alloc(2));
     p->n_cam = n_cam; p->n_pts = n_pts; p->n_obs = n_obs;
     return C2B_OK;
 }
@@ -209,37 +201,28 @@ static int upload_common(c2b_problem *p, int64_t n_cam, const double *cams, bool
         pi32[(size_t)o] = (uint32_t)pt_idx[o];
     }
     if (int rc = alloc_problem(p, n_cam, n_pts, n_obs, true)) return rc;
-    auto dalloc = [&](void **q, size_t bytes) -> hipError_t { return hipMalloc(q, bytes ? bytes : 16); };
-
     // staging through temporary device buffers (row_ptr, packed points)
-    uint64_t *d_row = nullptr;
-    double *d_p3 = nullptr;
-    HIP_TRY(dalloc((void **)&d_row, sizeof(uint64_t) * (n_cam + 1)));
-    hipError_t e = dalloc((void **)&d_p3, sizeof(double) * 3 * n_pts);
-    if (e != hipSuccess) { (void)hipFree(d_row); return fail(C2B_ERR_OOM, "problem_upload: %s", hipGetErrorString(e)); }
+    DevBuf<uint64_t> d_row;
+    DevBuf<double> d_p3;
+    HIP_TRY(d_row.alloc((size_t)n_cam + 1));
+    const hipError_t e = d_p3.alloc(3 * (size_t)n_pts);
+    if (e != hipSuccess) return fail(C2B_ERR_OOM, "problem_upload: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(d_row, row_ptr, sizeof(uint64_t) * (n_cam + 1), hipMemcpyHostToDevice, p->stream));
+    if (n_pts) HIP_TRY(hipMemcpyAsync(d_p3, pts3, sizeof(double) * 3 * n_pts, hipMemcpyHostToDevice, p->stream));
+    if (n_obs) {
+        HIP_TRY(hipMemcpyAsync(p->pt_idx, pi32.data(), sizeof(uint32_t) * n_obs, hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(hipMemcpyAsync(p->uv, uv, sizeof(double) * 2 * n_obs, hipMemcpyHostToDevice, p->stream));
+    }
     int rc = C2B_OK;
-    do {
-#define UP_TRY(expr) { hipError_t e2 = (expr); if (e2 != hipSuccess) { rc = fail(C2B_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e2)); break; } }
-        UP_TRY(hipMemcpyAsync(d_row, row_ptr, sizeof(uint64_t) * (n_cam + 1), hipMemcpyHostToDevice, p->stream));
-        if (n_pts) UP_TRY(hipMemcpyAsync(d_p3, pts3, sizeof(double) * 3 * n_pts, hipMemcpyHostToDevice, p->stream));
-        if (n_obs) {
-            UP_TRY(hipMemcpyAsync(p->pt_idx, pi32.data(), sizeof(uint32_t) * n_obs, hipMemcpyHostToDevice, p->stream));
-            UP_TRY(hipMemcpyAsync(p->uv, uv, sizeof(double) * 2 * n_obs, hipMemcpyHostToDevice, p->stream));
-        }
-        if (is_bal) {
-            if (n_cam) UP_TRY(hipMemcpyAsync(p->bal9, cams, sizeof(double) * 9 * n_cam, hipMemcpyHostToDevice, p->stream));
-            if ((rc = c2b_cameras_from_bal(p->bal9, n_cam, p->cam15, p->stream))) break;
-        } else {
-            if (n_cam) UP_TRY(hipMemcpyAsync(p->cam15, cams, sizeof(double) * 15 * n_cam, hipMemcpyHostToDevice, p->stream));
-        }
-        if ((rc = c2b_points_pad(d_p3, n_pts, p->pts4, p->stream))) break;
-        if ((rc = c2b_expand_rows(d_row, n_cam, 0, n_obs, p->cam_idx, p->stream))) break;
-        UP_TRY(hipStreamSynchronize(p->stream));
-#undef UP_TRY
-    } while (0);
-    (void)hipFree(d_row);
-    (void)hipFree(d_p3);
-    if (rc) return rc;
+    if (is_bal) {
+        if (n_cam) HIP_TRY(hipMemcpyAsync(p->bal9, cams, sizeof(double) * 9 * n_cam, hipMemcpyHostToDevice, p->stream));
+        if ((rc = c2b_cameras_from_bal(p->bal9, n_cam, p->cam15, p->stream))) return rc;
+    } else {
+        if (n_cam) HIP_TRY(hipMemcpyAsync(p->cam15, cams, sizeof(double) * 15 * n_cam, hipMemcpyHostToDevice, p->stream));
+    }
+    if ((rc = c2b_points_pad(d_p3, n_pts, p->pts4, p->stream))) return rc;
+    if ((rc = c2b_expand_rows(d_row, n_cam, 0, n_obs, p->cam_idx, p->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));
     p->bal_valid = is_bal;
     p->blk_valid = false;
     return C2B_OK;
@@ -293,7 +276,7 @@ int c2b_problem_synthetic_grid_layout(c2b_problem *p, int64_t cpb, int64_t ppb, 
     if (n_cam) hipLaunchKernelGGL(k_grid_cameras, dim3(blocks_for(n_cam, 256)), dim3(256), 0, p->stream, n_cam, cpb, blocks, block_length,
                                   camera_height, layout_dirs(), p->cam15);
     if (n_pts) hipLaunchKernelGGL(k_grid_points, dim3(blocks_for(n_pts, 256)), dim3(256), 0, p->stream, n_pts, ppb, blocks, block_length,
-                                  block_inset, point_height, reinterpret_cast<double4 *>(p->pts4));
+                                  block_inset, point_height, reinterpret_cast<double4 *>(p->pts4.ptr));
     LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->bal_valid = false; p->blk_valid = false;
@@ -311,7 +294,7 @@ int c2b_problem_synthetic_line_layout(c2b_problem *p, int64_t n_cam, int64_t n_p
     if (rc) return rc;
     const int64_t n = std::max(n_cam, n_pts);
     if (n) hipLaunchKernelGGL(k_line_layout, dim3(blocks_for(n, 256)), dim3(256), 0, p->stream, n_cam, n_pts, length, point_offset,
-                              camera_height, point_height, layout_dirs(), p->cam15, reinterpret_cast<double4 *>(p->pts4));
+                              camera_height, point_height, layout_dirs(), p->cam15, reinterpret_cast<double4 *>(p->pts4.ptr));
     LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->bal_valid = false; p->blk_valid = false;
@@ -341,16 +324,15 @@ int c2b_problem_download(c2b_problem *p, double *cams15, double *pts3, double *u
         HIP_TRY(hipMemcpyAsync(cams15, p->cam15, sizeof(double) * 15 * p->n_cam, hipMemcpyDeviceToHost, p->stream));
     if (uv && p->n_obs)
         HIP_TRY(hipMemcpyAsync(uv, p->uv, sizeof(double) * 2 * p->n_obs, hipMemcpyDeviceToHost, p->stream));
-    double *d_p3 = nullptr;
+    DevBuf<double> d_p3;
     if (pts3 && p->n_pts) {
-        HIP_TRY(hipMalloc((void **)&d_p3, sizeof(double) * 3 * p->n_pts));
+        HIP_TRY(d_p3.alloc(3 * (size_t)p->n_pts));
         int rc = c2b_points_unpad(p->pts4, p->n_pts, d_p3, p->stream);
-        if (rc) { (void)hipFree(d_p3); return rc; }
+        if (rc) return rc;
         hipError_t e = hipMemcpyAsync(pts3, d_p3, sizeof(double) * 3 * p->n_pts, hipMemcpyDeviceToHost, p->stream);
-        if (e != hipSuccess) { (void)hipFree(d_p3); return fail(C2B_ERR_HIP, "download points: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(C2B_ERR_HIP, "download points: %s", hipGetErrorString(e));
     }
     hipError_t e = hipStreamSynchronize(p->stream);
-    if (d_p3) (void)hipFree(d_p3);
     if (e != hipSuccess) return fail(C2B_ERR_HIP, "problem_download: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_download")
@@ -381,11 +363,11 @@ int c2b_problem_from_position_direction(c2b_problem *p, int64_t n_cam, const dou
         return fail(C2B_ERR_INVALID_ARGUMENT, "problem_from_position_direction: bad arguments");
     if (!n_cam) return C2B_OK;
     HIP_TRY(hipSetDevice(p->device));
-    double *d_pos = nullptr, *d_dir = nullptr, *d_cam = nullptr;
+    DevBuf<double> d_pos, d_dir, d_cam;
     int rc = C2B_OK;
-    hipError_t e = hipMalloc((void **)&d_pos, sizeof(double) * 3 * n_cam);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_dir, sizeof(double) * 9 * n_cam);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cam, sizeof(double) * 15 * n_cam);
+    hipError_t e = d_pos.alloc(3 * (size_t)n_cam);
+    if (e == hipSuccess) e = d_dir.alloc(9 * (size_t)n_cam);
+    if (e == hipSuccess) e = d_cam.alloc(15 * (size_t)n_cam);
     if (e == hipSuccess) e = hipMemcpyAsync(d_pos, pos3, sizeof(double) * 3 * n_cam, hipMemcpyHostToDevice, p->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_dir, dir9, sizeof(double) * 9 * n_cam, hipMemcpyHostToDevice, p->stream);
     if (e == hipSuccess) {
@@ -394,12 +376,9 @@ int c2b_problem_from_position_direction(c2b_problem *p, int64_t n_cam, const dou
         hipError_t e2 = hipStreamSynchronize(p->stream);
         if (e == hipSuccess) e = e2;
     }
-    if (d_pos) (void)hipFree(d_pos);
-    if (d_dir) (void)hipFree(d_dir);
-    if (d_cam) (void)hipFree(d_cam);
     if (rc) return rc;
     if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_from_position_direction: %s", hipGetErrorString(e));
+        return fail(hip_code(e), "problem_from_position_direction: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_from_position_direction")
 }
@@ -423,8 +402,8 @@ int c2b_problem_centers(c2b_problem *p, double *centers3) {
 static int ensure_rows(c2b_problem *p) {
     if (p->rows_valid || !p->n_obs) return C2B_OK;
     drop_rows(p);
-    HIP_TRY(hipMalloc((void **)&p->rows_ptr, sizeof(uint64_t) * (size_t)(p->n_cam + 1)));
-    HIP_TRY(hipMalloc(&p->rows_tiles, (size_t)c2b_rows_tiles_bytes(p->n_obs)));
+    HIP_TRY(p->rows_ptr.alloc((size_t)p->n_cam + 1));
+    HIP_TRY(p->rows_tiles.alloc((size_t)c2b_rows_tiles_bytes(p->n_obs)));
     hipLaunchKernelGGL(k_rows_from_sorted, dim3(blocks_for(p->n_obs + 1)), dim3(kBlock), 0, p->stream, (const uint32_t *)p->cam_idx,
                        p->n_obs, p->n_cam, p->rows_ptr);
     LAUNCH_CHECK();
@@ -442,13 +421,12 @@ int c2b_problem_project(c2b_problem *p, double *uv_out) {
     int rc = ensure_camblk(p);
     if (!rc) rc = ensure_rows(p);
     if (rc) return rc;
-    double *d_uv = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_uv, sizeof(double) * 2 * p->n_obs));
+    DevBuf<double> d_uv;
+    HIP_TRY(d_uv.alloc(2 * (size_t)p->n_obs));
     rc = c2b_project_rows(p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->rows_tiles, p->pt_idx, p->n_obs, d_uv, p->stream);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpyAsync(uv_out, d_uv, sizeof(double) * 2 * p->n_obs, hipMemcpyDeviceToHost, p->stream);
     hipError_t e2 = hipStreamSynchronize(p->stream);
-    (void)hipFree(d_uv);
     if (rc) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return fail(C2B_ERR_HIP, "problem_project: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return C2B_OK;
@@ -539,33 +517,23 @@ int c2b_problem_total_reprojection_errors_l1_l2_sharded(c2b_problem *p, c2b_comm
 // the point-major transpose of the current observation list (after ensure_rows; pt_idx does not change without drop_rows)
 static int ensure_transpose(c2b_problem *p) {
     if (p->nt_ptr) return C2B_OK;
-    uint64_t *ptr = nullptr;
-    uint32_t *obs = nullptr, *cam = nullptr;
-    void *temp = nullptr;
-    auto release = [&]() {
-        if (ptr) (void)hipFree(ptr);
-        if (obs) (void)hipFree(obs);
-        if (cam) (void)hipFree(cam);
-        if (temp) (void)hipFree(temp);
-    };
+    DevBuf<uint64_t> ptr;
+    DevBuf<uint32_t> obs, cam;
+    DevBuf<char> temp;
     const size_t n_obs = (size_t)p->n_obs;
-    hipError_t e = hipMalloc((void **)&ptr, sizeof(uint64_t) * (size_t)(p->n_pts + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&obs, sizeof(uint32_t) * (n_obs ? n_obs : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&cam, sizeof(uint32_t) * (n_obs ? n_obs : 1));
-    if (e == hipSuccess) e = hipMalloc(&temp, (size_t)c2b_normal_transpose_temp_bytes(p->n_obs, p->n_pts));
-    if (e != hipSuccess) {
-        release();
-        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "normal_equations: transpose allocation: %s", hipGetErrorString(e));
-    }
+    hipError_t e = ptr.alloc((size_t)p->n_pts + 1);
+    if (e == hipSuccess) e = obs.alloc(n_obs);
+    if (e == hipSuccess) e = cam.alloc(n_obs);
+    if (e == hipSuccess) e = temp.alloc((size_t)c2b_normal_transpose_temp_bytes(p->n_obs, p->n_pts));
+    if (e != hipSuccess) return fail(hip_code(e), "normal_equations: transpose allocation: %s", hipGetErrorString(e));
     int rc = c2b_normal_transpose(p->rows_ptr, p->n_cam, p->pt_idx, p->n_obs, p->n_pts, ptr, obs, cam, temp, p->stream);
     if (!rc) {
         e = hipStreamSynchronize(p->stream);                 // temp is freed below
         if (e != hipSuccess) rc = fail(C2B_ERR_HIP, "normal_equations: transpose: %s", hipGetErrorString(e));
     }
-    (void)hipFree(temp);
-    temp = nullptr;
-    if (rc) { release(); return rc; }
-    p->nt_ptr = ptr; p->nt_obs = obs; p->nt_cam = cam;
+    temp.reset();
+    if (rc) return rc;
+    p->nt_ptr = std::move(ptr); p->nt_obs = std::move(obs); p->nt_cam = std::move(cam);
     return C2B_OK;
 }
 
@@ -591,28 +559,24 @@ int c2b_problem_set_constant(c2b_problem *p, const uint16_t *cam_mask, const uin
     // the new device arrays first: a failure leaves the masks in force as they were.  An all-zero mask is no mask.
     std::vector<uint16_t> hc;
     std::vector<uint8_t> hp;
-    uint16_t *dcm = nullptr;
-    uint8_t *dpm = nullptr;
+    DevBuf<uint16_t> dcm;
+    DevBuf<uint8_t> dpm;
     hipError_t e = hipSuccess;
     if (n_params) {
         hc.assign(cam_mask, cam_mask + nc);
-        e = hipMalloc((void **)&dcm, sizeof(uint16_t) * (size_t)nc);
+        e = dcm.alloc((size_t)nc);
         if (e == hipSuccess) e = hipMemcpyAsync(dcm, hc.data(), sizeof(uint16_t) * (size_t)nc, hipMemcpyHostToDevice, p->stream);
     }
     if (e == hipSuccess && n_const_pts) {
         hp.assign(pt_mask, pt_mask + np);
-        e = hipMalloc((void **)&dpm, sizeof(uint8_t) * (size_t)np);
+        e = dpm.alloc((size_t)np);
         if (e == hipSuccess) e = hipMemcpyAsync(dpm, hp.data(), sizeof(uint8_t) * (size_t)np, hipMemcpyHostToDevice, p->stream);
     }
     const hipError_t es = hipStreamSynchronize(p->stream);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) {
-        if (dcm) (void)hipFree(dcm);
-        if (dpm) (void)hipFree(dpm);
-        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_set_constant: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(hip_code(e), "problem_set_constant: %s", hipGetErrorString(e));
     drop_constant(p);
-    p->cmask = dcm; p->pmask = dpm;
+    p->cmask = std::move(dcm); p->pmask = std::move(dpm);
     p->h_cmask.swap(hc); p->h_pmask.swap(hp);
     p->const_n_cam = nc; p->const_n_pts = np;
     p->const_params = n_params; p->const_pts = n_const_pts;
@@ -715,9 +679,9 @@ static int robust_sum(c2b_problem *p, bool weighted_sq, double *out) {
     if (rc) return rc;
     static_assert(kNormBlock == 256, "k_robust_cost's partials are sized by block_part_slots");
     const unsigned nb = blocks_for(p->n_obs, kNormBlock);
-    double *part = reinterpret_cast<double *>(p->ws) + kWsBlockPart;
-    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4);
-    const double2 *uv = reinterpret_cast<const double2 *>(p->uv);
+    double *part = reinterpret_cast<double *>(p->ws.ptr) + kWsBlockPart;
+    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4.ptr);
+    const double2 *uv = reinterpret_cast<const double2 *>(p->uv.ptr);
     const double a2 = p->loss_scale * p->loss_scale;
     if (weighted_sq)
         hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, p->stream, p->camblk, p4, (const uint32_t *)p->cam_idx,
@@ -830,14 +794,10 @@ static SolveBufs solve_bufs(c2b_problem *p) {
 static int ensure_solver(c2b_problem *p) {
     const int64_t n = solve_doubles(p);
     if (p->sv && p->sv_doubles >= n) return C2B_OK;
-    if (p->sv) (void)hipFree(p->sv);
     p->sv_doubles = 0;
-    const hipError_t e = hipMalloc((void **)&p->sv, sizeof(double) * (size_t)n);
-    if (e == hipSuccess) p->sv_doubles = n;
-    if (e != hipSuccess) {
-        p->sv = nullptr;
-        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_solve_step: allocation: %s", hipGetErrorString(e));
-    }
+    const hipError_t e = p->sv.alloc((size_t)n);                  // (the smaller one is freed first)
+    if (e != hipSuccess) return fail(hip_code(e), "problem_solve_step: allocation: %s", hipGetErrorString(e));
+    p->sv_doubles = n;
     return C2B_OK;
 }
 
@@ -869,8 +829,8 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     if (!rc) rc = ensure_solver(p);
     if (rc) return rc;
     const SolveBufs B = solve_bufs(p);
-    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4);
-    const double2 *uv = reinterpret_cast<const double2 *>(p->uv);
+    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4.ptr);
+    const double2 *uv = reinterpret_cast<const double2 *>(p->uv.ptr);
     const unsigned cgrid = schur_cameras_grid(nc), nbc = blocks_for(nc, kSchurBlock), nbo = blocks_for(no, kSchurBlock);
     const int n_cpart = (int)(cgrid * (kNormBlock / 64));
     const int kind = p->loss_kind;                           // 0: every launch below is the squared-loss kernel it always was
@@ -1020,9 +980,9 @@ int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
     if (dp && np) {
         if (p->pmask)
             hipLaunchKernelGGL(k_points_add_free, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp,
-                               (const uint8_t *)p->pmask, reinterpret_cast<double4 *>(p->pts4));
+                               (const uint8_t *)p->pmask, reinterpret_cast<double4 *>(p->pts4.ptr));
         else
-            hipLaunchKernelGGL(k_points_add, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp, reinterpret_cast<double4 *>(p->pts4));
+            hipLaunchKernelGGL(k_points_add, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp, reinterpret_cast<double4 *>(p->pts4.ptr));
         LAUNCH_CHECK();
     }
     cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
@@ -1047,7 +1007,7 @@ int c2b_problem_residual_jacobian(c2b_problem *p, double *r, double *Jc, double 
     if (rc) return rc;
     constexpr int kSlots = c2b_problem::kJacSlots;
     constexpr int64_t kChunk = c2b_problem::kJacChunk;
-    if (!p->jac_ring) HIP_TRY(hipMalloc((void **)&p->jac_ring, sizeof(double) * 26 * (size_t)kChunk * kSlots));
+    if (!p->jac_ring) HIP_TRY(p->jac_ring.alloc(26 * (size_t)kChunk * kSlots));
     if (!p->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
     for (int k = 0; k < kSlots; ++k) {
         if (!p->ev_done[k]) HIP_TRY(hipEventCreateWithFlags(&p->ev_done[k], hipEventDisableTiming));
@@ -1086,7 +1046,7 @@ int c2b_problem_residual_jacobian(c2b_problem *p, double *r, double *Jc, double 
     const hipError_t e1 = hipStreamSynchronize(p->copy_stream), e2 = hipStreamSynchronize(p->stream);
     if (e == hipSuccess) e = e1 != hipSuccess ? e1 : e2;
     if (rc) return rc;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_residual_jacobian: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hip_code(e), "problem_residual_jacobian: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_residual_jacobian")
 }
@@ -1183,13 +1143,13 @@ int c2b_problem_visibility_pairs(c2b_problem *p, int64_t n_pairs, const uint32_t
             return fail(C2B_ERR_INDEX_OUT_OF_RANGE, "problem_visibility_pairs: pair %lld out of range", (long long)i);
     int rc = ensure_camblk(p);
     if (rc) return rc;
-    uint32_t *d_c = nullptr, *d_p = nullptr;
-    double *d_uv = nullptr;
-    uint8_t *d_k = nullptr;
-    hipError_t e = hipMalloc((void **)&d_c, sizeof(uint32_t) * n_pairs);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_p, sizeof(uint32_t) * n_pairs);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_uv, sizeof(double) * 2 * n_pairs);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_k, n_pairs);
+    DevBuf<uint32_t> d_c, d_p;
+    DevBuf<double> d_uv;
+    DevBuf<uint8_t> d_k;
+    hipError_t e = d_c.alloc((size_t)n_pairs);
+    if (e == hipSuccess) e = d_p.alloc((size_t)n_pairs);
+    if (e == hipSuccess) e = d_uv.alloc(2 * (size_t)n_pairs);
+    if (e == hipSuccess) e = d_k.alloc((size_t)n_pairs);
     if (e == hipSuccess) e = hipMemcpyAsync(d_c, cam_idx, sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice, p->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_p, pt_idx, sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice, p->stream);
     if (e == hipSuccess) {
@@ -1201,12 +1161,8 @@ int c2b_problem_visibility_pairs(c2b_problem *p, int64_t n_pairs, const uint32_t
         hipError_t e2 = hipStreamSynchronize(p->stream);
         if (e == hipSuccess) e = e2;
     }
-    if (d_c) (void)hipFree(d_c);
-    if (d_p) (void)hipFree(d_p);
-    if (d_uv) (void)hipFree(d_uv);
-    if (d_k) (void)hipFree(d_k);
     if (rc) return rc;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_visibility_pairs: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_pairs: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_visibility_pairs")
 }
@@ -1214,34 +1170,6 @@ int c2b_problem_visibility_pairs(c2b_problem *p, int64_t n_pairs, const uint32_t
 /* ---- BAProblem::cull on the device (src/baproblem.rs:538-549) ---- */
 extern "C++" {
 namespace {
-
-// device allocation that frees itself (the cull pipeline holds ~20 scratch arrays)
-struct DevBuf {
-    void *ptr = nullptr;
-    bool owned = true;                         // false: a view into an arena (below), never freed or released by itself
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (ptr && owned) (void)hipFree(ptr); }
-    hipError_t alloc(size_t bytes) { owned = true; return hipMalloc(&ptr, bytes ? bytes : 16); }
-    void view(void *q) { ptr = q; owned = false; }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(ptr); }
-    void *release() { void *q = ptr; ptr = nullptr; return q; }
-};
-
-// Temporaries of one call carved out of ONE allocation: a device malloc / free pair costs ~1 ms at these sizes (the free
-// synchronises), and cull used to make ~25 of each -- most of its 45 ms at --blocks 128 once its kernels took 10.
-struct DevArena {
-    DevBuf block;
-    size_t used = 0, cap = 0;
-    static size_t rounded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    hipError_t reserve(size_t bytes) { cap = bytes; return block.alloc(bytes); }
-    void *take(size_t bytes) {
-        void *q = static_cast<char *>(block.ptr) + used;
-        used += rounded(bytes ? bytes : 16);
-        return used <= cap ? q : nullptr;
-    }
-};
 
 unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
 
@@ -1271,28 +1199,30 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
     const int64_t nc0 = p->n_cam, np0 = p->n_pts, no0 = p->n_obs;
     const int64_t nodes0 = nc0 + np0, big0 = std::max(std::max(nc0, np0), no0);
     // current graph (ping-pong pairs) + where everything came from
-    DevBuf cam[2], pt[2], eorig[2], corig[2], porig[2];
-    DevBuf parent, sets, size, keep_c, keep_p, keep_o, pos_c, pos_p, pos_o, tiles, best, total, deg, cnt;
+    DevBuf<uint32_t> cam[2], pt[2], eorig[2], corig[2], porig[2];
+    DevBuf<uint32_t> parent, sets, size, keep_c, keep_p, keep_o, pos_c, pos_p, pos_o, tiles, total, deg, cnt;
+    DevBuf<unsigned long long> best;
     hipError_t e = hipSuccess;
-    auto A = [&](DevBuf &b, size_t bytes) { if (e == hipSuccess) e = b.alloc(bytes); };
     // cam / pt are allocations of their own (one of each pair becomes the problem's index array); every other temporary
     // is a view into one arena
-    for (int k = 0; k < 2; ++k) { A(cam[k], 4 * (size_t)no0); A(pt[k], 4 * (size_t)no0); }
+    for (int k = 0; k < 2; ++k) {
+        if (e == hipSuccess) e = cam[k].alloc((size_t)no0);
+        if (e == hipSuccess) e = pt[k].alloc((size_t)no0);
+    }
     DevArena arena;
-    struct Want { DevBuf *b; size_t bytes; };
-    const Want wants[] = {
-        {&eorig[0], 4 * (size_t)no0}, {&eorig[1], 4 * (size_t)no0}, {&corig[0], 4 * (size_t)nc0}, {&corig[1], 4 * (size_t)nc0},
-        {&porig[0], 4 * (size_t)np0}, {&porig[1], 4 * (size_t)np0},
-        {&parent, 4 * (size_t)nodes0}, {&sets, 4 * (size_t)nodes0}, {&size, 4 * (size_t)nodes0},
-        {&keep_c, 4 * (size_t)nc0}, {&keep_p, 4 * (size_t)np0}, {&keep_o, 4 * (size_t)no0},
-        {&pos_c, 4 * (size_t)nc0}, {&pos_p, 4 * (size_t)np0}, {&pos_o, 4 * (size_t)no0},
-        {&tiles, 4 * (size_t)(big0 / kScanTile + 2)}, {&best, 8}, {&total, 4}, {&deg, 4 * (size_t)nc0}, {&cnt, 4 * (size_t)np0}};
+    auto temporaries = [&](auto &&each) {
+        each(eorig[0], (size_t)no0); each(eorig[1], (size_t)no0); each(corig[0], (size_t)nc0); each(corig[1], (size_t)nc0);
+        each(porig[0], (size_t)np0); each(porig[1], (size_t)np0);
+        each(parent, (size_t)nodes0); each(sets, (size_t)nodes0); each(size, (size_t)nodes0);
+        each(keep_c, (size_t)nc0); each(keep_p, (size_t)np0); each(keep_o, (size_t)no0);
+        each(pos_c, (size_t)nc0); each(pos_p, (size_t)np0); each(pos_o, (size_t)no0);
+        each(tiles, (size_t)(big0 / kScanTile + 2)); each(best, (size_t)1); each(total, (size_t)1); each(deg, (size_t)nc0); each(cnt, (size_t)np0);
+    };
     size_t arena_bytes = 0;
-    for (const Want &w : wants) arena_bytes += DevArena::rounded(w.bytes ? w.bytes : 16);
+    temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
     if (e == hipSuccess) e = arena.reserve(arena_bytes);
-    if (e == hipSuccess)
-        for (const Want &w : wants) w.b->view(arena.take(w.bytes));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_cull: %s", hipGetErrorString(e));
+    if (e == hipSuccess) temporaries([&](auto &b, size_t n) { arena.carve(b, n); });
+    if (e != hipSuccess) return fail(hip_code(e), "problem_cull: %s", hipGetErrorString(e));
 
     int cur = 0;
     int64_t nc = nc0, np = np0, no = no0;
@@ -1301,29 +1231,24 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
         if (e == hipSuccess) e = hipMemcpyAsync(pt[0].ptr, p->pt_idx, 4 * (size_t)no, hipMemcpyDeviceToDevice, st);
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, eorig[0].as<uint32_t>(), no);   // iota
-        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(nc, kBlock)), dim3(kBlock), 0, st, corig[0].as<uint32_t>(), nc);
-        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(np, kBlock)), dim3(kBlock), 0, st, porig[0].as<uint32_t>(), np);
+        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, eorig[0], no);   // iota
+        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(nc, kBlock)), dim3(kBlock), 0, st, corig[0], nc);
+        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(np, kBlock)), dim3(kBlock), 0, st, porig[0], np);
         e = launch_error();
     }
 
     // renumber by the keep flags currently in keep_c / keep_p / keep_o
     auto compact = [&]() -> hipError_t {
         uint32_t nc_new = 0, np_new = 0, no_new = 0;
-        hipError_t s = scan_flags(st, keep_c.as<uint32_t>(), nc, pos_c.as<uint32_t>(), tiles.as<uint32_t>(), total.as<uint32_t>(), &nc_new);
-        if (s == hipSuccess) s = scan_flags(st, keep_p.as<uint32_t>(), np, pos_p.as<uint32_t>(), tiles.as<uint32_t>(), total.as<uint32_t>(), &np_new);
-        if (s == hipSuccess) s = scan_flags(st, keep_o.as<uint32_t>(), no, pos_o.as<uint32_t>(), tiles.as<uint32_t>(), total.as<uint32_t>(), &no_new);
+        hipError_t s = scan_flags(st, keep_c, nc, pos_c, tiles, total, &nc_new);
+        if (s == hipSuccess) s = scan_flags(st, keep_p, np, pos_p, tiles, total, &np_new);
+        if (s == hipSuccess) s = scan_flags(st, keep_o, no, pos_o, tiles, total, &no_new);
         if (s != hipSuccess) return s;
         const int nxt = cur ^ 1;
-        hipLaunchKernelGGL(k_cull_move_nodes, dim3(blocks_of(nc, kBlock)), dim3(kBlock), 0, st, (const uint32_t *)keep_c.as<uint32_t>(),
-                           (const uint32_t *)pos_c.as<uint32_t>(), nc, (const uint32_t *)corig[cur].as<uint32_t>(), corig[nxt].as<uint32_t>());
-        hipLaunchKernelGGL(k_cull_move_nodes, dim3(blocks_of(np, kBlock)), dim3(kBlock), 0, st, (const uint32_t *)keep_p.as<uint32_t>(),
-                           (const uint32_t *)pos_p.as<uint32_t>(), np, (const uint32_t *)porig[cur].as<uint32_t>(), porig[nxt].as<uint32_t>());
-        hipLaunchKernelGGL(k_cull_move_edges, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, (const uint32_t *)keep_o.as<uint32_t>(),
-                           (const uint32_t *)pos_o.as<uint32_t>(), no, (const uint32_t *)cam[cur].as<uint32_t>(),
-                           (const uint32_t *)pt[cur].as<uint32_t>(), (const uint32_t *)eorig[cur].as<uint32_t>(),
-                           (const uint32_t *)pos_c.as<uint32_t>(), (const uint32_t *)pos_p.as<uint32_t>(), cam[nxt].as<uint32_t>(),
-                           pt[nxt].as<uint32_t>(), eorig[nxt].as<uint32_t>());
+        hipLaunchKernelGGL(k_cull_move_nodes, dim3(blocks_of(nc, kBlock)), dim3(kBlock), 0, st, keep_c, pos_c, nc, corig[cur], corig[nxt]);
+        hipLaunchKernelGGL(k_cull_move_nodes, dim3(blocks_of(np, kBlock)), dim3(kBlock), 0, st, keep_p, pos_p, np, porig[cur], porig[nxt]);
+        hipLaunchKernelGGL(k_cull_move_edges, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, keep_o, pos_o, no, cam[cur], pt[cur], eorig[cur],
+                           pos_c, pos_p, cam[nxt], pt[nxt], eorig[nxt]);
         cur = nxt;
         nc = nc_new; np = np_new; no = no_new;
         return launch_error();
@@ -1334,17 +1259,12 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
         hipError_t s = hipMemsetAsync(size.ptr, 0, 4 * (size_t)nodes, st);
         if (s == hipSuccess) s = hipMemsetAsync(best.ptr, 0, 8, st);
         if (s != hipSuccess) return s;
-        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, parent.as<uint32_t>(), nodes);
-        if (no) hipLaunchKernelGGL(k_uf_union, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, parent.as<uint32_t>(),
-                                   (const uint32_t *)cam[cur].as<uint32_t>(), (const uint32_t *)pt[cur].as<uint32_t>(), no, (uint32_t)nc);
-        hipLaunchKernelGGL(k_uf_flatten, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, parent.as<uint32_t>(), nodes,
-                           sets.as<uint32_t>(), size.as<uint32_t>());
-        hipLaunchKernelGGL(k_uf_largest, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, (const uint32_t *)sets.as<uint32_t>(),
-                           (const uint32_t *)size.as<uint32_t>(), nodes, best.as<unsigned long long>());
-        hipLaunchKernelGGL(k_lcc_flags, dim3(blocks_of(big, kBlock)), dim3(kBlock), 0, st, (const uint32_t *)sets.as<uint32_t>(),
-                           (const unsigned long long *)best.as<unsigned long long>(), (uint32_t)nc, (uint32_t)np,
-                           (const uint32_t *)cam[cur].as<uint32_t>(), (const uint32_t *)pt[cur].as<uint32_t>(), no, faithful ? 1 : 0,
-                           keep_c.as<uint32_t>(), keep_p.as<uint32_t>(), keep_o.as<uint32_t>());
+        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, parent, nodes);
+        if (no) hipLaunchKernelGGL(k_uf_union, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, parent, cam[cur], pt[cur], no, (uint32_t)nc);
+        hipLaunchKernelGGL(k_uf_flatten, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, parent, nodes, sets, size);
+        hipLaunchKernelGGL(k_uf_largest, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, sets, size, nodes, best);
+        hipLaunchKernelGGL(k_lcc_flags, dim3(blocks_of(big, kBlock)), dim3(kBlock), 0, st, sets, best, (uint32_t)nc,
+                           (uint32_t)np, cam[cur], pt[cur], no, faithful ? 1 : 0, keep_c, keep_p, keep_o);
         s = launch_error();
         return s == hipSuccess ? compact() : s;
     };
@@ -1353,11 +1273,9 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
         hipError_t s = hipMemsetAsync(deg.ptr, 0, 4 * (size_t)(nc ? nc : 1), st);
         if (s == hipSuccess) s = hipMemsetAsync(cnt.ptr, 0, 4 * (size_t)(np ? np : 1), st);
         if (s != hipSuccess) return s;
-        if (no) hipLaunchKernelGGL(k_degree, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, (const uint32_t *)cam[cur].as<uint32_t>(),
-                                   (const uint32_t *)pt[cur].as<uint32_t>(), no, deg.as<uint32_t>(), cnt.as<uint32_t>());
-        hipLaunchKernelGGL(k_singleton_flags, dim3(blocks_of(big, kBlock)), dim3(kBlock), 0, st, (const uint32_t *)deg.as<uint32_t>(),
-                           (const uint32_t *)cnt.as<uint32_t>(), (uint32_t)nc, (uint32_t)np, (const uint32_t *)cam[cur].as<uint32_t>(),
-                           (const uint32_t *)pt[cur].as<uint32_t>(), no, keep_c.as<uint32_t>(), keep_p.as<uint32_t>(), keep_o.as<uint32_t>());
+        if (no) hipLaunchKernelGGL(k_degree, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, cam[cur], pt[cur], no, deg, cnt);
+        hipLaunchKernelGGL(k_singleton_flags, dim3(blocks_of(big, kBlock)), dim3(kBlock), 0, st, deg, cnt, (uint32_t)nc,
+                           (uint32_t)np, cam[cur], pt[cur], no, keep_c, keep_p, keep_o);
         s = launch_error();
         return s == hipSuccess ? compact() : s;
     };
@@ -1372,17 +1290,19 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
     }
 
     // gather the payloads once and swap them in
-    DevBuf n_cam15, n_bal9, n_camblk, n_cen4, n_pts4, n_uv, n_ws;
+    DevBuf<double> n_cam15, n_bal9, n_camblk, n_cen4, n_pts4, n_uv;
+    DevBuf<char> n_ws;
+    if (e == hipSuccess) e = n_cam15.alloc(15 * (size_t)nc);
+    if (e == hipSuccess) e = n_bal9.alloc(9 * (size_t)nc);
+    if (e == hipSuccess) e = n_camblk.alloc((size_t)cam_table_doubles(nc));
+    if (e == hipSuccess) e = n_cen4.alloc(4 * (size_t)nc);
+    if (e == hipSuccess) e = n_pts4.alloc(4 * (size_t)np);
+    if (e == hipSuccess) e = n_uv.alloc(2 * (size_t)no);
+    if (e == hipSuccess) e = n_ws.alloc((size_t)c2b_workspace_bytes(no));
+    if (e == hipSuccess && c2b_workspace_init(n_ws, st) != C2B_OK) e = hipErrorUnknown;
     if (e == hipSuccess) {
-        A(n_cam15, sizeof(double) * 15 * (size_t)nc); A(n_bal9, sizeof(double) * 9 * (size_t)nc);
-        A(n_camblk, sizeof(double) * (size_t)cam_table_doubles(nc)); A(n_cen4, sizeof(double) * 4 * (size_t)nc); A(n_pts4, sizeof(double) * 4 * (size_t)np);
-        A(n_uv, sizeof(double) * 2 * (size_t)no); A(n_ws, (size_t)c2b_workspace_bytes(no));
-    }
-    if (e == hipSuccess && c2b_workspace_init(n_ws.ptr, st) != C2B_OK) e = hipErrorUnknown;
-    if (e == hipSuccess) {
-        auto gather = [&](const double *in, const DevBuf &orig, int64_t n, int width, DevBuf &out) {
-            if (n) hipLaunchKernelGGL(k_gather_rows, dim3(blocks_of(n * width, kBlock)), dim3(kBlock), 0, st, in,
-                                      (const uint32_t *)orig.as<uint32_t>(), n, width, out.as<double>());
+        auto gather = [&](const double *in, const uint32_t *orig, int64_t n, int width, double *out) {
+            if (n) hipLaunchKernelGGL(k_gather_rows, dim3(blocks_of(n * width, kBlock)), dim3(kBlock), 0, st, in, orig, n, width, out);
         };
         gather(p->cam15, corig[cur], nc, 15, n_cam15);
         if (p->bal_valid) gather(p->bal9, corig[cur], nc, 9, n_bal9);
@@ -1393,14 +1313,11 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
     }
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
-        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_cull: %s", hipGetErrorString(e));
+        return fail(hip_code(e), "problem_cull: %s", hipGetErrorString(e));
     }
-    void *old[] = {p->cam15, p->bal9, p->camblk, p->cen4, p->pts4, p->uv, p->cam_idx, p->pt_idx, p->ws};
-    for (void *q : old) if (q) (void)hipFree(q);
-    p->cam15 = (double *)n_cam15.release(); p->bal9 = (double *)n_bal9.release(); p->camblk = (double *)n_camblk.release();
-    p->cen4 = (double *)n_cen4.release();
-    p->pts4 = (double *)n_pts4.release(); p->uv = (double *)n_uv.release(); p->ws = n_ws.release();
-    p->cam_idx = (uint32_t *)cam[cur].release(); p->pt_idx = (uint32_t *)pt[cur].release();
+    p->cam15 = std::move(n_cam15); p->bal9 = std::move(n_bal9); p->camblk = std::move(n_camblk); p->cen4 = std::move(n_cen4);
+    p->pts4 = std::move(n_pts4); p->uv = std::move(n_uv);
+    p->cam_idx = std::move(cam[cur]); p->pt_idx = std::move(pt[cur]); p->ws = std::move(n_ws);
     drop_rows(p);
     drop_constant(p);                                         // the survivors are renumbered
     p->n_cam = nc; p->n_pts = np; p->n_obs = no;
@@ -1420,21 +1337,19 @@ int c2b_problem_adopt_visibility(c2b_problem *p) {
         return fail(C2B_ERR_INVALID_ARGUMENT, "problem_adopt_visibility: no pending visibility result");
     const int64_t n = p->dense_n;
     if (n >= ((int64_t)1 << 32)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_adopt_visibility: more than 2^32 observations");
-    DevBuf cam_idx, ws;
-    hipError_t e = cam_idx.alloc(sizeof(uint32_t) * (size_t)n);
+    DevBuf<uint32_t> cam_idx;
+    DevBuf<char> ws;
+    hipError_t e = cam_idx.alloc((size_t)n);
     if (e == hipSuccess) e = ws.alloc((size_t)c2b_workspace_bytes(n));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_adopt_visibility: %s", hipGetErrorString(e));
-    int rc = c2b_expand_rows(p->dense_row, p->n_cam, 0, n, cam_idx.as<uint32_t>(), p->stream);
-    if (!rc) rc = c2b_workspace_init(ws.ptr, p->stream);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_adopt_visibility: %s", hipGetErrorString(e));
+    int rc = c2b_expand_rows(p->dense_row, p->n_cam, 0, n, cam_idx, p->stream);
+    if (!rc) rc = c2b_workspace_init(ws, p->stream);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(p->stream));
-    void *old[] = {p->uv, p->cam_idx, p->pt_idx, p->ws, p->dense_row};
-    for (void *q : old) if (q) (void)hipFree(q);
-    p->cam_idx = (uint32_t *)cam_idx.release();
+    p->uv = std::move(p->dense_uv); p->cam_idx = std::move(cam_idx); p->pt_idx = std::move(p->dense_pt); p->ws = std::move(ws);
+    p->n_obs = n;
+    free_dense(p);                                            // (the row pointer; the lists were moved out)
     drop_rows(p);
-    p->ws = ws.release();
-    p->pt_idx = p->dense_pt; p->uv = p->dense_uv; p->n_obs = n;
-    p->dense_pt = nullptr; p->dense_uv = nullptr; p->dense_row = nullptr; p->dense_n = 0;
     return C2B_OK;
     C2B_API_END("problem_adopt_visibility")
 }
@@ -1446,21 +1361,21 @@ int c2b_problem_download_graph(c2b_problem *p, uint64_t *row_ptr, uint64_t *pt_i
     const int64_t n_cam = p->n_cam, n_obs = p->n_obs;
     // the point indices are widened to the host's u64 on the device and leave in ONE copy (r01-r02: a u32 copy into a
     // fresh host vector, then a serial widening loop over 19 M entries -- a third of the 120-ms download at --blocks 128)
-    DevBuf d_row, d_pt64;
-    hipError_t e = d_row.alloc(sizeof(uint64_t) * (size_t)(n_cam + 1));
-    if (e == hipSuccess && n_obs) e = d_pt64.alloc(sizeof(uint64_t) * (size_t)n_obs);
+    DevBuf<uint64_t> d_row, d_pt64;
+    hipError_t e = d_row.alloc((size_t)n_cam + 1);
+    if (e == hipSuccess && n_obs) e = d_pt64.alloc((size_t)n_obs);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_rows_from_sorted, dim3(blocks_for(n_obs + 1)), dim3(kBlock), 0, p->stream, (const uint32_t *)p->cam_idx, n_obs,
-                           n_cam, d_row.as<uint64_t>());
+                           n_cam, d_row);
         if (n_obs) hipLaunchKernelGGL(k_widen_u32, dim3(blocks_for(n_obs)), dim3(kBlock), 0, p->stream, (const uint32_t *)p->pt_idx, n_obs,
-                                      d_pt64.as<uint64_t>());
+                                      d_pt64);
         e = launch_error();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(row_ptr, d_row.ptr, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, p->stream);
     if (e == hipSuccess && n_obs) e = hipMemcpyAsync(pt_idx, d_pt64.ptr, sizeof(uint64_t) * (size_t)n_obs, hipMemcpyDeviceToHost, p->stream);
     hipError_t e2 = hipStreamSynchronize(p->stream);
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_download_graph: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hip_code(e), "problem_download_graph: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_download_graph")
 }
@@ -1511,41 +1426,31 @@ int c2b_problem_export_device(c2b_problem *p, int64_t cam_lo, int64_t cam_hi, do
 }
 
 // Stable compaction of CSR lists (point index, uv) by a keep mask, on the device: kept count per row -> row scan ->
-// one wave per camera scatters in order.  The new row pointer goes to row_ptr_host; on success the three new device
-// buffers are handed to the caller (who owns them), *w = kept count.  Synchronises the problem's stream.
+// one wave per camera scatters in order.  The new row pointer goes to row_ptr_host; on success the three new lists are
+// in row_new / pt_new / uv_new, *w = kept count (on failure what they hold is not a result).  Synchronises the problem's stream.
 static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_old, const uint8_t *d_keep, const uint32_t *d_pt,
-                                         const double *d_uv, int64_t n_cam, uint64_t *row_ptr_host, uint64_t **d_row_new,
-                                         uint32_t **d_pt_new, double **d_uv_new, int64_t *w) {
-    uint64_t *d_tot = nullptr;
-    *d_row_new = nullptr; *d_pt_new = nullptr; *d_uv_new = nullptr; *w = 0;
-    hipError_t e = hipMalloc((void **)&d_tot, sizeof(uint64_t) * (size_t)(n_cam + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)d_row_new, sizeof(uint64_t) * (size_t)(n_cam + 1));
-    if (e == hipSuccess) {
-        const unsigned row_blocks = (unsigned)((n_cam + 3) / 4);
-        if (n_cam) hipLaunchKernelGGL(k_keep_row_counts, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, d_keep, n_cam, d_tot);
-        hipLaunchKernelGGL(k_dense_cam_scan, dim3(1), dim3(256), 0, p->stream, (const uint64_t *)d_tot, n_cam, *d_row_new);
-        e = hipMemcpyAsync(row_ptr_host, *d_row_new, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, p->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-        if (e == hipSuccess) {
-            *w = (int64_t)row_ptr_host[n_cam];
-            e = hipMalloc((void **)d_pt_new, sizeof(uint32_t) * (size_t)(*w ? *w : 4));
-            if (e == hipSuccess) e = hipMalloc((void **)d_uv_new, sizeof(double) * 2 * (size_t)(*w ? *w : 1));
-            if (e == hipSuccess && n_cam) {
-                hipLaunchKernelGGL(k_keep_row_scatter, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old,
-                                   (const uint64_t *)*d_row_new, d_keep, d_pt, reinterpret_cast<const double2 *>(d_uv), n_cam,
-                                   *d_pt_new, reinterpret_cast<double2 *>(*d_uv_new));
-                e = launch_error();
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-        }
+                                         const double *d_uv, int64_t n_cam, uint64_t *row_ptr_host, DevBuf<uint64_t> &row_new,
+                                         DevBuf<uint32_t> &pt_new, DevBuf<double> &uv_new, int64_t *w) {
+    DevBuf<uint64_t> d_tot;
+    *w = 0;
+    hipError_t e = d_tot.alloc((size_t)n_cam + 1);
+    if (e == hipSuccess) e = row_new.alloc((size_t)n_cam + 1);
+    if (e != hipSuccess) return e;
+    const unsigned row_blocks = (unsigned)((n_cam + 3) / 4);
+    if (n_cam) hipLaunchKernelGGL(k_keep_row_counts, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, d_keep, n_cam, d_tot);
+    hipLaunchKernelGGL(k_dense_cam_scan, dim3(1), dim3(256), 0, p->stream, (const uint64_t *)d_tot, n_cam, row_new);
+    e = hipMemcpyAsync(row_ptr_host, row_new, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) return e;
+    *w = (int64_t)row_ptr_host[n_cam];
+    e = pt_new.alloc((size_t)*w);
+    if (e == hipSuccess) e = uv_new.alloc(2 * (size_t)*w);
+    if (e == hipSuccess && n_cam) {
+        hipLaunchKernelGGL(k_keep_row_scatter, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, (const uint64_t *)row_new, d_keep,
+                           d_pt, reinterpret_cast<const double2 *>(d_uv), n_cam, pt_new, reinterpret_cast<double2 *>(uv_new.ptr));
+        e = launch_error();
     }
-    if (d_tot) (void)hipFree(d_tot);
-    if (e != hipSuccess) {
-        if (*d_row_new) (void)hipFree(*d_row_new);
-        if (*d_pt_new) (void)hipFree(*d_pt_new);
-        if (*d_uv_new) (void)hipFree(*d_uv_new);
-        *d_row_new = nullptr; *d_pt_new = nullptr; *d_uv_new = nullptr;
-    }
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     return e;
 }
 
@@ -1566,16 +1471,16 @@ int c2b_problem_visibility_pairs_compact(c2b_problem *p, int64_t n_pairs, const 
     free_dense(p);
     const int64_t n_cam = p->n_cam;
     const size_t n = (size_t)(n_pairs ? n_pairs : 1);
-    uint32_t *d_c = nullptr, *d_p = nullptr, *d_pt_new = nullptr;
-    double *d_uv = nullptr, *d_uv_new = nullptr;
-    uint8_t *d_k = nullptr;
-    uint64_t *d_row = nullptr, *d_row_new = nullptr;
+    DevBuf<uint32_t> d_c, d_p, d_pt_new;
+    DevBuf<double> d_uv, d_uv_new;
+    DevBuf<uint8_t> d_k;
+    DevBuf<uint64_t> d_row, d_row_new;
     int64_t w = 0;
-    hipError_t e = hipMalloc((void **)&d_c, sizeof(uint32_t) * n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_p, sizeof(uint32_t) * n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_uv, sizeof(double) * 2 * n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_k, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_row, sizeof(uint64_t) * (size_t)(n_cam + 1));
+    hipError_t e = d_c.alloc(n);
+    if (e == hipSuccess) e = d_p.alloc(n);
+    if (e == hipSuccess) e = d_uv.alloc(2 * n);
+    if (e == hipSuccess) e = d_k.alloc(n);
+    if (e == hipSuccess) e = d_row.alloc((size_t)n_cam + 1);
     if (e == hipSuccess && n_pairs) e = hipMemcpyAsync(d_c, cam_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, p->stream);
     if (e == hipSuccess && n_pairs) e = hipMemcpyAsync(d_p, pt_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, p->stream);
     if (e == hipSuccess) {
@@ -1585,20 +1490,15 @@ int c2b_problem_visibility_pairs_compact(c2b_problem *p, int64_t n_pairs, const 
                                n_pairs, n_cam, d_row);
             e = launch_error();
             if (e == hipSuccess)
-                e = compact_rows_on_device(p, d_row, d_k, d_p, d_uv, n_cam, row_ptr, &d_row_new, &d_pt_new, &d_uv_new, &w);
+                e = compact_rows_on_device(p, d_row, d_k, d_p, d_uv, n_cam, row_ptr, d_row_new, d_pt_new, d_uv_new, &w);
         }
     }
     if (rc || e != hipSuccess) (void)hipStreamSynchronize(p->stream);
     if (!rc && e == hipSuccess) {                 // becomes the pending visibility result (fetch with _dense_fetch)
-        p->dense_row = d_row_new; p->dense_pt = d_pt_new; p->dense_uv = d_uv_new; p->dense_n = w;
+        p->dense_row = std::move(d_row_new); p->dense_pt = std::move(d_pt_new); p->dense_uv = std::move(d_uv_new); p->dense_n = w;
     }
-    if (d_c) (void)hipFree(d_c);
-    if (d_p) (void)hipFree(d_p);
-    if (d_uv) (void)hipFree(d_uv);
-    if (d_k) (void)hipFree(d_k);
-    if (d_row) (void)hipFree(d_row);
     if (rc) return rc;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_visibility_pairs_compact: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_pairs_compact: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_visibility_pairs_compact")
 }
@@ -1622,15 +1522,17 @@ int c2b_problem_visibility_within_distance(c2b_problem *p, double max_dist, int 
     free_dense(p);
     hipStream_t st = p->stream;
     if (n_cam == 0 || n_pts == 0) {                                      // nothing can be seen: an empty graph
-        DevBuf row0, pt0, uv0;
-        hipError_t e0 = row0.alloc(sizeof(uint64_t) * (size_t)(n_cam + 1));
-        if (e0 == hipSuccess) e0 = pt0.alloc(4);
-        if (e0 == hipSuccess) e0 = uv0.alloc(16);
+        DevBuf<uint64_t> row0;
+        DevBuf<uint32_t> pt0;
+        DevBuf<double> uv0;
+        hipError_t e0 = row0.alloc((size_t)n_cam + 1);
+        if (e0 == hipSuccess) e0 = pt0.alloc(1);
+        if (e0 == hipSuccess) e0 = uv0.alloc(2);
         if (e0 == hipSuccess) e0 = hipMemsetAsync(row0.ptr, 0, sizeof(uint64_t) * (size_t)(n_cam + 1), st);
         if (e0 == hipSuccess) e0 = hipStreamSynchronize(st);
         if (e0 != hipSuccess) return fail(C2B_ERR_HIP, "problem_visibility_within_distance: %s", hipGetErrorString(e0));
         if (row_ptr) std::fill(row_ptr, row_ptr + n_cam + 1, (uint64_t)0);
-        p->dense_row = (uint64_t *)row0.release(); p->dense_pt = (uint32_t *)pt0.release(); p->dense_uv = (double *)uv0.release();
+        p->dense_row = std::move(row0); p->dense_pt = std::move(pt0); p->dense_uv = std::move(uv0);
         p->dense_n = 0;
         return C2B_OK;
     }
@@ -1654,18 +1556,21 @@ int c2b_problem_visibility_within_distance(c2b_problem *p, double max_dist, int 
     const int64_t n_cells = (int64_t)g.ncx * g.ncz;
 
     DevArena arena;
-    DevBuf cell_of, counts, cursor, sorted, tiles, total, cam_count, pos, sum64, max32, row64;
-    struct Want { DevBuf *b; size_t bytes; };
+    DevBuf<uint32_t> cell_of, counts, cursor, sorted, tiles, total, cam_count, pos, max32;
+    DevBuf<unsigned long long> sum64;
+    DevBuf<uint64_t> row64;
     const int64_t big = std::max(n_cells + 1, n_cam + 1);
-    const Want wants[] = {{&cell_of, 4 * (size_t)n_pts}, {&counts, 4 * (size_t)(n_cells + 1)}, {&cursor, 4 * (size_t)(n_cells + 1)},
-                          {&sorted, 4 * (size_t)n_pts}, {&tiles, 4 * (size_t)(big / kScanTile + 2)}, {&total, 4},
-                          {&cam_count, 4 * (size_t)(n_cam + 1)}, {&pos, 4 * (size_t)(n_cam + 1)}, {&sum64, 8}, {&max32, 4}};
+    auto temporaries = [&](auto &&each) {
+        each(cell_of, (size_t)n_pts); each(counts, (size_t)(n_cells + 1)); each(cursor, (size_t)(n_cells + 1));
+        each(sorted, (size_t)n_pts); each(tiles, (size_t)(big / kScanTile + 2)); each(total, (size_t)1);
+        each(cam_count, (size_t)(n_cam + 1)); each(pos, (size_t)(n_cam + 1)); each(sum64, (size_t)1); each(max32, (size_t)1);
+    };
     size_t arena_bytes = 0;
-    for (const Want &w : wants) arena_bytes += DevArena::rounded(w.bytes ? w.bytes : 16);
+    temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
     hipError_t e = arena.reserve(arena_bytes);
-    if (e == hipSuccess) e = row64.alloc(sizeof(uint64_t) * (size_t)(n_cam + 1));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_visibility_within_distance: %s", hipGetErrorString(e));
-    for (const Want &w : wants) w.b->view(arena.take(w.bytes));
+    if (e == hipSuccess) e = row64.alloc((size_t)n_cam + 1);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_within_distance: %s", hipGetErrorString(e));
+    temporaries([&](auto &b, size_t n) { arena.carve(b, n); });
 
     // cell list: count, exclusive scan (start[n_cells] = n_pts), fill
     HIP_TRY(hipMemsetAsync(counts.ptr, 0, 4 * (size_t)(n_cells + 1), st));
@@ -1673,28 +1578,27 @@ int c2b_problem_visibility_within_distance(c2b_problem *p, double max_dist, int 
     HIP_TRY(hipMemsetAsync(cam_count.ptr, 0, 4 * (size_t)(n_cam + 1), st));
     HIP_TRY(hipMemsetAsync(sum64.ptr, 0, 8, st));
     HIP_TRY(hipMemsetAsync(max32.ptr, 0, 4, st));
-    if (n_pts) hipLaunchKernelGGL(k_cells_assign, dim3(blocks_of(n_pts, 256)), dim3(256), 0, st, reinterpret_cast<const double4 *>(p->pts4), n_pts,
-                                  g, cell_of.as<uint32_t>(), counts.as<uint32_t>());
+    if (n_pts) hipLaunchKernelGGL(k_cells_assign, dim3(blocks_of(n_pts, 256)), dim3(256), 0, st, reinterpret_cast<const double4 *>(p->pts4.ptr), n_pts,
+                                  g, cell_of, counts);
     uint32_t n_sorted = 0, n_kept32 = 0;
-    uint32_t *start = cursor.as<uint32_t>();                             // scanned counts; the fill's cursors live in `counts` afterwards
-    e = scan_flags(st, counts.as<uint32_t>(), n_cells + 1, start, tiles.as<uint32_t>(), total.as<uint32_t>(), &n_sorted);
+    uint32_t *start = cursor;                             // scanned counts; the fill's cursors live in `counts` afterwards
+    e = scan_flags(st, counts, n_cells + 1, start, tiles, total, &n_sorted);
     if (e == hipSuccess && (int64_t)n_sorted != n_pts) return fail(C2B_ERR_HIP, "problem_visibility_within_distance: cell counts do not add up");
     if (e == hipSuccess) e = hipMemsetAsync(counts.ptr, 0, 4 * (size_t)(n_cells + 1), st);
     if (e == hipSuccess && n_pts)
-        hipLaunchKernelGGL(k_cells_fill, dim3(blocks_of(n_pts, 256)), dim3(256), 0, st, (const uint32_t *)cell_of.as<uint32_t>(), n_pts,
-                           (const uint32_t *)start, counts.as<uint32_t>(), sorted.as<uint32_t>());
+        hipLaunchKernelGGL(k_cells_fill, dim3(blocks_of(n_pts, 256)), dim3(256), 0, st, cell_of, n_pts,
+                           (const uint32_t *)start, counts, sorted);
     // pass 1: survivors per camera; scan; total
     const unsigned cam_blocks = blocks_of(n_cam, kCellWPB);
     if (e == hipSuccess && n_cam && n_pts) {
         hipLaunchKernelGGL((k_cells_visibility<false>), dim3(cam_blocks), dim3(kCellWPB * 64), 0, st, (const double *)p->camblk, n_cam,
-                           reinterpret_cast<const double4 *>(p->pts4), g, (const uint32_t *)start, (const uint32_t *)sorted.as<uint32_t>(),
-                           max_dist, occlusion ? 1 : 0, block_length, block_inset, cam_count.as<uint32_t>(), (const uint64_t *)nullptr,
+                           reinterpret_cast<const double4 *>(p->pts4.ptr), g, (const uint32_t *)start, sorted,
+                           max_dist, occlusion ? 1 : 0, block_length, block_inset, cam_count, (const uint64_t *)nullptr,
                            (uint32_t *)nullptr, (double2 *)nullptr);
-        hipLaunchKernelGGL(k_sum_u32_u64, dim3(256), dim3(256), 0, st, (const uint32_t *)cam_count.as<uint32_t>(), n_cam,
-                           sum64.as<unsigned long long>());
-        hipLaunchKernelGGL(k_max_u32, dim3(256), dim3(256), 0, st, (const uint32_t *)cam_count.as<uint32_t>(), n_cam, max32.as<uint32_t>());
+        hipLaunchKernelGGL(k_sum_u32_u64, dim3(256), dim3(256), 0, st, cam_count, n_cam, sum64);
+        hipLaunchKernelGGL(k_max_u32, dim3(256), dim3(256), 0, st, cam_count, n_cam, max32);
     }
-    if (e == hipSuccess) e = scan_flags(st, cam_count.as<uint32_t>(), n_cam + 1, pos.as<uint32_t>(), tiles.as<uint32_t>(), total.as<uint32_t>(), &n_kept32);
+    if (e == hipSuccess) e = scan_flags(st, cam_count, n_cam + 1, pos, tiles, total, &n_kept32);
     unsigned long long n_kept = 0;
     uint32_t longest = 0;
     if (e == hipSuccess) e = hipMemcpy(&n_kept, sum64.ptr, 8, hipMemcpyDeviceToHost);
@@ -1702,22 +1606,23 @@ int c2b_problem_visibility_within_distance(c2b_problem *p, double max_dist, int 
     if (e == hipSuccess && n_kept != (unsigned long long)n_kept32)
         return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_within_distance: more than 2^32 observations");
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_widen_u32, dim3(blocks_for(n_cam + 1)), dim3(kBlock), 0, st, (const uint32_t *)pos.as<uint32_t>(), n_cam + 1,
-                           row64.as<uint64_t>());
+        hipLaunchKernelGGL(k_widen_u32, dim3(blocks_for(n_cam + 1)), dim3(kBlock), 0, st, pos, n_cam + 1, row64);
         e = launch_error();
     }
     // pass 2: fill in meeting order, then every row into ascending point index
-    DevBuf tmp_pt, tmp_uv, out_pt, out_uv;
+    DevBuf<uint32_t> tmp_pt, out_pt;
+    DevBuf<double2> tmp_uv;
+    DevBuf<double> out_uv;
     const size_t w = (size_t)n_kept;
-    if (e == hipSuccess) e = tmp_pt.alloc(4 * w);
-    if (e == hipSuccess) e = tmp_uv.alloc(16 * w);
-    if (e == hipSuccess) e = out_pt.alloc(4 * w);
-    if (e == hipSuccess) e = out_uv.alloc(16 * w);
+    if (e == hipSuccess) e = tmp_pt.alloc(w);
+    if (e == hipSuccess) e = tmp_uv.alloc(w);
+    if (e == hipSuccess) e = out_pt.alloc(w);
+    if (e == hipSuccess) e = out_uv.alloc(2 * w);
     if (e == hipSuccess && w) {
         hipLaunchKernelGGL((k_cells_visibility<true>), dim3(cam_blocks), dim3(kCellWPB * 64), 0, st, (const double *)p->camblk, n_cam,
-                           reinterpret_cast<const double4 *>(p->pts4), g, (const uint32_t *)start, (const uint32_t *)sorted.as<uint32_t>(),
-                           max_dist, occlusion ? 1 : 0, block_length, block_inset, (uint32_t *)nullptr, (const uint64_t *)row64.as<uint64_t>(),
-                           tmp_pt.as<uint32_t>(), tmp_uv.as<double2>());
+                           reinterpret_cast<const double4 *>(p->pts4.ptr), g, (const uint32_t *)start, sorted,
+                           max_dist, occlusion ? 1 : 0, block_length, block_inset, (uint32_t *)nullptr, row64,
+                           tmp_pt, tmp_uv);
         // The device row sort is quadratic in the row length: right for the generators' rows (a few dozen entries), wrong
         // for a radius that makes one camera see tens of thousands of points.  Beyond `long_row` entries the rows are sorted on the
         // host instead (threads over cameras) -- a path for odd inputs, not a fast one; such problems belong to the dense
@@ -1726,9 +1631,8 @@ int c2b_problem_visibility_within_distance(c2b_problem *p, double max_dist, int 
         // round 4 a scene with thousands of cameras seeing several thousand points each was a multi-second cliff)
         const uint32_t long_row = p->opt.rank_sort_max_row > 0 ? (uint32_t)p->opt.rank_sort_max_row : 2048u;
         if (longest <= long_row) {
-            hipLaunchKernelGGL(k_rows_rank_sort, dim3(cam_blocks), dim3(kCellWPB * 64), 0, st, (const uint64_t *)row64.as<uint64_t>(), n_cam,
-                               (const uint32_t *)tmp_pt.as<uint32_t>(), (const double2 *)tmp_uv.as<double2>(), out_pt.as<uint32_t>(),
-                               out_uv.as<double2>());
+            hipLaunchKernelGGL(k_rows_rank_sort, dim3(cam_blocks), dim3(kCellWPB * 64), 0, st, row64, n_cam, tmp_pt, tmp_uv, out_pt,
+                               reinterpret_cast<double2 *>(out_uv.ptr));
             e = launch_error();
         } else {
             e = launch_error();
@@ -1766,11 +1670,9 @@ int c2b_problem_visibility_within_distance(c2b_problem *p, double max_dist, int 
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
-        return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_visibility_within_distance: %s", hipGetErrorString(e));
+        return fail(hip_code(e), "problem_visibility_within_distance: %s", hipGetErrorString(e));
     }
-    p->dense_row = (uint64_t *)row64.release();
-    p->dense_pt = (uint32_t *)out_pt.release();
-    p->dense_uv = (double *)out_uv.release();
+    p->dense_row = std::move(row64); p->dense_pt = std::move(out_pt); p->dense_uv = std::move(out_uv);
     p->dense_n = (int64_t)n_kept;
     return C2B_OK;
     C2B_API_END("problem_visibility_within_distance")
@@ -1808,13 +1710,14 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
         }
     }
     // the cell list over the camera centres
-    DevBuf d_tri, d_cum;
-    const double4 *centres = reinterpret_cast<const double4 *>(p->cen4);     // written with camblk (ensure_camblk above)
-    hipError_t e = d_tri.alloc(36 * (size_t)n_tri);
-    if (e == hipSuccess) e = d_cum.alloc(8 * (size_t)n_tri);
+    DevBuf<float> d_tri;
+    DevBuf<double> d_cum;
+    const double4 *centres = reinterpret_cast<const double4 *>(p->cen4.ptr);     // written with camblk (ensure_camblk above)
+    hipError_t e = d_tri.alloc(9 * (size_t)n_tri);
+    if (e == hipSuccess) e = d_cum.alloc((size_t)n_tri);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tri.ptr, tri9, 36 * (size_t)n_tri, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_cum.ptr, cum.data(), 8 * (size_t)n_tri, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_generate_world_points: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hip_code(e), "problem_generate_world_points: %s", hipGetErrorString(e));
     // the centres' extent (a reduction the statistics kernel already is: cameras only)
     double stats[C2B_STATS_DOUBLES];
     rc = c2b_stats(p->camblk, p->cen4, n_cam, p->pts4, 0, p->ws, p->stats, st);
@@ -1833,30 +1736,31 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
     g.ncx = (int)std::floor(ex / cs) + 1; g.ncz = (int)std::floor(ez / cs) + 1;
     const int64_t n_cells = (int64_t)g.ncx * g.ncz;
     const int64_t chunk = std::max<int64_t>(4096, std::min<int64_t>(num_points, (int64_t)1 << 20));      // the host sampler's chunks
-    DevBuf cell_of, counts, startb, sorted, tiles, total, cand, ok, pos, cutoff, out;
+    DevBuf<uint32_t> cell_of, counts, startb, sorted, tiles, total, ok, pos;
+    DevBuf<double4> cand;
+    DevBuf<unsigned long long> cutoff;
+    DevBuf<double> out;
     const int64_t big = std::max(n_cells + 1, chunk);
-    e = cell_of.alloc(4 * (size_t)n_cam);
-    if (e == hipSuccess) e = counts.alloc(4 * (size_t)(n_cells + 1));
-    if (e == hipSuccess) e = startb.alloc(4 * (size_t)(n_cells + 1));
-    if (e == hipSuccess) e = sorted.alloc(4 * (size_t)n_cam);
-    if (e == hipSuccess) e = tiles.alloc(4 * (size_t)(big / kScanTile + 2));
-    if (e == hipSuccess) e = total.alloc(4);
-    if (e == hipSuccess) e = cand.alloc(32 * (size_t)chunk);
-    if (e == hipSuccess) e = ok.alloc(4 * (size_t)chunk);
-    if (e == hipSuccess) e = pos.alloc(4 * (size_t)chunk);
-    if (e == hipSuccess) e = cutoff.alloc(8);
-    if (e == hipSuccess) e = out.alloc(32 * (size_t)std::max<int64_t>(num_points, 1));
+    e = cell_of.alloc((size_t)n_cam);
+    if (e == hipSuccess) e = counts.alloc((size_t)(n_cells + 1));
+    if (e == hipSuccess) e = startb.alloc((size_t)(n_cells + 1));
+    if (e == hipSuccess) e = sorted.alloc((size_t)n_cam);
+    if (e == hipSuccess) e = tiles.alloc((size_t)(big / kScanTile + 2));
+    if (e == hipSuccess) e = total.alloc(1);
+    if (e == hipSuccess) e = cand.alloc((size_t)chunk);
+    if (e == hipSuccess) e = ok.alloc((size_t)chunk);
+    if (e == hipSuccess) e = pos.alloc((size_t)chunk);
+    if (e == hipSuccess) e = cutoff.alloc(1);
+    if (e == hipSuccess) e = out.alloc(4 * (size_t)std::max<int64_t>(num_points, 1));
     if (e == hipSuccess) e = hipMemsetAsync(counts.ptr, 0, 4 * (size_t)(n_cells + 1), st);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_generate_world_points: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_cells_assign, dim3(blocks_of(n_cam, 256)), dim3(256), 0, st, centres, n_cam, g,
-                       cell_of.as<uint32_t>(), counts.as<uint32_t>());
+    if (e != hipSuccess) return fail(hip_code(e), "problem_generate_world_points: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(k_cells_assign, dim3(blocks_of(n_cam, 256)), dim3(256), 0, st, centres, n_cam, g, cell_of, counts);
     uint32_t n_sorted = 0;
-    e = scan_flags(st, counts.as<uint32_t>(), n_cells + 1, startb.as<uint32_t>(), tiles.as<uint32_t>(), total.as<uint32_t>(), &n_sorted);
+    e = scan_flags(st, counts, n_cells + 1, startb, tiles, total, &n_sorted);
     if (e == hipSuccess && (int64_t)n_sorted != n_cam) return fail(C2B_ERR_HIP, "problem_generate_world_points: cell counts do not add up");
     if (e == hipSuccess) e = hipMemsetAsync(counts.ptr, 0, 4 * (size_t)(n_cells + 1), st);
     if (e == hipSuccess)
-        hipLaunchKernelGGL(k_cells_fill, dim3(blocks_of(n_cam, 256)), dim3(256), 0, st, (const uint32_t *)cell_of.as<uint32_t>(), n_cam,
-                           (const uint32_t *)startb.as<uint32_t>(), counts.as<uint32_t>(), sorted.as<uint32_t>());
+        hipLaunchKernelGGL(k_cells_fill, dim3(blocks_of(n_cam, 256)), dim3(256), 0, st, cell_of, n_cam, startb, counts, sorted);
     if (e == hipSuccess) e = launch_error();
     // the reference's loop, a chunk of candidates at a time
     int64_t accepted = 0, failed = 0;
@@ -1865,18 +1769,15 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
         const unsigned long long all = (unsigned long long)chunk;
         e = hipMemcpyAsync(cutoff.ptr, &all, 8, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_world_candidates, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, (const float *)d_tri.as<float>(), n_tri,
-                           (const double *)d_cum.as<double>(), seed, k0, chunk, centres, g,
-                           (const uint32_t *)startb.as<uint32_t>(), (const uint32_t *)sorted.as<uint32_t>(), max_dist, cand.as<double4>(),
-                           ok.as<uint32_t>());
+        hipLaunchKernelGGL(k_world_candidates, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, d_tri, n_tri, d_cum, seed, k0, chunk,
+                           centres, g, startb, sorted, max_dist, cand, ok);
         uint32_t n_ok = 0;
-        e = scan_flags(st, ok.as<uint32_t>(), chunk, pos.as<uint32_t>(), tiles.as<uint32_t>(), total.as<uint32_t>(), &n_ok);
+        e = scan_flags(st, ok, chunk, pos, tiles, total, &n_ok);
         if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_world_cutoff, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, (const uint32_t *)pos.as<uint32_t>(), chunk,
-                           (uint64_t)(num_points - accepted), (uint64_t)(fail_threshold - failed), cutoff.as<unsigned long long>());
-        hipLaunchKernelGGL(k_world_accept, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, (const double4 *)cand.as<double4>(),
-                           (const uint32_t *)ok.as<uint32_t>(), (const uint32_t *)pos.as<uint32_t>(), chunk,
-                           (const unsigned long long *)cutoff.as<unsigned long long>(), out.as<double4>() + accepted);
+        hipLaunchKernelGGL(k_world_cutoff, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, pos, chunk,
+                           (uint64_t)(num_points - accepted), (uint64_t)(fail_threshold - failed), cutoff);
+        hipLaunchKernelGGL(k_world_accept, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, cand, ok, pos, chunk, cutoff,
+                           reinterpret_cast<double4 *>(out.ptr) + accepted);
         e = launch_error();
         unsigned long long cut = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&cut, cutoff.ptr, 8, hipMemcpyDeviceToHost, st);
@@ -1884,7 +1785,7 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
         if (e != hipSuccess) break;
         uint32_t took = n_ok;                                 // accepted among the candidates before the cutoff
         if ((int64_t)cut < chunk) {
-            e = hipMemcpy(&took, pos.as<uint32_t>() + cut, 4, hipMemcpyDeviceToHost);
+            e = hipMemcpy(&took, pos + cut, 4, hipMemcpyDeviceToHost);
             if (e != hipSuccess) break;
         }
         accepted += (int64_t)took;
@@ -1898,8 +1799,7 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
     free_dense(p);
     drop_rows(p);
     drop_constant(p);
-    if (p->pts4) (void)hipFree(p->pts4);
-    p->pts4 = (double *)out.release();
+    p->pts4 = std::move(out);
     p->n_pts = accepted;
     *n_out = accepted;
     return C2B_OK;
@@ -1922,33 +1822,30 @@ int c2b_problem_visibility_dense(c2b_problem *p, double max_dist, uint64_t *row_
         return fail(C2B_ERR_INVALID_ARGUMENT,
                     "problem_visibility_dense: %lld cameras x %lld point tiles is too large for the dense sweep; "
                     "use candidate pairs + c2b_problem_visibility_pairs", (long long)p->n_cam, (long long)n_tiles);
-    uint32_t *d_counts = nullptr;
-    uint64_t *d_tot = nullptr, *d_row = nullptr;
-    hipError_t e = hipMalloc((void **)&d_counts, sizeof(uint32_t) * (size_t)(cells ? cells : 4));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tot, sizeof(uint64_t) * (size_t)(p->n_cam + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_row, sizeof(uint64_t) * (size_t)(p->n_cam + 1));
+    DevBuf<uint32_t> d_counts;
+    DevBuf<uint64_t> d_tot, d_row;
+    hipError_t e = d_counts.alloc((size_t)cells);
+    if (e == hipSuccess) e = d_tot.alloc((size_t)p->n_cam + 1);
+    if (e == hipSuccess) e = d_row.alloc((size_t)p->n_cam + 1);
     if (e == hipSuccess) {
         rc = c2b_visibility_dense_count(p->camblk, p->n_cam, p->pts4, p->n_pts, max_dist, d_counts, d_tot, d_row, p->stream);
         if (!rc) e = hipMemcpyAsync(row_ptr, d_row, sizeof(uint64_t) * (size_t)(p->n_cam + 1), hipMemcpyDeviceToHost, p->stream);
         if (!rc && e == hipSuccess) e = hipStreamSynchronize(p->stream);
         if (!rc && e == hipSuccess) {
             const int64_t total = (int64_t)row_ptr[p->n_cam];
-            e = hipMalloc((void **)&p->dense_pt, sizeof(uint32_t) * (size_t)(total ? total : 4));
-            if (e == hipSuccess) e = hipMalloc((void **)&p->dense_uv, sizeof(double) * 2 * (size_t)(total ? total : 1));
+            e = p->dense_pt.alloc((size_t)total);
+            if (e == hipSuccess) e = p->dense_uv.alloc(2 * (size_t)total);
             if (e == hipSuccess && total) {
                 rc = c2b_visibility_dense_fill(p->camblk, p->n_cam, p->pts4, p->n_pts, max_dist, d_counts, d_row, p->dense_pt,
                                                p->dense_uv, p->stream);
                 if (!rc) e = hipStreamSynchronize(p->stream);
             }
-            if (!rc && e == hipSuccess) { p->dense_n = total; p->dense_row = d_row; d_row = nullptr; }
+            if (!rc && e == hipSuccess) { p->dense_n = total; p->dense_row = std::move(d_row); }
         }
     }
-    if (d_counts) (void)hipFree(d_counts);
-    if (d_tot) (void)hipFree(d_tot);
-    if (d_row) (void)hipFree(d_row);
     if (rc || e != hipSuccess) free_dense(p);
     if (rc) return rc;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_visibility_dense: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_dense: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_visibility_dense")
 }
@@ -1967,17 +1864,16 @@ static int occlude_impl(c2b_problem *p, const float *tri9, int64_t n_tri, const 
         HIP_TRY(hipStreamSynchronize(p->stream));
         return C2B_OK;
     }
-    float *d_tri = nullptr;
-    uint32_t *d_cam = nullptr, *d_pt_new = nullptr, *d_flag = nullptr;
+    DevBuf<char> d_tri, d_nodes;
+    DevBuf<uint32_t> d_cam, d_pt_new, d_flag;
     uint32_t stack_overflow = 0;
-    uint8_t *d_keep = nullptr;
-    uint64_t *d_tot = nullptr, *d_row_new = nullptr;
-    double *d_uv_new = nullptr;
+    DevBuf<uint8_t> d_keep;
+    DevBuf<uint64_t> d_row_new;
+    DevBuf<double> d_uv_new;
     int rc = C2B_OK;
     // small meshes: every ray against every triangle; larger ones through a hierarchy built here on the host
     const bool use_bvh = ready || n_tri >= kBvhMinTriangles;
     c2b_bvh *built = nullptr;
-    void *d_nodes = nullptr;
     int64_t n_nodes = 0;
     if (use_bvh && !ready) {
         rc = c2b_bvh_build(tri9, n_tri, &built);
@@ -1987,11 +1883,11 @@ static int occlude_impl(c2b_problem *p, const float *tri9, int64_t n_tri, const 
     if (use_bvh) n_nodes = (int64_t)bvh->b.nodes.size();
     const size_t tri_bytes = use_bvh ? (size_t)C2B_BVH_TRI_BYTES * (size_t)n_tri : sizeof(float) * 9 * (size_t)n_tri;
     const void *tri_src = use_bvh ? (const void *)bvh->b.tris.data() : (const void *)tri9;
-    hipError_t e = hipMalloc((void **)&d_tri, tri_bytes);
-    if (e == hipSuccess && use_bvh) e = hipMalloc(&d_nodes, (size_t)C2B_BVH_NODE_BYTES * (size_t)n_nodes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cam, sizeof(uint32_t) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_keep, (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_flag, sizeof(uint32_t));
+    hipError_t e = d_tri.alloc(tri_bytes);
+    if (e == hipSuccess && use_bvh) e = d_nodes.alloc((size_t)C2B_BVH_NODE_BYTES * (size_t)n_nodes);
+    if (e == hipSuccess) e = d_cam.alloc((size_t)n);
+    if (e == hipSuccess) e = d_keep.alloc((size_t)n);
+    if (e == hipSuccess) e = d_flag.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(uint32_t), p->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tri, tri_src, tri_bytes, hipMemcpyHostToDevice, p->stream);
     if (e == hipSuccess && use_bvh)
@@ -2000,7 +1896,8 @@ static int occlude_impl(c2b_problem *p, const float *tri9, int64_t n_tri, const 
         rc = c2b_expand_rows(p->dense_row, n_cam, 0, n, d_cam, p->stream);
         if (!rc)
             rc = use_bvh ? c2b_occlusion_filter_bvh(p->camblk, p->pts4, d_cam, p->dense_pt, n, d_nodes, n_nodes, d_tri, n_tri, d_keep, d_flag, p->stream)
-                         : c2b_occlusion_filter(p->camblk, p->pts4, d_cam, p->dense_pt, n, d_tri, n_tri, d_keep, p->stream);
+                         : c2b_occlusion_filter(p->camblk, p->pts4, d_cam, p->dense_pt, n, reinterpret_cast<const float *>(d_tri.ptr), n_tri,
+                                                d_keep, p->stream);
         // Stable compaction of the survivor lists on the device (per-camera order of the sweep is kept): kept count per
         // row, row scan, scatter.  Only the new row pointer travels to the host.
         if (!rc) {                                         // a traversal-stack overflow invalidates the whole mask
@@ -2011,29 +1908,17 @@ static int occlude_impl(c2b_problem *p, const float *tri9, int64_t n_tri, const 
         }
         if (!rc && e == hipSuccess) {
             int64_t w = 0;
-            e = compact_rows_on_device(p, p->dense_row, d_keep, p->dense_pt, p->dense_uv, n_cam, row_ptr, &d_row_new, &d_pt_new,
-                                       &d_uv_new, &w);
+            e = compact_rows_on_device(p, p->dense_row, d_keep, p->dense_pt, p->dense_uv, n_cam, row_ptr, d_row_new, d_pt_new, d_uv_new, &w);
             if (e == hipSuccess) {                           // the filtered lists replace the sweep's
-                std::swap(p->dense_pt, d_pt_new);
-                std::swap(p->dense_uv, d_uv_new);
-                std::swap(p->dense_row, d_row_new);
+                p->dense_pt = std::move(d_pt_new); p->dense_uv = std::move(d_uv_new); p->dense_row = std::move(d_row_new);
                 p->dense_n = w;
             }
         }
     }
-    if (rc || e != hipSuccess) (void)hipStreamSynchronize(p->stream);   // nothing below may free what a copy still reads
-    if (d_tri) (void)hipFree(d_tri);
-    if (d_nodes) (void)hipFree(d_nodes);
-    if (d_cam) (void)hipFree(d_cam);
-    if (d_keep) (void)hipFree(d_keep);
-    if (d_flag) (void)hipFree(d_flag);
-    if (d_tot) (void)hipFree(d_tot);
-    if (d_row_new) (void)hipFree(d_row_new);
-    if (d_pt_new) (void)hipFree(d_pt_new);
-    if (d_uv_new) (void)hipFree(d_uv_new);
+    if (rc || e != hipSuccess) (void)hipStreamSynchronize(p->stream);   // no temporary may be freed while a copy still reads it
     c2b_bvh_free(built);
     if (rc) return rc;
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? C2B_ERR_OOM : C2B_ERR_HIP, "problem_visibility_dense_occlude: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_dense_occlude: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_visibility_dense_occlude")
 }
