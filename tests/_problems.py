@@ -346,3 +346,112 @@ def dome_problem(seed=0, dup=True, state=False, obs_noise=1e-3, start_noise=1e-3
     moved = pts + rng.normal(scale=start_noise, size=pts.shape)
     return dict(bal9=bal9, cams15=O.camera_from_bal(bal9), pts=moved, row_ptr=row_ptr, pt_idx=pt_idx, uv=uv,
                 lengths=lengths, true_bal9=true_bal9, true_pts=pts, bal=not state)
+
+
+# ---- general-position cameras and points for the noise and statistics passes (no observations) ----
+NOISE_CAM_COUNTS = (0, 1, 63, 64, 65, 255, 256, 257, 300)          # around a wave of 64 cameras and a workgroup of 256 entities
+NOISE_PT_COUNTS = (0, 1, 5, 700)
+NOISE_COUNT_PAIRS = tuple((c, p) for c in NOISE_CAM_COUNTS for p in NOISE_PT_COUNTS if c + p)
+# statistics: one lane, a batch tail, one wave / workgroup +- 1, four workgroups +- 1, the grid cap (512 workgroups of 256) +- 1, and
+# four entities per thread at the cap plus a tail
+STATS_TOTALS = (1, 2, 5, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 512 * 256 - 1, 512 * 256, 512 * 256 + 1, 4 * 512 * 256 + 3)
+NOISE_VARIANTS = (None, "planar", "far", "offset")
+PLANAR_Y = 0.625
+
+
+def noise_problem(n_cam, n_pts, seed, variant=None, tie_at=4):
+    """n_cam cameras in general position and n_pts points: random_problem's rotations, f in [0.8, 1.2], k1 and k2 nonzero
+    (every camera's three intrinsics are distinct bit patterns), centres and points in a box of +-30.  Point 0 lies
+    next to the coordinate origin -- the drift origin whenever there is a point -- and point tie_at (if there is one) repeats it: a
+    tie for the origin search, which the later one wins.  The translation is t = -R c taken in long double and rounded once.
+      planar  every centre and every point has y = PLANAR_Y (a zero dimension); only cameras for which the device's
+              centre formula returns that y bit for bit are kept (the oracle's center() has the device's order);
+      far     a box of +-200: extent 400;
+      offset  the cloud moved to (1e6, 1e6, 1e6)-ish with a spread of 1e-3.
+    Prefixes of both tables are problems of the same kind.  Returns dict(cams15 [n_cam, 15], pts [n_pts, 3])."""
+    assert variant in NOISE_VARIANTS
+    rng = np.random.default_rng(seed)
+    half = 200.0 if variant == "far" else 30.0
+    LDt = np.longdouble
+
+    def place(m):
+        x = rng.uniform(-half, half, size=(m, 3))
+        if variant == "planar":
+            x[:, 1] = PLANAR_Y
+        if variant == "offset":
+            x = np.array([1.0e6, 1.25e6, 0.75e6]) + x * (1e-3 / half)
+        return x
+    cams = np.empty((0, 15))
+    while len(cams) < n_cam:
+        m = 2 * n_cam + 8
+        w = rng.uniform(-np.pi, np.pi, size=(m, 3)) * rng.uniform(0.0, 1.0, size=(m, 1))
+        R = np.stack([O.from_rodrigues(wi) for wi in w])                       # column-major
+        c = place(m)
+        Rrow = R.reshape(m, 3, 3).transpose(0, 2, 1).astype(LDt)
+        t = (-np.einsum("nij,nj->ni", Rrow, c.astype(LDt))).astype(np.float64)
+        sign = np.where(rng.random((m, 2)) < 0.5, -1.0, 1.0)
+        intr = np.column_stack([rng.uniform(0.8, 1.2, m), sign * rng.uniform(1e-3, 1e-2, size=(m, 2))])
+        new = np.ascontiguousarray(np.column_stack([R, t, intr]))
+        if variant == "planar":
+            new = new[np.array([O.center(row)[1] == PLANAR_Y for row in new])]
+        cams = np.concatenate([cams, new])
+    cams = np.ascontiguousarray(cams[:n_cam])
+    assert len(np.unique(cams[:, 12:15].view(np.uint64))) == 3 * n_cam and np.all(cams[:, 13:15] != 0.0)
+    pts = place(n_pts)
+    if n_pts:
+        near = np.array([0.01, -0.02, 0.015])
+        if variant == "planar":
+            near[1] = PLANAR_Y
+        if variant == "offset":
+            near = pts.min(axis=0) - 1e-4                                      # the entity nearest (0, 0, 0) of a cloud at +1e6
+        pts[0] = near
+        if 0 < tie_at < n_pts:
+            pts[tie_at] = near
+    return dict(cams15=cams, pts=np.ascontiguousarray(pts))
+
+
+def stats_points(n, seed, variant=None):
+    """n points of noise_problem's kind (points only: the large statistics totals); the LAST point repeats the first, so that
+    the tie for the origin spans the whole table"""
+    return noise_problem(0, n, seed, variant, tie_at=n - 1)["pts"]
+
+
+NOISE_KINDS = ("drift", "drift_normalized", "noise", "sin")
+_noise_base = {}
+
+
+def noise_base(variant=None):
+    """the one 300 x 700 problem of each variant the noise tests slice their count pairs from (read-only, cached)"""
+    if variant not in _noise_base:
+        P = noise_problem(300, 700, seed={None: 11, "planar": 12, "far": 13, "offset": 14}[variant], variant=variant)
+        P["cams15"].setflags(write=False)
+        P["pts"].setflags(write=False)
+        _noise_base[variant] = P
+    return _noise_base[variant]
+
+
+def noise_edge_cases():
+    """(label, kind, variant, n_cam, n_pts, parameter overrides): the edge variants of the noise tests"""
+    return [("planar/sin", "sin", "planar", 300, 700, {}),
+            ("planar-points/sin", "sin", "planar", 0, 700, {}),
+            ("far/drift", "drift", "far", 65, 700, dict(angle_strength=0.3, strength=1e-5)),
+            ("rotation_std=4/noise", "noise", None, 300, 700, dict(rotation_std=4.0)),
+            ("std=0/drift", "drift", None, 65, 5, dict(std=0.0)),
+            ("std=0/noise", "noise", None, 65, 5, dict(translation_std=0.0, rotation_std=0.0, point_std=0.0)),
+            ("zero-strength/drift", "drift", None, 65, 5, dict(strength=0.0, angle_strength=0.0))]
+
+
+def noise_cases():
+    out = [("%s/%dx%d" % (k, c, p), k, None, c, p, {}) for k in NOISE_KINDS for (c, p) in NOISE_COUNT_PAIRS]
+    return out + noise_edge_cases()
+
+
+def grid_problem():
+    """the axis-aligned grid the oracle comparisons of tests/test_gpu_parity.py run on, with its visibility graph"""
+    cams, pts = grid_cameras_points(3, cpb=10, ppb=20, L=5.0)
+    ci, pi = grid_candidate_pairs(cams, pts, 10.0)
+    uv, keep = O.visibility_pairs(cams, pts, ci, pi, 10.0)
+    ci, pi, uv = ci[keep == 1], pi[keep == 1], uv[keep == 1]
+    row_ptr = np.zeros(len(cams) + 1, dtype=np.int64)
+    np.add.at(row_ptr, ci.astype(np.int64) + 1, 1)
+    return dict(cams15=cams, pts=pts, row_ptr=np.cumsum(row_ptr).astype(np.uint64), pt_idx=pi.astype(np.uint64), uv=uv)

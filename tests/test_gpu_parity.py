@@ -9,13 +9,16 @@ Tolerances (north_star: indices bit-exact, f64 <= 1e-6 relative):
     ~1e-3 of arguments where libm's pow is not correctly rounded (DESIGN.md section 5);
   * Jacobian, error sums, stats: <= 1e-6 relative required, ~1e-12 asserted;
   * noise: same Philox draws; the device's log / sin / cos (fdlibm kernels on the draws' domains, camera_math.hpp)
-    differ from glibc by ulps -> 1e-9 on results, 1e-13 on the raw observation draws.
+    differ from glibc by ulps -> 1e-9 on results, 1e-13 on the raw observation draws.  These compare with the oracle on one
+    axis-aligned problem at one absolute tolerance; tests/test_gpu_noise_reference.py holds the same kernels and the
+    statistics pass entry by entry to a long-double reference, in general position, at the count edges of their store
+    and reduction paths.
 """
 import numpy as np
 import pytest
 
 import oracle as O
-from _problems import grid_cameras_points, grid_candidate_pairs, random_problem
+from _problems import grid_cameras_points, grid_candidate_pairs, grid_problem, random_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -395,14 +398,7 @@ def test_visibility_pairs_bit_exact(c2b, blocks, cpb, ppb, L):
 # ---------------------------------------------------------------------------------------------
 # noise: same draws as the oracle's Philox scheme, reference inequalities (tests/main.rs:134-195)
 # ---------------------------------------------------------------------------------------------
-def _grid_problem():
-    cams, pts = grid_cameras_points(3, cpb=10, ppb=20, L=5.0)
-    ci, pi = grid_candidate_pairs(cams, pts, 10.0)
-    uv, keep = O.visibility_pairs(cams, pts, ci, pi, 10.0)
-    ci, pi, uv = ci[keep == 1], pi[keep == 1], uv[keep == 1]
-    row_ptr = np.zeros(len(cams) + 1, dtype=np.int64)
-    np.add.at(row_ptr, ci.astype(np.int64) + 1, 1)
-    return dict(cams15=cams, pts=pts, row_ptr=np.cumsum(row_ptr).astype(np.uint64), pt_idx=pi.astype(np.uint64), uv=uv)
+_grid_problem = grid_problem
 
 
 def test_add_drift_matches_oracle(c2b):
