@@ -64,6 +64,29 @@ class StepInfo(C.Structure):
                 ("model_decrease", C.c_double)]
 
 
+class LmOptions(C.Structure):
+    """c2b_lm_options (include/city2ba_hip_experimental.h)"""
+    _fields_ = [("max_iterations", C.c_int32), ("pcg_max_iters", C.c_int32), ("lambda0", C.c_double), ("pcg_rel_tol", C.c_double),
+                ("function_tol", C.c_double), ("gradient_tol", C.c_double), ("parameter_tol", C.c_double)]
+
+
+class LmIteration(C.Structure):
+    """c2b_lm_iteration"""
+    _fields_ = [("cost", C.c_double), ("cost_trial", C.c_double), ("lam", C.c_double), ("model_decrease", C.c_double),
+                ("gradient_max", C.c_double), ("step_norm", C.c_double), ("x_norm", C.c_double), ("pcg_rel_residual", C.c_double),
+                ("accepted", C.c_int32), ("pcg_iterations", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LmSummary(C.Structure):
+    """c2b_lm_summary"""
+    _fields_ = [("iterations", C.c_int32), ("termination", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("lambda_next", C.c_double)]
+
+
+# c2b_lm_summary.termination
+LM_TERMINATIONS = {0: "max_iterations", 1: "function_tolerance", 2: "gradient_tolerance", 3: "parameter_tolerance", 4: "not_finite"}
+
+
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
 SIGNATURES = {
     "c2b_version": (C.c_char_p, []),
@@ -121,6 +144,10 @@ SIGNATURES = {
     "c2b_schur_cameras_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _d, _vp, _vp, _vp, _vp]),
     "c2b_problem_solve_step": (_int, [_vp, _d, _int, _d, _vp, _vp, _vp]),
     "c2b_problem_apply_step": (_int, [_vp, _vp, _vp]),
+    "c2b_problem_checkpoint": (_int, [_vp]),
+    "c2b_problem_rollback": (_int, [_vp]),
+    "c2b_problem_drop_checkpoint": (_int, [_vp]),
+    "c2b_problem_levenberg_marquardt": (_int, [_vp, _vp, _vp, _int, _vp]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
     "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),

@@ -400,6 +400,21 @@ class BAProblem:
         torch.cuda.current_stream(dev).synchronize()
         L.check(L.lib().c2b_problem_apply_step(self._h, ptr(dc), ptr(dp)))
 
+    def checkpoint(self):
+        """Keep the cameras and points as they are now, on the device (c2b_problem_checkpoint); the problem is in bal mode
+        afterwards, as after apply_step(None, None).  rollback() returns to this state bit for bit.  apply_step and the
+        noise functions leave the checkpoint in place; any upload, a cull, a read and the generators drop it."""
+        L.check(L.lib().c2b_problem_checkpoint(self._h))
+
+    def rollback(self):
+        """Cameras and points back to the last checkpoint() (c2b_problem_rollback): two device-to-device copies; the row
+        structure, the solve buffers, the loss, the preconditioner and the masks stay.  Raises without a checkpoint."""
+        L.check(L.lib().c2b_problem_rollback(self._h))
+
+    def drop_checkpoint(self):
+        """Forget the checkpoint (c2b_problem_drop_checkpoint); rollback() raises until the next checkpoint()."""
+        L.check(L.lib().c2b_problem_drop_checkpoint(self._h))
+
     def _stats(self):
         s = np.empty(L.STATS_DOUBLES)
         L.check(L.lib().c2b_problem_stats(self._h, _ptr(s)))

@@ -17,6 +17,10 @@
 //                                              src/baproblem.rs:523, which discards most observations whenever the
 //                                              graph holds unseen points)
 //   city2ba ply IN OUT
+//   city2ba solve IN OUT [--iterations N --lambda X --pcg-iterations N --pcg-tol X --function-tol X --gradient-tol X
+//                         --parameter-tol X --loss squared|huber|cauchy|soft-l1 --loss-scale X
+//                         --preconditioner block-jacobi|schur-jacobi --fix-intrinsics --fix-first-camera]
+//                        (extension: Levenberg-Marquardt on the device, c2b_problem_levenberg_marquardt)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -780,6 +784,72 @@ int run_ply(int argc, char **argv) {
     return 0;
 }
 
+// `solve`: bundle adjustment of a .bal / .bbal by c2b_problem_levenberg_marquardt (an extension: the reference only makes
+// problems).  The file is decoded into the resident problem, solved there and its image assembled there.  Every argument
+// is parsed before the device is touched.
+int run_solve(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera"},
+                         {"iterations", "lambda", "pcg-iterations", "pcg-tol", "function-tol", "gradient-tol", "parameter-tol", "loss",
+                          "loss-scale", "preconditioner", "device"});
+    if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
+    c2b_lm_options opt;
+    opt.max_iterations = (int32_t)std::min<int64_t>(a.i("iterations", 10), 1 << 20);
+    opt.pcg_max_iters = (int32_t)std::min<int64_t>(a.i("pcg-iterations", 100), 1 << 20);
+    opt.lambda0 = a.f("lambda", 1e-4);
+    opt.pcg_rel_tol = a.f("pcg-tol", 1e-6);
+    opt.function_tol = a.f("function-tol", 0.0);
+    opt.gradient_tol = a.f("gradient-tol", 0.0);
+    opt.parameter_tol = a.f("parameter-tol", 0.0);
+    const double loss_scale = a.f("loss-scale", 1.0);
+    const int device = (int)a.i("device", 0);
+    int loss = 0, precond = C2B_PRECOND_BLOCK_JACOBI;
+    if (a.has("loss")) {
+        const std::string &v = a.opt.at("loss");
+        if (v == "squared") loss = 0;
+        else if (v == "huber") loss = 1;
+        else if (v == "cauchy") loss = 2;
+        else if (v == "soft-l1") loss = 3;
+        else die("Invalid value for '--loss <loss>': expected squared, huber, cauchy or soft-l1");
+    }
+    if (a.has("preconditioner")) {
+        const std::string &v = a.opt.at("preconditioner");
+        if (v == "block-jacobi") precond = C2B_PRECOND_BLOCK_JACOBI;
+        else if (v == "schur-jacobi") precond = C2B_PRECOND_SCHUR_JACOBI;
+        else die("Invalid value for '--preconditioner <preconditioner>': expected block-jacobi or schur-jacobi");
+    }
+    PhaseTimer timer;
+    c2b_problem *p = nullptr;
+    ck(create_problem(device, &p));
+    timer.mark("problem_create (HIP runtime start)");
+    ck(c2b_problem_read(p, a.positional[0].c_str(), -1));
+    timer.mark("read (c2b_problem_read: decoded on the device)");
+    int64_t nc = 0, np = 0, no = 0;
+    ck(c2b_problem_sizes(p, &nc, &np, &no));
+    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
+    ck(c2b_problem_set_loss(p, loss, loss_scale));
+    ck(c2b_problem_set_preconditioner(p, precond));
+    if (a.has("fix-intrinsics") || a.has("fix-first-camera")) {
+        std::vector<c2b_camera_mask> cm((size_t)nc + 1, (c2b_camera_mask)(a.has("fix-intrinsics") ? C2B_CONST_INTRINSICS : 0));
+        if (a.has("fix-first-camera") && nc) cm[0] |= C2B_CONST_POSE;
+        ck(c2b_problem_set_constant(p, cm.data(), nullptr));
+    }
+    std::vector<c2b_lm_iteration> hist((size_t)opt.max_iterations + 1);
+    c2b_lm_summary sum;
+    ck(c2b_problem_levenberg_marquardt(p, &opt, hist.data(), (int)hist.size(), &sum));
+    timer.mark("levenberg_marquardt (device)");
+    for (int k = 0; k < sum.iterations; ++k) {
+        const c2b_lm_iteration &it = hist[(size_t)k];
+        std::printf("iteration %d: cost %.17g lambda %.6e %s pcg %d\n", k, it.cost, it.lambda, it.accepted ? "accepted" : "rejected", it.pcg_iterations);
+    }
+    static const char *const why[] = {"iteration limit reached", "function tolerance reached", "gradient tolerance reached",
+                                      "parameter tolerance reached", "cost or gradient not finite"};
+    std::printf("Termination: %s after %d iterations; cost %.17g -> %.17g\n", why[sum.termination], sum.iterations, sum.initial_cost, sum.final_cost);
+    ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
+    timer.mark("write (c2b_problem_write: the file image is built on the device)");
+    c2b_problem_destroy(p);
+    return 0;
+}
+
 void usage() {
     std::printf("city2ba (MI355X build, %s)\nTools for generating synthetic bundle adjustment problems.\n\n"
                 "USAGE:\n    city2ba <SUBCOMMAND>\n\nSUBCOMMANDS:\n"
@@ -787,7 +857,8 @@ void usage() {
                 "    synthetic-line    Generate a synthetic bundle adjustment problem on a line.\n"
                 "    noise             Add noise to a bundle adjustment problem.\n"
                 "    generate          Generate a synthetic bundle adjustment problem from a 3D model.\n"
-                "    ply               Convert a .bal or .bbal to a .ply for visualization.\n",
+                "    ply               Convert a .bal or .bbal to a .ply for visualization.\n"
+                "    solve             Bundle-adjust a .bal or .bbal by Levenberg-Marquardt on the device.\n",
                 c2b_version());
 }
 
@@ -821,6 +892,15 @@ const char *subcommand_help(const std::string &sub) {
                "    --ground <X> [0]  --height <X> [1]     Poisson placement (without --path)\n"
                "    --move-to-origin   --no-lcc   --exact-lcc (extension)   --seed <N>\n";
     if (sub == "ply") return "city2ba ply <FILE> <OUT.ply>\n";
+    if (sub == "solve")
+        return "city2ba solve <FILE> <OUT>\n"
+               "    --iterations <N> [10]     --lambda <X> [1e-4]        Levenberg-Marquardt iterations, initial damping\n"
+               "    --pcg-iterations <N> [100]  --pcg-tol <X> [1e-6]     the step's conjugate gradients\n"
+               "    --function-tol <X> [0]  --gradient-tol <X> [0]  --parameter-tol <X> [0]   stopping tests (0: off)\n"
+               "    --loss <squared|huber|cauchy|soft-l1> [squared]   --loss-scale <X> [1]\n"
+               "    --preconditioner <block-jacobi|schur-jacobi> [block-jacobi]\n"
+               "    --fix-intrinsics          hold f, k1, k2 of every camera constant\n"
+               "    --fix-first-camera        hold the pose of camera 0 constant\n";
     return nullptr;
 }
 
@@ -843,5 +923,6 @@ int main(int argc, char **argv) {
     if (sub == "noise") return run_noise(argc, argv);
     if (sub == "generate") return run_generate(argc, argv);
     if (sub == "ply") return run_ply(argc, argv);
+    if (sub == "solve") return run_solve(argc, argv);
     die("The subcommand '" + sub + "' wasn't recognized");
 }

@@ -50,6 +50,12 @@ struct c2b_problem {
     // one allocation, sized by the list, dropped with it
     DevBuf<double> sv;
     int64_t sv_doubles = 0;
+    // c2b_problem_checkpoint: bal9 and pts4 as they were when it was taken, what c2b_problem_rollback copies
+    // back.  Allocated on first use and reused while the counts stay; ck_valid says whether they hold a checkpoint.
+    // lm: the scratch of c2b_problem_levenberg_marquardt (its step, the partials and scalars of k_lm_norms /
+    // k_lm_gradient_max), sized by the counts.  Both go with the entities (drop_lm_state).
+    DevBuf<double> ck_bal9, ck_pts4, lm;
+    bool ck_valid = false;
     DevBuf<uint32_t> dense_pt;      // survivors of the last dense visibility sweep
     DevBuf<double> dense_uv;
     DevBuf<uint64_t> dense_row;     // its CSR row pointer [n_cam + 1], kept for the occlusion filter
@@ -87,8 +93,15 @@ static void drop_constant(c2b_problem *p) {
     p->const_params = p->const_pts = 0;
 }
 
+// the entities were replaced, renumbered or their counts changed: no checkpoint describes them any more
+static void drop_lm_state(c2b_problem *p) {
+    p->ck_bal9.reset(); p->ck_pts4.reset(); p->lm.reset();
+    p->ck_valid = false;
+}
+
 // everything but the constant masks goes: "nothing uploaded"
 static void free_buffers(c2b_problem *p) {
+    drop_lm_state(p);
     p->cam15.reset(); p->bal9.reset(); p->camblk.reset(); p->cen4.reset(); p->pts4.reset(); p->uv.reset();
     p->cam_idx.reset(); p->pt_idx.reset();
     p->ws.reset(); p->stats.reset(); p->scalar.reset(); p->jac_ring.reset();
@@ -992,6 +1005,197 @@ int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
     C2B_API_END("problem_apply_step")
 }
 
+// ---- Levenberg-Marquardt on the device -----------------------------------------------------------------
+int c2b_problem_checkpoint(c2b_problem *p) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_checkpoint");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_checkpoint: a shard cannot be solved alone, so it takes no checkpoint");
+    p->ck_valid = false;
+    const int rc = c2b_problem_apply_step(p, nullptr, nullptr);          // bal mode: bal9 and pts4 are then the whole state
+    if (rc) return rc;
+    if (!p->ck_bal9 || !p->ck_pts4) {
+        hipError_t e = p->ck_bal9.alloc(9 * (size_t)p->n_cam);
+        if (e == hipSuccess) e = p->ck_pts4.alloc(4 * (size_t)p->n_pts);
+        if (e != hipSuccess) { drop_lm_state(p); return fail(hip_code(e), "problem_checkpoint: allocation: %s", hipGetErrorString(e)); }
+    }
+    if (p->n_cam) HIP_TRY(hipMemcpyAsync(p->ck_bal9, p->bal9, sizeof(double) * 9 * (size_t)p->n_cam, hipMemcpyDeviceToDevice, p->stream));
+    if (p->n_pts) HIP_TRY(hipMemcpyAsync(p->ck_pts4, p->pts4, sizeof(double) * 4 * (size_t)p->n_pts, hipMemcpyDeviceToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->ck_valid = true;
+    return C2B_OK;
+    C2B_API_END("problem_checkpoint")
+}
+
+int c2b_problem_rollback(c2b_problem *p) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_rollback");
+    if (!p->ck_valid) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_rollback: the problem holds no checkpoint");
+    hipStream_t st = p->stream;
+    if (p->n_cam) {
+        HIP_TRY(hipMemcpyAsync(p->bal9, p->ck_bal9, sizeof(double) * 9 * (size_t)p->n_cam, hipMemcpyDeviceToDevice, st));
+        const int rc = c2b_cameras_from_bal(p->bal9, p->n_cam, p->cam15, st);      // the kernel that built cam15: the same bits
+        if (rc) return rc;
+    }
+    if (p->n_pts) HIP_TRY(hipMemcpyAsync(p->pts4, p->ck_pts4, sizeof(double) * 4 * (size_t)p->n_pts, hipMemcpyDeviceToDevice, st));
+    cameras_mutated(p);                                      // the cameras' caches only: rows, transpose, solve buffers, masks stay
+    p->bal_valid = true;
+    HIP_TRY(hipStreamSynchronize(st));
+    return C2B_OK;
+    C2B_API_END("problem_rollback")
+}
+
+int c2b_problem_drop_checkpoint(c2b_problem *p) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_drop_checkpoint: problem is NULL");
+    p->ck_valid = false;                                     // (the buffers stay for the next checkpoint of these counts)
+    return C2B_OK;
+    C2B_API_END("problem_drop_checkpoint")
+}
+
+// c2b_problem::lm, carved: dc [n_cam][9], dp [n_pts][3], the partials of k_lm_norms (kLmSums x grid; k_lm_gradient_max
+// uses the first 2 x grid of them after those were summed), the device scalars: the four sums, then the two maxima
+struct LmBufs {
+    double *dc, *dp, *part, *sc;
+    unsigned grid;
+};
+enum { kLmScGradCam = kLmSums, kLmScGradPts = kLmSums + 1, kLmScSlots = 8 };
+
+static LmBufs lm_bufs(c2b_problem *p) {
+    LmBufs b;
+    b.grid = lm_grid(std::max<int64_t>(9 * p->n_cam, 3 * p->n_pts));
+    b.dc = p->lm;
+    b.dp = b.dc + 9 * p->n_cam;
+    b.part = b.dp + 3 * p->n_pts;
+    b.sc = b.part + (int64_t)kLmSums * b.grid;
+    return b;
+}
+
+static int ensure_lm(c2b_problem *p) {
+    if (p->lm) return C2B_OK;                                // (dropped whenever a count changes)
+    const int64_t n = 9 * p->n_cam + 3 * p->n_pts + (int64_t)kLmSums * lm_grid(std::max<int64_t>(9 * p->n_cam, 3 * p->n_pts)) + kLmScSlots;
+    const hipError_t e = p->lm.alloc((size_t)n);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_levenberg_marquardt: allocation: %s", hipGetErrorString(e));
+    return C2B_OK;
+}
+
+// x^y by libm's pow, as CPython's ** evaluates it: the exponent is kept from the compiler, which would otherwise turn a
+// constant 2 or 3 into multiplications (the last bit can differ)
+static double libm_pow(double x, double y) {
+    volatile double e = y;
+    return std::pow(x, e);
+}
+
+// the cost the loop compares: sum rho(|r|^2) under a loss, else the square of the root total_reprojection_error returns
+// (the numbers of city2ba_amd/solve.py's loop)
+static int lm_cost(c2b_problem *p, double *cost) {
+    if (p->loss_kind != kLossSquared) return c2b_problem_robust_cost(p, cost);
+    double e = 0.0;
+    const int rc = c2b_problem_total_reprojection_error(p, 2.0, &e);
+    if (rc) return rc;
+    *cost = libm_pow(e, 2.0);
+    return C2B_OK;
+}
+
+static int lm_loop(c2b_problem *p, const c2b_lm_options &o, c2b_lm_iteration *history, c2b_lm_summary *summary) {
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    hipStream_t st = p->stream;
+    auto clamp = [](double l) { return std::min(std::max(l, C2B_STEP_LAMBDA_MIN), C2B_STEP_LAMBDA_MAX); };
+    int rc = ensure_lm(p);
+    if (!rc) rc = c2b_problem_checkpoint(p);                 // bal mode; the state every rejected step returns to
+    if (rc) return rc;
+    const LmBufs L = lm_bufs(p);
+    double lam = clamp(o.lambda0), nu = 2.0, e0 = 0.0;
+    if ((rc = lm_cost(p, &e0))) return rc;
+    c2b_lm_summary sum{0, 0, e0, e0, lam};
+    if (!std::isfinite(e0)) sum.termination = 4;
+    while (!sum.termination && sum.iterations < o.max_iterations) {
+        c2b_step_info info;
+        if ((rc = c2b_problem_solve_step(p, lam, o.pcg_max_iters, o.pcg_rel_tol, L.dc, L.dp, &info))) return rc;
+        // the gradient the solve kept (no observation: it has none and g = 0) and the norms of its step and of the state
+        const bool have_g = p->n_obs > 0;
+        hipLaunchKernelGGL(k_lm_norms, dim3(L.grid), dim3(kSchurBlock), 0, st, 9 * nc, np, (const double *)p->bal9,
+                           reinterpret_cast<const double4 *>(p->pts4.ptr), (const double *)L.dc, (const double *)L.dp, L.part);
+        for (int k = 0; k < kLmSums; ++k)
+            hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)(L.part + (int64_t)k * L.grid), (int)L.grid, L.sc + k);
+        if (have_g) {
+            const SolveBufs B = solve_bufs(p);
+            hipLaunchKernelGGL(k_lm_gradient_max, dim3(L.grid), dim3(kSchurBlock), 0, st, 9 * nc, 3 * np, (const double *)B.gc,
+                               (const double *)B.gp, L.part);
+            hipLaunchKernelGGL(k_lm_max_fold, dim3(1), dim3(kSchurBlock), 0, st, (const double *)L.part, (int)L.grid, L.sc + kLmScGradCam);
+        }
+        HIP_TRY(launch_error());
+        double h[kLmScSlots] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        HIP_TRY(hipMemcpyAsync(h, L.sc, sizeof(double) * (have_g ? kLmScGradPts + 1 : kLmSums), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        c2b_lm_iteration it{};
+        it.cost = it.cost_trial = e0;
+        it.lambda = lam;
+        it.model_decrease = info.model_decrease;
+        it.gradient_max = (h[kLmScGradCam] > h[kLmScGradPts] || h[kLmScGradCam] != h[kLmScGradCam]) ? h[kLmScGradCam] : h[kLmScGradPts];
+        it.step_norm = std::sqrt(h[kLmStepCam] + h[kLmStepPts]);
+        it.x_norm = std::sqrt(h[kLmXCam] + h[kLmXPts]);
+        it.pcg_rel_residual = info.rel_residual;
+        it.pcg_iterations = info.iterations;
+        it.status = info.status;
+        c2b_lm_iteration *slot = history ? history + sum.iterations : nullptr;
+        ++sum.iterations;
+        if (!std::isfinite(it.gradient_max)) sum.termination = 4;                 // (the step was not applied: nothing to roll back)
+        else if (o.gradient_tol > 0.0 && it.gradient_max <= o.gradient_tol) sum.termination = 2;
+        else if (o.parameter_tol > 0.0 && it.step_norm <= o.parameter_tol * (it.x_norm + o.parameter_tol)) sum.termination = 3;
+        if (sum.termination) {
+            if (slot) *slot = it;
+            break;
+        }
+        if ((rc = c2b_problem_apply_step(p, L.dc, L.dp))) return rc;
+        double e1 = 0.0;
+        if ((rc = lm_cost(p, &e1))) return rc;
+        it.cost_trial = e1;
+        const double md = info.model_decrease;
+        const double rho = md > 0.0 ? (e0 - e1) / md : -1.0;
+        it.accepted = rho > 0.0 && e1 < e0;
+        if (slot) *slot = it;
+        if (it.accepted) {
+            lam = clamp(lam * std::max(1.0 / 3.0, 1.0 - libm_pow(2.0 * rho - 1.0, 3.0)));
+            nu = 2.0;
+            if ((rc = c2b_problem_checkpoint(p))) return rc;
+            if (o.function_tol > 0.0 && e0 - e1 <= o.function_tol * e0) sum.termination = 1;
+            e0 = e1;
+        } else {
+            if ((rc = c2b_problem_rollback(p))) return rc;
+            lam = clamp(lam * nu);
+            nu *= 2.0;
+            if (!std::isfinite(e1)) sum.termination = 4;
+        }
+    }
+    sum.final_cost = e0;
+    sum.lambda_next = lam;
+    if (summary) *summary = sum;
+    return C2B_OK;
+}
+
+int c2b_problem_levenberg_marquardt(c2b_problem *p, const c2b_lm_options *opt, c2b_lm_iteration *history, int capacity,
+                                    c2b_lm_summary *summary) {
+    C2B_API_BEGIN
+    if (!p || !opt) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: NULL argument");
+    if (opt->max_iterations < 0 || opt->pcg_max_iters < 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: max_iterations and pcg_max_iters must be >= 0");
+    if (!good_lambda(opt->lambda0)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: lambda0 must lie in [1e-20, 1e32]");
+    for (const double t : {opt->pcg_rel_tol, opt->function_tol, opt->gradient_tol, opt->parameter_tol})
+        if (!(t >= 0.0) || !std::isfinite(t))
+            return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: tolerances must be finite and >= 0");
+    if (history && capacity < opt->max_iterations)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: history holds %d entries, max_iterations is %d", capacity,
+                    (int)opt->max_iterations);
+    NEED_UPLOADED(p, "problem_levenberg_marquardt");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: a shard cannot be solved alone (the point-side sums span every rank)");
+    const int rc = lm_loop(p, *opt, history, summary);
+    p->ck_valid = false;                                     // the checkpoint was the loop's
+    return rc;
+    C2B_API_END("problem_levenberg_marquardt")
+}
+
 // Results leave in chunks of kJacChunk observations through a ring of kJacSlots device buffers: the kernel of chunk
 // k + 1 is queued before the copies of chunk k start, copies run on their own stream, so PCIe and the kernel overlap
 // and the device never holds more than the ring (159 MB) whatever the problem size.  Host buffers from
@@ -1320,6 +1524,7 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
     p->cam_idx = std::move(cam[cur]); p->pt_idx = std::move(pt[cur]); p->ws = std::move(n_ws);
     drop_rows(p);
     drop_constant(p);                                         // the survivors are renumbered
+    drop_lm_state(p);
     p->n_cam = nc; p->n_pts = np; p->n_obs = no;
     p->blk_valid = false;                                     // camblk is rebuilt on demand from the gathered cameras
     p->bal9_fresh = false;                                    // (bal9 was gathered only when it was the truth)
@@ -1799,6 +2004,7 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
     free_dense(p);
     drop_rows(p);
     drop_constant(p);
+    drop_lm_state(p);
     p->pts4 = std::move(out);
     p->n_pts = accepted;
     *n_out = accepted;

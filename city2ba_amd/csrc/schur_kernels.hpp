@@ -15,6 +15,8 @@
 //   * k_const_cameras / k_const_points / k_const_blocks / k_const_point_blocks: constant parameters, the
 //     projection onto the free ones applied around the passes above; k_add_free / k_points_add_free: the step added to
 //     the free entries alone.  None is launched while no mask is set.
+//   * k_lm_norms / k_lm_gradient_max / k_lm_max_fold: the step's and the state's squared norms and the gradient's largest
+//     magnitude, what the stopping tests of c2b_problem_levenberg_marquardt read.
 // Damping (Marquardt with Ceres' clamps): A_l = A + lambda diag(d), d_i = min(max(A_ii, 1e-6), 1e32).
 // Every partial is summed by k_normal_sum in a fixed order; no float atomics, so the same inputs give the same bits.
 // Robust losses: the passes over the observations scale (r, Jc, Jp) by sqrt(w) right after jacobian_obs.  Each is one
@@ -532,6 +534,103 @@ __global__ __launch_bounds__(kSchurBlock) void k_points_add_free(int64_t n_pts, 
     double4 X = pts4[p];
     X.x += dp[3 * p]; X.y += dp[3 * p + 1]; X.z += dp[3 * p + 2];
     pts4[p] = X;
+}
+
+// ---- what the Levenberg-Marquardt loop's stopping tests read ---------------------------------------------
+// Both kernels run on lm_grid(n) workgroups, n the longer of their two index ranges: one lane per entry up to kLmGridCap
+// workgroups, a grid-stride walk beyond.  A lane's entries and the order it adds them in depend on the counts alone, so
+// the same problem gives the same bits.  Lanes past an array's end (the tail wave; every lane of an empty array) carry the
+// identity, 0: an empty problem writes partials of 0 and never reads.
+constexpr int kLmGridCap = 2048;                  // 8 workgroups of 256 on each of the 256 CUs
+enum { kLmStepCam = 0, kLmStepPts = 1, kLmXCam = 2, kLmXPts = 3, kLmSums = 4 };
+
+inline unsigned lm_grid(int64_t n) {
+    const int64_t g = (n + kSchurBlock - 1) / kSchurBlock;
+    return (unsigned)(g < 1 ? 1 : (g > kLmGridCap ? kLmGridCap : g));
+}
+
+// |dc|^2, |dp|^2, |bal9|^2, |points|^2 in one pass: partial k of workgroup b at part[k * gridDim.x + b] (k in the enum's
+// order), each then summed by k_normal_sum.  A point's fourth lane is padding and is never added.  A constant entry's step
+// is already exactly 0 (c2b_problem_solve_step), so no mask is read.
+__global__ __launch_bounds__(kSchurBlock) void k_lm_norms(int64_t n_cam9, int64_t n_pts, const double *__restrict__ bal9,
+                                                          const double4 *__restrict__ pts4, const double *__restrict__ dc,
+                                                          const double *__restrict__ dp, double *__restrict__ part) {
+    __shared__ double sRed[kLmSums][4];
+    const int64_t stride = (int64_t)gridDim.x * kSchurBlock, n = n_cam9 > n_pts ? n_cam9 : n_pts;
+    double s[kLmSums] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x; i < n; i += stride) {
+        if (i < n_cam9) {
+            const double d = dc[i], x = bal9[i];
+            s[kLmStepCam] += d * d;
+            s[kLmXCam] += x * x;
+        }
+        if (i < n_pts) {
+            const double4 X = pts4[i];
+            const double d0 = dp[3 * i], d1 = dp[3 * i + 1], d2 = dp[3 * i + 2];
+            s[kLmStepPts] += (d0 * d0 + d1 * d1) + d2 * d2;
+            s[kLmXPts] += (X.x * X.x + X.y * X.y) + X.z * X.z;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kLmSums; ++k) {
+        const double w = wave_sum(s[k]);
+        if ((threadIdx.x & 63) == 0) sRed[k][threadIdx.x >> 6] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < kLmSums) {
+        const double *r = sRed[threadIdx.x];
+        part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = ((r[0] + r[1]) + r[2]) + r[3];
+    }
+}
+
+// the larger of two magnitudes, a NaN on either side kept (fmax would drop it): once m is a NaN no comparison replaces it
+C2B_DEV double max_keep_nan(double m, double v) { return (v > m || v != v) ? v : m; }
+
+C2B_DEV double wave_max_keep_nan(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max_keep_nan(v, __shfl_down(v, off, 64));
+    return v;
+}
+
+// max |gc_i| over n_gc entries and max |gp_i| over n_gp: workgroup b's pair at part[b] and part[gridDim.x + b].  A max does
+// not depend on the order, so the result is exact; a NaN anywhere reaches the result.
+__global__ __launch_bounds__(kSchurBlock) void k_lm_gradient_max(int64_t n_gc, int64_t n_gp, const double *__restrict__ gc,
+                                                                 const double *__restrict__ gp, double *__restrict__ part) {
+    __shared__ double sRed[2][4];
+    const int64_t stride = (int64_t)gridDim.x * kSchurBlock, n = n_gc > n_gp ? n_gc : n_gp;
+    double mc = 0.0, mp = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kSchurBlock + threadIdx.x; i < n; i += stride) {
+        if (i < n_gc) mc = max_keep_nan(mc, fabs(gc[i]));
+        if (i < n_gp) mp = max_keep_nan(mp, fabs(gp[i]));
+    }
+    mc = wave_max_keep_nan(mc);
+    mp = wave_max_keep_nan(mp);
+    if ((threadIdx.x & 63) == 0) { sRed[0][threadIdx.x >> 6] = mc; sRed[1][threadIdx.x >> 6] = mp; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const double *r = sRed[threadIdx.x];
+        part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = max_keep_nan(max_keep_nan(r[0], r[1]), max_keep_nan(r[2], r[3]));
+    }
+}
+
+// the two maxima of k_lm_gradient_max's partials (n per kind) into out[0], out[1]: one workgroup
+__global__ __launch_bounds__(kSchurBlock) void k_lm_max_fold(const double *__restrict__ part, int n, double *__restrict__ out) {
+    __shared__ double sRed[2][4];
+    double m[2] = {0.0, 0.0};
+    for (int k = threadIdx.x; k < n; k += kSchurBlock) {
+        m[0] = max_keep_nan(m[0], part[k]);
+        m[1] = max_keep_nan(m[1], part[n + k]);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const double w = wave_max_keep_nan(m[j]);
+        if ((threadIdx.x & 63) == 0) sRed[j][threadIdx.x >> 6] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const double *r = sRed[threadIdx.x];
+        out[threadIdx.x] = max_keep_nan(max_keep_nan(r[0], r[1]), max_keep_nan(r[2], r[3]));
+    }
 }
 
 }  // namespace c2b

@@ -66,3 +66,44 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     if history:
         history[-1]["error_after"] = e0
     return history
+
+
+def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, function_tol=0.0, gradient_tol=0.0,
+                               parameter_tol=0.0, loss=None, loss_scale=1.0, preconditioner=None, constant=None):
+    """levenberg_marquardt's loop inside the library (c2b_problem_levenberg_marquardt): the same steps, the same damping
+    and the same numbers, with a device-side checkpoint and rollback where the loop above downloads and uploads, and with
+    stopping tests.  Returns (history, summary).
+    history: one dict per iteration with levenberg_marquardt's keys (error, cost, lam, accepted, pcg_iterations, status;
+    'error_after' in the last entry) plus cost_trial (the cost with the step applied; the cost itself when the step was
+    not applied), model_decrease, gradient_max = max(|gc|, |gp|) at the state the step was solved at, step_norm =
+    |(dc, dp)|, x_norm = |(cameras_bal, points)| and pcg_rel_residual.
+    summary: dict(iterations, termination, reason, initial_cost, final_cost, lam_next); termination 0 = `iterations`
+    reached, 1 = function tolerance (cost - cost_trial <= function_tol cost after an accepted step, which is kept), 2 =
+    gradient tolerance (gradient_max <= gradient_tol; the step is not applied), 3 = parameter tolerance (step_norm <=
+    parameter_tol (x_norm + parameter_tol); the step is not applied), 4 = the cost or the gradient is not finite (the state
+    is the last accepted one).  A tolerance of 0 disables its test: with all three at 0 this is levenberg_marquardt,
+    iteration for iteration.  loss, preconditioner and constant as there."""
+    import ctypes as C
+
+    from . import _lib as L
+    if constant is not None:
+        ba.set_constant(*constant)
+    if preconditioner is not None:
+        ba.set_preconditioner(preconditioner)
+    if loss is not None:
+        ba.set_loss(loss, loss_scale)
+    n = int(iterations)
+    opt = L.LmOptions(n, int(max_iters), float(lam), float(rel_tol), float(function_tol), float(gradient_tol), float(parameter_tol))
+    entries = (L.LmIteration * max(n, 1))()
+    s = L.LmSummary()
+    L.check(L.lib().c2b_problem_levenberg_marquardt(ba._h, C.byref(opt), entries, n, C.byref(s)))
+    history = []
+    for e in entries[:s.iterations]:
+        d = dict(error=e.cost, cost=e.cost, lam=e.lam, accepted=bool(e.accepted), pcg_iterations=e.pcg_iterations, status=e.status)
+        d.update({k: getattr(e, k) for k in ("cost_trial", "model_decrease", "gradient_max", "step_norm", "x_norm", "pcg_rel_residual")})
+        history.append(d)
+    if history:
+        history[-1]["error_after"] = s.final_cost
+    summary = dict(iterations=s.iterations, termination=s.termination, reason=L.LM_TERMINATIONS[s.termination],
+                   initial_cost=s.initial_cost, final_cost=s.final_cost, lam_next=s.lambda_next)
+    return history, summary

@@ -209,6 +209,54 @@ int c2b_problem_set_constant(c2b_problem *p, const c2b_camera_mask *cam_mask, co
 int c2b_problem_get_constant(const c2b_problem *p, c2b_camera_mask *cam_mask, uint8_t *pt_mask, int64_t *n_const_cam_params,
                              int64_t *n_const_pts);
 
+/* ---- the Levenberg-Marquardt loop on the device: checkpoint, stopping tests ----
+ * _checkpoint: takes the problem to bal mode exactly as c2b_problem_apply_step(p, NULL, NULL) does and copies bal9 and the
+ *   points into two device buffers the problem owns (allocated on first use, reused while the counts stay).  Device to
+ *   device on the problem's stream; no host memory is touched.
+ * _rollback: copies them back, rebuilds the in-memory cameras from bal9 by the kernel that built them (the same bits) and
+ *   drops the cameras' derived tables.  The row structure, the transpose, the tile records, the solve buffers' allocation,
+ *   the loss, the preconditioner and the masks stay.  Without a checkpoint: C2B_ERR_INVALID_ARGUMENT.
+ * Lifetime: the checkpoint survives c2b_problem_apply_step and the noise functions.  It is dropped by whatever drops the
+ *   constant masks (a cull, a read, a generator, an upload of another size), by ANY upload, and by _drop_checkpoint.
+ *   A problem with a shard set is refused, as in c2b_problem_solve_step.
+ * _levenberg_marquardt: up to max_iterations iterations on the problem in place.  An iteration solves the damped step
+ *   (c2b_problem_solve_step with pcg_max_iters, pcg_rel_tol) into scratch the problem keeps, applies it and keeps it when
+ *   the cost falls.  Cost: c2b_problem_robust_cost under a loss, else the square of c2b_problem_total_reprojection_error
+ *   (p, 2.0).  Gain ratio rho = (cost - cost_trial) / model_decrease when model_decrease > 0, else -1; accepted when
+ *   rho > 0 and cost_trial < cost: lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2; rejected: the state is rolled back,
+ *   lambda *= nu, nu *= 2 (nu starts at 2); lambda is held in [C2B_STEP_LAMBDA_MIN, C2B_STEP_LAMBDA_MAX] throughout.
+ *   Per iteration, in this order: solve; gradient_max = max(|gc|, |gp|) over the gradient the solve formed (exact; a NaN
+ *   propagates), step_norm = |(dc, dp)|, x_norm = |(bal9, points)| (sums in a fixed order, no float atomics), and the
+ *   iteration's entry is recorded; the gradient test; the parameter test; apply, cost, accept or roll back; after an
+ *   accepted step the function test.  termination:
+ *     0  max_iterations reached
+ *     1  function: cost - cost_trial <= function_tol cost, after an accepted step (which is kept)
+ *     2  gradient: gradient_max <= gradient_tol at the state the step was solved at (the step is not applied)
+ *     3  parameter: step_norm <= parameter_tol (x_norm + parameter_tol) (the step is not applied)
+ *     4  the cost or the gradient is not finite; the state is the last accepted one
+ *   A tolerance of 0 disables its test.  An entry's cost_trial repeats cost when its step was not applied.  history (may
+ *   be NULL) takes one entry per iteration and needs capacity >= max_iterations; summary may be NULL.  Negative or
+ *   non-finite tolerances, max_iterations or pcg_max_iters < 0, lambda0 outside the damping range, capacity too small:
+ *   C2B_ERR_INVALID_ARGUMENT.  The loss, the preconditioner and the masks are the handle's and are honoured as
+ *   c2b_problem_solve_step honours them.  The checkpoint is the loop's: none is left on return.  Deterministic. */
+typedef struct {
+    int32_t max_iterations, pcg_max_iters;
+    double lambda0, pcg_rel_tol, function_tol, gradient_tol, parameter_tol;
+} c2b_lm_options;
+typedef struct {
+    double cost, cost_trial, lambda, model_decrease, gradient_max, step_norm, x_norm, pcg_rel_residual;
+    int32_t accepted, pcg_iterations, status, reserved;
+} c2b_lm_iteration;
+typedef struct {
+    int32_t iterations, termination;
+    double initial_cost, final_cost, lambda_next;
+} c2b_lm_summary;
+int c2b_problem_checkpoint(c2b_problem *p);
+int c2b_problem_rollback(c2b_problem *p);
+int c2b_problem_drop_checkpoint(c2b_problem *p);
+int c2b_problem_levenberg_marquardt(c2b_problem *p, const c2b_lm_options *opt, c2b_lm_iteration *history, int capacity,
+                                    c2b_lm_summary *summary);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
