@@ -87,6 +87,10 @@ class LmSummary(C.Structure):
 LM_TERMINATIONS = {0: "max_iterations", 1: "function_tolerance", 2: "gradient_tolerance", 3: "parameter_tolerance", 4: "not_finite"}
 
 
+# flags of c2b_problem_filter_observations / c2b_residual_keep_rows
+FILTER_IN_FRONT = 1        # C2B_FILTER_IN_FRONT: also drop an observation whose point is not in front of its camera
+
+
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
 SIGNATURES = {
     "c2b_version": (C.c_char_p, []),
@@ -116,6 +120,7 @@ SIGNATURES = {
     "c2b_reprojection_error_sum_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_visibility_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_visibility_rows_bits": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
+    "c2b_residual_keep_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _d, _int, _vp, _vp]),
     "c2b_reprojection_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "c2b_add_noise_observations_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _d, _u64, _vp, _vp, _vp]),
     "c2b_jacobian_stream_policy": (_int, [_i64, _i64, _i64]),
@@ -148,6 +153,7 @@ SIGNATURES = {
     "c2b_problem_rollback": (_int, [_vp]),
     "c2b_problem_drop_checkpoint": (_int, [_vp]),
     "c2b_problem_levenberg_marquardt": (_int, [_vp, _vp, _vp, _int, _vp]),
+    "c2b_problem_filter_observations": (_int, [_vp, _d, _int, C.POINTER(_i64)]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
     "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),

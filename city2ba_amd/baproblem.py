@@ -513,6 +513,19 @@ class BAProblem:
         L.check(L.lib().c2b_problem_remove_singletons(self._h))
         return self._refresh_graph()
 
+    def filter_observations(self, max_error, in_front=False):
+        """Outlier rejection in place, on the device (c2b_problem_filter_observations): every observation whose
+        reprojection residual has |r|^2 > max_error^2, or is NaN, is dropped (max_error = inf drops the NaN ones alone), and with in_front=True
+        every one whose point is not in front of its camera too.  The survivors keep their order inside every camera's
+        list; cameras and points are not renumbered, so the constant masks, the loss, the preconditioner and a checkpoint
+        stay.  Returns the number removed (0: nothing changed).  A filter can leave a camera or a point with too few
+        observations: cull() is the caller's call."""
+        n = C.c_int64()
+        L.check(L.lib().c2b_problem_filter_observations(self._h, float(max_error), L.FILTER_IN_FRONT if in_front else 0, C.byref(n)))
+        if n.value:
+            self._refresh_graph()
+        return n.value
+
     def subset(self, ci, pi):
         """BAProblem::subset (src/baproblem.rs:394-423): cameras ci and points pi in the given order; observations of
         dropped points disappear.  Host-side index shuffling; returns a NEW device problem."""

@@ -19,8 +19,10 @@
 //   city2ba ply IN OUT
 //   city2ba solve IN OUT [--iterations N --lambda X --pcg-iterations N --pcg-tol X --function-tol X --gradient-tol X
 //                         --parameter-tol X --loss squared|huber|cauchy|soft-l1 --loss-scale X
-//                         --preconditioner block-jacobi|schur-jacobi --fix-intrinsics --fix-first-camera]
-//                        (extension: Levenberg-Marquardt on the device, c2b_problem_levenberg_marquardt)
+//                         --preconditioner block-jacobi|schur-jacobi --fix-intrinsics --fix-first-camera
+//                         --filter-max-error X --filter-rounds N --filter-in-front]
+//                        (extension: Levenberg-Marquardt on the device, c2b_problem_levenberg_marquardt; with
+//                         --filter-max-error: N times solve + c2b_problem_filter_observations, then a solve without a loss)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -786,11 +788,13 @@ int run_ply(int argc, char **argv) {
 
 // `solve`: bundle adjustment of a .bal / .bbal by c2b_problem_levenberg_marquardt (an extension: the reference only makes
 // problems).  The file is decoded into the resident problem, solved there and its image assembled there.  Every argument
-// is parsed before the device is touched.
+// is parsed before the device is touched.  --filter-max-error X: --filter-rounds times (solve, then drop the observations
+// whose residual exceeds X -- with --filter-in-front also those behind their camera), then one more solve with the loss
+// cleared; cameras and points keep their numbers, nothing is culled.
 int run_solve(int argc, char **argv) {
-    const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera"},
+    const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera", "filter-in-front"},
                          {"iterations", "lambda", "pcg-iterations", "pcg-tol", "function-tol", "gradient-tol", "parameter-tol", "loss",
-                          "loss-scale", "preconditioner", "device"});
+                          "loss-scale", "preconditioner", "device", "filter-max-error", "filter-rounds"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
     c2b_lm_options opt;
     opt.max_iterations = (int32_t)std::min<int64_t>(a.i("iterations", 10), 1 << 20);
@@ -802,6 +806,13 @@ int run_solve(int argc, char **argv) {
     opt.parameter_tol = a.f("parameter-tol", 0.0);
     const double loss_scale = a.f("loss-scale", 1.0);
     const int device = (int)a.i("device", 0);
+    const bool filter = a.has("filter-max-error");
+    const double filter_max_error = a.f("filter-max-error", 0.0);
+    const int64_t filter_rounds = a.i("filter-rounds", 1);
+    const int filter_flags = a.has("filter-in-front") ? C2B_FILTER_IN_FRONT : 0;
+    if (filter && !(filter_max_error >= 0.0)) die("Invalid value for '--filter-max-error <X>': expected a number >= 0");
+    if (filter_rounds > 1000) die("Invalid value for '--filter-rounds <N>': expected 0 ... 1000");
+    if (!filter && (a.has("filter-rounds") || a.has("filter-in-front"))) die("--filter-rounds and --filter-in-front need --filter-max-error <X>");
     int loss = 0, precond = C2B_PRECOND_BLOCK_JACOBI;
     if (a.has("loss")) {
         const std::string &v = a.opt.at("loss");
@@ -834,16 +845,30 @@ int run_solve(int argc, char **argv) {
         ck(c2b_problem_set_constant(p, cm.data(), nullptr));
     }
     std::vector<c2b_lm_iteration> hist((size_t)opt.max_iterations + 1);
-    c2b_lm_summary sum;
-    ck(c2b_problem_levenberg_marquardt(p, &opt, hist.data(), (int)hist.size(), &sum));
-    timer.mark("levenberg_marquardt (device)");
-    for (int k = 0; k < sum.iterations; ++k) {
-        const c2b_lm_iteration &it = hist[(size_t)k];
-        std::printf("iteration %d: cost %.17g lambda %.6e %s pcg %d\n", k, it.cost, it.lambda, it.accepted ? "accepted" : "rejected", it.pcg_iterations);
-    }
     static const char *const why[] = {"iteration limit reached", "function tolerance reached", "gradient tolerance reached",
                                       "parameter tolerance reached", "cost or gradient not finite"};
-    std::printf("Termination: %s after %d iterations; cost %.17g -> %.17g\n", why[sum.termination], sum.iterations, sum.initial_cost, sum.final_cost);
+    auto solve_once = [&]() {
+        c2b_lm_summary sum;
+        ck(c2b_problem_levenberg_marquardt(p, &opt, hist.data(), (int)hist.size(), &sum));
+        timer.mark("levenberg_marquardt (device)");
+        for (int k = 0; k < sum.iterations; ++k) {
+            const c2b_lm_iteration &it = hist[(size_t)k];
+            std::printf("iteration %d: cost %.17g lambda %.6e %s pcg %d\n", k, it.cost, it.lambda, it.accepted ? "accepted" : "rejected", it.pcg_iterations);
+        }
+        std::printf("Termination: %s after %d iterations; cost %.17g -> %.17g\n", why[sum.termination], sum.iterations, sum.initial_cost, sum.final_cost);
+    };
+    if (filter) {
+        for (int64_t round = 0; round < filter_rounds; ++round) {
+            solve_once();
+            int64_t removed = 0;
+            ck(c2b_problem_filter_observations(p, filter_max_error, filter_flags, &removed));
+            ck(c2b_problem_sizes(p, &nc, &np, &no));
+            timer.mark("filter_observations (device)");
+            std::printf("filter round %lld: removed %lld observations, %lld left\n", (long long)round, (long long)removed, (long long)no);
+        }
+        ck(c2b_problem_set_loss(p, 0, 1.0));
+    }
+    solve_once();
     ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
     timer.mark("write (c2b_problem_write: the file image is built on the device)");
     c2b_problem_destroy(p);
@@ -900,7 +925,11 @@ const char *subcommand_help(const std::string &sub) {
                "    --loss <squared|huber|cauchy|soft-l1> [squared]   --loss-scale <X> [1]\n"
                "    --preconditioner <block-jacobi|schur-jacobi> [block-jacobi]\n"
                "    --fix-intrinsics          hold f, k1, k2 of every camera constant\n"
-               "    --fix-first-camera        hold the pose of camera 0 constant\n";
+               "    --fix-first-camera        hold the pose of camera 0 constant\n"
+               "    --filter-max-error <X>    outlier rejection: solve, drop the observations whose reprojection residual exceeds X,\n"
+               "                              then solve again without a loss [off]\n"
+               "    --filter-rounds <N> [1]   solve + filter rounds before the last solve\n"
+               "    --filter-in-front         also drop observations whose point is not in front of its camera\n";
     return nullptr;
 }
 

@@ -319,6 +319,29 @@ int c2b_visibility_rows_bits(const double *camblk, const double *pts4, const uin
     C2B_API_END("visibility_rows_bits")
 }
 
+// the outlier filter's predicate over a camera-major list: keep[o] = |projected - observed|^2 <= max_error^2, and with
+// C2B_FILTER_IN_FRONT also q.z < 0 (the point in front of its camera, the reference's sign).  max_error is squared here,
+// once, in double.
+int c2b_residual_keep_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const void *tiles,
+                           const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double max_error, int flags, uint8_t *keep,
+                           void *stream) {
+    C2B_API_BEGIN
+    int rc = check_obs_args("residual_keep_rows", camblk, pts4, tiles, pt_idx, n_obs);
+    if (!rc) rc = check_rows_args("residual_keep_rows", row_ptr, n_cam, tiles, n_obs);
+    if (rc) return rc;
+    if (!(max_error >= 0.0)) return fail(C2B_ERR_INVALID_ARGUMENT, "residual_keep_rows: max_error must be >= 0 (+inf keeps every finite residual)");
+    if (flags & ~C2B_FILTER_IN_FRONT) return fail(C2B_ERR_INVALID_ARGUMENT, "residual_keep_rows: unknown flag bits 0x%x", (unsigned)(flags & ~C2B_FILTER_IN_FRONT));
+    if (!n_obs) return C2B_OK;
+    if (!uv_obs || !keep || !aligned16(uv_obs)) return fail(C2B_ERR_INVALID_ARGUMENT, "residual_keep_rows: uv_obs / keep NULL or misaligned");
+    const double max_err2 = max_error * max_error;
+    rc = launch_obs<MODE_RESIDUAL_KEEP>(camblk, pts4, reinterpret_cast<const uint32_t *>(tiles), pt_idx, uv_obs, n_obs, max_err2, 0.0, nullptr,
+                                        keep, nullptr, nullptr, S(stream), row_ptr, n_cam, 0, (uint64_t)(flags & C2B_FILTER_IN_FRONT));
+    if (rc) return rc;
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("residual_keep_rows")
+}
+
 int c2b_residual_jacobian(const double *camblk, const double *pts4, const uint32_t *cam_idx,
                           const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *r, double *Jc,
                           double *Jp, double norm, void *workspace, void *stream) {

@@ -1633,9 +1633,10 @@ int c2b_problem_export_device(c2b_problem *p, int64_t cam_lo, int64_t cam_hi, do
 // Stable compaction of CSR lists (point index, uv) by a keep mask, on the device: kept count per row -> row scan ->
 // one wave per camera scatters in order.  The new row pointer goes to row_ptr_host; on success the three new lists are
 // in row_new / pt_new / uv_new, *w = kept count (on failure what they hold is not a result).  Synchronises the problem's stream.
+// stop_at: a kept count at which the caller wants no lists (the mask kept everything): pt_new / uv_new are then left empty.
 static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_old, const uint8_t *d_keep, const uint32_t *d_pt,
                                          const double *d_uv, int64_t n_cam, uint64_t *row_ptr_host, DevBuf<uint64_t> &row_new,
-                                         DevBuf<uint32_t> &pt_new, DevBuf<double> &uv_new, int64_t *w) {
+                                         DevBuf<uint32_t> &pt_new, DevBuf<double> &uv_new, int64_t *w, int64_t stop_at = -1) {
     DevBuf<uint64_t> d_tot;
     *w = 0;
     hipError_t e = d_tot.alloc((size_t)n_cam + 1);
@@ -1648,6 +1649,7 @@ static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_o
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     if (e != hipSuccess) return e;
     *w = (int64_t)row_ptr_host[n_cam];
+    if (*w == stop_at) return hipSuccess;
     e = pt_new.alloc((size_t)*w);
     if (e == hipSuccess) e = uv_new.alloc(2 * (size_t)*w);
     if (e == hipSuccess && n_cam) {
@@ -1657,6 +1659,53 @@ static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_o
     }
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     return e;
+}
+
+// The outlier filter: the residual predicate over the resident list, a stable compaction of (pt_idx, uv) by its
+// mask, cam_idx from the new row pointer, a workspace for the new count -- swapped in only once the stream has synchronised
+// without error, as cull_impl does.  The entities do not move: cameras, points, both counts, the masks, the loss, the
+// preconditioner, the checkpoint and the LM scratch stay; what was derived from the list (drop_rows) goes.
+int c2b_problem_filter_observations(c2b_problem *p, double max_error, int flags, int64_t *n_removed) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_filter_observations");
+    if (n_removed) *n_removed = 0;
+    if (!(max_error >= 0.0)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_filter_observations: max_error must be >= 0 (+inf keeps every finite residual)");
+    if (flags & ~C2B_FILTER_IN_FRONT)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_filter_observations: unknown flag bits 0x%x", (unsigned)(flags & ~C2B_FILTER_IN_FRONT));
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_filter_observations: a shard is not filtered alone (its list is a slice of the whole one)");
+    if (!p->n_obs) return C2B_OK;
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (rc) return rc;
+    const int64_t n_cam = p->n_cam, n_old = p->n_obs;
+    DevBuf<uint8_t> keep;
+    DevBuf<uint64_t> row_new;
+    DevBuf<uint32_t> pt_new, cam_new;
+    DevBuf<double> uv_new;
+    DevBuf<char> ws_new;
+    std::vector<uint64_t> row_host((size_t)n_cam + 1);
+    int64_t w = 0;
+    hipError_t e = keep.alloc((size_t)n_old);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_filter_observations: %s", hipGetErrorString(e));
+    rc = c2b_residual_keep_rows(p->camblk, p->pts4, p->rows_ptr, n_cam, p->rows_tiles, p->pt_idx, p->uv, n_old, max_error, flags, keep, p->stream);
+    if (!rc) e = compact_rows_on_device(p, p->rows_ptr, keep, p->pt_idx, p->uv, n_cam, row_host.data(), row_new, pt_new, uv_new, &w, n_old);
+    if (!rc && e == hipSuccess && w == n_old) return C2B_OK;       // nothing removed: nothing changes, no cache is dropped
+    if (!rc && e == hipSuccess) e = cam_new.alloc((size_t)w);
+    if (!rc && e == hipSuccess) e = ws_new.alloc((size_t)c2b_workspace_bytes(w));
+    if (!rc && e == hipSuccess) rc = c2b_expand_rows(row_new, n_cam, 0, w, cam_new, p->stream);
+    if (!rc && e == hipSuccess) rc = c2b_workspace_init(ws_new, p->stream);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (rc || e != hipSuccess) {
+        (void)hipStreamSynchronize(p->stream);
+        return rc ? rc : fail(hip_code(e), "problem_filter_observations: %s", hipGetErrorString(e));
+    }
+    p->uv = std::move(uv_new); p->pt_idx = std::move(pt_new); p->cam_idx = std::move(cam_new); p->ws = std::move(ws_new);
+    p->n_obs = w;
+    drop_rows(p);
+    if (n_removed) *n_removed = n_old - w;
+    return C2B_OK;
+    C2B_API_END("problem_filter_observations")
 }
 
 int c2b_problem_visibility_pairs_compact(c2b_problem *p, int64_t n_pairs, const uint32_t *cam_idx, const uint32_t *pt_idx,

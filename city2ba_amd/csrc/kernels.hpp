@@ -474,7 +474,11 @@ C2B_DEV void store16(char *dst, const double2 v) {
 // perturb and store uv -- fused with the two error sums of the perturbed observations that follow it in run_noise.
 // MODE_VISIBILITY_BITS: the predicate with the keep mask as ONE 64-bit ballot word per tile of 64 pairs (bit l = pair 64 t + l)
 // instead of a byte per pair -- 1 of the pass's 26 bytes per pair less, and what a compaction wants anyway
-enum { MODE_PROJECT = 0, MODE_ERROR = 1, MODE_VISIBILITY = 2, MODE_ERROR12 = 3, MODE_NOISE_ERROR12 = 4, MODE_VISIBILITY_BITS = 5 };
+// MODE_RESIDUAL_KEEP: the outlier filter's predicate -- MODE_PROJECT's head, the observed uv as the error modes load
+// it, and one keep byte per observation as MODE_VISIBILITY writes it: no uv_out, no sum, no fold.  `norm` carries max_error^2
+// (squared once on the host), bit 0 of `seed` the in-front test.
+enum { MODE_PROJECT = 0, MODE_ERROR = 1, MODE_VISIBILITY = 2, MODE_ERROR12 = 3, MODE_NOISE_ERROR12 = 4, MODE_VISIBILITY_BITS = 5,
+       MODE_RESIDUAL_KEEP = 6 };
 constexpr int kObsWPB = 8;                     // waves per workgroup
 constexpr int kCamLight = 16;
 
@@ -630,7 +634,7 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_observations(
             // the observed uv of THIS tile is requested only now: holding all OPL of them from the start costs 12
             // VGPRs and the eighth wave per SIMD (measured: 119 us held, 111 us requested per tile)
             double2 ob = make_double2(0.0, 0.0);
-            if (MODE == MODE_ERROR || MODE == MODE_ERROR12 || MODE == MODE_NOISE_ERROR12) {
+            if (MODE == MODE_ERROR || MODE == MODE_ERROR12 || MODE == MODE_NOISE_ERROR12 || MODE == MODE_RESIDUAL_KEEP) {
                 const double2 *src = (MODE == MODE_NOISE_ERROR12 ? uv_out : uv_obs) + (valid ? o : n - 1);
                 if (NTL & 2) {
                     const d2_t t2 = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(src));
@@ -722,6 +726,16 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_observations(
                 }
             } else if (MODE == MODE_PROJECT) {
                 if (valid) store16<NTS>(reinterpret_cast<char *>(uv_out + o), make_double2(p.u, p.v));
+            } else if (MODE == MODE_RESIDUAL_KEEP) {
+                // keep = |projected - observed|^2 <= max_error^2 [&& q.z < 0]: five unfused operations, then the comparisons; a
+                // residual that is NaN compares false and goes (an infinite one too, against every finite bound)
+                const double du = p.u - ob.x, dv = p.v - ob.y;
+                const double r2 = du * du + dv * dv;
+                const bool k = r2 <= norm && (!(seed & 1ull) || p.qz < 0.0);
+                if (valid) {
+                    if (NTS) __builtin_nontemporal_store((uint8_t)(k ? 1 : 0), keep + o);
+                    else keep[o] = k ? 1 : 0;
+                }
             } else if (MODE == MODE_ERROR) {
                 if (POWTAB) eacc += valid ? abs_pow_tab(p.u - ob.x, norm, (lds_tab)sTab) + abs_pow_tab(p.v - ob.y, norm, (lds_tab)sTab) : 0.0;
                 else eacc += valid ? abs_pow_k<NK>(p.u - ob.x, norm) + abs_pow_k<NK>(p.v - ob.y, norm) : 0.0;

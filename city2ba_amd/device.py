@@ -276,6 +276,14 @@ def visibility_rows_bits(camblk, pts4, rows, pt_idx, max_dist, uv_out, keep_bits
                                              rows.n_obs, float(max_dist), _p(uv_out), _p(keep_bits), _stream()))
 
 
+def residual_keep_rows(camblk, pts4, rows, pt_idx, uv, max_error, keep, in_front=False):
+    """the outlier filter's mask (c2b_residual_keep_rows): keep [n_obs] uint8, 1 where |projected - observed|^2 <=
+    max_error^2 (and, with in_front, the point is in front of its camera); a NaN residual gives 0"""
+    L.check(L.lib().c2b_residual_keep_rows(_p(camblk), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(rows.tiles), _p(pt_idx), _p(uv),
+                                           rows.n_obs, float(max_error), L.FILTER_IN_FRONT if in_front else 0, _p(keep), _stream()))
+    return keep
+
+
 def residual_jacobian_rows(camblk, pts4, rows, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None, out_sum=None, obs_base=0,
                            n_obs=None):
     """residual + Jacobian (+ sum |r|^norm when ws is given: into out_sum, or into ws for error_sum_finish) of the

@@ -1,7 +1,8 @@
 """Levenberg-Marquardt on a resident BAProblem: BAProblem.solve_step (the damped Gauss-Newton step by PCG on the
 cameras' Schur complement, on the device) and apply_step, with Nielsen's update of the damping; optionally under a
 robust loss (BAProblem.set_loss), by iteratively reweighted least squares, and with chosen camera parameters and points
-held constant (BAProblem.set_constant)."""
+held constant (BAProblem.set_constant); and the usual pipeline around it (solve_filtered): a robust solve, the observations
+whose residual is still large dropped on the device (BAProblem.filter_observations), a last solve without a loss."""
 
 LAMBDA_MIN, LAMBDA_MAX = 1e-20, 1e32                # the damping c2b_problem_solve_step accepts (C2B_STEP_LAMBDA_MIN / _MAX)
 # bits of a camera's constant mask (BAProblem.set_constant; C2B_CONST_*): parameter k of to_vec order is bit k
@@ -107,3 +108,24 @@ def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_t
     summary = dict(iterations=s.iterations, termination=s.termination, reason=L.LM_TERMINATIONS[s.termination],
                    initial_cost=s.initial_cost, final_cost=s.final_cost, lam_next=s.lambda_next)
     return history, summary
+
+
+def solve_filtered(ba, max_error, rounds=1, in_front=False, **lm):
+    """Robust solve, reject outliers, solve again -- all on the resident problem.  `rounds` times
+    levenberg_marquardt_device(ba, **lm) followed by ba.filter_observations(max_error, in_front), then a last
+    levenberg_marquardt_device with loss="squared", which clears the loss (it stays cleared on ba).  **lm is what
+    levenberg_marquardt_device takes (iterations, lam, tolerances, loss, loss_scale, preconditioner, constant); the last
+    solve takes the same arguments but for the loss.  Returns (solves, removed): solves = the (history, summary) of every
+    solve, rounds + 1 of them, removed = the observations each round's filter dropped.
+    A filter can leave cameras or points with too few observations to constrain them (a camera needs more than 3, a point
+    more than 1 for cull() to keep them); nothing is culled here, because a cull renumbers the entities and drops the
+    masks: ba.cull() is the caller's call."""
+    solves, removed = [], []
+    for _ in range(int(rounds)):
+        solves.append(levenberg_marquardt_device(ba, **lm))
+        removed.append(ba.filter_observations(max_error, in_front=in_front))
+    last = dict(lm)
+    last.pop("loss_scale", None)
+    last["loss"] = "squared"
+    solves.append(levenberg_marquardt_device(ba, **last))
+    return solves, removed

@@ -257,6 +257,30 @@ int c2b_problem_drop_checkpoint(c2b_problem *p);
 int c2b_problem_levenberg_marquardt(c2b_problem *p, const c2b_lm_options *opt, c2b_lm_iteration *history, int capacity,
                                     c2b_lm_summary *summary);
 
+/* ---- outlier rejection: drop the observations whose reprojection residual is large, in place ----
+ * Per observation, with (u, v) what c2b_project gives for it (the same bits) and q the point in its camera's frame:
+ *   du = u - obs.x; dv = v - obs.y; r2 = du * du + dv * dv;        (five operations, none fused)
+ *   keep = r2 <= max_error * max_error && (!(flags & C2B_FILTER_IN_FRONT) || q.z < 0)
+ * max_error is squared once on the host, in double.  A residual that is NaN compares false and is dropped, and so does an
+ * infinite one against every finite max_error.  max_error = +inf keeps every finite residual (and, since inf <= inf, an
+ * infinite r2 too: only NaN goes).  max_error negative or NaN, or a flag bit other than C2B_FILTER_IN_FRONT:
+ * C2B_ERR_INVALID_ARGUMENT.
+ * c2b_residual_keep_rows: Level 0, stateless, asynchronous on `stream`: the inputs of c2b_reprojection_error_sum_rows,
+ *   keep [n_obs] one byte (0 / 1) per observation.
+ * c2b_problem_filter_observations: Level 1, synchronous.  The problem's list is compacted by that mask in place: the
+ *   survivors keep their order inside every camera's row (deterministic), n_obs falls, and everything derived from the
+ *   list (row structure, transpose, solve buffers) is rebuilt by its next user.  Cameras, points and both counts stay --
+ *   nothing is renumbered -- and with them the constant masks, the loss, the preconditioner, the checkpoint and the LM
+ *   loop's scratch.  A filter can leave a camera or a point with too few observations: c2b_problem_cull is the caller's
+ *   call.  *n_removed (may be NULL) = how many went; when it is 0 the call changed nothing at all and dropped no cache.
+ *   A problem without observations returns 0.  A problem with a shard set is refused, and so is every bad argument, with
+ *   the problem unchanged. */
+#define C2B_FILTER_IN_FRONT 1
+int c2b_residual_keep_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const void *tiles,
+                           const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double max_error, int flags, uint8_t *keep,
+                           void *stream);
+int c2b_problem_filter_observations(c2b_problem *p, double max_error, int flags, int64_t *n_removed);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
