@@ -526,6 +526,22 @@ class BAProblem:
             self._refresh_graph()
         return n.value
 
+    def triangulate_points(self, min_angle_deg=1.0, return_status=False):
+        """Linear midpoint triangulation on the device (c2b_problem_triangulate_points): every point is set to
+        the position nearest, in the sum of squared distances, to the rays of its observations through the cameras as
+        they are -- a start for a solve, not a refinement.  A point keeps its bits when it is constant, has fewer than two
+        usable observations, has rays less than min_angle_deg apart (the parallax test), or would lie behind one of its
+        cameras.  The loss on the handle is ignored; masks, loss, preconditioner and a checkpoint stay.  Returns
+        dict(triangulated, too_few, degenerate, behind, constant), the number of points of each outcome, and with
+        return_status also the uint8 status per point (the dict's order: 0 .. 4)."""
+        counts = np.zeros(5, dtype=np.int64)
+        status = np.zeros(self.num_points(), dtype=np.uint8) if return_status else None
+        L.check(L.lib().c2b_problem_triangulate_points(self._h, float(np.deg2rad(float(min_angle_deg))),
+                                                       status.ctypes.data_as(C.c_void_p) if return_status else None,
+                                                       counts.ctypes.data_as(C.c_void_p)))
+        out = dict(zip(L.TRI_STATUS, (int(v) for v in counts)))
+        return (out, status) if return_status else out
+
     def subset(self, ci, pi):
         """BAProblem::subset (src/baproblem.rs:394-423): cameras ci and points pi in the given order; observations of
         dropped points disappear.  Host-side index shuffling; returns a NEW device problem."""

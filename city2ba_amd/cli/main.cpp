@@ -23,6 +23,8 @@
 //                         --filter-max-error X --filter-rounds N --filter-in-front]
 //                        (extension: Levenberg-Marquardt on the device, c2b_problem_levenberg_marquardt; with
 //                         --filter-max-error: N times solve + c2b_problem_filter_observations, then a solve without a loss)
+//   city2ba triangulate IN OUT [--min-angle DEG]
+//                        (extension: the points from the cameras and observations, c2b_problem_triangulate_points)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -875,6 +877,36 @@ int run_solve(int argc, char **argv) {
     return 0;
 }
 
+// `triangulate`: every point of a .bal / .bbal from its cameras and observations by c2b_problem_triangulate_points (an
+// extension: linear midpoint triangulation on the device; cameras and observations are written as they were read).  Every
+// argument is parsed before the device is touched.
+int run_triangulate(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {}, {"min-angle", "device"});
+    if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
+    const double min_angle_deg = a.f("min-angle", 1.0);
+    const int device = (int)a.i("device", 0);
+    if (!(min_angle_deg >= 0.0 && min_angle_deg <= 90.0)) die("Invalid value for '--min-angle <DEG>': expected a number in 0 ... 90");
+    PhaseTimer timer;
+    c2b_problem *p = nullptr;
+    ck(create_problem(device, &p));
+    timer.mark("problem_create (HIP runtime start)");
+    ck(c2b_problem_read(p, a.positional[0].c_str(), -1));
+    timer.mark("read (c2b_problem_read: decoded on the device)");
+    int64_t nc = 0, np = 0, no = 0;
+    ck(c2b_problem_sizes(p, &nc, &np, &no));
+    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
+    int64_t counts[5] = {0, 0, 0, 0, 0};
+    ck(c2b_problem_triangulate_points(p, min_angle_deg * (3.14159265358979323846 / 180.0), nullptr, counts));
+    timer.mark("triangulate_points (device)");
+    std::printf("triangulated %lld points; kept: %lld too few observations, %lld degenerate, %lld behind a camera, %lld constant\n",
+                (long long)counts[C2B_TRI_OK], (long long)counts[C2B_TRI_TOO_FEW], (long long)counts[C2B_TRI_DEGENERATE],
+                (long long)counts[C2B_TRI_BEHIND], (long long)counts[C2B_TRI_CONSTANT]);
+    ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
+    timer.mark("write (c2b_problem_write: the file image is built on the device)");
+    c2b_problem_destroy(p);
+    return 0;
+}
+
 void usage() {
     std::printf("city2ba (MI355X build, %s)\nTools for generating synthetic bundle adjustment problems.\n\n"
                 "USAGE:\n    city2ba <SUBCOMMAND>\n\nSUBCOMMANDS:\n"
@@ -883,7 +915,8 @@ void usage() {
                 "    noise             Add noise to a bundle adjustment problem.\n"
                 "    generate          Generate a synthetic bundle adjustment problem from a 3D model.\n"
                 "    ply               Convert a .bal or .bbal to a .ply for visualization.\n"
-                "    solve             Bundle-adjust a .bal or .bbal by Levenberg-Marquardt on the device.\n",
+                "    solve             Bundle-adjust a .bal or .bbal by Levenberg-Marquardt on the device.\n"
+                "    triangulate       Set the points of a .bal or .bbal from its cameras and observations.\n",
                 c2b_version());
 }
 
@@ -930,6 +963,9 @@ const char *subcommand_help(const std::string &sub) {
                "                              then solve again without a loss [off]\n"
                "    --filter-rounds <N> [1]   solve + filter rounds before the last solve\n"
                "    --filter-in-front         also drop observations whose point is not in front of its camera\n";
+    if (sub == "triangulate")
+        return "city2ba triangulate <FILE> <OUT>\n"
+               "    --min-angle <DEG> [1]     parallax test: a point whose rays are less than DEG degrees apart keeps its position\n";
     return nullptr;
 }
 
@@ -953,5 +989,6 @@ int main(int argc, char **argv) {
     if (sub == "generate") return run_generate(argc, argv);
     if (sub == "ply") return run_ply(argc, argv);
     if (sub == "solve") return run_solve(argc, argv);
+    if (sub == "triangulate") return run_triangulate(argc, argv);
     die("The subcommand '" + sub + "' wasn't recognized");
 }

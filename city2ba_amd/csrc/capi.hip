@@ -34,6 +34,7 @@
 #include "kernels.hpp"
 #include "normal_kernels.hpp"
 #include "schur_kernels.hpp"
+#include "triangulate_kernels.hpp"
 #include "cull_kernels.hpp"
 #include "cell_kernels.hpp"
 #include "text_kernels.hpp"

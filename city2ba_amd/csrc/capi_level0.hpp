@@ -1461,6 +1461,32 @@ int c2b_schur_points_rows_loss(const double *camblk, const double *pts4, int64_t
     C2B_API_END("schur_points_rows_loss")
 }
 
+// ---- linear midpoint triangulation (triangulate_kernels.hpp) ------------------------------------------------
+// the parallax threshold 1 - cos(min_angle), evaluated once on the host as 2 sin^2(min_angle / 2): no cancellation at a small angle
+static bool good_min_angle(double a) { return a >= 0.0 && a <= 1.57079632679489661923; }
+
+int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                         const uint32_t *cam_of, const double *uv_obs, double min_angle, const uint8_t *pt_mask, uint8_t *status,
+                         int64_t *counts, void *stream) {
+    C2B_API_BEGIN
+    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_rows: n_pts out of range");
+    if (!good_min_angle(min_angle)) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_rows: min_angle must lie in [0, pi/2] radians");
+    if (!counts || (n_pts && (!pts4 || !pt_row_ptr || !status))) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_rows: NULL argument");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(counts) ||
+        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kTriKinds, st));
+    if (!n_pts) return C2B_OK;
+    const double sh = std::sin(0.5 * min_angle);
+    hipLaunchKernelGGL(k_triangulate_points, dim3(blocks_for(n_pts, kTriBlock)), dim3(kTriBlock), 0, st, camblk,
+                       reinterpret_cast<double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of, reinterpret_cast<const double2 *>(uv_obs),
+                       2.0 * sh * sh, pt_mask, status, reinterpret_cast<unsigned long long *>(counts));
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("triangulate_rows")
+}
+
 // grid of k_schur_cameras: one wave per kNormCamsPerWave cameras
 static unsigned schur_cameras_grid(int64_t n_cam) {
     const int64_t quads = (n_cam + kNormCamsPerWave - 1) / kNormCamsPerWave, waves = kNormBlock / 64;

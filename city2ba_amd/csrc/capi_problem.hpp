@@ -1005,6 +1005,45 @@ int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
     C2B_API_END("problem_apply_step")
 }
 
+// ---- linear midpoint triangulation -------------------------------------------------------------------------
+// The resident points from the resident cameras and observations: c2b_triangulate_rows over the cached transpose (built as
+// c2b_problem_solve_step builds it), the cameras read in the mode the problem is in.  Only pts4 changes, and nothing the
+// problem caches is derived from the points (c2b_problem_apply_step drops nothing for a moved point either): the list, the
+// row structure, the transpose, the solve buffers, the masks, the loss, the preconditioner and a checkpoint all stay.
+int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *status, int64_t *counts) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_triangulate_points");
+    if (!good_min_angle(min_angle)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_points: min_angle must lie in [0, pi/2] radians");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_points: a shard is not triangulated alone (a point's observations span every rank)");
+    const int64_t np = p->n_pts;
+    int64_t got[kTriKinds] = {0, 0, 0, 0, 0};
+    if (!p->n_obs) {                                         // no observation: every point has too few, nothing is read or written
+        got[kTriTooFew] = np;
+        if (status && np) std::fill(status, status + np, (uint8_t)kTriTooFew);
+        if (counts) std::copy(got, got + kTriKinds, counts);
+        return C2B_OK;
+    }
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (!rc) rc = ensure_transpose(p);
+    if (rc) return rc;
+    DevBuf<uint8_t> d_status;
+    DevBuf<int64_t> d_counts;
+    hipError_t e = d_status.alloc((size_t)np);
+    if (e == hipSuccess) e = d_counts.alloc(kTriKinds);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_triangulate_points: allocation: %s", hipGetErrorString(e));
+    rc = c2b_triangulate_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, min_angle, p->pmask, d_status, d_counts, p->stream);
+    if (!rc && status) e = hipMemcpyAsync(status, d_status, (size_t)np, hipMemcpyDeviceToHost, p->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, p->stream);
+    const hipError_t es = hipStreamSynchronize(p->stream);   // the temporaries are freed below
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(C2B_ERR_HIP, "problem_triangulate_points: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    if (counts) std::copy(got, got + kTriKinds, counts);
+    return C2B_OK;
+    C2B_API_END("problem_triangulate_points")
+}
+
 // ---- Levenberg-Marquardt on the device -----------------------------------------------------------------
 int c2b_problem_checkpoint(c2b_problem *p) {
     C2B_API_BEGIN

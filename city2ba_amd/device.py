@@ -284,6 +284,15 @@ def residual_keep_rows(camblk, pts4, rows, pt_idx, uv, max_error, keep, in_front
     return keep
 
 
+def triangulate_rows(camblk, pts4, prows, uv, status, counts, min_angle, pt_mask=None):
+    """linear midpoint triangulation (c2b_triangulate_rows): pts4 [n_pts,4] in place from each point's observations
+    (PointRows); status [n_pts] uint8 (_lib.TRI_STATUS order), counts [5] int64 = how many points took each status;
+    min_angle in radians; pt_mask [n_pts] uint8 (1 = constant) or None"""
+    L.check(L.lib().c2b_triangulate_rows(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of),
+                                         _p(uv), float(min_angle), _p(pt_mask), _p(status), _p(counts), _stream()))
+    return status, counts
+
+
 def residual_jacobian_rows(camblk, pts4, rows, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None, out_sum=None, obs_base=0,
                            n_obs=None):
     """residual + Jacobian (+ sum |r|^norm when ws is given: into out_sum, or into ws for error_sum_finish) of the

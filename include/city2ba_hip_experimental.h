@@ -281,6 +281,48 @@ int c2b_residual_keep_rows(const double *camblk, const double *pts4, const uint6
                            void *stream);
 int c2b_problem_filter_observations(c2b_problem *p, double max_error, int flags, int64_t *n_removed);
 
+/* ---- triangulation: points from cameras and observations (linear midpoint, one lane per point) ----
+ * Point p's observations are walked in ascending observation index through the point-major transpose (pt_row_ptr / obs_of /
+ * cam_of of c2b_normal_transpose).  Per observation of camera c, observed (u, v), with f, k1, k2, R, t of its camblk record
+ * and its centre C (record doubles 24..26, the centre of the visibility predicate):
+ *   m = (u, v) / f; rd = |m|; rho >= 0 with rho (1 + k1 rho^2 + k2 rho^4) = rd, by Newton from rho = rd, at most 16
+ *   iterations, stopping when the update leaves rho unchanged (k1 == 0 && k2 == 0: rho = rd exactly, no iteration);
+ *   pn = m rho / rd (0 when rd == 0); the projection is p = -q.xy / q.z with the scene at q.z < 0, so the ray in the camera
+ *   frame is (pn.x, pn.y, -1) and d = R^T ray, normalised, is its direction in the world;
+ *   A += I - d d^T; b += (I - d d^T) C; n_used += 1.
+ * The observation is unusable, and skipped, when f is 0 or not finite, when the derivative 1 + 3 k1 rho^2 + 5 k2 rho^4 is
+ * <= 0 at an iterate, or when rho is not finite.  Then, in this order:
+ *   C2B_TRI_CONSTANT   the point is constant under pt_mask / c2b_problem_set_constant; none of its observations is read;
+ *   C2B_TRI_TOO_FEW    n_used < 2;
+ *   C2B_TRI_DEGENERATE lambda_min(A) < 1 - cos(min_angle) (for two rays exactly "less than min_angle apart"; more rays only
+ *                      raise lambda_min), or the 3x3 Cholesky of A fails, or X = A^-1 b is not finite.  lambda_min is
+ *                      n_used - lambda_max(sum d d^T) in closed form; the threshold is evaluated once on the host as
+ *                      2 sin^2(min_angle / 2);
+ *   C2B_TRI_BEHIND     a usable observation's camera sees X at q.z >= 0 (a second walk over the row);
+ *   C2B_TRI_OK         pts4[p].xyz = X; the fourth lane keeps its value.
+ * A point whose status is not C2B_TRI_OK keeps its bits.  No robust loss enters: the loss on the handle is ignored.  The
+ * sums of a point depend on its own list alone and there are no float atomics: the same inputs give the same bits.  The
+ * pass uses no scratch memory.  min_angle is in radians; negative, NaN or > pi/2: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_triangulate_rows: Level 0, stateless, asynchronous on `stream`.  pts4 [n_pts][4] is updated in place; pt_mask (device,
+ *   [n_pts] 0 / 1) may be NULL; status [n_pts] one byte per point; counts [5] (device int64, indexed by status) is zeroed
+ *   and then summed by integer atomics.  camblk, obs_of, cam_of and uv_obs are read only where a row holds an observation.
+ * c2b_problem_triangulate_points: Level 1, synchronous.  The resident points are triangulated from the resident cameras,
+ *   read in the mode the problem is in (bal or state; the mode does not change), over the problem's cached transpose,
+ *   which is built as c2b_problem_solve_step builds it when absent.  status (host, [n_pts]) and counts (host, [5]) may be
+ *   NULL.  Only the points change, as after c2b_problem_apply_step with a point step: the list, the row structure, the
+ *   transpose, the solve buffers, the constant masks, the loss, the preconditioner and a checkpoint all stay.  A problem
+ *   without observations returns C2B_TRI_TOO_FEW for every point and writes nothing.  A problem with a shard set is
+ *   refused, and so is every bad argument, with the problem unchanged. */
+#define C2B_TRI_OK 0
+#define C2B_TRI_TOO_FEW 1
+#define C2B_TRI_DEGENERATE 2
+#define C2B_TRI_BEHIND 3
+#define C2B_TRI_CONSTANT 4
+int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                         const uint32_t *cam_of, const double *uv_obs, double min_angle, const uint8_t *pt_mask, uint8_t *status,
+                         int64_t *counts, void *stream);
+int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *status, int64_t *counts);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
