@@ -2,7 +2,9 @@
 //   this file          includes, error plumbing, the kernel launchers (templates over the kernel instances), workspace entries
 //   capi_level0.hpp    Level 0: stateless asynchronous launchers over device pointers; placed outputs; communicator
 //   capi_host_rows.hpp host-side rows (CPU C++ behind the same ABI): layouts, candidates, mesh samplers, cull, files
-//   capi_problem.hpp   Level 1: a BAProblem resident on one device (host buffers in / out, synchronous), *_sharded forms
+//   capi_problem.hpp   Level 1: a BAProblem resident on one device (host buffers in / out, synchronous), *_sharded forms;
+//                      it includes capi_solve.hpp (constant parameters ... Levenberg-Marquardt), capi_graph.hpp (cull, adopt,
+//                      filter, visibility, generate_world_points) and capi_files.hpp (.bal / .bbal) where their text sat
 #include "../../include/city2ba_hip.h"
 #include "../../include/city2ba_hip_host.h"
 #include "../../include/city2ba_hip_experimental.h"
@@ -104,7 +106,20 @@ inline hipError_t launch_error() {
 }
 inline unsigned blocks_for(int64_t n, int b = kBlock) { return (unsigned)((n + b - 1) / b); }
 
-// The owner of Level 1's device memory (capi_problem.hpp, capi_files.hpp): `count` elements of T that free themselves,
+// the sum of n partials into one device scalar: one workgroup of k_normal_sum (normal_kernels.hpp), asynchronous and
+// unchecked like any launch in a sequence (LAUNCH_CHECK / launch_error after the last)
+inline void fold_sum(hipStream_t st, const double *part, int n, double *out) {
+    hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, part, n, out);
+}
+
+// n device scalars to the host (n == 0: none), then wait for the stream: how every synchronous entry ends that returns numbers
+inline int scalars_to_host(hipStream_t st, const double *dev, int n, double *host) {
+    if (n) HIP_TRY(hipMemcpyAsync(host, dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return C2B_OK;
+}
+
+// The owner of Level 1's device memory (capi_problem.hpp and the headers it includes): `count` elements of T that free themselves,
 // or a view into memory someone else owns (a DevArena block), which is never freed here.  It moves, never copies; it
 // passes for the pointer it holds, so a launch takes it as it would take a T *.  Untyped arrays are DevBuf<char>.
 template <class T>

@@ -1,0 +1,877 @@
+// capi_graph.hpp -- Level 1, what changes or produces the resident problem's observation graph: cull, adopt_visibility, the outlier filter,
+// the visibility entries (pairs, cell lists, the dense sweep and its occlusion filter), generate_world_points, graph download / export
+// Part of the one translation unit of the C ABI: included by capi_problem.hpp where this text sat, never compiled or included on its own.
+
+int c2b_problem_visibility_pairs(c2b_problem *p, int64_t n_pairs, const uint32_t *cam_idx, const uint32_t *pt_idx,
+                                 double max_dist, double *uv_out, uint8_t *keep) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_visibility_pairs");
+    if (n_pairs < 0 || (n_pairs && (!cam_idx || !pt_idx || !uv_out || !keep)))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_pairs: bad arguments");
+    if (!n_pairs) return C2B_OK;
+    for (int64_t i = 0; i < n_pairs; ++i)
+        if (cam_idx[i] >= (uint64_t)p->n_cam || pt_idx[i] >= (uint64_t)p->n_pts)
+            return fail(C2B_ERR_INDEX_OUT_OF_RANGE, "problem_visibility_pairs: pair %lld out of range", (long long)i);
+    int rc = ensure_camblk(p);
+    if (rc) return rc;
+    DevBuf<uint32_t> d_c, d_p;
+    DevBuf<double> d_uv;
+    DevBuf<uint8_t> d_k;
+    hipError_t e = d_c.alloc((size_t)n_pairs);
+    if (e == hipSuccess) e = d_p.alloc((size_t)n_pairs);
+    if (e == hipSuccess) e = d_uv.alloc(2 * (size_t)n_pairs);
+    if (e == hipSuccess) e = d_k.alloc((size_t)n_pairs);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_c, cam_idx, sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_p, pt_idx, sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess) {
+        rc = c2b_visibility_pairs(p->camblk, p->pts4, d_c, d_p, n_pairs, max_dist, d_uv, d_k, p->stream);
+        if (!rc) {
+            e = hipMemcpyAsync(uv_out, d_uv, sizeof(double) * 2 * n_pairs, hipMemcpyDeviceToHost, p->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(keep, d_k, n_pairs, hipMemcpyDeviceToHost, p->stream);
+        }
+        hipError_t e2 = hipStreamSynchronize(p->stream);
+        if (e == hipSuccess) e = e2;
+    }
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_pairs: %s", hipGetErrorString(e));
+    return C2B_OK;
+    C2B_API_END("problem_visibility_pairs")
+}
+
+/* ---- BAProblem::cull on the device (src/baproblem.rs:538-549) ---- */
+extern "C++" {
+namespace {
+
+unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
+
+// exclusive scan of n 0/1 flags into pos; *total_host = number of set flags.  Synchronises.
+hipError_t scan_flags(hipStream_t st, const uint32_t *flags, int64_t n, uint32_t *pos, uint32_t *tile_scratch, uint32_t *d_total,
+                      uint32_t *total_host) {
+    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
+    if (n > 0) hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)tiles), dim3(kScanBlock), 0, st, flags, n, pos, tile_scratch);
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, st, tile_scratch, tiles, d_total);
+    if (n > 0) hipLaunchKernelGGL(k_scan_add, dim3((unsigned)tiles), dim3(kScanBlock), 0, st, pos, n, (const uint32_t *)tile_scratch);
+    hipError_t e = launch_error();
+    if (e == hipSuccess) e = hipMemcpyAsync(total_host, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e;
+}
+
+// THE place where the problem's observation list is replaced (cull, adopt_visibility, filter_observations): n_obs
+// observations in uv / pt_idx, their cameras in *cam_idx, or (cam_idx NULL) expanded here from the device row pointer `rows`
+// over the problem's cameras.  Two phases: cam_idx, a workspace for the new count and whatever the caller queues behind them
+// (`more`) are allocated and queued first; the problem is touched only after the stream has synchronised without error:
+// then the four arrays move in, n_obs is set and what was derived from the old list goes.  A failure leaves the problem as it was.
+template <class More>
+int install_observations(c2b_problem *p, const char *who, int64_t n_obs, DevBuf<double> &uv, DevBuf<uint32_t> &pt_idx,
+                         DevBuf<uint32_t> *cam_idx, const uint64_t *rows, More &&more) {
+    DevBuf<uint32_t> expanded;
+    DevBuf<char> ws;
+    int rc = C2B_OK;
+    hipError_t e = cam_idx ? hipSuccess : expanded.alloc((size_t)n_obs);
+    if (e == hipSuccess && !cam_idx) rc = c2b_expand_rows(rows, p->n_cam, 0, n_obs, expanded, p->stream);
+    if (e == hipSuccess && !rc) rc = new_workspace(ws, n_obs, p->stream);
+    if (e == hipSuccess && !rc) e = more();
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(p->stream);
+    if (rc || e != hipSuccess) {
+        (void)hipStreamSynchronize(p->stream);               // no temporary may be freed while queued work still uses it
+        return rc ? rc : fail(hip_code(e), "%s: %s", who, hipGetErrorString(e));
+    }
+    p->uv = std::move(uv); p->pt_idx = std::move(pt_idx); p->cam_idx = std::move(cam_idx ? *cam_idx : expanded); p->ws = std::move(ws);
+    p->n_obs = n_obs;
+    drop_rows(p);
+    return C2B_OK;
+}
+inline hipError_t nothing_more() { return hipSuccess; }
+
+}  // namespace
+}  // extern "C++"
+
+// mode 0: cull() = both passes to a fixed point; 1: largest_connected_component() once; 2: remove_singletons() once
+static int cull_impl(c2b_problem *p, int faithful, int mode) {
+    NEED_UPLOADED(p, "problem_cull");
+    if (p->n_obs >= ((int64_t)1 << 32) || p->n_cam + p->n_pts >= ((int64_t)1 << 32))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_cull: more than 2^32 observations or entities");
+    free_dense(p);
+    hipStream_t st = p->stream;
+    const int64_t nc0 = p->n_cam, np0 = p->n_pts, no0 = p->n_obs;
+    const int64_t nodes0 = nc0 + np0, big0 = std::max(std::max(nc0, np0), no0);
+    // current graph (ping-pong pairs) + where everything came from
+    DevBuf<uint32_t> cam[2], pt[2], eorig[2], corig[2], porig[2];
+    DevBuf<uint32_t> parent, sets, size, keep_c, keep_p, keep_o, pos_c, pos_p, pos_o, tiles, total, deg, cnt;
+    DevBuf<unsigned long long> best;
+    hipError_t e = hipSuccess;
+    // cam / pt are allocations of their own (one of each pair becomes the problem's index array); every other temporary
+    // is a view into one arena
+    for (int k = 0; k < 2; ++k) {
+        if (e == hipSuccess) e = cam[k].alloc((size_t)no0);
+        if (e == hipSuccess) e = pt[k].alloc((size_t)no0);
+    }
+    DevArena arena;
+    auto temporaries = [&](auto &&each) {
+        each(eorig[0], (size_t)no0); each(eorig[1], (size_t)no0); each(corig[0], (size_t)nc0); each(corig[1], (size_t)nc0);
+        each(porig[0], (size_t)np0); each(porig[1], (size_t)np0);
+        each(parent, (size_t)nodes0); each(sets, (size_t)nodes0); each(size, (size_t)nodes0);
+        each(keep_c, (size_t)nc0); each(keep_p, (size_t)np0); each(keep_o, (size_t)no0);
+        each(pos_c, (size_t)nc0); each(pos_p, (size_t)np0); each(pos_o, (size_t)no0);
+        each(tiles, (size_t)(big0 / kScanTile + 2)); each(best, (size_t)1); each(total, (size_t)1); each(deg, (size_t)nc0); each(cnt, (size_t)np0);
+    };
+    size_t arena_bytes = 0;
+    temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
+    if (e == hipSuccess) e = arena.reserve(arena_bytes);
+    if (e == hipSuccess) temporaries([&](auto &b, size_t n) { arena.carve(b, n); });
+    if (e != hipSuccess) return fail(hip_code(e), "problem_cull: %s", hipGetErrorString(e));
+
+    int cur = 0;
+    int64_t nc = nc0, np = np0, no = no0;
+    if (no) {
+        e = hipMemcpyAsync(cam[0].ptr, p->cam_idx, 4 * (size_t)no, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pt[0].ptr, p->pt_idx, 4 * (size_t)no, hipMemcpyDeviceToDevice, st);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, eorig[0], no);   // iota
+        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(nc, kBlock)), dim3(kBlock), 0, st, corig[0], nc);
+        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(np, kBlock)), dim3(kBlock), 0, st, porig[0], np);
+        e = launch_error();
+    }
+
+    // renumber by the keep flags currently in keep_c / keep_p / keep_o
+    auto compact = [&]() -> hipError_t {
+        uint32_t nc_new = 0, np_new = 0, no_new = 0;
+        hipError_t s = scan_flags(st, keep_c, nc, pos_c, tiles, total, &nc_new);
+        if (s == hipSuccess) s = scan_flags(st, keep_p, np, pos_p, tiles, total, &np_new);
+        if (s == hipSuccess) s = scan_flags(st, keep_o, no, pos_o, tiles, total, &no_new);
+        if (s != hipSuccess) return s;
+        const int nxt = cur ^ 1;
+        hipLaunchKernelGGL(k_cull_move_nodes, dim3(blocks_of(nc, kBlock)), dim3(kBlock), 0, st, keep_c, pos_c, nc, corig[cur], corig[nxt]);
+        hipLaunchKernelGGL(k_cull_move_nodes, dim3(blocks_of(np, kBlock)), dim3(kBlock), 0, st, keep_p, pos_p, np, porig[cur], porig[nxt]);
+        hipLaunchKernelGGL(k_cull_move_edges, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, keep_o, pos_o, no, cam[cur], pt[cur], eorig[cur],
+                           pos_c, pos_p, cam[nxt], pt[nxt], eorig[nxt]);
+        cur = nxt;
+        nc = nc_new; np = np_new; no = no_new;
+        return launch_error();
+    };
+    auto lcc_pass = [&]() -> hipError_t {
+        if (nc == 0) return hipSuccess;                      // largest_connected_component returns self (:457-459)
+        const int64_t nodes = nc + np, big = std::max(std::max(nc, np), no);
+        hipError_t s = hipMemsetAsync(size.ptr, 0, 4 * (size_t)nodes, st);
+        if (s == hipSuccess) s = hipMemsetAsync(best.ptr, 0, 8, st);
+        if (s != hipSuccess) return s;
+        hipLaunchKernelGGL(k_uf_init, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, parent, nodes);
+        if (no) hipLaunchKernelGGL(k_uf_union, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, parent, cam[cur], pt[cur], no, (uint32_t)nc);
+        hipLaunchKernelGGL(k_uf_flatten, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, parent, nodes, sets, size);
+        hipLaunchKernelGGL(k_uf_largest, dim3(blocks_of(nodes, kBlock)), dim3(kBlock), 0, st, sets, size, nodes, best);
+        hipLaunchKernelGGL(k_lcc_flags, dim3(blocks_of(big, kBlock)), dim3(kBlock), 0, st, sets, best, (uint32_t)nc,
+                           (uint32_t)np, cam[cur], pt[cur], no, faithful ? 1 : 0, keep_c, keep_p, keep_o);
+        s = launch_error();
+        return s == hipSuccess ? compact() : s;
+    };
+    auto singleton_pass = [&]() -> hipError_t {
+        const int64_t big = std::max(std::max(nc, np), no);
+        hipError_t s = hipMemsetAsync(deg.ptr, 0, 4 * (size_t)(nc ? nc : 1), st);
+        if (s == hipSuccess) s = hipMemsetAsync(cnt.ptr, 0, 4 * (size_t)(np ? np : 1), st);
+        if (s != hipSuccess) return s;
+        if (no) hipLaunchKernelGGL(k_degree, dim3(blocks_of(no, kBlock)), dim3(kBlock), 0, st, cam[cur], pt[cur], no, deg, cnt);
+        hipLaunchKernelGGL(k_singleton_flags, dim3(blocks_of(big, kBlock)), dim3(kBlock), 0, st, deg, cnt, (uint32_t)nc,
+                           (uint32_t)np, cam[cur], pt[cur], no, keep_c, keep_p, keep_o);
+        s = launch_error();
+        return s == hipSuccess ? compact() : s;
+    };
+    // culled = lcc().remove_singletons(); while the counts change: again (src/baproblem.rs:541-547)
+    int64_t pnc = nc, pnp = np;
+    if (e == hipSuccess && mode != 2) e = lcc_pass();
+    if (e == hipSuccess && mode != 1) e = singleton_pass();
+    while (mode == 0 && e == hipSuccess && (nc != pnc || np != pnp)) {
+        pnc = nc; pnp = np;
+        e = lcc_pass();
+        if (e == hipSuccess) e = singleton_pass();
+    }
+
+    // gather the payloads once and swap them in
+    DevBuf<double> n_cam15, n_bal9, n_camblk, n_cen4, n_pts4, n_uv;
+    if (e == hipSuccess) e = n_cam15.alloc(15 * (size_t)nc);
+    if (e == hipSuccess) e = n_bal9.alloc(9 * (size_t)nc);
+    if (e == hipSuccess) e = n_camblk.alloc((size_t)cam_table_doubles(nc));
+    if (e == hipSuccess) e = n_cen4.alloc(4 * (size_t)nc);
+    if (e == hipSuccess) e = n_pts4.alloc(4 * (size_t)np);
+    if (e == hipSuccess) e = n_uv.alloc(2 * (size_t)no);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return fail(hip_code(e), "problem_cull: %s", hipGetErrorString(e));
+    }
+    auto gathers = [&]() -> hipError_t {
+        auto gather = [&](const double *in, const uint32_t *orig, int64_t n, int width, double *out) {
+            if (n) hipLaunchKernelGGL(k_gather_rows, dim3(blocks_of(n * width, kBlock)), dim3(kBlock), 0, st, in, orig, n, width, out);
+        };
+        gather(p->cam15, corig[cur], nc, 15, n_cam15);
+        if (p->bal_valid) gather(p->bal9, corig[cur], nc, 9, n_bal9);
+        gather(p->pts4, porig[cur], np, 4, n_pts4);
+        gather(p->uv, eorig[cur], no, 2, n_uv);
+        return launch_error();
+    };
+    if (const int rc = install_observations(p, "problem_cull", no, n_uv, pt[cur], &cam[cur], nullptr, gathers)) return rc;
+    // the list is in; the entities, which cull alone replaces and renumbers
+    p->cam15 = std::move(n_cam15); p->bal9 = std::move(n_bal9); p->camblk = std::move(n_camblk); p->cen4 = std::move(n_cen4);
+    p->pts4 = std::move(n_pts4); p->n_cam = nc; p->n_pts = np;
+    drop_constant(p);                                         // the survivors are renumbered
+    drop_lm_state(p);
+    p->blk_valid = false;                                     // camblk is rebuilt on demand from the gathered cameras
+    p->bal9_fresh = false;                                    // (bal9 was gathered only when it was the truth)
+    return C2B_OK;
+}
+
+int c2b_problem_cull(c2b_problem *p, int faithful) { return cull_impl(p, faithful, 0); }
+int c2b_problem_largest_connected_component(c2b_problem *p, int faithful) { return cull_impl(p, faithful, 1); }
+int c2b_problem_remove_singletons(c2b_problem *p) { return cull_impl(p, 1, 2); }
+
+int c2b_problem_adopt_visibility(c2b_problem *p) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_adopt_visibility");
+    if (!p->dense_pt || !p->dense_uv || !p->dense_row)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_adopt_visibility: no pending visibility result");
+    const int64_t n = p->dense_n;
+    if (n >= ((int64_t)1 << 32)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_adopt_visibility: more than 2^32 observations");
+    if (const int rc = install_observations(p, "problem_adopt_visibility", n, p->dense_uv, p->dense_pt, nullptr, p->dense_row, nothing_more)) return rc;
+    free_dense(p);                                            // the pending result is spent (its row pointer; the lists were moved out)
+    return C2B_OK;
+    C2B_API_END("problem_adopt_visibility")
+}
+
+int c2b_problem_download_graph(c2b_problem *p, uint64_t *row_ptr, uint64_t *pt_idx) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_download_graph");
+    if (!row_ptr || (p->n_obs && !pt_idx)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_download_graph: bad arguments");
+    const int64_t n_cam = p->n_cam, n_obs = p->n_obs;
+    // the point indices are widened to the host's u64 on the device and leave in ONE copy (r01-r02: a u32 copy into a
+    // fresh host vector, then a serial widening loop over 19 M entries -- a third of the 120-ms download at --blocks 128)
+    DevBuf<uint64_t> d_row, d_pt64;
+    hipError_t e = d_row.alloc((size_t)n_cam + 1);
+    if (e == hipSuccess && n_obs) e = d_pt64.alloc((size_t)n_obs);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_rows_from_sorted, dim3(blocks_for(n_obs + 1)), dim3(kBlock), 0, p->stream, (const uint32_t *)p->cam_idx, n_obs,
+                           n_cam, d_row);
+        if (n_obs) hipLaunchKernelGGL(k_widen_u32, dim3(blocks_for(n_obs)), dim3(kBlock), 0, p->stream, (const uint32_t *)p->pt_idx, n_obs,
+                                      d_pt64);
+        e = launch_error();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(row_ptr, d_row.ptr, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess && n_obs) e = hipMemcpyAsync(pt_idx, d_pt64.ptr, sizeof(uint64_t) * (size_t)n_obs, hipMemcpyDeviceToHost, p->stream);
+    hipError_t e2 = hipStreamSynchronize(p->stream);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(hip_code(e), "problem_download_graph: %s", hipGetErrorString(e));
+    return C2B_OK;
+    C2B_API_END("problem_download_graph")
+}
+
+// The bridge from a problem that was BORN on the device (layout, visibility loop, cull, file read) to the Level-0
+// launchers: the resident arrays -- or the slice that belongs to the camera range [cam_lo, cam_hi) -- copied device to
+// device into buffers the caller owns.  No byte crosses PCIe but the two row-pointer words that size the slice.
+__global__ __launch_bounds__(256) void k_rows_rebase(const uint64_t *__restrict__ in, int64_t n, uint64_t base, uint64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = in[i] - base;
+}
+
+int c2b_problem_export_device(c2b_problem *p, int64_t cam_lo, int64_t cam_hi, double *cam15, double *pts4, uint64_t *row_ptr,
+                              uint32_t *pt_idx, double *uv, int64_t *obs_lo, int64_t *n_obs_slice) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_export_device");
+    if (cam_lo < 0 || cam_hi < cam_lo || cam_hi > p->n_cam)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_export_device: camera range [%lld, %lld) outside [0, %lld]", (long long)cam_lo,
+                    (long long)cam_hi, (long long)p->n_cam);
+    int rc = ensure_rows(p);
+    if (rc) return rc;
+    hipStream_t st = p->stream;
+    uint64_t ends[2] = {0, 0};
+    if (p->n_obs) {
+        HIP_TRY(hipMemcpyAsync(&ends[0], p->rows_ptr + cam_lo, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&ends[1], p->rows_ptr + cam_hi, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const int64_t o0 = (int64_t)ends[0], n = (int64_t)(ends[1] - ends[0]), nc = cam_hi - cam_lo;
+    if (obs_lo) *obs_lo = o0;
+    if (n_obs_slice) *n_obs_slice = n;
+    if (cam15 && nc) HIP_TRY(hipMemcpyAsync(cam15, p->cam15 + 15 * cam_lo, sizeof(double) * 15 * (size_t)nc, hipMemcpyDeviceToDevice, st));
+    if (pts4 && p->n_pts) HIP_TRY(hipMemcpyAsync(pts4, p->pts4, sizeof(double) * 4 * (size_t)p->n_pts, hipMemcpyDeviceToDevice, st));
+    if (row_ptr) {
+        if (p->n_obs) {
+            hipLaunchKernelGGL(k_rows_rebase, dim3(blocks_of(nc + 1, 256)), dim3(256), 0, st, (const uint64_t *)(p->rows_ptr + cam_lo), nc + 1,
+                               ends[0], row_ptr);
+            LAUNCH_CHECK();
+        } else {
+            HIP_TRY(hipMemsetAsync(row_ptr, 0, sizeof(uint64_t) * (size_t)(nc + 1), st));
+        }
+    }
+    if (pt_idx && n) HIP_TRY(hipMemcpyAsync(pt_idx, p->pt_idx + o0, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    if (uv && n) HIP_TRY(hipMemcpyAsync(uv, p->uv + 2 * o0, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return C2B_OK;
+    C2B_API_END("problem_export_device")
+}
+
+// Stable compaction of CSR lists (point index, uv) by a keep mask, on the device: kept count per row -> row scan ->
+// one wave per camera scatters in order.  The new row pointer goes to row_ptr_host; on success the three new lists are
+// in row_new / pt_new / uv_new, *w = kept count (on failure what they hold is not a result).  Synchronises the problem's stream.
+// stop_at: a kept count at which the caller wants no lists (the mask kept everything): pt_new / uv_new are then left empty.
+static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_old, const uint8_t *d_keep, const uint32_t *d_pt,
+                                         const double *d_uv, int64_t n_cam, uint64_t *row_ptr_host, DevBuf<uint64_t> &row_new,
+                                         DevBuf<uint32_t> &pt_new, DevBuf<double> &uv_new, int64_t *w, int64_t stop_at = -1) {
+    DevBuf<uint64_t> d_tot;
+    *w = 0;
+    hipError_t e = d_tot.alloc((size_t)n_cam + 1);
+    if (e == hipSuccess) e = row_new.alloc((size_t)n_cam + 1);
+    if (e != hipSuccess) return e;
+    const unsigned row_blocks = (unsigned)((n_cam + 3) / 4);
+    if (n_cam) hipLaunchKernelGGL(k_keep_row_counts, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, d_keep, n_cam, d_tot);
+    hipLaunchKernelGGL(k_dense_cam_scan, dim3(1), dim3(256), 0, p->stream, (const uint64_t *)d_tot, n_cam, row_new);
+    e = hipMemcpyAsync(row_ptr_host, row_new, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) return e;
+    *w = (int64_t)row_ptr_host[n_cam];
+    if (*w == stop_at) return hipSuccess;
+    e = pt_new.alloc((size_t)*w);
+    if (e == hipSuccess) e = uv_new.alloc(2 * (size_t)*w);
+    if (e == hipSuccess && n_cam) {
+        hipLaunchKernelGGL(k_keep_row_scatter, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, (const uint64_t *)row_new, d_keep,
+                           d_pt, reinterpret_cast<const double2 *>(d_uv), n_cam, pt_new, reinterpret_cast<double2 *>(uv_new.ptr));
+        e = launch_error();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    return e;
+}
+
+// The outlier filter: the residual predicate over the resident list, a stable compaction of (pt_idx, uv) by its
+// mask, then install_observations: cam_idx from the new row pointer, a workspace for the new count, swapped in only once the
+// stream has synchronised without error.  The entities do not move: cameras, points, both counts, the masks, the loss, the
+// preconditioner, the checkpoint and the LM scratch stay; what was derived from the list (drop_rows) goes.
+int c2b_problem_filter_observations(c2b_problem *p, double max_error, int flags, int64_t *n_removed) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_filter_observations");
+    if (n_removed) *n_removed = 0;
+    if (!(max_error >= 0.0)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_filter_observations: max_error must be >= 0 (+inf keeps every finite residual)");
+    if (flags & ~C2B_FILTER_IN_FRONT)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_filter_observations: unknown flag bits 0x%x", (unsigned)(flags & ~C2B_FILTER_IN_FRONT));
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_filter_observations: a shard is not filtered alone (its list is a slice of the whole one)");
+    if (!p->n_obs) return C2B_OK;
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (rc) return rc;
+    const int64_t n_cam = p->n_cam, n_old = p->n_obs;
+    DevBuf<uint8_t> keep;
+    DevBuf<uint64_t> row_new;
+    DevBuf<uint32_t> pt_new;
+    DevBuf<double> uv_new;
+    std::vector<uint64_t> row_host((size_t)n_cam + 1);
+    int64_t w = 0;
+    hipError_t e = keep.alloc((size_t)n_old);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_filter_observations: %s", hipGetErrorString(e));
+    rc = c2b_residual_keep_rows(p->camblk, p->pts4, p->rows_ptr, n_cam, p->rows_tiles, p->pt_idx, p->uv, n_old, max_error, flags, keep, p->stream);
+    if (!rc) e = compact_rows_on_device(p, p->rows_ptr, keep, p->pt_idx, p->uv, n_cam, row_host.data(), row_new, pt_new, uv_new, &w, n_old);
+    if (rc || e != hipSuccess) {
+        (void)hipStreamSynchronize(p->stream);
+        return rc ? rc : fail(hip_code(e), "problem_filter_observations: %s", hipGetErrorString(e));
+    }
+    if (w == n_old) return C2B_OK;                                 // nothing removed: nothing changes, no cache is dropped
+    if ((rc = install_observations(p, "problem_filter_observations", w, uv_new, pt_new, nullptr, row_new, nothing_more))) return rc;
+    if (n_removed) *n_removed = n_old - w;
+    return C2B_OK;
+    C2B_API_END("problem_filter_observations")
+}
+
+int c2b_problem_visibility_pairs_compact(c2b_problem *p, int64_t n_pairs, const uint32_t *cam_idx, const uint32_t *pt_idx,
+                                         double max_dist, uint64_t *row_ptr) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_visibility_pairs_compact");
+    if (n_pairs < 0 || !row_ptr || (n_pairs && (!cam_idx || !pt_idx)))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_pairs_compact: bad arguments");
+    for (int64_t i = 0; i < n_pairs; ++i) {
+        if (cam_idx[i] >= (uint64_t)p->n_cam || pt_idx[i] >= (uint64_t)p->n_pts)
+            return fail(C2B_ERR_INDEX_OUT_OF_RANGE, "problem_visibility_pairs_compact: pair %lld out of range", (long long)i);
+        if (i && cam_idx[i] < cam_idx[i - 1])
+            return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_pairs_compact: cam_idx must be non-decreasing (pair %lld)", (long long)i);
+    }
+    int rc = ensure_camblk(p);
+    if (rc) return rc;
+    free_dense(p);
+    const int64_t n_cam = p->n_cam;
+    const size_t n = (size_t)(n_pairs ? n_pairs : 1);
+    DevBuf<uint32_t> d_c, d_p, d_pt_new;
+    DevBuf<double> d_uv, d_uv_new;
+    DevBuf<uint8_t> d_k;
+    DevBuf<uint64_t> d_row, d_row_new;
+    int64_t w = 0;
+    hipError_t e = d_c.alloc(n);
+    if (e == hipSuccess) e = d_p.alloc(n);
+    if (e == hipSuccess) e = d_uv.alloc(2 * n);
+    if (e == hipSuccess) e = d_k.alloc(n);
+    if (e == hipSuccess) e = d_row.alloc((size_t)n_cam + 1);
+    if (e == hipSuccess && n_pairs) e = hipMemcpyAsync(d_c, cam_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess && n_pairs) e = hipMemcpyAsync(d_p, pt_idx, sizeof(uint32_t) * n, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess) {
+        if (n_pairs) rc = c2b_visibility_pairs(p->camblk, p->pts4, d_c, d_p, n_pairs, max_dist, d_uv, d_k, p->stream);
+        if (!rc) {
+            hipLaunchKernelGGL(k_rows_from_sorted, dim3(blocks_for(n_pairs + 1)), dim3(kBlock), 0, p->stream, (const uint32_t *)d_c,
+                               n_pairs, n_cam, d_row);
+            e = launch_error();
+            if (e == hipSuccess)
+                e = compact_rows_on_device(p, d_row, d_k, d_p, d_uv, n_cam, row_ptr, d_row_new, d_pt_new, d_uv_new, &w);
+        }
+    }
+    if (rc || e != hipSuccess) (void)hipStreamSynchronize(p->stream);
+    if (!rc && e == hipSuccess) {                 // becomes the pending visibility result (fetch with _dense_fetch)
+        p->dense_row = std::move(d_row_new); p->dense_pt = std::move(d_pt_new); p->dense_uv = std::move(d_uv_new); p->dense_n = w;
+    }
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_pairs_compact: %s", hipGetErrorString(e));
+    return C2B_OK;
+    C2B_API_END("problem_visibility_pairs_compact")
+}
+
+// A statistics record's extent (stats[6..11]: min and max) and max_dist -> the cell grid over x / z.  Cells are a hair
+// wider than max_dist so that rounding in the cell arithmetic can never separate two positions within max_dist by more
+// than one cell; they double until there are at most 2^24 of them (wider cells stay correct, only slower).
+static int cell_grid_from_stats(const double *stats, double max_dist, const char *who, CellGrid *g, int64_t *n_cells) {
+    g->x0 = stats[6]; g->z0 = stats[8];
+    const double ex = stats[9] - stats[6], ez = stats[11] - stats[8];
+    double cs = (max_dist > 0.0 ? max_dist : 1.0) * (1.0 + 0x1.0p-20);
+    if (!(ex >= 0.0) || !(ez >= 0.0) || !std::isfinite(ex) || !std::isfinite(ez) || !std::isfinite(cs))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "%s: non-finite coordinates", who);
+    auto cells = [&](double c) { return (std::floor(ex / c) + 1.0) * (std::floor(ez / c) + 1.0); };
+    while (cells(cs) > (double)(1 << 24)) cs *= 2.0;
+    g->inv_cs = 1.0 / cs;
+    g->ncx = (int)std::floor(ex / cs) + 1; g->ncz = (int)std::floor(ez / cs) + 1;
+    *n_cells = (int64_t)g->ncx * g->ncz;
+    return C2B_OK;
+}
+
+// The cell list of n > 0 positions (32-byte rows) on that grid: count, exclusive scan (start[n_cells] = n), fill.  `counts`
+// [n_cells + 1] is zero on entry -- the caller's memset -- and holds the fill's cursors afterwards.  Synchronises (scan_flags).
+static int build_cell_list(hipStream_t st, const char *who, const double4 *pos4, int64_t n, const CellGrid &g, int64_t n_cells,
+                           uint32_t *cell_of, uint32_t *counts, uint32_t *start, uint32_t *sorted, uint32_t *tiles, uint32_t *total) {
+    hipLaunchKernelGGL(k_cells_assign, dim3(blocks_of(n, 256)), dim3(256), 0, st, pos4, n, g, cell_of, counts);
+    uint32_t n_sorted = 0;
+    hipError_t e = scan_flags(st, counts, n_cells + 1, start, tiles, total, &n_sorted);
+    if (e == hipSuccess && (int64_t)n_sorted != n) return fail(C2B_ERR_HIP, "%s: cell counts do not add up", who);
+    if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 4 * (size_t)(n_cells + 1), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_cells_fill, dim3(blocks_of(n, 256)), dim3(256), 0, st, (const uint32_t *)cell_of, n, (const uint32_t *)start, counts, sorted);
+        e = launch_error();
+    }
+    if (e != hipSuccess) return fail(hip_code(e), "%s: %s", who, hipGetErrorString(e));
+    return C2B_OK;
+}
+
+// The generators' whole visibility loop (src/synthetic.rs:268-297, :353-378) on the device: candidates by a cell list
+// (rstar's locate_within_distance), the sight line against the buildings (hits_building), the predicate, and the kept
+// (point, uv) lists compacted per camera in ascending point index -- csrc/cell_kernels.hpp.  The result becomes the
+// pending visibility result like c2b_problem_visibility_pairs_compact's (adopt / fetch it the same way); row_ptr (host,
+// n_cam + 1) may be NULL.
+int c2b_problem_visibility_within_distance(c2b_problem *p, double max_dist, int occlusion, double block_length, double block_inset,
+                                           uint64_t *row_ptr) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_visibility_within_distance");
+    if (!(max_dist >= 0.0) || (occlusion && !(block_length > 0.0)))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_within_distance: max_dist must be >= 0 (and block_length > 0 with occlusion)");
+    const int64_t n_cam = p->n_cam, n_pts = p->n_pts;
+    if (n_pts >= ((int64_t)1 << 32) || n_cam >= ((int64_t)1 << 31))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_within_distance: too many cameras or points");
+    int rc = ensure_camblk(p);
+    if (rc) return rc;
+    free_dense(p);
+    hipStream_t st = p->stream;
+    if (n_cam == 0 || n_pts == 0) {                                      // nothing can be seen: an empty graph
+        DevBuf<uint64_t> row0;
+        DevBuf<uint32_t> pt0;
+        DevBuf<double> uv0;
+        hipError_t e0 = row0.alloc((size_t)n_cam + 1);
+        if (e0 == hipSuccess) e0 = pt0.alloc(1);
+        if (e0 == hipSuccess) e0 = uv0.alloc(2);
+        if (e0 == hipSuccess) e0 = hipMemsetAsync(row0.ptr, 0, sizeof(uint64_t) * (size_t)(n_cam + 1), st);
+        if (e0 == hipSuccess) e0 = hipStreamSynchronize(st);
+        if (e0 != hipSuccess) return fail(C2B_ERR_HIP, "problem_visibility_within_distance: %s", hipGetErrorString(e0));
+        if (row_ptr) std::fill(row_ptr, row_ptr + n_cam + 1, (uint64_t)0);
+        p->dense_row = std::move(row0); p->dense_pt = std::move(pt0); p->dense_uv = std::move(uv0);
+        p->dense_n = 0;
+        return C2B_OK;
+    }
+    // extent of cameras and points -> the cell grid
+    double stats[C2B_STATS_DOUBLES];
+    CellGrid g;
+    int64_t n_cells = 0;
+    rc = compute_stats(p);
+    if (!rc) rc = scalars_to_host(st, p->stats, C2B_STATS_DOUBLES, stats);
+    if (!rc) rc = cell_grid_from_stats(stats, max_dist, "problem_visibility_within_distance", &g, &n_cells);
+    if (rc) return rc;
+
+    DevArena arena;
+    DevBuf<uint32_t> cell_of, counts, cursor, sorted, tiles, total, cam_count, pos, max32;
+    DevBuf<unsigned long long> sum64;
+    DevBuf<uint64_t> row64;
+    const int64_t big = std::max(n_cells + 1, n_cam + 1);
+    auto temporaries = [&](auto &&each) {
+        each(cell_of, (size_t)n_pts); each(counts, (size_t)(n_cells + 1)); each(cursor, (size_t)(n_cells + 1));
+        each(sorted, (size_t)n_pts); each(tiles, (size_t)(big / kScanTile + 2)); each(total, (size_t)1);
+        each(cam_count, (size_t)(n_cam + 1)); each(pos, (size_t)(n_cam + 1)); each(sum64, (size_t)1); each(max32, (size_t)1);
+    };
+    size_t arena_bytes = 0;
+    temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
+    hipError_t e = arena.reserve(arena_bytes);
+    if (e == hipSuccess) e = row64.alloc((size_t)n_cam + 1);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_within_distance: %s", hipGetErrorString(e));
+    temporaries([&](auto &b, size_t n) { arena.carve(b, n); });
+
+    // cell list: count, exclusive scan (start[n_cells] = n_pts), fill
+    HIP_TRY(hipMemsetAsync(counts.ptr, 0, 4 * (size_t)(n_cells + 1), st));
+    HIP_TRY(hipMemsetAsync(cursor.ptr, 0, 4 * (size_t)(n_cells + 1), st));
+    HIP_TRY(hipMemsetAsync(cam_count.ptr, 0, 4 * (size_t)(n_cam + 1), st));
+    HIP_TRY(hipMemsetAsync(sum64.ptr, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(max32.ptr, 0, 4, st));
+    uint32_t n_kept32 = 0;
+    uint32_t *start = cursor;                             // scanned counts; the fill's cursors live in `counts` afterwards
+    rc = build_cell_list(st, "problem_visibility_within_distance", reinterpret_cast<const double4 *>(p->pts4.ptr), n_pts, g, n_cells,
+                         cell_of, counts, start, sorted, tiles, total);
+    if (rc) return rc;
+    // pass 1: survivors per camera; scan; total
+    const unsigned cam_blocks = blocks_of(n_cam, kCellWPB);
+    if (e == hipSuccess && n_cam && n_pts) {
+        hipLaunchKernelGGL((k_cells_visibility<false>), dim3(cam_blocks), dim3(kCellWPB * 64), 0, st, (const double *)p->camblk, n_cam,
+                           reinterpret_cast<const double4 *>(p->pts4.ptr), g, (const uint32_t *)start, sorted,
+                           max_dist, occlusion ? 1 : 0, block_length, block_inset, cam_count, (const uint64_t *)nullptr,
+                           (uint32_t *)nullptr, (double2 *)nullptr);
+        hipLaunchKernelGGL(k_sum_u32_u64, dim3(256), dim3(256), 0, st, cam_count, n_cam, sum64);
+        hipLaunchKernelGGL(k_max_u32, dim3(256), dim3(256), 0, st, cam_count, n_cam, max32);
+    }
+    if (e == hipSuccess) e = scan_flags(st, cam_count, n_cam + 1, pos, tiles, total, &n_kept32);
+    unsigned long long n_kept = 0;
+    uint32_t longest = 0;
+    if (e == hipSuccess) e = hipMemcpy(&n_kept, sum64.ptr, 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&longest, max32.ptr, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && n_kept != (unsigned long long)n_kept32)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_within_distance: more than 2^32 observations");
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_widen_u32, dim3(blocks_for(n_cam + 1)), dim3(kBlock), 0, st, pos, n_cam + 1, row64);
+        e = launch_error();
+    }
+    // pass 2: fill in meeting order, then every row into ascending point index
+    DevBuf<uint32_t> tmp_pt, out_pt;
+    DevBuf<double2> tmp_uv;
+    DevBuf<double> out_uv;
+    const size_t w = (size_t)n_kept;
+    if (e == hipSuccess) e = tmp_pt.alloc(w);
+    if (e == hipSuccess) e = tmp_uv.alloc(w);
+    if (e == hipSuccess) e = out_pt.alloc(w);
+    if (e == hipSuccess) e = out_uv.alloc(2 * w);
+    if (e == hipSuccess && w) {
+        hipLaunchKernelGGL((k_cells_visibility<true>), dim3(cam_blocks), dim3(kCellWPB * 64), 0, st, (const double *)p->camblk, n_cam,
+                           reinterpret_cast<const double4 *>(p->pts4.ptr), g, (const uint32_t *)start, sorted,
+                           max_dist, occlusion ? 1 : 0, block_length, block_inset, (uint32_t *)nullptr, row64,
+                           tmp_pt, tmp_uv);
+        // The device row sort is quadratic in the row length: right for the generators' rows (a few dozen entries), wrong
+        // for a radius that makes one camera see tens of thousands of points.  Beyond `long_row` entries the rows are sorted on the
+        // host instead (threads over cameras) -- a path for odd inputs, not a fast one; such problems belong to the dense
+        // sweep (c2b_problem_visibility_dense).
+        // (2 048: a lane of the rank sort then makes at most 64 k dependent compares -- ~0.1 ms per row-wave; at the 8 192 of
+        // round 4 a scene with thousands of cameras seeing several thousand points each was a multi-second cliff)
+        const uint32_t long_row = p->opt.rank_sort_max_row > 0 ? (uint32_t)p->opt.rank_sort_max_row : 2048u;
+        if (longest <= long_row) {
+            hipLaunchKernelGGL(k_rows_rank_sort, dim3(cam_blocks), dim3(kCellWPB * 64), 0, st, row64, n_cam, tmp_pt, tmp_uv, out_pt,
+                               reinterpret_cast<double2 *>(out_uv.ptr));
+            e = launch_error();
+        } else {
+            e = launch_error();
+            std::vector<uint64_t> rp((size_t)n_cam + 1);
+            std::vector<uint32_t> hp(w), hq(w);
+            std::vector<double> hu(2 * w), hv(2 * w);
+            if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), row64.ptr, 8 * ((size_t)n_cam + 1), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(hp.data(), tmp_pt.ptr, 4 * w, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(hu.data(), tmp_uv.ptr, 16 * w, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e == hipSuccess) {
+                const int T = (int)std::min<int64_t>(std::max(1u, std::thread::hardware_concurrency()), std::max<int64_t>(1, n_cam));
+                c2b_host::run_threads(T, [&](int t) {
+                        std::vector<uint32_t> order;
+                        for (int64_t c = n_cam * t / T; c < n_cam * (t + 1) / T; ++c) {
+                            const size_t b = (size_t)rp[(size_t)c], k = (size_t)(rp[(size_t)c + 1] - rp[(size_t)c]);
+                            order.resize(k);
+                            for (size_t i = 0; i < k; ++i) order[i] = (uint32_t)i;
+                            std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return hp[b + x] < hp[b + y]; });
+                            for (size_t i = 0; i < k; ++i) {
+                                hq[b + i] = hp[b + order[i]];
+                                hv[2 * (b + i)] = hu[2 * (b + order[i])];
+                                hv[2 * (b + i) + 1] = hu[2 * (b + order[i]) + 1];
+                            }
+                        }
+                    });
+                e = hipMemcpyAsync(out_pt.ptr, hq.data(), 4 * w, hipMemcpyHostToDevice, st);
+                if (e == hipSuccess) e = hipMemcpyAsync(out_uv.ptr, hv.data(), 16 * w, hipMemcpyHostToDevice, st);
+                if (e == hipSuccess) e = hipStreamSynchronize(st);
+            }
+        }
+    }
+    if (e == hipSuccess && row_ptr)
+        e = hipMemcpyAsync(row_ptr, row64.ptr, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return fail(hip_code(e), "problem_visibility_within_distance: %s", hipGetErrorString(e));
+    }
+    p->dense_row = std::move(row64); p->dense_pt = std::move(out_pt); p->dense_uv = std::move(out_uv);
+    p->dense_n = (int64_t)n_kept;
+    return C2B_OK;
+    C2B_API_END("problem_visibility_within_distance")
+}
+
+// generate_world_points_uniform (src/generate.rs:356-420) for the cameras of the resident problem, on the device
+// (cell_kernels.hpp: k_world_*): the problem's points are REPLACED by the sampled ones (its observations must be empty).
+// Candidate k draws from the k-th splitmix64 stream of `seed` exactly like c2b_generate_world_points, and candidates are
+// accepted in order, so the points are that function's, bit for bit.  tri9: HOST triangles [n_tri][9] f32.
+int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t n_tri, int64_t num_points, double max_dist,
+                                      uint64_t seed, int64_t *n_out) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_generate_world_points");
+    if (!tri9 || n_tri < 0 || num_points < 0 || !n_out || num_points >= ((int64_t)1 << 31))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_generate_world_points: bad arguments");
+    if (p->n_obs != 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_generate_world_points: the problem already has observations");
+    if (p->n_cam == 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "Cannot generate world points with 0 cameras. Try increasing the number of cameras generated (via --cameras).");
+    if (n_tri == 0) return fail(C2B_ERR_INVALID_ARGUMENT, "the model has no triangles");
+    int rc = ensure_camblk(p);
+    if (rc) return rc;
+    hipStream_t st = p->stream;
+    const int64_t n_cam = p->n_cam;
+    // triangle areas and their running sum, on the host in the host sampler's own arithmetic (a sequential sum: 1 ms)
+    std::vector<double> cum((size_t)n_tri);
+    {
+        double acc = 0.0;
+        for (int64_t t = 0; t < n_tri; ++t) {
+            const float *q = tri9 + 9 * t;
+            const double a[3] = {(double)q[3] - (double)q[0], (double)q[4] - (double)q[1], (double)q[5] - (double)q[2]};
+            const double b[3] = {(double)q[6] - (double)q[0], (double)q[7] - (double)q[1], (double)q[8] - (double)q[2]};
+            const double c[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+            acc += std::sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]) / 2.0;
+            cum[(size_t)t] = acc;
+        }
+    }
+    // the cell list over the camera centres
+    DevBuf<float> d_tri;
+    DevBuf<double> d_cum;
+    const double4 *centres = reinterpret_cast<const double4 *>(p->cen4.ptr);     // written with camblk (ensure_camblk above)
+    hipError_t e = d_tri.alloc(9 * (size_t)n_tri);
+    if (e == hipSuccess) e = d_cum.alloc((size_t)n_tri);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tri.ptr, tri9, 36 * (size_t)n_tri, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cum.ptr, cum.data(), 8 * (size_t)n_tri, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_generate_world_points: %s", hipGetErrorString(e));
+    // the centres' extent (a reduction the statistics kernel already is: cameras only)
+    double stats[C2B_STATS_DOUBLES];
+    CellGrid g;
+    int64_t n_cells = 0;
+    rc = c2b_stats(p->camblk, p->cen4, n_cam, p->pts4, 0, p->ws, p->stats, st);
+    if (!rc) rc = scalars_to_host(st, p->stats, C2B_STATS_DOUBLES, stats);
+    if (!rc) rc = cell_grid_from_stats(stats, max_dist, "problem_generate_world_points", &g, &n_cells);
+    if (rc) return rc;
+    const int64_t chunk = std::max<int64_t>(4096, std::min<int64_t>(num_points, (int64_t)1 << 20));      // the host sampler's chunks
+    DevBuf<uint32_t> cell_of, counts, startb, sorted, tiles, total, ok, pos;
+    DevBuf<double4> cand;
+    DevBuf<unsigned long long> cutoff;
+    DevBuf<double> out;
+    const int64_t big = std::max(n_cells + 1, chunk);
+    e = cell_of.alloc((size_t)n_cam);
+    if (e == hipSuccess) e = counts.alloc((size_t)(n_cells + 1));
+    if (e == hipSuccess) e = startb.alloc((size_t)(n_cells + 1));
+    if (e == hipSuccess) e = sorted.alloc((size_t)n_cam);
+    if (e == hipSuccess) e = tiles.alloc((size_t)(big / kScanTile + 2));
+    if (e == hipSuccess) e = total.alloc(1);
+    if (e == hipSuccess) e = cand.alloc((size_t)chunk);
+    if (e == hipSuccess) e = ok.alloc((size_t)chunk);
+    if (e == hipSuccess) e = pos.alloc((size_t)chunk);
+    if (e == hipSuccess) e = cutoff.alloc(1);
+    if (e == hipSuccess) e = out.alloc(4 * (size_t)std::max<int64_t>(num_points, 1));
+    if (e == hipSuccess) e = hipMemsetAsync(counts.ptr, 0, 4 * (size_t)(n_cells + 1), st);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_generate_world_points: %s", hipGetErrorString(e));
+    rc = build_cell_list(st, "problem_generate_world_points", centres, n_cam, g, n_cells, cell_of, counts, startb, sorted, tiles, total);
+    if (rc) return rc;
+    // the reference's loop, a chunk of candidates at a time
+    int64_t accepted = 0, failed = 0;
+    const int64_t fail_threshold = 10 * num_points;
+    for (int64_t k0 = 0; e == hipSuccess && accepted < num_points && failed < fail_threshold; k0 += chunk) {
+        const unsigned long long all = (unsigned long long)chunk;
+        e = hipMemcpyAsync(cutoff.ptr, &all, 8, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(k_world_candidates, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, d_tri, n_tri, d_cum, seed, k0, chunk,
+                           centres, g, startb, sorted, max_dist, cand, ok);
+        uint32_t n_ok = 0;
+        e = scan_flags(st, ok, chunk, pos, tiles, total, &n_ok);
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(k_world_cutoff, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, pos, chunk,
+                           (uint64_t)(num_points - accepted), (uint64_t)(fail_threshold - failed), cutoff);
+        hipLaunchKernelGGL(k_world_accept, dim3(blocks_of(chunk, 256)), dim3(256), 0, st, cand, ok, pos, chunk, cutoff,
+                           reinterpret_cast<double4 *>(out.ptr) + accepted);
+        e = launch_error();
+        unsigned long long cut = 0;
+        if (e == hipSuccess) e = hipMemcpyAsync(&cut, cutoff.ptr, 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        uint32_t took = n_ok;                                 // accepted among the candidates before the cutoff
+        if ((int64_t)cut < chunk) {
+            e = hipMemcpy(&took, pos + cut, 4, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) break;
+        }
+        accepted += (int64_t)took;
+        failed += (int64_t)cut - (int64_t)took;
+    }
+    if (e != hipSuccess) return fail(C2B_ERR_HIP, "problem_generate_world_points: %s", hipGetErrorString(e));
+    if (failed >= fail_threshold && num_points > 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "Failed to generate enough points. %lld successes, %lld failures, %lld requested points.",
+                    (long long)accepted, (long long)failed, (long long)num_points);
+    // the sampled points become the problem's
+    free_dense(p);
+    drop_rows(p);
+    drop_constant(p);
+    drop_lm_state(p);
+    p->pts4 = std::move(out);
+    p->n_pts = accepted;
+    *n_out = accepted;
+    return C2B_OK;
+    C2B_API_END("problem_generate_world_points")
+}
+
+int c2b_problem_visibility_dense(c2b_problem *p, double max_dist, uint64_t *row_ptr) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_visibility_dense");
+    if (!row_ptr) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_dense: row_ptr is NULL");
+    if (!(max_dist >= 0.0)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_dense: max_dist must be >= 0");
+    int rc = ensure_camblk(p);
+    if (rc) return rc;
+    free_dense(p);
+    const int64_t n_tiles = c2b_visibility_dense_tiles(p->n_pts);
+    const int64_t cells = p->n_cam * n_tiles;
+    if (cells > ((int64_t)1 << 33))
+        return fail(C2B_ERR_INVALID_ARGUMENT,
+                    "problem_visibility_dense: %lld cameras x %lld point tiles is too large for the dense sweep; "
+                    "use candidate pairs + c2b_problem_visibility_pairs", (long long)p->n_cam, (long long)n_tiles);
+    DevBuf<uint32_t> d_counts;
+    DevBuf<uint64_t> d_tot, d_row;
+    hipError_t e = d_counts.alloc((size_t)cells);
+    if (e == hipSuccess) e = d_tot.alloc((size_t)p->n_cam + 1);
+    if (e == hipSuccess) e = d_row.alloc((size_t)p->n_cam + 1);
+    if (e == hipSuccess) {
+        rc = c2b_visibility_dense_count(p->camblk, p->n_cam, p->pts4, p->n_pts, max_dist, d_counts, d_tot, d_row, p->stream);
+        if (!rc) e = hipMemcpyAsync(row_ptr, d_row, sizeof(uint64_t) * (size_t)(p->n_cam + 1), hipMemcpyDeviceToHost, p->stream);
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(p->stream);
+        if (!rc && e == hipSuccess) {
+            const int64_t total = (int64_t)row_ptr[p->n_cam];
+            e = p->dense_pt.alloc((size_t)total);
+            if (e == hipSuccess) e = p->dense_uv.alloc(2 * (size_t)total);
+            if (e == hipSuccess && total) {
+                rc = c2b_visibility_dense_fill(p->camblk, p->n_cam, p->pts4, p->n_pts, max_dist, d_counts, d_row, p->dense_pt,
+                                               p->dense_uv, p->stream);
+                if (!rc) e = hipStreamSynchronize(p->stream);
+            }
+            if (!rc && e == hipSuccess) { p->dense_n = total; p->dense_row = std::move(d_row); }
+        }
+    }
+    if (rc || e != hipSuccess) free_dense(p);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_dense: %s", hipGetErrorString(e));
+    return C2B_OK;
+    C2B_API_END("problem_visibility_dense")
+}
+
+// `ready`: a hierarchy the caller built over the same triangles (c2b_bvh_build), or NULL: built here when the mesh is
+// large enough for one
+static int occlude_impl(c2b_problem *p, const float *tri9, int64_t n_tri, const c2b_bvh *ready, uint64_t *row_ptr) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_visibility_dense_occlude");
+    if (!p->dense_pt || !p->dense_uv || !p->dense_row)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_dense_occlude: no sweep result");
+    if (!row_ptr || n_tri < 0 || (n_tri && !tri9 && !ready)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_dense_occlude: bad arguments");
+    const int64_t n = p->dense_n, n_cam = p->n_cam;
+    if (!n || !n_tri) {
+        HIP_TRY(hipMemcpyAsync(row_ptr, p->dense_row, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return C2B_OK;
+    }
+    DevBuf<char> d_tri, d_nodes;
+    DevBuf<uint32_t> d_cam, d_pt_new, d_flag;
+    uint32_t stack_overflow = 0;
+    DevBuf<uint8_t> d_keep;
+    DevBuf<uint64_t> d_row_new;
+    DevBuf<double> d_uv_new;
+    int rc = C2B_OK;
+    // small meshes: every ray against every triangle; larger ones through a hierarchy built here on the host
+    const bool use_bvh = ready || n_tri >= kBvhMinTriangles;
+    c2b_bvh *built = nullptr;
+    int64_t n_nodes = 0;
+    if (use_bvh && !ready) {
+        rc = c2b_bvh_build(tri9, n_tri, &built);
+        if (rc) return rc;
+    }
+    const c2b_bvh *bvh = ready ? ready : built;
+    if (use_bvh) n_nodes = (int64_t)bvh->b.nodes.size();
+    const size_t tri_bytes = use_bvh ? (size_t)C2B_BVH_TRI_BYTES * (size_t)n_tri : sizeof(float) * 9 * (size_t)n_tri;
+    const void *tri_src = use_bvh ? (const void *)bvh->b.tris.data() : (const void *)tri9;
+    hipError_t e = d_tri.alloc(tri_bytes);
+    if (e == hipSuccess && use_bvh) e = d_nodes.alloc((size_t)C2B_BVH_NODE_BYTES * (size_t)n_nodes);
+    if (e == hipSuccess) e = d_cam.alloc((size_t)n);
+    if (e == hipSuccess) e = d_keep.alloc((size_t)n);
+    if (e == hipSuccess) e = d_flag.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(uint32_t), p->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tri, tri_src, tri_bytes, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess && use_bvh)
+        e = hipMemcpyAsync(d_nodes, bvh->b.nodes.data(), (size_t)C2B_BVH_NODE_BYTES * (size_t)n_nodes, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess) {
+        rc = c2b_expand_rows(p->dense_row, n_cam, 0, n, d_cam, p->stream);
+        if (!rc)
+            rc = use_bvh ? c2b_occlusion_filter_bvh(p->camblk, p->pts4, d_cam, p->dense_pt, n, d_nodes, n_nodes, d_tri, n_tri, d_keep, d_flag, p->stream)
+                         : c2b_occlusion_filter(p->camblk, p->pts4, d_cam, p->dense_pt, n, reinterpret_cast<const float *>(d_tri.ptr), n_tri,
+                                                d_keep, p->stream);
+        // Stable compaction of the survivor lists on the device (per-camera order of the sweep is kept): kept count per
+        // row, row scan, scatter.  Only the new row pointer travels to the host.
+        if (!rc) {                                         // a traversal-stack overflow invalidates the whole mask
+            e = hipMemcpyAsync(&stack_overflow, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+            if (e == hipSuccess && stack_overflow)
+                rc = fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_dense_occlude: hierarchy deeper than the traversal stack");
+        }
+        if (!rc && e == hipSuccess) {
+            int64_t w = 0;
+            e = compact_rows_on_device(p, p->dense_row, d_keep, p->dense_pt, p->dense_uv, n_cam, row_ptr, d_row_new, d_pt_new, d_uv_new, &w);
+            if (e == hipSuccess) {                           // the filtered lists replace the sweep's
+                p->dense_pt = std::move(d_pt_new); p->dense_uv = std::move(d_uv_new); p->dense_row = std::move(d_row_new);
+                p->dense_n = w;
+            }
+        }
+    }
+    if (rc || e != hipSuccess) (void)hipStreamSynchronize(p->stream);   // no temporary may be freed while a copy still reads it
+    c2b_bvh_free(built);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(hip_code(e), "problem_visibility_dense_occlude: %s", hipGetErrorString(e));
+    return C2B_OK;
+    C2B_API_END("problem_visibility_dense_occlude")
+}
+
+int c2b_problem_visibility_dense_occlude(c2b_problem *p, const float *tri9, int64_t n_tri, uint64_t *row_ptr) {
+    return occlude_impl(p, tri9, n_tri, nullptr, row_ptr);
+}
+int c2b_problem_visibility_dense_occlude_bvh(c2b_problem *p, const c2b_bvh *bvh, uint64_t *row_ptr) {
+    if (!bvh) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_dense_occlude_bvh: bvh is NULL");
+    return occlude_impl(p, nullptr, (int64_t)(bvh->b.tris.size() / (C2B_BVH_TRI_BYTES / sizeof(bvh->b.tris[0]))), bvh, row_ptr);
+}
+
+int c2b_problem_visibility_dense_fetch(c2b_problem *p, uint64_t *pt_idx, double *uv) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_visibility_dense_fetch");
+    if (!p->dense_pt || !p->dense_uv) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_visibility_dense_fetch: no sweep result");
+    const int64_t n = p->dense_n;
+    if (!n) return C2B_OK;
+    if (uv) HIP_TRY(hipMemcpyAsync(uv, p->dense_uv, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, p->stream));
+    if (pt_idx) {
+        std::vector<uint32_t> tmp((size_t)n);
+        HIP_TRY(hipMemcpyAsync(tmp.data(), p->dense_pt, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        for (int64_t i = 0; i < n; ++i) pt_idx[i] = tmp[(size_t)i];
+    }
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return C2B_OK;
+    C2B_API_END("problem_visibility_dense_fetch")
+}

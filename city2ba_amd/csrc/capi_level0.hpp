@@ -1349,7 +1349,7 @@ static int normal_cameras_rows_impl(const double *camblk, const double *pts4, co
     if (sum_sq && kind == kLossSquared) {
         hipLaunchKernelGGL(k_normal_cameras<true>, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv,
                            U, gc, block_part);
-        hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)block_part, (int)(grid * waves), sum_sq);
+        fold_sum(st, block_part, (int)(grid * waves), sum_sq);
     } else {
         with_loss(kind, a2, [&](auto... loss) {
             hipLaunchKernelGGL((k_normal_cameras<false, decltype(loss)...>), dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr,
@@ -1359,7 +1359,7 @@ static int normal_cameras_rows_impl(const double *camblk, const double *pts4, co
             const unsigned nb = blocks_for(n_obs, kNormBlock);   // <= block_part_slots(n_obs): one partial per 4 tiles of 64
             if (nb) hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, st, camblk, p4, (const uint32_t *)nullptr, row_ptr,
                                        (int)n_cam, pt_idx, uv, n_obs, kind, a2, block_part);
-            hipLaunchKernelGGL(k_normal_sum, dim3(1), dim3(256), 0, st, (const double *)block_part, (int)nb, sum_sq);
+            fold_sum(st, block_part, (int)nb, sum_sq);
         }
     }
     LAUNCH_CHECK();

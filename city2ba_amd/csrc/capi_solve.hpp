@@ -1,0 +1,683 @@
+// capi_solve.hpp -- Level 1, the solver side of the resident problem: constant parameters, robust loss, preconditioner, normal equations, the damped
+// Gauss-Newton step (implicit Schur complement + PCG), apply_step, triangulation, checkpoint / rollback and Levenberg-Marquardt on the device
+// Part of the one translation unit of the C ABI: included by capi_problem.hpp where this text sat, never compiled or included on its own.
+
+// ---- constant parameters -----------------------------------------------------------------------------------
+int c2b_problem_set_constant(c2b_problem *p, const uint16_t *cam_mask, const uint8_t *pt_mask) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_set_constant");
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    int64_t n_params = 0, n_const_pts = 0;
+    if (cam_mask)
+        for (int64_t c = 0; c < nc; ++c) {
+            if (cam_mask[c] & ~C2B_CONST_ALL)
+                return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_constant: camera %lld has a bit above bit 8 set (0x%x)", (long long)c,
+                            (unsigned)cam_mask[c]);
+            n_params += __builtin_popcount(cam_mask[c]);
+        }
+    if (pt_mask)
+        for (int64_t i = 0; i < np; ++i) {
+            if (pt_mask[i] > 1)
+                return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_constant: point %lld has mask %d, not 0 or 1", (long long)i, (int)pt_mask[i]);
+            n_const_pts += pt_mask[i];
+        }
+    // the new device arrays first: a failure leaves the masks in force as they were.  An all-zero mask is no mask.
+    std::vector<uint16_t> hc;
+    std::vector<uint8_t> hp;
+    DevBuf<uint16_t> dcm;
+    DevBuf<uint8_t> dpm;
+    hipError_t e = hipSuccess;
+    if (n_params) {
+        hc.assign(cam_mask, cam_mask + nc);
+        e = dcm.alloc((size_t)nc);
+        if (e == hipSuccess) e = hipMemcpyAsync(dcm, hc.data(), sizeof(uint16_t) * (size_t)nc, hipMemcpyHostToDevice, p->stream);
+    }
+    if (e == hipSuccess && n_const_pts) {
+        hp.assign(pt_mask, pt_mask + np);
+        e = dpm.alloc((size_t)np);
+        if (e == hipSuccess) e = hipMemcpyAsync(dpm, hp.data(), sizeof(uint8_t) * (size_t)np, hipMemcpyHostToDevice, p->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(p->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(hip_code(e), "problem_set_constant: %s", hipGetErrorString(e));
+    drop_constant(p);
+    p->cmask = std::move(dcm); p->pmask = std::move(dpm);
+    p->h_cmask.swap(hc); p->h_pmask.swap(hp);
+    p->const_n_cam = nc; p->const_n_pts = np;
+    p->const_params = n_params; p->const_pts = n_const_pts;
+    return C2B_OK;
+    C2B_API_END("problem_set_constant")
+}
+
+int c2b_problem_get_constant(const c2b_problem *p, uint16_t *cam_mask, uint8_t *pt_mask, int64_t *n_const_cam_params, int64_t *n_const_pts) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_constant: problem is NULL");
+    if (!p->ws) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_constant: nothing uploaded");
+    if (cam_mask) {
+        if (p->cmask) std::copy(p->h_cmask.begin(), p->h_cmask.end(), cam_mask);
+        else std::fill(cam_mask, cam_mask + p->n_cam, (uint16_t)0);
+    }
+    if (pt_mask) {
+        if (p->pmask) std::copy(p->h_pmask.begin(), p->h_pmask.end(), pt_mask);
+        else std::fill(pt_mask, pt_mask + p->n_pts, (uint8_t)0);
+    }
+    if (n_const_cam_params) *n_const_cam_params = p->const_params;
+    if (n_const_pts) *n_const_pts = p->const_pts;
+    return C2B_OK;
+    C2B_API_END("problem_get_constant")
+}
+
+// the zeros of J~ into blocks the passes filled from J (asynchronous; nothing is launched for a kind with nothing constant):
+// rows and columns of A [n_cam][9][9] with `diag` on their diagonal, entries of y [n_cam][9] (either may be NULL) ...
+static int constant_cameras(c2b_problem *p, double *A, double diag, double *y) {
+    if (!p->cmask || !p->n_cam) return C2B_OK;
+    if (A) hipLaunchKernelGGL(k_const_blocks, dim3(blocks_for(9 * p->n_cam, kSchurBlock)), dim3(kSchurBlock), 0, p->stream, 9 * p->n_cam,
+                              (const uint16_t *)p->cmask, diag, A);
+    if (y) hipLaunchKernelGGL(k_const_cameras, dim3(blocks_for(p->n_cam, kSchurBlock)), dim3(kSchurBlock), 0, p->stream, p->n_cam,
+                              (const uint16_t *)p->cmask, y);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
+// ... V [n_pts][3][3] = diag I3 with gp [n_pts][3] = 0 (gp may be NULL), or t [n_pts][3] = 0 alone (V NULL), of the constant points
+static int constant_points(c2b_problem *p, double *V, double diag, double *t) {
+    if (!p->pmask || !p->n_pts) return C2B_OK;
+    if (V) hipLaunchKernelGGL(k_const_point_blocks, dim3(blocks_for(p->n_pts, kSchurBlock)), dim3(kSchurBlock), 0, p->stream, p->n_pts,
+                              (const uint8_t *)p->pmask, diag, V, t);
+    else hipLaunchKernelGGL(k_const_points, dim3(blocks_for(p->n_pts, kSchurBlock)), dim3(kSchurBlock), 0, p->stream, p->n_pts,
+                            (const uint8_t *)p->pmask, t);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
+// ---- robust loss -----------------------------------------------------------------------------------------
+int c2b_problem_set_loss(c2b_problem *p, int kind, double scale) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_loss: problem is NULL");
+    NEED_LOSS(kind, scale, "problem_set_loss");
+    p->loss_kind = kind;
+    p->loss_scale = kind == kLossSquared ? 1.0 : scale;
+    return C2B_OK;
+    C2B_API_END("problem_set_loss")
+}
+
+int c2b_problem_get_loss(const c2b_problem *p, int *kind, double *scale) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_loss: problem is NULL");
+    if (kind) *kind = p->loss_kind;
+    if (scale) *scale = p->loss_scale;
+    return C2B_OK;
+    C2B_API_END("problem_get_loss")
+}
+
+// ---- preconditioner of the step ----------------------------------------------------------------------------
+int c2b_problem_set_preconditioner(c2b_problem *p, int kind) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_preconditioner: problem is NULL");
+    if (kind != C2B_PRECOND_BLOCK_JACOBI && kind != C2B_PRECOND_SCHUR_JACOBI)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_preconditioner: kind must be 0 (block-Jacobi) or 1 (Schur-Jacobi), not %d", kind);
+    p->precond_kind = kind;
+    return C2B_OK;
+    C2B_API_END("problem_set_preconditioner")
+}
+
+int c2b_problem_get_preconditioner(const c2b_problem *p, int *kind) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_preconditioner: problem is NULL");
+    if (kind) *kind = p->precond_kind;
+    return C2B_OK;
+    C2B_API_END("problem_get_preconditioner")
+}
+
+int c2b_problem_preconditioner_fallbacks(const c2b_problem *p, int64_t *n) {
+    C2B_API_BEGIN
+    if (!p || !n) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_preconditioner_fallbacks: NULL argument");
+    *n = p->precond_fallbacks;
+    return C2B_OK;
+    C2B_API_END("problem_preconditioner_fallbacks")
+}
+
+// sum over the observations of rho(s) (weighted_sq: of w s) under the problem's loss into out[0] (device), asynchronous;
+// one partial per workgroup of 256 observations: the workspace holds one per 4 tiles of 64 (block_part_slots)
+static int robust_sum(c2b_problem *p, bool weighted_sq, double *out) {
+    const int rc = ensure_camblk(p);
+    if (rc) return rc;
+    static_assert(kNormBlock == 256, "k_robust_cost's partials are sized by block_part_slots");
+    const unsigned nb = blocks_for(p->n_obs, kNormBlock);
+    double *part = reinterpret_cast<double *>(p->ws.ptr) + kWsBlockPart;
+    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4.ptr);
+    const double2 *uv = reinterpret_cast<const double2 *>(p->uv.ptr);
+    const double a2 = p->loss_scale * p->loss_scale;
+    if (weighted_sq)
+        hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, p->stream, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                           (const uint64_t *)nullptr, 0, (const uint32_t *)p->pt_idx, uv, p->n_obs, p->loss_kind, a2, part);
+    else
+        hipLaunchKernelGGL(k_robust_cost<false>, dim3(nb), dim3(kNormBlock), 0, p->stream, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                           (const uint64_t *)nullptr, 0, (const uint32_t *)p->pt_idx, uv, p->n_obs, p->loss_kind, a2, part);
+    fold_sum(p->stream, part, (int)nb, out);
+    HIP_TRY(launch_error());
+    return C2B_OK;
+}
+
+int c2b_problem_robust_cost(c2b_problem *p, double *cost) {
+    C2B_API_BEGIN
+    if (!p || !cost) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_robust_cost: NULL argument");
+    NEED_UPLOADED(p, "problem_robust_cost");
+    double s = 0.0;
+    if (p->n_obs) {
+        int rc = robust_sum(p, false, p->scalar);
+        if (!rc) rc = scalars_to_host(p->stream, p->scalar, 1, &s);
+        if (rc) return rc;
+    }
+    *cost = s;
+    return C2B_OK;
+    C2B_API_END("problem_robust_cost")
+}
+
+int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *V, double *gp, double *sum_sq) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: problem is NULL");
+    if (!U != !gc || !V != !gp) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: U / gc and V / gp go in pairs (both or neither)");
+    for (const void *q : {(const void *)U, (const void *)gc, (const void *)V, (const void *)gp, (const void *)sum_sq})
+        if (reinterpret_cast<uintptr_t>(q) & 7) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: misaligned pointer");
+    NEED_UPLOADED(p, "problem_normal_equations");
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (rc) return rc;
+    const bool want_sum = sum_sq != nullptr;
+    if (U) {
+        rc = normal_cameras_rows_impl(p->camblk, p->pts4, p->n_obs ? p->rows_ptr : nullptr, p->n_obs ? p->n_cam : 0, p->pt_idx, p->uv,
+                                      p->n_obs, U, gc, want_sum ? p->ws : nullptr, want_sum ? p->scalar : nullptr, p->loss_kind,
+                                      p->loss_scale, p->stream);
+        if (!rc && !p->n_obs && p->n_cam) {                   // no list: every camera's block is empty
+            HIP_TRY(hipMemsetAsync(U, 0, sizeof(double) * 81 * (size_t)p->n_cam, p->stream));
+            HIP_TRY(hipMemsetAsync(gc, 0, sizeof(double) * 9 * (size_t)p->n_cam, p->stream));
+        }
+        if (!rc && p->n_obs) rc = constant_cameras(p, U, 0.0, gc);
+    } else if (want_sum && p->loss_kind != kLossSquared && p->n_obs) {
+        rc = robust_sum(p, true, p->scalar);                 // the weighted sum of squares without the blocks
+    } else if (want_sum) {
+        rc = p->n_obs ? c2b_reprojection_error_sum_rows(p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->rows_tiles, p->pt_idx, p->uv,
+                                                        p->n_obs, 2.0, p->ws, p->scalar, p->stream)
+                      : (hipMemsetAsync(p->scalar, 0, sizeof(double), p->stream) == hipSuccess ? C2B_OK
+                                                                                             : fail(C2B_ERR_HIP, "problem_normal_equations: memset"));
+    }
+    if (rc) return rc;
+    if (V && p->n_pts) {
+        if (p->n_obs) {
+            rc = ensure_transpose(p);
+            if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, V, gp, p->loss_kind,
+                                                  p->loss_scale, p->stream);
+            if (!rc) rc = constant_points(p, V, 0.0, gp);
+            if (rc) return rc;
+        } else {
+            HIP_TRY(hipMemsetAsync(V, 0, sizeof(double) * 9 * (size_t)p->n_pts, p->stream));
+            HIP_TRY(hipMemsetAsync(gp, 0, sizeof(double) * 3 * (size_t)p->n_pts, p->stream));
+        }
+    }
+    double s = 0.0;
+    if ((rc = scalars_to_host(p->stream, p->scalar, want_sum ? 1 : 0, &s))) return rc;
+    if (want_sum) *sum_sq = s;
+    return C2B_OK;
+    C2B_API_END("problem_normal_equations")
+}
+
+// ---- damped Gauss-Newton step (schur_kernels.hpp) ------------------------------------------------------------------
+// c2b_problem::sv, carved: U [n_cam][81], gc [n_cam][9], V [n_pts][9], gp [n_pts][3], Lf [n_cam][45], t [n_pts][3],
+// r / z / p / q [n_cam][9], two partial arrays [n_part], the device scalars [kScSlots]; under the Schur-Jacobi
+// preconditioner its blocks M [n_cam][81] after them (the rest lies where it lies without)
+struct SolveBufs {
+    double *U, *gc, *V, *gp, *Lf, *t, *r, *z, *pv, *q, *pa, *pb, *sc, *M;
+    int64_t n_part;
+};
+
+static int64_t solve_parts(const c2b_problem *p) {
+    const int64_t a = (int64_t)schur_cameras_grid(p->n_cam) * (kNormBlock / 64);
+    return std::max<int64_t>({a, (int64_t)blocks_for(p->n_cam, kSchurBlock), (int64_t)blocks_for(p->n_obs, kSchurBlock), 1});
+}
+
+static int64_t solve_doubles(const c2b_problem *p) {
+    return p->n_cam * (81 + 9 + kCholPacked + 4 * 9) + p->n_pts * (9 + 3 + 3) + 2 * solve_parts(p) + kScSlots +
+           (p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? 81 * p->n_cam : 0);
+}
+
+static SolveBufs solve_bufs(c2b_problem *p) {
+    SolveBufs b;
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    double *q = p->sv;
+    auto take = [&](int64_t n) { double *r = q; q += n; return r; };
+    b.U = take(81 * nc); b.gc = take(9 * nc); b.V = take(9 * np); b.gp = take(3 * np); b.Lf = take(kCholPacked * nc);
+    b.t = take(3 * np); b.r = take(9 * nc); b.z = take(9 * nc); b.pv = take(9 * nc); b.q = take(9 * nc);
+    b.n_part = solve_parts(p);
+    b.pa = take(b.n_part); b.pb = take(b.n_part); b.sc = take(kScSlots);
+    b.M = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? take(81 * nc) : nullptr;
+    return b;
+}
+
+static int ensure_solver(c2b_problem *p) {
+    const int64_t n = solve_doubles(p);
+    if (p->sv && p->sv_doubles >= n) return C2B_OK;
+    p->sv_doubles = 0;
+    const hipError_t e = p->sv.alloc((size_t)n);                  // (the smaller one is freed first)
+    if (e != hipSuccess) return fail(hip_code(e), "problem_solve_step: allocation: %s", hipGetErrorString(e));
+    p->sv_doubles = n;
+    return C2B_OK;
+}
+
+int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double rel_tol, double *dc, double *dp, c2b_step_info *info) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: problem is NULL");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: lambda must lie in [1e-20, 1e32]");
+    if (max_iters < 0 || !(rel_tol >= 0.0) || !std::isfinite(rel_tol))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: max_iters must be >= 0 and rel_tol finite and >= 0");
+    NEED_UPLOADED(p, "problem_solve_step");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: a shard cannot be solved alone (the point-side sums span every rank)");
+    const int64_t nc = p->n_cam, np = p->n_pts, no = p->n_obs;
+    if ((nc && !dc) || (np && !dp)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: dc / dp is NULL");
+    if (!aligned8(dc) || !aligned8(dp)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: misaligned pointer");
+    hipStream_t st = p->stream;
+    c2b_step_info out{0, 0, 0.0, 0.0, 0.0};
+    p->precond_fallbacks = 0;
+    if (!no) {                                               // no observation: g = 0, the step is 0
+        if (nc) HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
+        if (np) HIP_TRY(hipMemsetAsync(dp, 0, sizeof(double) * 3 * (size_t)np, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (info) *info = out;
+        return C2B_OK;
+    }
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (!rc) rc = ensure_transpose(p);
+    if (!rc) rc = ensure_solver(p);
+    if (rc) return rc;
+    const SolveBufs B = solve_bufs(p);
+    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4.ptr);
+    const double2 *uv = reinterpret_cast<const double2 *>(p->uv.ptr);
+    const unsigned cgrid = schur_cameras_grid(nc), nbc = blocks_for(nc, kSchurBlock), nbo = blocks_for(no, kSchurBlock);
+    const int n_cpart = (int)(cgrid * (kNormBlock / 64));
+    const int kind = p->loss_kind;                           // 0: every launch below is the squared-loss kernel it always was
+    const double a2 = p->loss_scale * p->loss_scale;
+    auto points = [&](const double *x, const double *h, double *t, bool neg) {
+        with_loss(kind, a2, [&](auto... loss) {
+            if (neg)
+                hipLaunchKernelGGL((k_schur_points<true, decltype(loss)...>), dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st,
+                                   p->camblk, p4, np, p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, loss...);
+            else
+                hipLaunchKernelGGL((k_schur_points<false, decltype(loss)...>), dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st,
+                                   p->camblk, p4, np, p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, loss...);
+        });
+        if (p->pmask) (void)constant_points(p, nullptr, 0.0, t);        // t = 0 for the constant points (fetch sees a launch error)
+    };
+    auto mask_y = [&](double *y) {                           // after a camera pass: y's constant entries to 0
+        if (p->cmask) (void)constant_cameras(p, nullptr, 0.0, y);
+    };
+    double h[kScSlots];
+    auto fetch = [&](int slots) -> int {                     // the first `slots` scalars to the host, after all queued work
+        HIP_TRY(launch_error());
+        return scalars_to_host(st, B.sc, slots, h);
+    };
+
+    // U, gc, V, gp; the preconditioner; b = -gc + W V_l^-1 gp into r
+    rc = normal_cameras_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.gc, nullptr, nullptr, kind,
+                                  p->loss_scale, st);
+    if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, B.gp, kind, p->loss_scale, st);
+    if (rc) return rc;
+    const bool schur_jacobi = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI;
+    // constant parameters: from here on U, gc, V, gp are those of J~.  k_schur_jacobi first sees the constant
+    // points' V as kConstPointV, under which their observations add Jc^T Jc as they do with Jp = 0
+    rc = constant_cameras(p, B.U, 0.0, B.gc);
+    if (!rc) rc = constant_points(p, B.V, schur_jacobi ? kConstPointV : 0.0, B.gp);
+    if (rc) return rc;
+    if (schur_jacobi) {                                      // M from U's diagonal and V, its factors, the fallbacks' count
+        rc = schur_jacobi_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.V, lambda, B.M, kind, p->loss_scale, st);
+        if (!rc) rc = constant_cameras(p, B.M, lambda * 1e-6, nullptr);
+        if (!rc) rc = constant_points(p, B.V, 0.0, nullptr);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_schur_factor_blocks, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.M, (const double *)B.U,
+                           lambda, B.Lf, B.pa);
+        fold_sum(st, B.pa, (int)nbc, B.sc + kScFallback);
+    } else {
+        hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
+    }
+    points(nullptr, B.gp, B.t, false);
+    with_loss(kind, a2, [&](auto... loss) {
+        hipLaunchKernelGGL((k_schur_cameras<kSchurRhs, decltype(loss)...>), dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr,
+                           (int)nc, p->pt_idx, uv, (const double *)B.U, lambda, (const double *)nullptr, (const double *)B.gc,
+                           (const double *)B.t, B.r, (double *)nullptr, loss...);
+    });
+    mask_y(B.r);
+    hipLaunchKernelGGL(k_pcg_update<true>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc, 0, dc,
+                       B.r, B.pv, (const double *)nullptr, B.z, B.pa, B.pb);
+    fold_sum(st, B.pa, (int)nbc, B.sc + kScRr);
+    fold_sum(st, B.pb, (int)nbc, B.sc + kScRz0);
+    if ((rc = fetch(kScRz1 + 1))) return rc;
+
+    // PCG from x = 0 (x is dc)
+    const double bb = h[kScRr], bnorm = std::sqrt(bb);
+    double rnorm = bnorm;
+    int it = 0, status = 1;
+    if (!std::isfinite(bb) || !std::isfinite(h[kScRz0])) {
+        status = 2;
+    } else if (rnorm <= rel_tol * bnorm) {                   // b = 0 (or rel_tol >= 1)
+        status = 0;
+    } else {
+        while (it < max_iters) {
+            const int cur = (it & 1) ? kScRz1 : kScRz0, nxt = (it & 1) ? kScRz0 : kScRz1;
+            points(B.pv, nullptr, B.t, false);
+            with_loss(kind, a2, [&](auto... loss) {
+                hipLaunchKernelGGL((k_schur_cameras<kSchurDot, decltype(loss)...>), dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4,
+                                   p->rows_ptr, (int)nc, p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv,
+                                   (const double *)nullptr, (const double *)B.t, B.q, B.pa, loss...);
+            });
+            mask_y(B.q);                                     // p's constant entries are 0: the p.q partials need no correction
+            fold_sum(st, B.pa, n_cpart, B.sc + kScPq);
+            hipLaunchKernelGGL(k_pcg_update<false>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc,
+                               cur, dc, B.r, B.pv, (const double *)B.q, B.z, B.pa, B.pb);
+            fold_sum(st, B.pa, (int)nbc, B.sc + kScRr);
+            fold_sum(st, B.pb, (int)nbc, B.sc + nxt);
+            if ((rc = fetch(kScRz1 + 1))) return rc;
+            const double pq = h[kScPq], rz = h[cur], alpha = rz / pq;
+            if (!(pq > 0.0) || !std::isfinite(alpha)) { status = 2; break; }     // k_pcg_update left x as it was
+            ++it;
+            const double rr = h[kScRr], rzn = h[nxt];
+            if (!std::isfinite(rr) || !std::isfinite(rzn)) { status = 2; break; }
+            rnorm = std::sqrt(rr);
+            if (rnorm <= rel_tol * bnorm) { status = 0; break; }
+            if (it == max_iters) break;
+            hipLaunchKernelGGL(k_pcg_direction, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, rzn / rz,
+                               (const double *)B.z, B.pv);
+        }
+    }
+
+    // dp = -V_l^-1 (gp + W^T dc); then |r|^2 and the model decrease from J, per observation
+    points(dc, B.gp, dp, true);
+    with_loss(kind, a2, [&](auto... loss) {
+        hipLaunchKernelGGL(k_schur_model<decltype(loss)...>, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
+                           (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb, loss...);
+    });
+    fold_sum(st, B.pa, (int)nbo, B.sc + kScSumSq);
+    fold_sum(st, B.pb, (int)nbo, B.sc + kScModel);
+    if ((rc = fetch(schur_jacobi ? kScFallback + 1 : kScModel + 1))) return rc;
+    if (schur_jacobi) p->precond_fallbacks = (int64_t)h[kScFallback];
+    out.iterations = it;
+    out.status = status;
+    out.rel_residual = bb == 0.0 ? 0.0 : rnorm / bnorm;
+    out.sum_sq = h[kScSumSq];
+    out.model_decrease = h[kScModel];
+    if (!std::isfinite(out.sum_sq) || !std::isfinite(out.model_decrease) || !std::isfinite(out.rel_residual)) {
+        // a factorisation failed (a pivot <= 0 at the damping's low end) and a NaN reached the step: no step at all
+        HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
+        if (np) HIP_TRY(hipMemsetAsync(dp, 0, sizeof(double) * 3 * (size_t)np, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        out.status = 2;
+        out.rel_residual = 1.0;
+        out.model_decrease = 0.0;
+    }
+    if (info) *info = out;
+    return C2B_OK;
+    C2B_API_END("problem_solve_step")
+}
+
+int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_apply_step");
+    if (!aligned8(dc) || !aligned8(dp)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_apply_step: misaligned pointer");
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    hipStream_t st = p->stream;
+    if (nc) {
+        if (!p->bal_valid && !p->bal9_fresh) {               // state mode: the columns of dc refer to to_vec(cam15)
+            const int rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st);
+            if (rc) return rc;
+        }
+        if (dc && p->cmask)                                  // a constant entry keeps its bits
+            hipLaunchKernelGGL(k_add_free, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc,
+                               (const uint16_t *)p->cmask, p->bal9);
+        else if (dc) hipLaunchKernelGGL(k_add_f64, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc, p->bal9);
+        LAUNCH_CHECK();
+        const int rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
+        if (rc) return rc;
+    }
+    if (dp && np) {
+        if (p->pmask)
+            hipLaunchKernelGGL(k_points_add_free, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp,
+                               (const uint8_t *)p->pmask, reinterpret_cast<double4 *>(p->pts4.ptr));
+        else
+            hipLaunchKernelGGL(k_points_add, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp, reinterpret_cast<double4 *>(p->pts4.ptr));
+        LAUNCH_CHECK();
+    }
+    cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
+    p->bal_valid = true;
+    HIP_TRY(hipStreamSynchronize(st));
+    return C2B_OK;
+    C2B_API_END("problem_apply_step")
+}
+
+// ---- linear midpoint triangulation -------------------------------------------------------------------------
+// The resident points from the resident cameras and observations: c2b_triangulate_rows over the cached transpose (built as
+// c2b_problem_solve_step builds it), the cameras read in the mode the problem is in.  Only pts4 changes, and nothing the
+// problem caches is derived from the points (c2b_problem_apply_step drops nothing for a moved point either): the list, the
+// row structure, the transpose, the solve buffers, the masks, the loss, the preconditioner and a checkpoint all stay.
+int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *status, int64_t *counts) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_triangulate_points");
+    if (!good_min_angle(min_angle)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_points: min_angle must lie in [0, pi/2] radians");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_points: a shard is not triangulated alone (a point's observations span every rank)");
+    const int64_t np = p->n_pts;
+    int64_t got[kTriKinds] = {0, 0, 0, 0, 0};
+    if (!p->n_obs) {                                         // no observation: every point has too few, nothing is read or written
+        got[kTriTooFew] = np;
+        if (status && np) std::fill(status, status + np, (uint8_t)kTriTooFew);
+        if (counts) std::copy(got, got + kTriKinds, counts);
+        return C2B_OK;
+    }
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (!rc) rc = ensure_transpose(p);
+    if (rc) return rc;
+    DevBuf<uint8_t> d_status;
+    DevBuf<int64_t> d_counts;
+    hipError_t e = d_status.alloc((size_t)np);
+    if (e == hipSuccess) e = d_counts.alloc(kTriKinds);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_triangulate_points: allocation: %s", hipGetErrorString(e));
+    rc = c2b_triangulate_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, min_angle, p->pmask, d_status, d_counts, p->stream);
+    if (!rc && status) e = hipMemcpyAsync(status, d_status, (size_t)np, hipMemcpyDeviceToHost, p->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, p->stream);
+    const hipError_t es = hipStreamSynchronize(p->stream);   // the temporaries are freed below
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(C2B_ERR_HIP, "problem_triangulate_points: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    if (counts) std::copy(got, got + kTriKinds, counts);
+    return C2B_OK;
+    C2B_API_END("problem_triangulate_points")
+}
+
+// ---- Levenberg-Marquardt on the device -----------------------------------------------------------------
+int c2b_problem_checkpoint(c2b_problem *p) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_checkpoint");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_checkpoint: a shard cannot be solved alone, so it takes no checkpoint");
+    p->ck_valid = false;
+    const int rc = c2b_problem_apply_step(p, nullptr, nullptr);          // bal mode: bal9 and pts4 are then the whole state
+    if (rc) return rc;
+    if (!p->ck_bal9 || !p->ck_pts4) {
+        hipError_t e = p->ck_bal9.alloc(9 * (size_t)p->n_cam);
+        if (e == hipSuccess) e = p->ck_pts4.alloc(4 * (size_t)p->n_pts);
+        if (e != hipSuccess) { drop_lm_state(p); return fail(hip_code(e), "problem_checkpoint: allocation: %s", hipGetErrorString(e)); }
+    }
+    if (p->n_cam) HIP_TRY(hipMemcpyAsync(p->ck_bal9, p->bal9, sizeof(double) * 9 * (size_t)p->n_cam, hipMemcpyDeviceToDevice, p->stream));
+    if (p->n_pts) HIP_TRY(hipMemcpyAsync(p->ck_pts4, p->pts4, sizeof(double) * 4 * (size_t)p->n_pts, hipMemcpyDeviceToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->ck_valid = true;
+    return C2B_OK;
+    C2B_API_END("problem_checkpoint")
+}
+
+int c2b_problem_rollback(c2b_problem *p) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_rollback");
+    if (!p->ck_valid) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_rollback: the problem holds no checkpoint");
+    hipStream_t st = p->stream;
+    if (p->n_cam) {
+        HIP_TRY(hipMemcpyAsync(p->bal9, p->ck_bal9, sizeof(double) * 9 * (size_t)p->n_cam, hipMemcpyDeviceToDevice, st));
+        const int rc = c2b_cameras_from_bal(p->bal9, p->n_cam, p->cam15, st);      // the kernel that built cam15: the same bits
+        if (rc) return rc;
+    }
+    if (p->n_pts) HIP_TRY(hipMemcpyAsync(p->pts4, p->ck_pts4, sizeof(double) * 4 * (size_t)p->n_pts, hipMemcpyDeviceToDevice, st));
+    cameras_mutated(p);                                      // the cameras' caches only: rows, transpose, solve buffers, masks stay
+    p->bal_valid = true;
+    HIP_TRY(hipStreamSynchronize(st));
+    return C2B_OK;
+    C2B_API_END("problem_rollback")
+}
+
+int c2b_problem_drop_checkpoint(c2b_problem *p) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_drop_checkpoint: problem is NULL");
+    p->ck_valid = false;                                     // (the buffers stay for the next checkpoint of these counts)
+    return C2B_OK;
+    C2B_API_END("problem_drop_checkpoint")
+}
+
+// c2b_problem::lm, carved: dc [n_cam][9], dp [n_pts][3], the partials of k_lm_norms (kLmSums x grid; k_lm_gradient_max
+// uses the first 2 x grid of them after those were summed), the device scalars: the four sums, then the two maxima
+struct LmBufs {
+    double *dc, *dp, *part, *sc;
+    unsigned grid;
+};
+enum { kLmScGradCam = kLmSums, kLmScGradPts = kLmSums + 1, kLmScSlots = 8 };
+
+static LmBufs lm_bufs(c2b_problem *p) {
+    LmBufs b;
+    b.grid = lm_grid(std::max<int64_t>(9 * p->n_cam, 3 * p->n_pts));
+    b.dc = p->lm;
+    b.dp = b.dc + 9 * p->n_cam;
+    b.part = b.dp + 3 * p->n_pts;
+    b.sc = b.part + (int64_t)kLmSums * b.grid;
+    return b;
+}
+
+static int ensure_lm(c2b_problem *p) {
+    if (p->lm) return C2B_OK;                                // (dropped whenever a count changes)
+    const int64_t n = 9 * p->n_cam + 3 * p->n_pts + (int64_t)kLmSums * lm_grid(std::max<int64_t>(9 * p->n_cam, 3 * p->n_pts)) + kLmScSlots;
+    const hipError_t e = p->lm.alloc((size_t)n);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_levenberg_marquardt: allocation: %s", hipGetErrorString(e));
+    return C2B_OK;
+}
+
+// x^y by libm's pow, as CPython's ** evaluates it: the exponent is kept from the compiler, which would otherwise turn a
+// constant 2 or 3 into multiplications (the last bit can differ)
+static double libm_pow(double x, double y) {
+    volatile double e = y;
+    return std::pow(x, e);
+}
+
+// the cost the loop compares: sum rho(|r|^2) under a loss, else the square of the root total_reprojection_error returns
+// (the numbers of city2ba_amd/solve.py's loop)
+static int lm_cost(c2b_problem *p, double *cost) {
+    if (p->loss_kind != kLossSquared) return c2b_problem_robust_cost(p, cost);
+    double e = 0.0;
+    const int rc = c2b_problem_total_reprojection_error(p, 2.0, &e);
+    if (rc) return rc;
+    *cost = libm_pow(e, 2.0);
+    return C2B_OK;
+}
+
+static int lm_loop(c2b_problem *p, const c2b_lm_options &o, c2b_lm_iteration *history, c2b_lm_summary *summary) {
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    hipStream_t st = p->stream;
+    auto clamp = [](double l) { return std::min(std::max(l, C2B_STEP_LAMBDA_MIN), C2B_STEP_LAMBDA_MAX); };
+    int rc = ensure_lm(p);
+    if (!rc) rc = c2b_problem_checkpoint(p);                 // bal mode; the state every rejected step returns to
+    if (rc) return rc;
+    const LmBufs L = lm_bufs(p);
+    double lam = clamp(o.lambda0), nu = 2.0, e0 = 0.0;
+    if ((rc = lm_cost(p, &e0))) return rc;
+    c2b_lm_summary sum{0, 0, e0, e0, lam};
+    if (!std::isfinite(e0)) sum.termination = 4;
+    while (!sum.termination && sum.iterations < o.max_iterations) {
+        c2b_step_info info;
+        if ((rc = c2b_problem_solve_step(p, lam, o.pcg_max_iters, o.pcg_rel_tol, L.dc, L.dp, &info))) return rc;
+        // the gradient the solve kept (no observation: it has none and g = 0) and the norms of its step and of the state
+        const bool have_g = p->n_obs > 0;
+        hipLaunchKernelGGL(k_lm_norms, dim3(L.grid), dim3(kSchurBlock), 0, st, 9 * nc, np, (const double *)p->bal9,
+                           reinterpret_cast<const double4 *>(p->pts4.ptr), (const double *)L.dc, (const double *)L.dp, L.part);
+        for (int k = 0; k < kLmSums; ++k)
+            fold_sum(st, L.part + (int64_t)k * L.grid, (int)L.grid, L.sc + k);
+        if (have_g) {
+            const SolveBufs B = solve_bufs(p);
+            hipLaunchKernelGGL(k_lm_gradient_max, dim3(L.grid), dim3(kSchurBlock), 0, st, 9 * nc, 3 * np, (const double *)B.gc,
+                               (const double *)B.gp, L.part);
+            hipLaunchKernelGGL(k_lm_max_fold, dim3(1), dim3(kSchurBlock), 0, st, (const double *)L.part, (int)L.grid, L.sc + kLmScGradCam);
+        }
+        HIP_TRY(launch_error());
+        double h[kLmScSlots] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if ((rc = scalars_to_host(st, L.sc, have_g ? kLmScGradPts + 1 : kLmSums, h))) return rc;
+        c2b_lm_iteration it{};
+        it.cost = it.cost_trial = e0;
+        it.lambda = lam;
+        it.model_decrease = info.model_decrease;
+        it.gradient_max = (h[kLmScGradCam] > h[kLmScGradPts] || h[kLmScGradCam] != h[kLmScGradCam]) ? h[kLmScGradCam] : h[kLmScGradPts];
+        it.step_norm = std::sqrt(h[kLmStepCam] + h[kLmStepPts]);
+        it.x_norm = std::sqrt(h[kLmXCam] + h[kLmXPts]);
+        it.pcg_rel_residual = info.rel_residual;
+        it.pcg_iterations = info.iterations;
+        it.status = info.status;
+        c2b_lm_iteration *slot = history ? history + sum.iterations : nullptr;
+        ++sum.iterations;
+        if (!std::isfinite(it.gradient_max)) sum.termination = 4;                 // (the step was not applied: nothing to roll back)
+        else if (o.gradient_tol > 0.0 && it.gradient_max <= o.gradient_tol) sum.termination = 2;
+        else if (o.parameter_tol > 0.0 && it.step_norm <= o.parameter_tol * (it.x_norm + o.parameter_tol)) sum.termination = 3;
+        if (sum.termination) {
+            if (slot) *slot = it;
+            break;
+        }
+        if ((rc = c2b_problem_apply_step(p, L.dc, L.dp))) return rc;
+        double e1 = 0.0;
+        if ((rc = lm_cost(p, &e1))) return rc;
+        it.cost_trial = e1;
+        const double md = info.model_decrease;
+        const double rho = md > 0.0 ? (e0 - e1) / md : -1.0;
+        it.accepted = rho > 0.0 && e1 < e0;
+        if (slot) *slot = it;
+        if (it.accepted) {
+            lam = clamp(lam * std::max(1.0 / 3.0, 1.0 - libm_pow(2.0 * rho - 1.0, 3.0)));
+            nu = 2.0;
+            if ((rc = c2b_problem_checkpoint(p))) return rc;
+            if (o.function_tol > 0.0 && e0 - e1 <= o.function_tol * e0) sum.termination = 1;
+            e0 = e1;
+        } else {
+            if ((rc = c2b_problem_rollback(p))) return rc;
+            lam = clamp(lam * nu);
+            nu *= 2.0;
+            if (!std::isfinite(e1)) sum.termination = 4;
+        }
+    }
+    sum.final_cost = e0;
+    sum.lambda_next = lam;
+    if (summary) *summary = sum;
+    return C2B_OK;
+}
+
+int c2b_problem_levenberg_marquardt(c2b_problem *p, const c2b_lm_options *opt, c2b_lm_iteration *history, int capacity,
+                                    c2b_lm_summary *summary) {
+    C2B_API_BEGIN
+    if (!p || !opt) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: NULL argument");
+    if (opt->max_iterations < 0 || opt->pcg_max_iters < 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: max_iterations and pcg_max_iters must be >= 0");
+    if (!good_lambda(opt->lambda0)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: lambda0 must lie in [1e-20, 1e32]");
+    for (const double t : {opt->pcg_rel_tol, opt->function_tol, opt->gradient_tol, opt->parameter_tol})
+        if (!(t >= 0.0) || !std::isfinite(t))
+            return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: tolerances must be finite and >= 0");
+    if (history && capacity < opt->max_iterations)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: history holds %d entries, max_iterations is %d", capacity,
+                    (int)opt->max_iterations);
+    NEED_UPLOADED(p, "problem_levenberg_marquardt");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: a shard cannot be solved alone (the point-side sums span every rank)");
+    const int rc = lm_loop(p, *opt, history, summary);
+    p->ck_valid = false;                                     // the checkpoint was the loop's
+    return rc;
+    C2B_API_END("problem_levenberg_marquardt")
+}

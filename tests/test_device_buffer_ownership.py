@@ -1,6 +1,6 @@
 """The resident problem's device memory has one owner type ("Who owns it"): DevBuf<T>, defined once in csrc/capi.hip.
-Every device array of struct c2b_problem and every temporary of csrc/capi_problem.hpp and csrc/capi_files.hpp is one,
-so neither file allocates or frees by hand: there is no free list to keep in step with the members, and a launch takes
+Every device array of struct c2b_problem and every temporary of csrc/capi_problem.hpp, the two headers split from it (capi_solve.hpp, capi_graph.hpp) and
+csrc/capi_files.hpp is one, so none of them allocates or frees by hand: there is no free list to keep in step with the members, and a launch takes
 the buffer as the typed pointer it holds.  What is held here is that it stays that way.  (That nothing leaks through
 it on the device is tests/test_gpu_leak.py's.)"""
 import glob
@@ -9,7 +9,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "city2ba_amd", "csrc")
-LEVEL1 = ("capi_problem.hpp", "capi_files.hpp")
+LEVEL1 = ("capi_problem.hpp", "capi_solve.hpp", "capi_graph.hpp", "capi_files.hpp")
 DEFINITION = r"(?m)^template <class T>\nstruct DevBuf \{\n"
 
 
