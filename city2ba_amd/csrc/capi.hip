@@ -254,11 +254,19 @@ void launch_jac_l(const double *camblk, const double *pts4, const uint32_t *cam_
     } else {
     const int btiles = (int)(((n_obs + 63) / 64 + WPB * OPL - 1) / (WPB * OPL));
     constexpr int kMinW = (MINW == 1 && OPL == 2) ? 4 : MINW;
+    // 512 threads x 2 tiles: the XCDs' ranges cut 11 : 9 between even and odd XCDs (xcd_cuts.hpp) -- host arithmetic on the tile count
+    // alone, so nothing is kept per row structure; one partial per workgroup must fit the workspace (always: <= 1.1 btiles + 8)
+    XcdCuts cuts{};
+    int grid = btiles;
+    if constexpr (WPB == 8 && OPL == 2) {
+        grid = xcd_cuts_make(btiles, kXcdEvenShare, kXcdOddShare, cuts);
+        if (grid > block_part_slots(n_obs)) grid = xcd_cuts_make(btiles, 1, 1, cuts);
+    }
 #define C2B_GO(NK)                                                                                                      \
-    hipLaunchKernelGGL((k_residual_jacobian_l<NK, WITH_ERR, WPB, NTS, OPL, kMinW, OBUP, CSR, NTL>), dim3((unsigned)btiles),        \
+    hipLaunchKernelGGL((k_residual_jacobian_l<NK, WITH_ERR, WPB, NTS, OPL, kMinW, OBUP, CSR, NTL>), dim3((unsigned)grid),          \
                        dim3(WPB * 64), 0, st, camblk, reinterpret_cast<const double4 *>(pts4), cam_idx, pt_idx,        \
                        reinterpret_cast<const double2 *>(uv_obs), (int)n_obs, btiles, norm,                            \
-                       reinterpret_cast<double2 *>(r), Jc, Jp, block_part, ticket, out_sum, row_ptr, (int)n_cam, obs_base)
+                       reinterpret_cast<double2 *>(r), Jc, Jp, block_part, ticket, out_sum, row_ptr, (int)n_cam, obs_base, cuts)
     if constexpr (!WITH_ERR) { C2B_GO(NORM_2); }
     else if (norm == 2.0) C2B_GO(NORM_2);
     else if (norm == 1.0) C2B_GO(NORM_1);

@@ -12,11 +12,13 @@
 //     lane strides are bank-conflict-free for ds_write_b128) and leave as 1-KiB-per-instruction
 //     contiguous non-temporal stores -- the kernel's 208 B/observation of output binds it to HBM;
 //   * tile -> workgroup map is XCD-aware: the 8 XCDs each stream a contiguous eighth of the
-//     observation list so that a camera's / point's neighbours hit the same 4 MiB L2;
+//     observation list so that a camera's / point's neighbours hit the same 4 MiB L2 (the step
+//     kernel's 512 x 2 shape: a contiguous range cut by the XCDs' measured rates, xcd_cuts.hpp);
 //   * reductions are wave shuffles -> per-tile partial -> fixed-order two-stage fold
 //     (no float atomics: run-to-run reproducible).
 #pragma once
 #include "camera_math.hpp"
+#include "xcd_cuts.hpp"
 
 namespace c2b {
 
@@ -825,6 +827,8 @@ C2B_DEV void jacobian_obs(P cam, const double4 X, const double2 ob, double &r0, 
 // CSR: cam_idx points at the tile records of k_rows_pack (for this launch's first observation, which is observation
 //      obs_base of the list row_ptr describes) instead of one camera index per observation
 // NTL: bit 0 = non-temporal loads of the index streams, bit 1 = of the observed uv (streams read once per launch)
+// cuts: the 512-thread x 2-tile shape takes its workgroup tile from the XCD ranges the launcher cut (xcd_cuts.hpp; workgroups past
+// their range's end only fold); the other shapes keep the equal eighths of xcd_tile32 and ignore it
 template <int NK, bool WITH_ERR, int WPB, bool NT, int OPL, int MINW, bool OBUP = true, bool CSR = false, int NTL = 0>
 __global__ __launch_bounds__(WPB * 64, MINW) void k_residual_jacobian_l(
     const double *__restrict__ camblk, const double4 *__restrict__ pts4,
@@ -832,14 +836,16 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_residual_jacobian_l(
     const double2 *__restrict__ uv_obs, int n, int n_btiles, double norm,
     double2 *__restrict__ r_out, double *__restrict__ Jc, double *__restrict__ Jp,
     double *__restrict__ block_part, unsigned *__restrict__ ticket, double *__restrict__ out_sum,
-    const uint64_t *__restrict__ row_ptr, int n_cam, int64_t obs_base) {
+    const uint64_t *__restrict__ row_ptr, int n_cam, int64_t obs_base, const XcdCuts cuts) {
     constexpr int kSlab = 64 * 144 / 2;                                  // half a tile's 2x9 blocks (two rounds)
     constexpr int kCamBytes = 2 * kCamW * kCamHot * 8 + 64;              // staged cameras | slow-path slots | picked ids
     __shared__ __attribute__((aligned(16))) char smem[WPB * (kSlab + kCamBytes)];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int base = (xcd_tile32(blockIdx.x, n_btiles) * WPB + wave) * (OPL * 64);
+    constexpr bool CUTS = WPB == 8 && OPL == 2;
+    const int wtile = CUTS ? xcd_cut_tile(blockIdx.x, cuts) : xcd_tile32(blockIdx.x, n_btiles);
+    const int base = wtile < 0 ? n : (wtile * WPB + wave) * (OPL * 64);
     double eacc = 0.0;
     if (base < n) {                                                      // wave-uniform; waves past the end only fold
         uint32_t ci[OPL], pi[OPL];
