@@ -94,6 +94,10 @@ FILTER_IN_FRONT = 1        # C2B_FILTER_IN_FRONT: also drop an observation whose
 TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_BEHIND, TRI_CONSTANT = range(5)
 TRI_STATUS = ("triangulated", "too_few", "degenerate", "behind", "constant")
 
+# statuses of c2b_problem_resect_cameras / c2b_resect_rows (C2B_RES_*), the order of their counts
+RES_OK, RES_TOO_FEW, RES_DEGENERATE, RES_BEHIND, RES_CONSTANT = range(5)
+RES_STATUS = ("resected", "too_few", "degenerate", "behind", "constant")
+
 
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
 SIGNATURES = {
@@ -126,6 +130,7 @@ SIGNATURES = {
     "c2b_visibility_rows_bits": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_residual_keep_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _d, _int, _vp, _vp]),
     "c2b_triangulate_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "c2b_resect_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp]),
     "c2b_reprojection_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "c2b_add_noise_observations_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _d, _u64, _vp, _vp, _vp]),
     "c2b_jacobian_stream_policy": (_int, [_i64, _i64, _i64]),
@@ -160,6 +165,7 @@ SIGNATURES = {
     "c2b_problem_levenberg_marquardt": (_int, [_vp, _vp, _vp, _int, _vp]),
     "c2b_problem_filter_observations": (_int, [_vp, _d, _int, C.POINTER(_i64)]),
     "c2b_problem_triangulate_points": (_int, [_vp, _d, _vp, _vp]),
+    "c2b_problem_resect_cameras": (_int, [_vp, _int, _d, _vp, _vp]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
     "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),

@@ -542,6 +542,24 @@ class BAProblem:
         out = dict(zip(L.TRI_STATUS, (int(v) for v in counts)))
         return (out, status) if return_status else out
 
+    def resect_cameras(self, min_points=6, min_gap=1e-4, return_status=False):
+        """Camera resection on the device (c2b_problem_resect_cameras): every camera's pose is set from the
+        points as they are and its observations -- the minimiser of the object-space error, from a linear start, with f,
+        k1 and k2 kept: a start for a solve, not a refinement, and the dual of triangulate_points.  A camera keeps its
+        bits when its pose is (partly) constant, when it has fewer than min_points (>= 6) usable observations, when its
+        points are too close to coplanar or too little spread (lambda_2 < min_gap lambda_9 of the 9x9 form, or noise
+        that swamps the gap), or when a point would lie behind it.  The loss on the handle is ignored; masks, loss,
+        preconditioner and a checkpoint stay; the problem is in bal mode afterwards, as after apply_step.  Returns
+        dict(resected, too_few, degenerate, behind, constant), the number of cameras of each outcome, and with
+        return_status also the uint8 status per camera (the dict's order: 0 .. 4)."""
+        counts = np.zeros(5, dtype=np.int64)
+        status = np.zeros(self.num_cameras(), dtype=np.uint8) if return_status else None
+        L.check(L.lib().c2b_problem_resect_cameras(self._h, int(min_points), float(min_gap),
+                                                   status.ctypes.data_as(C.c_void_p) if return_status else None,
+                                                   counts.ctypes.data_as(C.c_void_p)))
+        out = dict(zip(L.RES_STATUS, (int(v) for v in counts)))
+        return (out, status) if return_status else out
+
     def subset(self, ci, pi):
         """BAProblem::subset (src/baproblem.rs:394-423): cameras ci and points pi in the given order; observations of
         dropped points disappear.  Host-side index shuffling; returns a NEW device problem."""

@@ -25,6 +25,8 @@
 //                         --filter-max-error: N times solve + c2b_problem_filter_observations, then a solve without a loss)
 //   city2ba triangulate IN OUT [--min-angle DEG]
 //                        (extension: the points from the cameras and observations, c2b_problem_triangulate_points)
+//   city2ba resect IN OUT [--min-points N] [--min-gap G]
+//                        (extension: the camera poses from the points and observations, c2b_problem_resect_cameras)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -907,6 +909,38 @@ int run_triangulate(int argc, char **argv) {
     return 0;
 }
 
+// `resect`: every camera pose of a .bal / .bbal from its points and observations by c2b_problem_resect_cameras (an
+// extension: the minimiser of the object-space error on the device; points, intrinsics and observations are written as they
+// were read).  Every argument is parsed before the device is touched.
+int run_resect(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {}, {"min-points", "min-gap", "device"});
+    if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
+    const int64_t min_points = a.i("min-points", 6);
+    const double min_gap = a.f("min-gap", 1e-4);
+    const int device = (int)a.i("device", 0);
+    if (min_points < 6 || min_points > 2147483647) die("Invalid value for '--min-points <N>': expected an integer of at least 6");
+    if (!(min_gap >= 0.0 && min_gap < 1.0)) die("Invalid value for '--min-gap <G>': expected a number in 0 ... 1 (1 excluded)");
+    PhaseTimer timer;
+    c2b_problem *p = nullptr;
+    ck(create_problem(device, &p));
+    timer.mark("problem_create (HIP runtime start)");
+    ck(c2b_problem_read(p, a.positional[0].c_str(), -1));
+    timer.mark("read (c2b_problem_read: decoded on the device)");
+    int64_t nc = 0, np = 0, no = 0;
+    ck(c2b_problem_sizes(p, &nc, &np, &no));
+    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
+    int64_t counts[5] = {0, 0, 0, 0, 0};
+    ck(c2b_problem_resect_cameras(p, (int)min_points, min_gap, nullptr, counts));
+    timer.mark("resect_cameras (device)");
+    std::printf("resected %lld cameras; kept: %lld too few observations, %lld degenerate, %lld behind a point, %lld constant\n",
+                (long long)counts[C2B_RES_OK], (long long)counts[C2B_RES_TOO_FEW], (long long)counts[C2B_RES_DEGENERATE],
+                (long long)counts[C2B_RES_BEHIND], (long long)counts[C2B_RES_CONSTANT]);
+    ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
+    timer.mark("write (c2b_problem_write: the file image is built on the device)");
+    c2b_problem_destroy(p);
+    return 0;
+}
+
 void usage() {
     std::printf("city2ba (MI355X build, %s)\nTools for generating synthetic bundle adjustment problems.\n\n"
                 "USAGE:\n    city2ba <SUBCOMMAND>\n\nSUBCOMMANDS:\n"
@@ -916,7 +950,8 @@ void usage() {
                 "    generate          Generate a synthetic bundle adjustment problem from a 3D model.\n"
                 "    ply               Convert a .bal or .bbal to a .ply for visualization.\n"
                 "    solve             Bundle-adjust a .bal or .bbal by Levenberg-Marquardt on the device.\n"
-                "    triangulate       Set the points of a .bal or .bbal from its cameras and observations.\n",
+                "    triangulate       Set the points of a .bal or .bbal from its cameras and observations.\n"
+                "    resect            Set the camera poses of a .bal or .bbal from its points and observations.\n",
                 c2b_version());
 }
 
@@ -966,6 +1001,11 @@ const char *subcommand_help(const std::string &sub) {
     if (sub == "triangulate")
         return "city2ba triangulate <FILE> <OUT>\n"
                "    --min-angle <DEG> [1]     parallax test: a point whose rays are less than DEG degrees apart keeps its position\n";
+    if (sub == "resect")
+        return "city2ba resect <FILE> <OUT>\n"
+               "    --min-points <N> [6]      a camera with fewer usable observations keeps its pose (at least 6)\n"
+               "    --min-gap <G> [1e-4]      degeneracy test: a camera whose points are so close to coplanar, or so little spread, that\n"
+               "                              lambda_2 < G lambda_9 keeps its pose\n";
     return nullptr;
 }
 
@@ -990,5 +1030,6 @@ int main(int argc, char **argv) {
     if (sub == "ply") return run_ply(argc, argv);
     if (sub == "solve") return run_solve(argc, argv);
     if (sub == "triangulate") return run_triangulate(argc, argv);
+    if (sub == "resect") return run_resect(argc, argv);
     die("The subcommand '" + sub + "' wasn't recognized");
 }

@@ -1487,6 +1487,30 @@ int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, cons
     C2B_API_END("triangulate_rows")
 }
 
+// ---- camera resection (resect_kernels.hpp) ------------------------------------------------------------------
+static bool good_min_gap(double g) { return g >= 0.0 && g < 1.0; }                  // (a NaN fails both)
+
+int c2b_resect_rows(double *bal9, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx, const double *uv_obs,
+                    int min_points, double min_gap, const uint16_t *cam_mask, uint8_t *status, int64_t *counts, void *stream) {
+    C2B_API_BEGIN
+    if (n_cam < 0 || n_cam > (int64_t)0x7fffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_rows: n_cam out of range");
+    if (min_points < kResMinPoints) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_rows: min_points must be at least %d", kResMinPoints);
+    if (!good_min_gap(min_gap)) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_rows: min_gap must lie in [0, 1)");
+    if (!counts || (n_cam && (!bal9 || !row_ptr || !status))) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_rows: NULL argument");
+    if (!aligned8(bal9) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(row_ptr) || !aligned8(counts) ||
+        (reinterpret_cast<uintptr_t>(pt_idx) & 3) || (reinterpret_cast<uintptr_t>(cam_mask) & 1))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "resect_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kResKinds, st));
+    if (!n_cam) return C2B_OK;
+    hipLaunchKernelGGL(k_resect_cameras, dim3(blocks_for(n_cam, kResWaves)), dim3(kResBlock), 0, st, bal9, reinterpret_cast<const double4 *>(pts4),
+                       row_ptr, n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs), min_points, min_gap, cam_mask, status,
+                       reinterpret_cast<unsigned long long *>(counts));
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("resect_rows")
+}
+
 // grid of k_schur_cameras: one wave per kNormCamsPerWave cameras
 static unsigned schur_cameras_grid(int64_t n_cam) {
     const int64_t quads = (n_cam + kNormCamsPerWave - 1) / kNormCamsPerWave, waves = kNormBlock / 64;

@@ -80,6 +80,7 @@ struct c2b_problem {
 //   apply_step, rollback (5)   X            truth      -     -          -      -             -           -
 //   noise (drift, noise, sin)  X            X          -     -          -      -             -           -
 //   triangulate_points         -            -          -     -          -      -             -           -
+//   resect_cameras             X            truth      -     -          -      -             -           -
 // (1) kept when both counts are those the masks were set for.  (2) gathered with the cameras while it is the truth; a merely
 // fresh bal9 (bal9_fresh: to_vec of the current cameras, filled by download_bal / write / apply_step) is dropped.  (3) on
 // entry, so also by a cull that fails later.  (4) one that removes nothing drops nothing.  (5) checkpoint is an apply_step

@@ -492,6 +492,52 @@ int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *st
     C2B_API_END("problem_triangulate_points")
 }
 
+// ---- camera resection ---------------------------------------------------------------------------------
+// The resident cameras' poses from the resident points and observations: c2b_resect_rows over the row structure, in place
+// on bal9, which is made the truth first as c2b_problem_apply_step makes it (state mode: to_vec of the cameras) and stays
+// the truth: the cameras moved, so their caches go (cameras_mutated) exactly as after a camera step.  The list, the row
+// structure, the transpose, the solve buffers, the masks, the loss, the preconditioner and a checkpoint all stay.
+int c2b_problem_resect_cameras(c2b_problem *p, int min_points, double min_gap, uint8_t *status, int64_t *counts) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_resect_cameras");
+    if (min_points < kResMinPoints) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_cameras: min_points must be at least %d", kResMinPoints);
+    if (!good_min_gap(min_gap)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_cameras: min_gap must lie in [0, 1)");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_cameras: a shard is not resected alone");
+    const int64_t nc = p->n_cam;
+    int64_t got[kResKinds] = {0, 0, 0, 0, 0};
+    if (!p->n_obs) {                                         // no observation: every camera has too few, nothing is read or written
+        got[kResTooFew] = nc;
+        if (status && nc) std::fill(status, status + nc, (uint8_t)kResTooFew);
+        if (counts) std::copy(got, got + kResKinds, counts);
+        return C2B_OK;
+    }
+    int rc = ensure_rows(p);
+    if (rc) return rc;
+    DevBuf<uint8_t> d_status;
+    DevBuf<int64_t> d_counts;
+    hipError_t e = d_status.alloc((size_t)nc);
+    if (e == hipSuccess) e = d_counts.alloc(kResKinds);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_resect_cameras: allocation: %s", hipGetErrorString(e));
+    hipStream_t st = p->stream;
+    if (!p->bal_valid && !p->bal9_fresh) {                   // state mode: the pass works on to_vec(cam15)
+        if ((rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st))) return rc;
+        p->bal9_fresh = true;
+    }
+    rc = c2b_resect_rows(p->bal9, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, min_points, min_gap, p->cmask, d_status, d_counts, st);
+    if (!rc) rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
+    if (!rc && status) e = hipMemcpyAsync(status, d_status, (size_t)nc, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);          // the temporaries are freed below
+    cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
+    p->bal_valid = true;
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(C2B_ERR_HIP, "problem_resect_cameras: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    if (counts) std::copy(got, got + kResKinds, counts);
+    return C2B_OK;
+    C2B_API_END("problem_resect_cameras")
+}
+
 // ---- Levenberg-Marquardt on the device -----------------------------------------------------------------
 int c2b_problem_checkpoint(c2b_problem *p) {
     C2B_API_BEGIN

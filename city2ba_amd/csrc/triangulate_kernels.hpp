@@ -23,13 +23,16 @@ constexpr int kTriBlock = 256;
 // C2B_TRI_* of include/city2ba_hip_experimental.h
 enum { kTriOk = 0, kTriTooFew = 1, kTriDegenerate = 2, kTriBehind = 3, kTriConstant = 4, kTriKinds = 5 };
 
-// The unit ray of the observed pixel `ob` of camera `cam` in the world frame; false when the observation is unusable
-// (f zero or not finite, the derivative of the distortion <= 0 at a Newton iterate, a radius that is not finite).
+// The unit ray of the observed pixel `ob` of camera `cam` (a camblk record, or anything indexed like one); false when the
+// observation is unusable (f zero or not finite, the derivative of the distortion <= 0 at a Newton iterate, a radius that
+// is not finite).
 //   m = ob / f, rd = |m|; rho >= 0 with rho (1 + k1 rho^2 + k2 rho^4) = rd by Newton from rho = rd, at most 16 iterations,
 //   stopping when the update leaves rho unchanged (k1 == 0 && k2 == 0: rho = rd, no iteration); pn = m rho / rd (0 at rd == 0).
-// The projection is p = -q.xy / q.z with the scene at q.z < 0, so the ray in the camera frame is (pn.x, pn.y, -1); the
-// record's R is row-major, d = R^T ray, normalised.
-template <typename P>
+// The projection is p = -q.xy / q.z with the scene at q.z < 0, so the ray in the camera frame is (pn.x, pn.y, -1).  That
+// much depends on the intrinsics cam[12..14] alone and is shared by triangulation and resection (resect_kernels.hpp):
+//   kWorld      the ray in the world frame: the record's R is row-major, d = R^T ray, normalised (reads cam[0..8]);
+//   !kWorld     the ray in the camera frame, normalised: nothing of the pose is read.
+template <bool kWorld = true, typename P>
 C2B_DEV bool tri_ray(P cam, const double2 ob, double &dx, double &dy, double &dz) {
     const double f = cam[12], k1 = cam[13], k2 = cam[14];
     if (f == 0.0 || !isfinite(f)) return false;
@@ -51,11 +54,16 @@ C2B_DEV bool tri_ray(P cam, const double2 ob, double &dx, double &dy, double &dz
     if (!isfinite(rho)) return false;
     const double s = rd == 0.0 ? 0.0 : rho / rd;
     const double px = mx * s, py = my * s;
-    const double wx = (cam[0] * px + cam[3] * py) - cam[6];
-    const double wy = (cam[1] * px + cam[4] * py) - cam[7];
-    const double wz = (cam[2] * px + cam[5] * py) - cam[8];
-    const double inv = 1.0 / sqrt((wx * wx + wy * wy) + wz * wz);
-    dx = wx * inv; dy = wy * inv; dz = wz * inv;
+    if constexpr (kWorld) {
+        const double wx = (cam[0] * px + cam[3] * py) - cam[6];
+        const double wy = (cam[1] * px + cam[4] * py) - cam[7];
+        const double wz = (cam[2] * px + cam[5] * py) - cam[8];
+        const double inv = 1.0 / sqrt((wx * wx + wy * wy) + wz * wz);
+        dx = wx * inv; dy = wy * inv; dz = wz * inv;
+    } else {
+        const double inv = 1.0 / sqrt((px * px + py * py) + 1.0);
+        dx = px * inv; dy = py * inv; dz = -inv;
+    }
     return true;
 }
 

@@ -293,6 +293,15 @@ def triangulate_rows(camblk, pts4, prows, uv, status, counts, min_angle, pt_mask
     return status, counts
 
 
+def resect_rows(bal9, pts4, rows, pt_idx, uv, status, counts, min_points=6, min_gap=1e-4, cam_mask=None):
+    """camera resection (c2b_resect_rows): bal9 [n_cam,9] in place (entries 0..5; 6..8 are the intrinsics read) from each
+    camera's row of observations (Rows); status [n_cam] uint8 (_lib.RES_STATUS order), counts [5] int64 = how many cameras
+    took each status; cam_mask [n_cam] uint16 (an OR of C2B_CONST_* bits: a pose bit keeps the camera) or None"""
+    L.check(L.lib().c2b_resect_rows(_p(bal9), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), int(min_points), float(min_gap),
+                                    _p(cam_mask), _p(status), _p(counts), _stream()))
+    return status, counts
+
+
 def residual_jacobian_rows(camblk, pts4, rows, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None, out_sum=None, obs_base=0,
                            n_obs=None):
     """residual + Jacobian (+ sum |r|^norm when ws is given: into out_sum, or into ws for error_sum_finish) of the

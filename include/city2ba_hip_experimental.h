@@ -323,6 +323,48 @@ int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, cons
                          int64_t *counts, void *stream);
 int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *status, int64_t *counts);
 
+/* ---- resection: camera poses from points and observations (object-space error, one wave per camera) ----
+ * The dual of triangulation: camera c's pose (R, t) from the points as they are, its f, k1, k2 kept.  The camera's row of
+ * the camera-major list is walked in ascending order.  Per observation of point X, observed (u, v), with f, k1, k2 =
+ * bal9[c][6..8]:
+ *   the undistorted pixel pn exactly as triangulation forms it (m = (u, v) / f; Newton for rho (1 + k1 rho^2 + k2 rho^4) =
+ *   |m| from rho = |m|, at most 16 iterations; pn = m rho / |m|), the same unusable cases, and also unusable when X is not
+ *   finite; b = (pn.x, pn.y, -1) normalised, P = I - b b^T.
+ * With Xbar the mean of the usable points and Y = X - Xbar, sixty sums are formed in row order: S0 = sum P, S1[a] = sum
+ * Y_a P, S2[ac] = sum Y_a Y_c P (the upper triangles).  The object-space error sum |P (R Y + t')|^2 has t' = -S0^-1 sum_a
+ * S1[a] R[:, a]; what remains is r^T M r with r[3 a + i] = R[i][a] and M[(a,i),(c,j)] = S2[ac][ij] - (S1[a] S0^-1 S1[c])_ij.
+ * lambda_1 <= ... <= lambda_9 are M's eigenvalues (cyclic Jacobi), g the unit eigenvector of lambda_1, G[i][a] = g[3 a + i]
+ * negated if det G < 0, R0 the rotation nearest G; then at most 8 Gauss-Newton iterations on r^T M r over R <- exp([d]x) R
+ * (H = J^T M J, d = -H^-1 J^T M r, J = [vec([e_k]x R)]), stopping when |d| <= 1e-14; t = t'(R) - R Xbar.  In this order:
+ *   C2B_RES_CONSTANT   the camera's mask word holds any of the six pose bits (C2B_CONST_POSE); none of its observations is read;
+ *   C2B_RES_TOO_FEW    n_used < min_points;
+ *   C2B_RES_DEGENERATE a pivot of S0's 3x3 Cholesky is not > 0; or an eigenvalue is not finite, lambda_2 < min_gap lambda_9
+ *                      (coplanar points, too little spread; evaluated from the raw min_gap: 0 disables it) or lambda_1 >=
+ *                      lambda_2 / 4 (noise swamps the gap); or H is not positive definite, or d, R or t is not finite;
+ *   C2B_RES_BEHIND     a usable observation has (R X + t).z >= 0 (a second walk over the row);
+ *   C2B_RES_OK         bal9[c][0..5] = (to_rodrigues(R), t); entries 6..8 keep their bits.
+ * A camera whose status is not C2B_RES_OK keeps all nine.  No robust loss enters: the loss on the handle is ignored.  A
+ * camera's result depends on its own row alone and there are no float atomics: the same inputs give the same bits.  The
+ * pass uses no scratch memory.  min_points < 6, min_gap negative, NaN or >= 1: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_resect_rows: Level 0, stateless, asynchronous on `stream`.  bal9 [n_cam][9] is updated in place; cam_mask (device,
+ *   [n_cam] c2b_camera_mask) may be NULL; status [n_cam] one byte per camera; counts [5] (device int64, indexed by status)
+ *   is zeroed and then summed by integer atomics.  pts4, pt_idx and uv_obs are read only where a row holds an observation.
+ * c2b_problem_resect_cameras: Level 1, synchronous.  bal9 is made the truth as c2b_problem_apply_step makes it (state mode:
+ *   to_vec of the cameras first), the pass runs over the problem's row structure with its camera mask, and the state is
+ *   rebuilt from bal9 (from_vec); the problem is in bal mode afterwards, as after a camera step.  status (host, [n_cam]) and
+ *   counts (host, [5]) may be NULL.  The list, the row structure, the transpose, the solve buffers, the constant masks, the
+ *   loss, the preconditioner and a checkpoint all stay; a checkpoint taken before the call rolls the cameras back.  A problem
+ *   without observations returns C2B_RES_TOO_FEW for every camera and writes nothing.  A problem with a shard set is
+ *   refused, and so is every bad argument, with the problem unchanged. */
+#define C2B_RES_OK 0
+#define C2B_RES_TOO_FEW 1
+#define C2B_RES_DEGENERATE 2
+#define C2B_RES_BEHIND 3
+#define C2B_RES_CONSTANT 4
+int c2b_resect_rows(double *bal9, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx, const double *uv_obs,
+                    int min_points, double min_gap, const c2b_camera_mask *cam_mask, uint8_t *status, int64_t *counts, void *stream);
+int c2b_problem_resect_cameras(c2b_problem *p, int min_points, double min_gap, uint8_t *status, int64_t *counts);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
