@@ -93,6 +93,10 @@ FILTER_IN_FRONT = 1        # C2B_FILTER_IN_FRONT: also drop an observation whose
 # statuses of c2b_problem_triangulate_points / c2b_triangulate_rows (C2B_TRI_*), the order of their counts
 TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_BEHIND, TRI_CONSTANT = range(5)
 TRI_STATUS = ("triangulated", "too_few", "degenerate", "behind", "constant")
+# c2b_problem_triangulate_consensus / c2b_triangulate_consensus_rows add one status (C2B_TRI_NO_CONSENSUS) and one flag
+TRI_NO_CONSENSUS = 5
+TRI_CONSENSUS_STATUS = TRI_STATUS + ("no_consensus",)
+TRI_DROP_OUTLIERS = 1      # C2B_TRI_DROP_OUTLIERS: compact the list by the inlier mask afterwards
 
 # statuses of c2b_problem_resect_cameras / c2b_resect_rows (C2B_RES_*), the order of their counts
 RES_OK, RES_TOO_FEW, RES_DEGENERATE, RES_BEHIND, RES_CONSTANT = range(5)
@@ -130,6 +134,7 @@ SIGNATURES = {
     "c2b_visibility_rows_bits": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_residual_keep_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _d, _int, _vp, _vp]),
     "c2b_triangulate_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "c2b_triangulate_consensus_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_resect_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp]),
     "c2b_reprojection_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "c2b_add_noise_observations_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _d, _u64, _vp, _vp, _vp]),
@@ -165,6 +170,7 @@ SIGNATURES = {
     "c2b_problem_levenberg_marquardt": (_int, [_vp, _vp, _vp, _int, _vp]),
     "c2b_problem_filter_observations": (_int, [_vp, _d, _int, C.POINTER(_i64)]),
     "c2b_problem_triangulate_points": (_int, [_vp, _d, _vp, _vp]),
+    "c2b_problem_triangulate_consensus": (_int, [_vp, _d, _d, _int, _int, _int, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_resect_cameras": (_int, [_vp, _int, _d, _vp, _vp]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),

@@ -542,6 +542,42 @@ class BAProblem:
         out = dict(zip(L.TRI_STATUS, (int(v) for v in counts)))
         return (out, status) if return_status else out
 
+    def triangulate_points_robust(self, max_error, min_angle_deg=1.0, min_inliers=3, max_hypotheses=64, drop_outliers=False,
+                                  return_status=False, return_inliers=False):
+        """Consensus triangulation on the device (c2b_problem_triangulate_consensus): triangulate_points for a
+        list that holds wrong matches.  Per point, candidates are formed from pairs of its rays (at most max_hypotheses <= 64,
+        wide pairs first, from the usable observations among the row's first 64), each is scored by how many observations of
+        the point it reprojects within max_error in front of their cameras (filter_observations' predicate with in_front),
+        and the point is set to the midpoint of the best candidate's inliers -- if there are min_inliers (>= 2) of them,
+        they pass the parallax test and none of their cameras sees the point from behind; otherwise it keeps its bits.
+        With drop_outliers the observations of the triangulated points that are not inliers are then removed from the
+        list as filter_observations removes its own.  Returns dict(triangulated, too_few, degenerate, behind, constant,
+        no_consensus, outliers, removed): the number of points of each outcome, the zeros of the inlier mask and how many
+        observations left the list; with return_status also (status [n_pts] uint8 in the dict's order 0 .. 5, hyp
+        [n_pts] int32 = the selected pair or -1), with return_inliers also the mask [n_obs] uint8 over the list as it was
+        at the call."""
+        n_pts, n_obs = self.num_points(), self.num_observations()
+        counts = np.zeros(6, dtype=np.int64)
+        status = np.zeros(n_pts, dtype=np.uint8)
+        hyp = np.zeros(n_pts, dtype=np.int32)
+        inlier = np.ones(n_obs, dtype=np.uint8)
+        removed = C.c_int64()
+        L.check(L.lib().c2b_problem_triangulate_consensus(
+            self._h, float(np.deg2rad(float(min_angle_deg))), float(max_error), int(min_inliers), int(max_hypotheses),
+            L.TRI_DROP_OUTLIERS if drop_outliers else 0, status.ctypes.data_as(C.c_void_p), hyp.ctypes.data_as(C.c_void_p),
+            inlier.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), C.byref(removed)))
+        if removed.value:
+            self._refresh_graph()
+        out = dict(zip(L.TRI_CONSENSUS_STATUS, (int(v) for v in counts)))
+        out["outliers"] = int(n_obs - np.count_nonzero(inlier))
+        out["removed"] = int(removed.value)
+        ret = (out,)
+        if return_status:
+            ret += (status, hyp)
+        if return_inliers:
+            ret += (inlier,)
+        return ret if len(ret) > 1 else out
+
     def resect_cameras(self, min_points=6, min_gap=1e-4, return_status=False):
         """Camera resection on the device (c2b_problem_resect_cameras): every camera's pose is set from the
         points as they are and its observations -- the minimiser of the object-space error, from a linear start, with f,

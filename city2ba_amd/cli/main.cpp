@@ -23,8 +23,9 @@
 //                         --filter-max-error X --filter-rounds N --filter-in-front]
 //                        (extension: Levenberg-Marquardt on the device, c2b_problem_levenberg_marquardt; with
 //                         --filter-max-error: N times solve + c2b_problem_filter_observations, then a solve without a loss)
-//   city2ba triangulate IN OUT [--min-angle DEG]
-//                        (extension: the points from the cameras and observations, c2b_problem_triangulate_points)
+//   city2ba triangulate IN OUT [--min-angle DEG] [--max-error X [--min-inliers N] [--max-hypotheses H] [--drop-outliers]]
+//                        (extension: the points from the cameras and observations, c2b_problem_triangulate_points; with
+//                         --max-error: from the rays that agree with each other, c2b_problem_triangulate_consensus)
 //   city2ba resect IN OUT [--min-points N] [--min-gap G]
 //                        (extension: the camera poses from the points and observations, c2b_problem_resect_cameras)
 //
@@ -881,13 +882,23 @@ int run_solve(int argc, char **argv) {
 
 // `triangulate`: every point of a .bal / .bbal from its cameras and observations by c2b_problem_triangulate_points (an
 // extension: linear midpoint triangulation on the device; cameras and observations are written as they were read).  Every
-// argument is parsed before the device is touched.
+// argument is parsed before the device is touched.  --max-error X selects consensus triangulation
+// (c2b_problem_triangulate_consensus): candidates from pairs of rays, the one most observations reproject within X of, a
+// refit on those; --drop-outliers then removes the other observations of the triangulated points from the list.
 int run_triangulate(int argc, char **argv) {
-    const Args a = parse(argc, argv, 2, {}, {"min-angle", "device"});
+    const Args a = parse(argc, argv, 2, {"drop-outliers"}, {"min-angle", "device", "max-error", "min-inliers", "max-hypotheses"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
     const double min_angle_deg = a.f("min-angle", 1.0);
     const int device = (int)a.i("device", 0);
     if (!(min_angle_deg >= 0.0 && min_angle_deg <= 90.0)) die("Invalid value for '--min-angle <DEG>': expected a number in 0 ... 90");
+    const bool robust = a.has("max-error");
+    const double max_error = a.f("max-error", 0.0);
+    const int64_t min_inliers = a.i("min-inliers", 3), max_hypotheses = a.i("max-hypotheses", 64);
+    if (robust && !(max_error >= 0.0 && std::isfinite(max_error))) die("Invalid value for '--max-error <X>': expected a finite number >= 0");
+    if (min_inliers < 2 || min_inliers > 2147483647) die("Invalid value for '--min-inliers <N>': expected an integer of at least 2");
+    if (max_hypotheses < 1 || max_hypotheses > 64) die("Invalid value for '--max-hypotheses <H>': expected an integer in 1 ... 64");
+    if (!robust && (a.has("min-inliers") || a.has("max-hypotheses") || a.has("drop-outliers")))
+        die("--min-inliers, --max-hypotheses and --drop-outliers need --max-error <X>");
     PhaseTimer timer;
     c2b_problem *p = nullptr;
     ck(create_problem(device, &p));
@@ -897,12 +908,25 @@ int run_triangulate(int argc, char **argv) {
     int64_t nc = 0, np = 0, no = 0;
     ck(c2b_problem_sizes(p, &nc, &np, &no));
     std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
-    int64_t counts[5] = {0, 0, 0, 0, 0};
-    ck(c2b_problem_triangulate_points(p, min_angle_deg * (3.14159265358979323846 / 180.0), nullptr, counts));
-    timer.mark("triangulate_points (device)");
-    std::printf("triangulated %lld points; kept: %lld too few observations, %lld degenerate, %lld behind a camera, %lld constant\n",
-                (long long)counts[C2B_TRI_OK], (long long)counts[C2B_TRI_TOO_FEW], (long long)counts[C2B_TRI_DEGENERATE],
-                (long long)counts[C2B_TRI_BEHIND], (long long)counts[C2B_TRI_CONSTANT]);
+    int64_t counts[6] = {0, 0, 0, 0, 0, 0};
+    if (robust) {
+        int64_t removed = 0;
+        std::vector<uint8_t> inlier((size_t)no);
+        ck(c2b_problem_triangulate_consensus(p, min_angle_deg * (3.14159265358979323846 / 180.0), max_error, (int)min_inliers, (int)max_hypotheses,
+                                             a.has("drop-outliers") ? C2B_TRI_DROP_OUTLIERS : 0, nullptr, nullptr, inlier.data(), counts, &removed));
+        timer.mark("triangulate_consensus (device)");
+        std::printf("triangulated %lld points; kept: %lld too few observations, %lld degenerate, %lld behind a camera, %lld constant, "
+                    "%lld without consensus\n%lld outlier observations, %lld removed\n",
+                    (long long)counts[C2B_TRI_OK], (long long)counts[C2B_TRI_TOO_FEW], (long long)counts[C2B_TRI_DEGENERATE],
+                    (long long)counts[C2B_TRI_BEHIND], (long long)counts[C2B_TRI_CONSTANT], (long long)counts[C2B_TRI_NO_CONSENSUS],
+                    (long long)std::count(inlier.begin(), inlier.end(), (uint8_t)0), (long long)removed);
+    } else {
+        ck(c2b_problem_triangulate_points(p, min_angle_deg * (3.14159265358979323846 / 180.0), nullptr, counts));
+        timer.mark("triangulate_points (device)");
+        std::printf("triangulated %lld points; kept: %lld too few observations, %lld degenerate, %lld behind a camera, %lld constant\n",
+                    (long long)counts[C2B_TRI_OK], (long long)counts[C2B_TRI_TOO_FEW], (long long)counts[C2B_TRI_DEGENERATE],
+                    (long long)counts[C2B_TRI_BEHIND], (long long)counts[C2B_TRI_CONSTANT]);
+    }
     ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
     timer.mark("write (c2b_problem_write: the file image is built on the device)");
     c2b_problem_destroy(p);
@@ -1000,7 +1024,12 @@ const char *subcommand_help(const std::string &sub) {
                "    --filter-in-front         also drop observations whose point is not in front of its camera\n";
     if (sub == "triangulate")
         return "city2ba triangulate <FILE> <OUT>\n"
-               "    --min-angle <DEG> [1]     parallax test: a point whose rays are less than DEG degrees apart keeps its position\n";
+               "    --min-angle <DEG> [1]     parallax test: a point whose rays are less than DEG degrees apart keeps its position\n"
+               "    --max-error <X>           consensus triangulation for a list with wrong matches: candidates from pairs of rays, the\n"
+               "                              one most observations reproject within X of (in front of their cameras), a refit on those [off]\n"
+               "    --min-inliers <N> [3]     a point whose best candidate has fewer inliers keeps its position (at least 2)\n"
+               "    --max-hypotheses <H> [64] candidates per point, widest pairs first (1 ... 64)\n"
+               "    --drop-outliers           then remove the observations of the triangulated points that are not inliers\n";
     if (sub == "resect")
         return "city2ba resect <FILE> <OUT>\n"
                "    --min-points <N> [6]      a camera with fewer usable observations keeps its pose (at least 6)\n"

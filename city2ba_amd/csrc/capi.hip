@@ -37,6 +37,7 @@
 #include "normal_kernels.hpp"
 #include "schur_kernels.hpp"
 #include "triangulate_kernels.hpp"
+#include "triangulate_robust_kernels.hpp"
 #include "resect_kernels.hpp"
 #include "cull_kernels.hpp"
 #include "cell_kernels.hpp"

@@ -378,6 +378,74 @@ int c2b_problem_filter_observations(c2b_problem *p, double max_error, int flags,
     C2B_API_END("problem_filter_observations")
 }
 
+// Consensus triangulation: c2b_triangulate_consensus_rows over the cached transpose, as
+// c2b_problem_triangulate_points runs c2b_triangulate_rows -- only pts4 changes, nothing the problem caches is derived from
+// the points -- and, with C2B_TRI_DROP_OUTLIERS, the filter's compaction of the list by the pass's inlier mask: then what was
+// derived from the list goes, and nothing else.  The points have moved by the time the list is compacted.
+int c2b_problem_triangulate_consensus(c2b_problem *p, double min_angle, double max_error, int min_inliers, int max_hypotheses, int flags,
+                                      uint8_t *status, int32_t *hyp, uint8_t *inlier, int64_t *counts, int64_t *n_removed) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_triangulate_consensus");
+    if (!good_min_angle(min_angle)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_consensus: min_angle must lie in [0, pi/2] radians");
+    if (!good_tri_max_error(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_consensus: max_error must be finite and >= 0");
+    if (min_inliers < 2) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_consensus: min_inliers must be at least 2");
+    if (max_hypotheses < 1 || max_hypotheses > kTrcSample)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_consensus: max_hypotheses must lie in [1, %d]", kTrcSample);
+    if (flags & ~C2B_TRI_DROP_OUTLIERS)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_consensus: unknown flag bits 0x%x", (unsigned)(flags & ~C2B_TRI_DROP_OUTLIERS));
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_consensus: a shard is not triangulated alone (a point's observations span every rank)");
+    if (n_removed) *n_removed = 0;
+    const int64_t np = p->n_pts, n_cam = p->n_cam, n_old = p->n_obs;
+    int64_t got[kTrcKinds] = {0, 0, 0, 0, 0, 0};
+    if (!n_old) {                                            // no observation: every point has too few, nothing is read or written
+        got[kTriTooFew] = np;
+        if (status && np) std::fill(status, status + np, (uint8_t)kTriTooFew);
+        if (hyp && np) std::fill(hyp, hyp + np, (int32_t)-1);
+        if (counts) std::copy(got, got + kTrcKinds, counts);
+        return C2B_OK;
+    }
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (!rc) rc = ensure_transpose(p);
+    if (rc) return rc;
+    DevBuf<uint8_t> d_status, d_inlier;
+    DevBuf<int32_t> d_hyp;
+    DevBuf<int64_t> d_counts;
+    hipError_t e = d_status.alloc((size_t)np);
+    if (e == hipSuccess) e = d_inlier.alloc((size_t)n_old);
+    if (e == hipSuccess) e = d_hyp.alloc((size_t)np);
+    if (e == hipSuccess) e = d_counts.alloc(kTrcKinds);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_triangulate_consensus: allocation: %s", hipGetErrorString(e));
+    rc = c2b_triangulate_consensus_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, n_old, min_angle, max_error, min_inliers,
+                                        max_hypotheses, p->pmask, d_status, d_hyp, nullptr, d_inlier, d_counts, p->stream);
+    if (!rc && status) e = hipMemcpyAsync(status, d_status, (size_t)np, hipMemcpyDeviceToHost, p->stream);
+    if (!rc && e == hipSuccess && hyp) e = hipMemcpyAsync(hyp, d_hyp, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, p->stream);
+    if (!rc && e == hipSuccess && inlier) e = hipMemcpyAsync(inlier, d_inlier, (size_t)n_old, hipMemcpyDeviceToHost, p->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, p->stream);
+    const hipError_t es = hipStreamSynchronize(p->stream);   // the temporaries are freed below
+    if (rc) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(C2B_ERR_HIP, "problem_triangulate_consensus: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    if (counts) std::copy(got, got + kTrcKinds, counts);
+    if (!(flags & C2B_TRI_DROP_OUTLIERS)) return C2B_OK;
+    // the filter's compaction (c2b_problem_filter_observations) by the inlier mask
+    DevBuf<uint64_t> row_new;
+    DevBuf<uint32_t> pt_new;
+    DevBuf<double> uv_new;
+    std::vector<uint64_t> row_host((size_t)n_cam + 1);
+    int64_t w = 0;
+    e = compact_rows_on_device(p, p->rows_ptr, d_inlier, p->pt_idx, p->uv, n_cam, row_host.data(), row_new, pt_new, uv_new, &w, n_old);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(p->stream);
+        return fail(hip_code(e), "problem_triangulate_consensus: %s", hipGetErrorString(e));
+    }
+    if (w == n_old) return C2B_OK;                           // nothing removed: no cache is dropped
+    if ((rc = install_observations(p, "problem_triangulate_consensus", w, uv_new, pt_new, nullptr, row_new, nothing_more))) return rc;
+    if (n_removed) *n_removed = n_old - w;
+    return C2B_OK;
+    C2B_API_END("problem_triangulate_consensus")
+}
+
 int c2b_problem_visibility_pairs_compact(c2b_problem *p, int64_t n_pairs, const uint32_t *cam_idx, const uint32_t *pt_idx,
                                          double max_dist, uint64_t *row_ptr) {
     C2B_API_BEGIN

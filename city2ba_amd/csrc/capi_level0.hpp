@@ -1487,6 +1487,41 @@ int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, cons
     C2B_API_END("triangulate_rows")
 }
 
+// ---- consensus triangulation (triangulate_robust_kernels.hpp) ----------------------------------------------
+static bool good_tri_max_error(double e) { return e >= 0.0 && std::isfinite(e); }   // (a NaN fails the first)
+
+int c2b_triangulate_consensus_rows(const double *camblk, double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                                   const uint32_t *cam_of, const double *uv_obs, int64_t n_obs, double min_angle, double max_error,
+                                   int min_inliers, int max_hypotheses, const uint8_t *pt_mask, uint8_t *status, int32_t *hyp,
+                                   int32_t *n_inl, uint8_t *inlier, int64_t *counts, void *stream) {
+    C2B_API_BEGIN
+    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: n_pts out of range");
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 64)        // (a row's length and its chunk offsets are ints in the kernel)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: n_obs out of range");
+    if (!good_min_angle(min_angle)) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: min_angle must lie in [0, pi/2] radians");
+    if (!good_tri_max_error(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: max_error must be finite and >= 0");
+    if (min_inliers < 2) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: min_inliers must be at least 2");
+    if (max_hypotheses < 1 || max_hypotheses > kTrcSample)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: max_hypotheses must lie in [1, %d]", kTrcSample);
+    if (!counts || (n_pts && (!pts4 || !pt_row_ptr || !status))) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: NULL argument");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(counts) ||
+        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3) || (reinterpret_cast<uintptr_t>(hyp) & 3) ||
+        (reinterpret_cast<uintptr_t>(n_inl) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kTrcKinds, st));
+    if (inlier && n_obs) HIP_TRY(hipMemsetAsync(inlier, 1, (size_t)n_obs, st));      // the kernel writes the zeros
+    if (!n_pts) return C2B_OK;
+    const double sh = std::sin(0.5 * min_angle);
+    hipLaunchKernelGGL(k_triangulate_consensus, dim3(blocks_for(n_pts, kTrcWaves)), dim3(kTrcBlock), 0, st, camblk,
+                       reinterpret_cast<double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of, reinterpret_cast<const double2 *>(uv_obs),
+                       2.0 * sh * sh, max_error * max_error, min_inliers, max_hypotheses, pt_mask, status, hyp, n_inl, inlier,
+                       reinterpret_cast<unsigned long long *>(counts));
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("triangulate_consensus_rows")
+}
+
 // ---- camera resection (resect_kernels.hpp) ------------------------------------------------------------------
 static bool good_min_gap(double g) { return g >= 0.0 && g < 1.0; }                  // (a NaN fails both)
 

@@ -293,6 +293,18 @@ def triangulate_rows(camblk, pts4, prows, uv, status, counts, min_angle, pt_mask
     return status, counts
 
 
+def triangulate_consensus_rows(camblk, pts4, prows, uv, status, counts, min_angle, max_error, min_inliers=3, max_hypotheses=64,
+                               pt_mask=None, hyp=None, n_inl=None, inlier=None):
+    """consensus triangulation (c2b_triangulate_consensus_rows): triangulate_rows over the rays of a point that agree with
+    each other; status [n_pts] uint8 (_lib.TRI_CONSENSUS_STATUS order), counts [6] int64; hyp, n_inl [n_pts] int32 and
+    inlier [n_obs] uint8 (0 = an observation of a triangulated point that is not an inlier) or None; min_angle in radians"""
+    L.check(L.lib().c2b_triangulate_consensus_rows(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of),
+                                                   _p(prows.cam_of), _p(uv), prows.n_obs, float(min_angle), float(max_error),
+                                                   int(min_inliers), int(max_hypotheses), _p(pt_mask), _p(status), _p(hyp), _p(n_inl),
+                                                   _p(inlier), _p(counts), _stream()))
+    return status, counts
+
+
 def resect_rows(bal9, pts4, rows, pt_idx, uv, status, counts, min_points=6, min_gap=1e-4, cam_mask=None):
     """camera resection (c2b_resect_rows): bal9 [n_cam,9] in place (entries 0..5; 6..8 are the intrinsics read) from each
     camera's row of observations (Rows); status [n_cam] uint8 (_lib.RES_STATUS order), counts [5] int64 = how many cameras

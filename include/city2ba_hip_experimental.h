@@ -323,6 +323,62 @@ int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, cons
                          int64_t *counts, void *stream);
 int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *status, int64_t *counts);
 
+/* ---- consensus triangulation: points from the rays that agree (two-ray hypotheses, inlier mask, refit) ----
+ * c2b_triangulate_rows is a least-squares midpoint over every ray of a point: one ray that belongs to another point (a
+ * wrong match, a joined landmark) drags it arbitrarily far.  This pass forms candidates from pairs of rays, keeps the
+ * candidate most of the row agrees with, and refits on those.  Notation as above: point p's row of the transpose in
+ * ascending observation index, usable(o) as defined there, thr = 2 sin^2(min_angle / 2) and E2 = max_error * max_error each
+ * formed once on the host.  One wave per point.  In this order:
+ *   C2B_TRI_CONSTANT     the point is constant under pt_mask; nothing of its row is read.
+ *   sample               the usable observations among the FIRST 64 ENTRIES of the row, in row order, numbered 0 .. m - 1.
+ *   C2B_TRI_TOO_FEW      m < 2 (or fewer than two usable observations in the whole row, which m < 2 implies).
+ *   hypotheses           pair number k = 0, 1, ...: the gap g runs from floor(m / 2) down to 1 and, per gap, i over 0 .. m - 1
+ *                        (when 2 g == m only i < g: each pair once); the pair is (i, (i + g) mod m), lower index first.  The
+ *                        enumeration stops after max_hypotheses pairs, 1 <= max_hypotheses <= 64.  Hypothesis k is formed
+ *                        iff c2b_triangulate_rows' own arithmetic on those two observations alone (the same sums, lower
+ *                        index first, the same lambda_min and Cholesky) passes that pass's test lambda_min >= thr && solved;
+ *                        X_k is that solution.  Cheirality is not tested here.
+ *   C2B_TRI_DEGENERATE   no hypothesis is formed.
+ *   score                observation o of the row -- every entry, also past the 64th, also the pair itself -- is an inlier
+ *                        of X iff it is usable and c2b_residual_keep_rows with C2B_FILTER_IN_FRONT would keep it at X: with
+ *                        (u, v) and q.z of c2b_project at X, du = u - obs.x, dv = v - obs.y, du * du + dv * dv <= E2 (five
+ *                        unfused operations; NaN compares false) and q.z < 0.  The score of k is its integer inlier count.
+ *   select               the highest score, the LOWEST k among equal scores; I* is its inlier set.
+ *   C2B_TRI_NO_CONSENSUS |I*| < min_inliers (min_inliers >= 2).
+ *   refit                A, b over I* in ascending row order by c2b_triangulate_rows' expressions and Cholesky:
+ *   C2B_TRI_DEGENERATE   lambda_min(A) < thr or not solved;
+ *   C2B_TRI_BEHIND       some inlier's camera sees X at q.z >= 0;
+ *   C2B_TRI_OK           pts4[p].xyz = X, the fourth lane keeps its value: bit for bit what c2b_triangulate_rows returns
+ *                        on the list restricted to I*.
+ * A point whose status is not C2B_TRI_OK keeps its bits.  Per point also hyp = the selected k and n_inl = |I*| (set once a
+ * hypothesis was selected, whatever the status after it; -1 and 0 under CONSTANT, TOO_FEW and when none was formed).  Per
+ * observation, indexed as the camera-major list: inlier[o] = 0 for the observations of a C2B_TRI_OK point that are not in
+ * I* (the unusable ones among them), 1 everywhere else -- nothing is claimed about a point that was not triangulated.
+ * counts[6] is the histogram of the statuses.  No float atomics, no scratch memory, no workspace, no loss from the handle:
+ * the same inputs give the same bits whatever the launch shape.  min_angle outside [0, pi/2] or NaN, max_error negative, NaN
+ * or infinite, min_inliers < 2, max_hypotheses outside [1, 64], an unknown flag bit: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_triangulate_consensus_rows: Level 0, stateless, asynchronous on `stream`.  The arguments of c2b_triangulate_rows, and
+ *   n_obs, the length of the list obs_of indexes; hyp, n_inl [n_pts] (device int32) and inlier [n_obs] (device, one byte)
+ *   may each be NULL; counts [6] (device int64) is zeroed and inlier set to 1 before the kernel runs.
+ * c2b_problem_triangulate_consensus: Level 1, synchronous, with the preconditions and the cache story of
+ *   c2b_problem_triangulate_points: the resident cameras in the mode the problem is in, the cached transpose (built when
+ *   absent), only the points change, a shard is refused, a problem without observations returns C2B_TRI_TOO_FEW for every
+ *   point and launches nothing.  status [n_pts], hyp [n_pts], inlier [n_obs, in the list's order at call time] and counts [6]
+ *   are host arrays and may be NULL.  flags = C2B_TRI_DROP_OUTLIERS: the list is then compacted by the inlier mask exactly
+ *   as c2b_problem_filter_observations compacts by its mask (stable inside every camera's row, nothing renumbered, what was
+ *   derived from the list is rebuilt by its next user); *n_removed (may be NULL) = how many went, and when it is 0 no cache
+ *   is dropped.  Should the compaction fail (an allocation), the points have already moved and the list has not: the
+ *   status, the mask and the counts returned describe the pass, and the call returns the error.  Every refusal leaves the
+ *   problem unchanged. */
+#define C2B_TRI_NO_CONSENSUS 5
+#define C2B_TRI_DROP_OUTLIERS 1
+int c2b_triangulate_consensus_rows(const double *camblk, double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                                   const uint32_t *cam_of, const double *uv_obs, int64_t n_obs, double min_angle, double max_error,
+                                   int min_inliers, int max_hypotheses, const uint8_t *pt_mask, uint8_t *status, int32_t *hyp,
+                                   int32_t *n_inl, uint8_t *inlier, int64_t *counts, void *stream);
+int c2b_problem_triangulate_consensus(c2b_problem *p, double min_angle, double max_error, int min_inliers, int max_hypotheses, int flags,
+                                      uint8_t *status, int32_t *hyp, uint8_t *inlier, int64_t *counts, int64_t *n_removed);
+
 /* ---- resection: camera poses from points and observations (object-space error, one wave per camera) ----
  * The dual of triangulation: camera c's pose (R, t) from the points as they are, its f, k1, k2 kept.  The camera's row of
  * the camera-major list is walked in ascending order.  Per observation of point X, observed (u, v), with f, k1, k2 =
