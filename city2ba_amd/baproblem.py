@@ -526,6 +526,14 @@ class BAProblem:
             self._refresh_graph()
         return n.value
 
+    def _status_pass(self, entry, args, n, names, return_status):
+        """entry(handle, *args, status, counts) over n entities: the counts as a dict under `names`, and the status bytes"""
+        counts = np.zeros(len(names), dtype=np.int64)
+        status = np.zeros(n, dtype=np.uint8) if return_status else None
+        L.check(entry(self._h, *args, status.ctypes.data_as(C.c_void_p) if return_status else None, counts.ctypes.data_as(C.c_void_p)))
+        out = dict(zip(names, (int(v) for v in counts)))
+        return (out, status) if return_status else out
+
     def triangulate_points(self, min_angle_deg=1.0, return_status=False):
         """Linear midpoint triangulation on the device (c2b_problem_triangulate_points): every point is set to
         the position nearest, in the sum of squared distances, to the rays of its observations through the cameras as
@@ -534,13 +542,8 @@ class BAProblem:
         cameras.  The loss on the handle is ignored; masks, loss, preconditioner and a checkpoint stay.  Returns
         dict(triangulated, too_few, degenerate, behind, constant), the number of points of each outcome, and with
         return_status also the uint8 status per point (the dict's order: 0 .. 4)."""
-        counts = np.zeros(5, dtype=np.int64)
-        status = np.zeros(self.num_points(), dtype=np.uint8) if return_status else None
-        L.check(L.lib().c2b_problem_triangulate_points(self._h, float(np.deg2rad(float(min_angle_deg))),
-                                                       status.ctypes.data_as(C.c_void_p) if return_status else None,
-                                                       counts.ctypes.data_as(C.c_void_p)))
-        out = dict(zip(L.TRI_STATUS, (int(v) for v in counts)))
-        return (out, status) if return_status else out
+        return self._status_pass(L.lib().c2b_problem_triangulate_points, (float(np.deg2rad(float(min_angle_deg))),),
+                                 self.num_points(), L.TRI_STATUS, return_status)
 
     def triangulate_points_robust(self, max_error, min_angle_deg=1.0, min_inliers=3, max_hypotheses=64, drop_outliers=False,
                                   return_status=False, return_inliers=False):
@@ -588,13 +591,8 @@ class BAProblem:
         preconditioner and a checkpoint stay; the problem is in bal mode afterwards, as after apply_step.  Returns
         dict(resected, too_few, degenerate, behind, constant), the number of cameras of each outcome, and with
         return_status also the uint8 status per camera (the dict's order: 0 .. 4)."""
-        counts = np.zeros(5, dtype=np.int64)
-        status = np.zeros(self.num_cameras(), dtype=np.uint8) if return_status else None
-        L.check(L.lib().c2b_problem_resect_cameras(self._h, int(min_points), float(min_gap),
-                                                   status.ctypes.data_as(C.c_void_p) if return_status else None,
-                                                   counts.ctypes.data_as(C.c_void_p)))
-        out = dict(zip(L.RES_STATUS, (int(v) for v in counts)))
-        return (out, status) if return_status else out
+        return self._status_pass(L.lib().c2b_problem_resect_cameras, (int(min_points), float(min_gap)), self.num_cameras(),
+                                 L.RES_STATUS, return_status)
 
     def subset(self, ci, pi):
         """BAProblem::subset (src/baproblem.rs:394-423): cameras ci and points pi in the given order; observations of

@@ -791,6 +791,25 @@ int run_ply(int argc, char **argv) {
     return 0;
 }
 
+// The head and the tail `solve`, `triangulate` and `resect` share: a problem on `device` read from `file`, its sizes printed;
+// the problem written to `file` and destroyed.
+static c2b_problem *open_problem(PhaseTimer &timer, int device, const std::string &file, int64_t &nc, int64_t &np, int64_t &no) {
+    c2b_problem *p = nullptr;
+    ck(create_problem(device, &p));
+    timer.mark("problem_create (HIP runtime start)");
+    ck(c2b_problem_read(p, file.c_str(), -1));
+    timer.mark("read (c2b_problem_read: decoded on the device)");
+    ck(c2b_problem_sizes(p, &nc, &np, &no));
+    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
+    return p;
+}
+
+static void close_problem(PhaseTimer &timer, c2b_problem *p, const std::string &file) {
+    ck(c2b_problem_write(p, file.c_str(), -1));
+    timer.mark("write (c2b_problem_write: the file image is built on the device)");
+    c2b_problem_destroy(p);
+}
+
 // `solve`: bundle adjustment of a .bal / .bbal by c2b_problem_levenberg_marquardt (an extension: the reference only makes
 // problems).  The file is decoded into the resident problem, solved there and its image assembled there.  Every argument
 // is parsed before the device is touched.  --filter-max-error X: --filter-rounds times (solve, then drop the observations
@@ -834,14 +853,8 @@ int run_solve(int argc, char **argv) {
         else die("Invalid value for '--preconditioner <preconditioner>': expected block-jacobi or schur-jacobi");
     }
     PhaseTimer timer;
-    c2b_problem *p = nullptr;
-    ck(create_problem(device, &p));
-    timer.mark("problem_create (HIP runtime start)");
-    ck(c2b_problem_read(p, a.positional[0].c_str(), -1));
-    timer.mark("read (c2b_problem_read: decoded on the device)");
     int64_t nc = 0, np = 0, no = 0;
-    ck(c2b_problem_sizes(p, &nc, &np, &no));
-    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
+    c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
     ck(c2b_problem_set_loss(p, loss, loss_scale));
     ck(c2b_problem_set_preconditioner(p, precond));
     if (a.has("fix-intrinsics") || a.has("fix-first-camera")) {
@@ -874,9 +887,7 @@ int run_solve(int argc, char **argv) {
         ck(c2b_problem_set_loss(p, 0, 1.0));
     }
     solve_once();
-    ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
-    timer.mark("write (c2b_problem_write: the file image is built on the device)");
-    c2b_problem_destroy(p);
+    close_problem(timer, p, a.positional[1]);
     return 0;
 }
 
@@ -900,14 +911,8 @@ int run_triangulate(int argc, char **argv) {
     if (!robust && (a.has("min-inliers") || a.has("max-hypotheses") || a.has("drop-outliers")))
         die("--min-inliers, --max-hypotheses and --drop-outliers need --max-error <X>");
     PhaseTimer timer;
-    c2b_problem *p = nullptr;
-    ck(create_problem(device, &p));
-    timer.mark("problem_create (HIP runtime start)");
-    ck(c2b_problem_read(p, a.positional[0].c_str(), -1));
-    timer.mark("read (c2b_problem_read: decoded on the device)");
     int64_t nc = 0, np = 0, no = 0;
-    ck(c2b_problem_sizes(p, &nc, &np, &no));
-    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
+    c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
     int64_t counts[6] = {0, 0, 0, 0, 0, 0};
     if (robust) {
         int64_t removed = 0;
@@ -927,9 +932,7 @@ int run_triangulate(int argc, char **argv) {
                     (long long)counts[C2B_TRI_OK], (long long)counts[C2B_TRI_TOO_FEW], (long long)counts[C2B_TRI_DEGENERATE],
                     (long long)counts[C2B_TRI_BEHIND], (long long)counts[C2B_TRI_CONSTANT]);
     }
-    ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
-    timer.mark("write (c2b_problem_write: the file image is built on the device)");
-    c2b_problem_destroy(p);
+    close_problem(timer, p, a.positional[1]);
     return 0;
 }
 
@@ -945,23 +948,15 @@ int run_resect(int argc, char **argv) {
     if (min_points < 6 || min_points > 2147483647) die("Invalid value for '--min-points <N>': expected an integer of at least 6");
     if (!(min_gap >= 0.0 && min_gap < 1.0)) die("Invalid value for '--min-gap <G>': expected a number in 0 ... 1 (1 excluded)");
     PhaseTimer timer;
-    c2b_problem *p = nullptr;
-    ck(create_problem(device, &p));
-    timer.mark("problem_create (HIP runtime start)");
-    ck(c2b_problem_read(p, a.positional[0].c_str(), -1));
-    timer.mark("read (c2b_problem_read: decoded on the device)");
     int64_t nc = 0, np = 0, no = 0;
-    ck(c2b_problem_sizes(p, &nc, &np, &no));
-    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
+    c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
     int64_t counts[5] = {0, 0, 0, 0, 0};
     ck(c2b_problem_resect_cameras(p, (int)min_points, min_gap, nullptr, counts));
     timer.mark("resect_cameras (device)");
     std::printf("resected %lld cameras; kept: %lld too few observations, %lld degenerate, %lld behind a point, %lld constant\n",
                 (long long)counts[C2B_RES_OK], (long long)counts[C2B_RES_TOO_FEW], (long long)counts[C2B_RES_DEGENERATE],
                 (long long)counts[C2B_RES_BEHIND], (long long)counts[C2B_RES_CONSTANT]);
-    ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
-    timer.mark("write (c2b_problem_write: the file image is built on the device)");
-    c2b_problem_destroy(p);
+    close_problem(timer, p, a.positional[1]);
     return 0;
 }
 

@@ -88,6 +88,44 @@ C2B_DEV void cm_mat_mul(const T *a, const T *b, T *o) {
             o[3 * c + r] = dot3(a[r], a[3 + r], a[6 + r], b[3 * c], b[3 * c + 1], b[3 * c + 2]);
 }
 
+// ---- the 3x3 Cholesky factor, in registers -------------------------------------------
+// A = L L^T of the symmetric (a00 a01 a02; . a11 a12; . . a22): L's entries below the diagonal, the reciprocals i0 i1 i2 of
+// its diagonal and the pivots d1 d2 d3 (the diagonal's squares).  A is positive definite exactly when positive(); nothing
+// here tests it, and a pivot <= 0 leaves NaN or infinity in what follows it.  The one copy of this algebra: every 3x3 solve
+// of the step, of triangulation and of resection rounds alike because it is this expression tree (-ffp-contract=off).
+struct Chol3 {
+    double i0, l10, l20, i1, l21, i2, d1, d2, d3;
+    // (& on the three bools, not &&: nothing to short-circuit, and a caller that returns on !positive() takes one branch)
+    C2B_DEV bool positive() const { return (d1 > 0.0) & (d2 > 0.0) & (d3 > 0.0); }
+    // y = L^-1 b
+    C2B_DEV void forward(double b0, double b1, double b2, double &y0, double &y1, double &y2) const {
+        y0 = b0 * i0; y1 = (b1 - l10 * y0) * i1; y2 = ((b2 - l20 * y0) - l21 * y1) * i2;
+    }
+    // x = L^-T y
+    C2B_DEV void back(double y0, double y1, double y2, double &x0, double &x1, double &x2) const {
+        x2 = y2 * i2; x1 = (y1 - l21 * x2) * i1; x0 = ((y0 - l10 * x1) - l20 * x2) * i0;
+    }
+    // x = A^-1 b
+    C2B_DEV void solve(double b0, double b1, double b2, double &x0, double &x1, double &x2) const {
+        double y0, y1, y2;
+        forward(b0, b1, b2, y0, y1, y2);
+        back(y0, y1, y2, x0, x1, x2);
+    }
+};
+
+C2B_DEV Chol3 chol3_factor(double a00, double a01, double a02, double a11, double a12, double a22) {
+    Chol3 f;
+    f.d1 = a00;
+    f.i0 = 1.0 / sqrt(f.d1);
+    f.l10 = a01 * f.i0; f.l20 = a02 * f.i0;
+    f.d2 = a11 - f.l10 * f.l10;
+    f.i1 = 1.0 / sqrt(f.d2);
+    f.l21 = (a12 - f.l20 * f.l10) * f.i1;
+    f.d3 = (a22 - f.l20 * f.l20) - f.l21 * f.l21;
+    f.i2 = 1.0 / sqrt(f.d3);
+    return f;
+}
+
 // -(R^-1 t) with cgmath's Matrix3::invert (cross products / determinant), src/baproblem.rs:161-163
 template <typename T>
 C2B_DEV void cm_center(const T *m, T tx, T ty, T tz, T c[3]) {

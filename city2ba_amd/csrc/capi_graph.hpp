@@ -339,10 +339,30 @@ static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_o
     return e;
 }
 
+// The resident list compacted by a keep mask of its n_old entries and swapped in (install_observations: cam_idx from the new
+// row pointer, a workspace for the new count, swapped in only once the stream has synchronised without error).  A mask that
+// keeps everything changes nothing and drops no cache.  *n_removed (may be NULL) is written on success alone.
+static int compact_and_install(c2b_problem *p, const char *who, const uint8_t *d_keep, int64_t n_old, int64_t *n_removed) {
+    DevBuf<uint64_t> row_new;
+    DevBuf<uint32_t> pt_new;
+    DevBuf<double> uv_new;
+    std::vector<uint64_t> row_host((size_t)p->n_cam + 1);
+    int64_t w = 0;
+    const hipError_t e = compact_rows_on_device(p, p->rows_ptr, d_keep, p->pt_idx, p->uv, p->n_cam, row_host.data(), row_new, pt_new, uv_new, &w, n_old);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(p->stream);
+        return fail(hip_code(e), "%s: %s", who, hipGetErrorString(e));
+    }
+    if (w == n_old) return C2B_OK;
+    const int rc = install_observations(p, who, w, uv_new, pt_new, nullptr, row_new, nothing_more);
+    if (rc) return rc;
+    if (n_removed) *n_removed = n_old - w;
+    return C2B_OK;
+}
+
 // The outlier filter: the residual predicate over the resident list, a stable compaction of (pt_idx, uv) by its
-// mask, then install_observations: cam_idx from the new row pointer, a workspace for the new count, swapped in only once the
-// stream has synchronised without error.  The entities do not move: cameras, points, both counts, the masks, the loss, the
-// preconditioner, the checkpoint and the LM scratch stay; what was derived from the list (drop_rows) goes.
+// mask and its installation (compact_and_install).  The entities do not move: cameras, points, both counts, the masks, the
+// loss, the preconditioner, the checkpoint and the LM scratch stay; what was derived from the list (drop_rows) goes.
 int c2b_problem_filter_observations(c2b_problem *p, double max_error, int flags, int64_t *n_removed) {
     C2B_API_BEGIN
     NEED_UPLOADED(p, "problem_filter_observations");
@@ -356,25 +376,16 @@ int c2b_problem_filter_observations(c2b_problem *p, double max_error, int flags,
     int rc = ensure_camblk(p);
     if (!rc) rc = ensure_rows(p);
     if (rc) return rc;
-    const int64_t n_cam = p->n_cam, n_old = p->n_obs;
+    const int64_t n_old = p->n_obs;
     DevBuf<uint8_t> keep;
-    DevBuf<uint64_t> row_new;
-    DevBuf<uint32_t> pt_new;
-    DevBuf<double> uv_new;
-    std::vector<uint64_t> row_host((size_t)n_cam + 1);
-    int64_t w = 0;
-    hipError_t e = keep.alloc((size_t)n_old);
+    const hipError_t e = keep.alloc((size_t)n_old);
     if (e != hipSuccess) return fail(hip_code(e), "problem_filter_observations: %s", hipGetErrorString(e));
-    rc = c2b_residual_keep_rows(p->camblk, p->pts4, p->rows_ptr, n_cam, p->rows_tiles, p->pt_idx, p->uv, n_old, max_error, flags, keep, p->stream);
-    if (!rc) e = compact_rows_on_device(p, p->rows_ptr, keep, p->pt_idx, p->uv, n_cam, row_host.data(), row_new, pt_new, uv_new, &w, n_old);
-    if (rc || e != hipSuccess) {
+    rc = c2b_residual_keep_rows(p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->rows_tiles, p->pt_idx, p->uv, n_old, max_error, flags, keep, p->stream);
+    if (rc) {
         (void)hipStreamSynchronize(p->stream);
-        return rc ? rc : fail(hip_code(e), "problem_filter_observations: %s", hipGetErrorString(e));
+        return rc;
     }
-    if (w == n_old) return C2B_OK;                                 // nothing removed: nothing changes, no cache is dropped
-    if ((rc = install_observations(p, "problem_filter_observations", w, uv_new, pt_new, nullptr, row_new, nothing_more))) return rc;
-    if (n_removed) *n_removed = n_old - w;
-    return C2B_OK;
+    return compact_and_install(p, "problem_filter_observations", keep, n_old, n_removed);
     C2B_API_END("problem_filter_observations")
 }
 
@@ -396,53 +407,29 @@ int c2b_problem_triangulate_consensus(c2b_problem *p, double min_angle, double m
     if (p->shard_n_cam_global >= 0)
         return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_consensus: a shard is not triangulated alone (a point's observations span every rank)");
     if (n_removed) *n_removed = 0;
-    const int64_t np = p->n_pts, n_cam = p->n_cam, n_old = p->n_obs;
-    int64_t got[kTrcKinds] = {0, 0, 0, 0, 0, 0};
+    const int64_t np = p->n_pts, n_old = p->n_obs;
+    StatusReport rep(kTrcKinds);
     if (!n_old) {                                            // no observation: every point has too few, nothing is read or written
-        got[kTriTooFew] = np;
-        if (status && np) std::fill(status, status + np, (uint8_t)kTriTooFew);
         if (hyp && np) std::fill(hyp, hyp + np, (int32_t)-1);
-        if (counts) std::copy(got, got + kTrcKinds, counts);
-        return C2B_OK;
+        return rep.all_have(kTriTooFew, np, status, counts);
     }
     int rc = ensure_camblk(p);
     if (!rc) rc = ensure_rows(p);
     if (!rc) rc = ensure_transpose(p);
     if (rc) return rc;
-    DevBuf<uint8_t> d_status, d_inlier;
+    DevBuf<uint8_t> d_inlier;
     DevBuf<int32_t> d_hyp;
-    DevBuf<int64_t> d_counts;
-    hipError_t e = d_status.alloc((size_t)np);
+    hipError_t e = rep.alloc(np);
     if (e == hipSuccess) e = d_inlier.alloc((size_t)n_old);
     if (e == hipSuccess) e = d_hyp.alloc((size_t)np);
-    if (e == hipSuccess) e = d_counts.alloc(kTrcKinds);
     if (e != hipSuccess) return fail(hip_code(e), "problem_triangulate_consensus: allocation: %s", hipGetErrorString(e));
     rc = c2b_triangulate_consensus_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, n_old, min_angle, max_error, min_inliers,
-                                        max_hypotheses, p->pmask, d_status, d_hyp, nullptr, d_inlier, d_counts, p->stream);
-    if (!rc && status) e = hipMemcpyAsync(status, d_status, (size_t)np, hipMemcpyDeviceToHost, p->stream);
-    if (!rc && e == hipSuccess && hyp) e = hipMemcpyAsync(hyp, d_hyp, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, p->stream);
+                                        max_hypotheses, p->pmask, rep.d_status, d_hyp, nullptr, d_inlier, rep.d_counts, p->stream);
+    if (!rc && hyp) e = hipMemcpyAsync(hyp, d_hyp, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, p->stream);
     if (!rc && e == hipSuccess && inlier) e = hipMemcpyAsync(inlier, d_inlier, (size_t)n_old, hipMemcpyDeviceToHost, p->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, p->stream);
-    const hipError_t es = hipStreamSynchronize(p->stream);   // the temporaries are freed below
-    if (rc) return rc;
-    if (e != hipSuccess || es != hipSuccess) return fail(C2B_ERR_HIP, "problem_triangulate_consensus: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    if (counts) std::copy(got, got + kTrcKinds, counts);
-    if (!(flags & C2B_TRI_DROP_OUTLIERS)) return C2B_OK;
-    // the filter's compaction (c2b_problem_filter_observations) by the inlier mask
-    DevBuf<uint64_t> row_new;
-    DevBuf<uint32_t> pt_new;
-    DevBuf<double> uv_new;
-    std::vector<uint64_t> row_host((size_t)n_cam + 1);
-    int64_t w = 0;
-    e = compact_rows_on_device(p, p->rows_ptr, d_inlier, p->pt_idx, p->uv, n_cam, row_host.data(), row_new, pt_new, uv_new, &w, n_old);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(p->stream);
-        return fail(hip_code(e), "problem_triangulate_consensus: %s", hipGetErrorString(e));
-    }
-    if (w == n_old) return C2B_OK;                           // nothing removed: no cache is dropped
-    if ((rc = install_observations(p, "problem_triangulate_consensus", w, uv_new, pt_new, nullptr, row_new, nothing_more))) return rc;
-    if (n_removed) *n_removed = n_old - w;
-    return C2B_OK;
+    rc = rep.read_back("problem_triangulate_consensus", p->stream, rc, e, np, status, counts);
+    if (rc || !(flags & C2B_TRI_DROP_OUTLIERS)) return rc;
+    return compact_and_install(p, "problem_triangulate_consensus", d_inlier, n_old, n_removed);     // the filter's compaction, by the inlier mask
     C2B_API_END("problem_triangulate_consensus")
 }
 

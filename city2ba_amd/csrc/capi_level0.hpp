@@ -1465,16 +1465,26 @@ int c2b_schur_points_rows_loss(const double *camblk, const double *pts4, int64_t
 // the parallax threshold 1 - cos(min_angle), evaluated once on the host as 2 sin^2(min_angle / 2): no cancellation at a small angle
 static bool good_min_angle(double a) { return a >= 0.0 && a <= 1.57079632679489661923; }
 
+// what both triangulation entries ask of the arguments they share; `more4`: further pointers that must be 4-byte aligned
+static int check_tri_rows_args(const char *who, const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                               const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double min_angle,
+                               const uint8_t *status, const int64_t *counts, const void *more4_a = nullptr, const void *more4_b = nullptr) {
+    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: n_pts out of range", who);
+    if (!good_min_angle(min_angle)) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: min_angle must lie in [0, pi/2] radians", who);
+    if (!counts || (n_pts && (!pts4 || !pt_row_ptr || !status))) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(counts) ||
+        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3) ||
+        (reinterpret_cast<uintptr_t>(more4_a) & 3) || (reinterpret_cast<uintptr_t>(more4_b) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "%s: misaligned pointer", who);
+    return C2B_OK;
+}
+
 int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
                          const uint32_t *cam_of, const double *uv_obs, double min_angle, const uint8_t *pt_mask, uint8_t *status,
                          int64_t *counts, void *stream) {
     C2B_API_BEGIN
-    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_rows: n_pts out of range");
-    if (!good_min_angle(min_angle)) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_rows: min_angle must lie in [0, pi/2] radians");
-    if (!counts || (n_pts && (!pts4 || !pt_row_ptr || !status))) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_rows: NULL argument");
-    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(counts) ||
-        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
-        return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_rows: misaligned pointer");
+    const int bad = check_tri_rows_args("triangulate_rows", camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, min_angle, status, counts);
+    if (bad) return bad;
     hipStream_t st = S(stream);
     HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kTriKinds, st));
     if (!n_pts) return C2B_OK;
@@ -1495,19 +1505,15 @@ int c2b_triangulate_consensus_rows(const double *camblk, double *pts4, int64_t n
                                    int min_inliers, int max_hypotheses, const uint8_t *pt_mask, uint8_t *status, int32_t *hyp,
                                    int32_t *n_inl, uint8_t *inlier, int64_t *counts, void *stream) {
     C2B_API_BEGIN
-    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: n_pts out of range");
     if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 64)        // (a row's length and its chunk offsets are ints in the kernel)
         return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: n_obs out of range");
-    if (!good_min_angle(min_angle)) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: min_angle must lie in [0, pi/2] radians");
     if (!good_tri_max_error(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: max_error must be finite and >= 0");
     if (min_inliers < 2) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: min_inliers must be at least 2");
     if (max_hypotheses < 1 || max_hypotheses > kTrcSample)
         return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: max_hypotheses must lie in [1, %d]", kTrcSample);
-    if (!counts || (n_pts && (!pts4 || !pt_row_ptr || !status))) return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: NULL argument");
-    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(counts) ||
-        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3) || (reinterpret_cast<uintptr_t>(hyp) & 3) ||
-        (reinterpret_cast<uintptr_t>(n_inl) & 3))
-        return fail(C2B_ERR_INVALID_ARGUMENT, "triangulate_consensus_rows: misaligned pointer");
+    const int bad = check_tri_rows_args("triangulate_consensus_rows", camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, min_angle, status,
+                                        counts, hyp, n_inl);
+    if (bad) return bad;
     hipStream_t st = S(stream);
     HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kTrcKinds, st));
     if (inlier && n_obs) HIP_TRY(hipMemsetAsync(inlier, 1, (size_t)n_obs, st));      // the kernel writes the zeros

@@ -453,6 +453,44 @@ int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
     C2B_API_END("problem_apply_step")
 }
 
+// ---- what the start-up passes report ------------------------------------------------------------------------------------
+// One status byte per entity and a count per kind of status: on the device while the pass runs (the Level 0 entries write
+// them there), then copied to the caller.  Triangulation, resection and consensus triangulation report through it.
+struct StatusReport {
+    static constexpr int kMostKinds = 8;
+    const int kinds;
+    DevBuf<uint8_t> d_status;
+    DevBuf<int64_t> d_counts;
+
+    explicit StatusReport(int kinds_) : kinds(kinds_) {}
+
+    hipError_t alloc(int64_t n) {
+        const hipError_t e = d_status.alloc((size_t)n);
+        return e == hipSuccess ? d_counts.alloc((size_t)kinds) : e;
+    }
+    // no observation: every one of the n entities has `kind` (too few), nothing is read or written on the device
+    int all_have(int kind, int64_t n, uint8_t *status, int64_t *counts) {
+        if (status && n) std::fill(status, status + n, (uint8_t)kind);
+        if (counts) {
+            std::fill(counts, counts + kinds, (int64_t)0);
+            counts[kind] = n;
+        }
+        return C2B_OK;
+    }
+    // After the pass returned rc and the caller's own copies e: queue status and counts back, synchronise (the temporaries
+    // are freed when the caller returns), and fold the three into the entry's result.
+    int read_back(const char *who, hipStream_t st, int rc, hipError_t e, int64_t n, uint8_t *status, int64_t *counts) {
+        int64_t got[kMostKinds];
+        if (!rc && e == hipSuccess && status) e = hipMemcpyAsync(status, d_status, (size_t)n, hipMemcpyDeviceToHost, st);
+        if (!rc && e == hipSuccess) e = hipMemcpyAsync(got, d_counts, sizeof(int64_t) * (size_t)kinds, hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        if (rc) return rc;
+        if (e != hipSuccess || es != hipSuccess) return fail(C2B_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+        if (counts) std::copy(got, got + kinds, counts);
+        return C2B_OK;
+    }
+};
+
 // ---- linear midpoint triangulation -------------------------------------------------------------------------
 // The resident points from the resident cameras and observations: c2b_triangulate_rows over the cached transpose (built as
 // c2b_problem_solve_step builds it), the cameras read in the mode the problem is in.  Only pts4 changes, and nothing the
@@ -465,30 +503,16 @@ int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *st
     if (p->shard_n_cam_global >= 0)
         return fail(C2B_ERR_INVALID_ARGUMENT, "problem_triangulate_points: a shard is not triangulated alone (a point's observations span every rank)");
     const int64_t np = p->n_pts;
-    int64_t got[kTriKinds] = {0, 0, 0, 0, 0};
-    if (!p->n_obs) {                                         // no observation: every point has too few, nothing is read or written
-        got[kTriTooFew] = np;
-        if (status && np) std::fill(status, status + np, (uint8_t)kTriTooFew);
-        if (counts) std::copy(got, got + kTriKinds, counts);
-        return C2B_OK;
-    }
+    StatusReport rep(kTriKinds);
+    if (!p->n_obs) return rep.all_have(kTriTooFew, np, status, counts);
     int rc = ensure_camblk(p);
     if (!rc) rc = ensure_rows(p);
     if (!rc) rc = ensure_transpose(p);
     if (rc) return rc;
-    DevBuf<uint8_t> d_status;
-    DevBuf<int64_t> d_counts;
-    hipError_t e = d_status.alloc((size_t)np);
-    if (e == hipSuccess) e = d_counts.alloc(kTriKinds);
+    const hipError_t e = rep.alloc(np);
     if (e != hipSuccess) return fail(hip_code(e), "problem_triangulate_points: allocation: %s", hipGetErrorString(e));
-    rc = c2b_triangulate_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, min_angle, p->pmask, d_status, d_counts, p->stream);
-    if (!rc && status) e = hipMemcpyAsync(status, d_status, (size_t)np, hipMemcpyDeviceToHost, p->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, p->stream);
-    const hipError_t es = hipStreamSynchronize(p->stream);   // the temporaries are freed below
-    if (rc) return rc;
-    if (e != hipSuccess || es != hipSuccess) return fail(C2B_ERR_HIP, "problem_triangulate_points: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    if (counts) std::copy(got, got + kTriKinds, counts);
-    return C2B_OK;
+    rc = c2b_triangulate_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, min_angle, p->pmask, rep.d_status, rep.d_counts, p->stream);
+    return rep.read_back("problem_triangulate_points", p->stream, rc, hipSuccess, np, status, counts);
     C2B_API_END("problem_triangulate_points")
 }
 
@@ -505,36 +529,23 @@ int c2b_problem_resect_cameras(c2b_problem *p, int min_points, double min_gap, u
     if (p->shard_n_cam_global >= 0)
         return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_cameras: a shard is not resected alone");
     const int64_t nc = p->n_cam;
-    int64_t got[kResKinds] = {0, 0, 0, 0, 0};
-    if (!p->n_obs) {                                         // no observation: every camera has too few, nothing is read or written
-        got[kResTooFew] = nc;
-        if (status && nc) std::fill(status, status + nc, (uint8_t)kResTooFew);
-        if (counts) std::copy(got, got + kResKinds, counts);
-        return C2B_OK;
-    }
+    StatusReport rep(kResKinds);
+    if (!p->n_obs) return rep.all_have(kResTooFew, nc, status, counts);
     int rc = ensure_rows(p);
     if (rc) return rc;
-    DevBuf<uint8_t> d_status;
-    DevBuf<int64_t> d_counts;
-    hipError_t e = d_status.alloc((size_t)nc);
-    if (e == hipSuccess) e = d_counts.alloc(kResKinds);
+    const hipError_t e = rep.alloc(nc);
     if (e != hipSuccess) return fail(hip_code(e), "problem_resect_cameras: allocation: %s", hipGetErrorString(e));
     hipStream_t st = p->stream;
     if (!p->bal_valid && !p->bal9_fresh) {                   // state mode: the pass works on to_vec(cam15)
         if ((rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st))) return rc;
         p->bal9_fresh = true;
     }
-    rc = c2b_resect_rows(p->bal9, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, min_points, min_gap, p->cmask, d_status, d_counts, st);
+    rc = c2b_resect_rows(p->bal9, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, min_points, min_gap, p->cmask, rep.d_status, rep.d_counts, st);
     if (!rc) rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
-    if (!rc && status) e = hipMemcpyAsync(status, d_status, (size_t)nc, hipMemcpyDeviceToHost, st);
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);          // the temporaries are freed below
+    rc = rep.read_back("problem_resect_cameras", st, rc, hipSuccess, nc, status, counts);
     cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
     p->bal_valid = true;
-    if (rc) return rc;
-    if (e != hipSuccess || es != hipSuccess) return fail(C2B_ERR_HIP, "problem_resect_cameras: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    if (counts) std::copy(got, got + kResKinds, counts);
-    return C2B_OK;
+    return rc;
     C2B_API_END("problem_resect_cameras")
 }
 

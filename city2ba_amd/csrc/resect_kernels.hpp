@@ -162,16 +162,9 @@ C2B_DEV int resect_camera(ResLds &W, const int lane, double *__restrict__ cam, c
     }
     res_sync();
     // ---- S0 = L L^T, S0^-1 = L^-T L^-1 (every lane, in registers) ----
-    const double a00 = W.S0[0], a01 = W.S0[1], a02 = W.S0[2], a11 = W.S0[4], a12 = W.S0[5], a22 = W.S0[8];
-    const double d1 = a00;
-    const double i0 = 1.0 / sqrt(d1);
-    const double l10 = a01 * i0, l20 = a02 * i0;
-    const double d2 = a11 - l10 * l10;
-    const double i1 = 1.0 / sqrt(d2);
-    const double l21 = (a12 - l20 * l10) * i1;
-    const double d3 = (a22 - l20 * l20) - l21 * l21;
-    const double i2 = 1.0 / sqrt(d3);
-    if (!(d1 > 0.0 && d2 > 0.0 && d3 > 0.0)) return kResDegenerate;
+    const Chol3 L = chol3_factor(W.S0[0], W.S0[1], W.S0[2], W.S0[4], W.S0[5], W.S0[8]);
+    if (!L.positive()) return kResDegenerate;
+    const double i0 = L.i0, l10 = L.l10, l20 = L.l20, i1 = L.i1, l21 = L.l21, i2 = L.i2;
     const double m10 = -(l10 * i0) * i1, m20 = -(l20 * i0 + l21 * m10) * i2, m21 = -(l21 * i1) * i2;
     const double si00 = (i0 * i0 + m10 * m10) + m20 * m20, si01 = m10 * i1 + m20 * m21, si02 = m20 * i2;
     const double si11 = i1 * i1 + m21 * m21, si12 = m21 * i2, si22 = i2 * i2;
@@ -324,17 +317,10 @@ C2B_DEV int resect_camera(ResLds &W, const int lane, double *__restrict__ cam, c
         res_jt(R, W.T + 27, h2);
         const double H[6] = {h0[0], h1[0], h2[0], h1[1], h2[1], h2[2]};          // 00 01 02 11 12 22: the upper triangle
         res_sync();
-        const double e1 = H[0];
-        const double j0 = 1.0 / sqrt(e1);
-        const double n10 = H[1] * j0, n20 = H[2] * j0;
-        const double e2 = H[3] - n10 * n10;
-        const double j1 = 1.0 / sqrt(e2);
-        const double n21 = (H[4] - n20 * n10) * j1;
-        const double e3 = (H[5] - n20 * n20) - n21 * n21;
-        const double j2 = 1.0 / sqrt(e3);
-        if (!(e1 > 0.0 && e2 > 0.0 && e3 > 0.0)) return kResDegenerate;
-        const double z0 = -g[0] * j0, z1 = (-g[1] - n10 * z0) * j1, z2 = ((-g[2] - n20 * z0) - n21 * z1) * j2;
-        const double dl2 = z2 * j2, dl1 = (z1 - n21 * dl2) * j1, dl0 = ((z0 - n10 * dl1) - n20 * dl2) * j0;
+        const Chol3 Lh = chol3_factor(H[0], H[1], H[2], H[3], H[4], H[5]);
+        if (!Lh.positive()) return kResDegenerate;
+        double dl0, dl1, dl2;
+        Lh.solve(-g[0], -g[1], -g[2], dl0, dl1, dl2);
         if (!(isfinite(dl0) && isfinite(dl1) && isfinite(dl2))) return kResDegenerate;
         double E[9], N[9];
         from_rodrigues(dl0, dl1, dl2, E);

@@ -82,16 +82,11 @@ __global__ __launch_bounds__(kSchurBlock) void k_schur_points(
             }
         }
     }
-    // V_l = L L^T, L in registers (the reciprocals of its diagonal)
+    // V_l = L L^T, L in registers
     const double *Vp = V + p * 9;
-    const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
-    const double i0 = 1.0 / sqrt(v00);
-    const double l10 = v10 * i0, l20 = v20 * i0;
-    const double i1 = 1.0 / sqrt(v11 - l10 * l10);
-    const double l21 = (v21 - l20 * l10) * i1;
-    const double i2 = 1.0 / sqrt((v22 - l20 * l20) - l21 * l21);
-    const double y0 = a0 * i0, y1 = (a1 - l10 * y0) * i1, y2 = ((a2 - l20 * y0) - l21 * y1) * i2;
-    const double t2 = y2 * i2, t1 = (y1 - l21 * t2) * i1, t0 = ((y0 - l10 * t1) - l20 * t2) * i0;
+    const Chol3 L = chol3_factor(damped(Vp[0], lam), Vp[3], Vp[6], damped(Vp[4], lam), Vp[7], damped(Vp[8], lam));
+    double t0, t1, t2;
+    L.solve(a0, a1, a2, t0, t1, t2);
     t[3 * p] = NEG ? -t0 : t0;
     t[3 * p + 1] = NEG ? -t1 : t1;
     t[3 * p + 2] = NEG ? -t2 : t2;
@@ -307,16 +302,12 @@ __global__ __launch_bounds__(kNormBlock) void k_schur_jacobi(
         double r0, r1, jc[18], jp[6];
         jacobian_obs(cam, pts4[pi], uv_obs[o], r0, r1, jc, jp);
         if constexpr (sizeof...(Loss) > 0) loss_scale_obs(loss..., r0, r1, jc, jp);
-        // V_l = L L^T, L in registers (the reciprocals of its diagonal)
+        // V_l = L L^T, L in registers
         const double *Vp = V + (int64_t)pi * 9;
-        const double v00 = damped(Vp[0], lam), v10 = Vp[3], v20 = Vp[6], v11 = damped(Vp[4], lam), v21 = Vp[7], v22 = damped(Vp[8], lam);
-        const double i0 = 1.0 / sqrt(v00);
-        const double l10 = v10 * i0, l20 = v20 * i0;
-        const double i1 = 1.0 / sqrt(v11 - l10 * l10);
-        const double l21 = (v21 - l20 * l10) * i1;
-        const double i2 = 1.0 / sqrt((v22 - l20 * l20) - l21 * l21);
-        const double ya0 = jp[0] * i0, ya1 = (jp[1] - l10 * ya0) * i1, ya2 = ((jp[2] - l20 * ya0) - l21 * ya1) * i2;
-        const double yb0 = jp[3] * i0, yb1 = (jp[4] - l10 * yb0) * i1, yb2 = ((jp[5] - l20 * yb0) - l21 * yb1) * i2;
+        const Chol3 L = chol3_factor(damped(Vp[0], lam), Vp[3], Vp[6], damped(Vp[4], lam), Vp[7], damped(Vp[8], lam));
+        double ya0, ya1, ya2, yb0, yb1, yb2;
+        L.forward(jp[0], jp[1], jp[2], ya0, ya1, ya2);
+        L.forward(jp[3], jp[4], jp[5], yb0, yb1, yb2);
         const double f00 = 1.0 - ((ya0 * ya0 + ya1 * ya1) + ya2 * ya2);
         const double f01 = -((ya0 * yb0 + ya1 * yb1) + ya2 * yb2);
         const double f11 = 1.0 - ((yb0 * yb0 + yb1 * yb1) + yb2 * yb2);

@@ -6,10 +6,11 @@
 //     index, the walk of k_normal_points and k_schur_points.  Per observation the unit ray d of the observed pixel in the
 //     world frame (tri_ray: the pixel undistorted by Newton, the camera's R^T) and A += I - d d^T, b += (I - d d^T) C with C
 //     the camera's centre (record doubles 24..26): six + three accumulators in registers.  X = A^-1 b is the point nearest,
-//     in the sum of squared distances, to every ray's line.  Then the parallax test lambda_min(A) >= 1 - cos(min_angle)
-//     (tri_lambda_max: lambda_min(A) = n - lambda_max(sum d d^T), in closed form), the 3x3 Cholesky in registers, and a
-//     second walk for cheirality (q.z < 0 in every usable observation's camera).  One status byte per point; the point is
-//     written only when the status is kTriOk, its fourth lane untouched.
+//     in the sum of squared distances, to every ray's line (TriSums, tri_add).  Then tri_solve: the parallax test
+//     lambda_min(A) >= 1 - cos(min_angle) (tri_lambda_max: lambda_min(A) = n - lambda_max(sum d d^T), in closed form) and
+//     the 3x3 Cholesky in registers (Chol3, camera_math.hpp); and a second walk for cheirality (q.z < 0 in every usable
+//     observation's camera).  One status byte per point; the point is written only when the status is kTriOk, its fourth
+//     lane untouched.
 //   * the five status counts: LDS integer atomics per workgroup, then at most five 64-bit integer atomics per workgroup
 //     into counts[5] (zeroed by the launcher).  Integer sums carry no order dependence.
 // No float atomics, no scratch memory, no robust loss; a point's sums depend on its own list alone, so the same inputs
@@ -93,6 +94,29 @@ C2B_DEV double tri_lambda_max(double m00, double m01, double m02, double m11, do
     return q + 2.0 * p * tri_cos(acos(r) / 3.0);
 }
 
+// The sums over a point's usable rays: A = sum (I - d d^T) (its upper triangle), b = sum (I - d d^T) C
+struct TriSums { double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0; };
+
+// the unit ray d through the centre C joins the sums
+C2B_DEV void tri_add(TriSums &s, double dx, double dy, double dz, double cx, double cy, double cz) {
+    const double dc = (dx * cx + dy * cy) + dz * cz;
+    s.a00 += 1.0 - dx * dx; s.a01 -= dx * dy; s.a02 -= dx * dz;
+    s.a11 += 1.0 - dy * dy; s.a12 -= dy * dz; s.a22 += 1.0 - dz * dz;
+    s.b0 += cx - dx * dc; s.b1 += cy - dy * dc; s.b2 += cz - dz * dc;
+}
+
+// The acceptance test and the solve over the sums of n_used rays: X = A^-1 b, true when lambda_min(A) >= one_minus_cos,
+// the three pivots are positive and X is finite.  Both triangulation passes accept and solve through this routine, so a
+// consensus refit is plain triangulation of its inliers bit for bit.
+C2B_DEV bool tri_solve(const TriSums &s, int n_used, double one_minus_cos, double &x0, double &x1, double &x2) {
+    const double n = (double)n_used;
+    const double lam_min = n - tri_lambda_max(n - s.a00, -s.a01, -s.a02, n - s.a11, -s.a12, n - s.a22);
+    const Chol3 L = chol3_factor(s.a00, s.a01, s.a02, s.a11, s.a12, s.a22);
+    L.solve(s.b0, s.b1, s.b2, x0, x1, x2);
+    const bool solved = L.positive() && isfinite(x0) && isfinite(x1) && isfinite(x2);
+    return lam_min >= one_minus_cos && solved;
+}
+
 // pt_mask == NULL: no point is constant.  counts[kTriKinds] must be zero when the kernel starts.
 __global__ __launch_bounds__(kTriBlock) void k_triangulate_points(
     const double *__restrict__ camblk, double4 *__restrict__ pts4, int64_t n_pts, const uint64_t *__restrict__ pt_row_ptr,
@@ -106,7 +130,7 @@ __global__ __launch_bounds__(kTriBlock) void k_triangulate_points(
         int st = kTriConstant;
         if (!pt_mask || !pt_mask[p]) {
             const uint64_t b = pt_row_ptr[p], e = pt_row_ptr[p + 1];
-            double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
+            TriSums s;
             int n_used = 0;
 #pragma unroll 1
             for (uint64_t j = b; j < e; ++j) {
@@ -114,31 +138,14 @@ __global__ __launch_bounds__(kTriBlock) void k_triangulate_points(
                 double dx, dy, dz;
                 if (!tri_ray(cam_ref(camblk, c), uv_obs[obs_of[j]], dx, dy, dz)) continue;
                 const double *C = camblk + cam_center_at((int64_t)c);
-                const double cx = C[0], cy = C[1], cz = C[2];
-                const double dc = (dx * cx + dy * cy) + dz * cz;
-                a00 += 1.0 - dx * dx; a01 -= dx * dy; a02 -= dx * dz;
-                a11 += 1.0 - dy * dy; a12 -= dy * dz; a22 += 1.0 - dz * dz;
-                b0 += cx - dx * dc; b1 += cy - dy * dc; b2 += cz - dz * dc;
+                tri_add(s, dx, dy, dz, C[0], C[1], C[2]);
                 ++n_used;
             }
             st = kTriTooFew;
             if (n_used >= 2) {
                 st = kTriDegenerate;
-                const double n = (double)n_used;
-                const double lam_min = n - tri_lambda_max(n - a00, -a01, -a02, n - a11, -a12, n - a22);
-                // A = L L^T, L in registers (the reciprocals of its diagonal), as k_schur_points factors V_l
-                const double d1 = a00;
-                const double i0 = 1.0 / sqrt(d1);
-                const double l10 = a01 * i0, l20 = a02 * i0;
-                const double d2 = a11 - l10 * l10;
-                const double i1 = 1.0 / sqrt(d2);
-                const double l21 = (a12 - l20 * l10) * i1;
-                const double d3 = (a22 - l20 * l20) - l21 * l21;
-                const double i2 = 1.0 / sqrt(d3);
-                const double y0 = b0 * i0, y1 = (b1 - l10 * y0) * i1, y2 = ((b2 - l20 * y0) - l21 * y1) * i2;
-                const double x2 = y2 * i2, x1 = (y1 - l21 * x2) * i1, x0 = ((y0 - l10 * x1) - l20 * x2) * i0;
-                const bool solved = d1 > 0.0 && d2 > 0.0 && d3 > 0.0 && isfinite(x0) && isfinite(x1) && isfinite(x2);
-                if (lam_min >= one_minus_cos && solved) {
+                double x0, x1, x2;
+                if (tri_solve(s, n_used, one_minus_cos, x0, x1, x2)) {
                     st = kTriOk;
 #pragma unroll 1
                     for (uint64_t j = b; j < e; ++j) {

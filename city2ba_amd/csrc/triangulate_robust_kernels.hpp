@@ -6,8 +6,8 @@
 //   * k_triangulate_consensus: point-major through the transpose, one wave per point, the row walked 64 entries at a time.
 //       sample    lanes = the row's first 64 entries: tri_ray, a ballot, the usable rays and centres compacted in row order
 //                 into wave-private LDS (48 B x 64);
-//       hypothesis lanes = pairs of the sample, wide gaps first (trc_pair): X_k from k_triangulate_points' own sums and
-//                 Cholesky over the two rays, formed when it passes that kernel's acceptance test;
+//       hypothesis lanes = pairs of the sample, wide gaps first (trc_pair): X_k from tri_add over the two rays, formed
+//                 when tri_solve accepts it;
 //       score     the row again chunk by chunk: the lanes find the usable entries (tri_ray, ballot), then for every set bit
 //                 every lane projects ITS X_k through the SAME camera and pixel -- wave-uniform addresses, so the k2 != 0
 //                 route of project_obs is a wave-uniform branch -- and counts the filter's predicate (MODE_RESIDUAL_KEEP with
@@ -18,8 +18,8 @@
 //                 parallax test and the Cholesky;
 //       cheirality and mask: one more walk, q.z < 0 for the refit X in every inlier's camera; the zeros of the inlier mask
 //                 are written here and taken back by a last walk if a camera turns out to see X from behind.
-//     The nine-accumulator update and the 3x3 Cholesky are k_triangulate_points' restated (trc_add, trc_solve), as that
-//     kernel restated k_schur_points': with -ffp-contract=off the refit is bit for bit k_triangulate_points on the inliers.
+//     The nine-accumulator update, the acceptance test and the solve are k_triangulate_points' own routines (tri_add,
+//     tri_solve): the refit is bit for bit k_triangulate_points on the inliers.
 //   * the six status counts: LDS integer atomics per workgroup, then at most six 64-bit integer atomics per workgroup.
 // Every loop is bounded by the row length, the 16 Newton steps or 64; no wave waits for another.  No float atomics, no
 // scratch memory, no robust loss, nothing stored per row: a point's result depends on its own row alone.
@@ -39,35 +39,6 @@ C2B_DEV void trc_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-struct TrcSums { double a00, a01, a02, a11, a12, a22, b0, b1, b2; };
-
-// k_triangulate_points' update for the ray d through the centre C
-C2B_DEV void trc_add(TrcSums &s, double dx, double dy, double dz, double cx, double cy, double cz) {
-    const double dc = (dx * cx + dy * cy) + dz * cz;
-    s.a00 += 1.0 - dx * dx; s.a01 -= dx * dy; s.a02 -= dx * dz;
-    s.a11 += 1.0 - dy * dy; s.a12 -= dy * dz; s.a22 += 1.0 - dz * dz;
-    s.b0 += cx - dx * dc; s.b1 += cy - dy * dc; s.b2 += cz - dz * dc;
-}
-
-// k_triangulate_points' acceptance test and solve over the sums of n_used rays: lambda_min(A) >= one_minus_cos && solved
-C2B_DEV bool trc_solve(const TrcSums &s, int n_used, double one_minus_cos, double &x0, double &x1, double &x2) {
-    const double a00 = s.a00, a01 = s.a01, a02 = s.a02, a11 = s.a11, a12 = s.a12, a22 = s.a22, b0 = s.b0, b1 = s.b1, b2 = s.b2;
-    const double n = (double)n_used;
-    const double lam_min = n - tri_lambda_max(n - a00, -a01, -a02, n - a11, -a12, n - a22);
-    const double d1 = a00;
-    const double i0 = 1.0 / sqrt(d1);
-    const double l10 = a01 * i0, l20 = a02 * i0;
-    const double d2 = a11 - l10 * l10;
-    const double i1 = 1.0 / sqrt(d2);
-    const double l21 = (a12 - l20 * l10) * i1;
-    const double d3 = (a22 - l20 * l20) - l21 * l21;
-    const double i2 = 1.0 / sqrt(d3);
-    const double y0 = b0 * i0, y1 = (b1 - l10 * y0) * i1, y2 = ((b2 - l20 * y0) - l21 * y1) * i2;
-    x2 = y2 * i2; x1 = (y1 - l21 * x2) * i1; x0 = ((y0 - l10 * x1) - l20 * x2) * i0;
-    const bool solved = d1 > 0.0 && d2 > 0.0 && d3 > 0.0 && isfinite(x0) && isfinite(x1) && isfinite(x2);
-    return lam_min >= one_minus_cos && solved;
 }
 
 // Pair number k of a sample of m >= 2: the gap g runs from m / 2 down to 1, i over 0 .. m - 1 (2 g == m: i < g only, each
@@ -136,10 +107,10 @@ C2B_DEV int triangulate_consensus_point(TrcLds &W, const int lane, const double 
     {
         int lo, hi;
         if (trc_pair(lane, m, lo, hi) && lane < max_hypotheses) {
-            TrcSums s = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            trc_add(s, W.f[0][lo], W.f[1][lo], W.f[2][lo], W.f[3][lo], W.f[4][lo], W.f[5][lo]);
-            trc_add(s, W.f[0][hi], W.f[1][hi], W.f[2][hi], W.f[3][hi], W.f[4][hi], W.f[5][hi]);
-            formed = trc_solve(s, 2, one_minus_cos, x0, x1, x2);
+            TriSums s;
+            tri_add(s, W.f[0][lo], W.f[1][lo], W.f[2][lo], W.f[3][lo], W.f[4][lo], W.f[5][lo]);
+            tri_add(s, W.f[0][hi], W.f[1][hi], W.f[2][hi], W.f[3][hi], W.f[4][hi], W.f[5][hi]);
+            formed = tri_solve(s, 2, one_minus_cos, x0, x1, x2);
         }
         if (!formed) { x0 = 0.0; x1 = 0.0; x2 = 0.0; }
     }
@@ -184,7 +155,7 @@ C2B_DEV int triangulate_consensus_point(TrcLds &W, const int lane, const double 
     x0 = __shfl(x0, win, 64); x1 = __shfl(x1, win, 64); x2 = __shfl(x2, win, 64);
     trc_sync();                                              // the sample's slots are staged over below
     // ---- refit: the winner's inliers in ascending row order ----
-    TrcSums s = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    TriSums s;
 #pragma unroll 1
     for (int t0 = 0; t0 < n; t0 += 64) {
         const uint64_t j = b + (uint64_t)(t0 + lane);
@@ -207,12 +178,12 @@ C2B_DEV int triangulate_consensus_point(TrcLds &W, const int lane, const double 
         while (in_mask != 0ull) {                            // wave-uniform: every lane forms the same sums
             const int t = __builtin_ctzll(in_mask);
             in_mask &= in_mask - 1ull;
-            trc_add(s, W.f[0][t], W.f[1][t], W.f[2][t], W.f[3][t], W.f[4][t], W.f[5][t]);
+            tri_add(s, W.f[0][t], W.f[1][t], W.f[2][t], W.f[3][t], W.f[4][t], W.f[5][t]);
         }
         trc_sync();
     }
     double r0, r1, r2;
-    if (!trc_solve(s, n_inl, one_minus_cos, r0, r1, r2)) return kTriDegenerate;
+    if (!tri_solve(s, n_inl, one_minus_cos, r0, r1, r2)) return kTriDegenerate;
     // ---- cheirality of the refit in every inlier's camera; the mask's zeros ----
     bool behind = false;
 #pragma unroll 1

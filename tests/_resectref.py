@@ -23,6 +23,7 @@ deviation from the unperturbed run (R entry by entry, t in norm), floored at FLO
 import numpy as np
 
 import _schurref as R_
+import _triangref as T_
 
 LD = np.longdouble
 EPS = R_.EPS
@@ -70,31 +71,8 @@ def jacobi_eigh(A, sweeps=40):
 def pixel_rays(intr, uv, cam_of):
     """(b [n_obs, 3] longdouble, usable [n_obs] bool): the unit ray of every observed pixel in its camera's frame"""
     intr = np.asarray(intr).astype(LD)[cam_of]
-    uv = np.asarray(uv).astype(LD).reshape(-1, 2)
-    n = len(cam_of)
-    f, k1, k2 = intr[:, 0], intr[:, 1], intr[:, 2]
-    usable = (f != 0) & np.isfinite(f)
+    b, usable = T_.undistorted_pixels(intr[:, 0], intr[:, 1], intr[:, 2], uv)
     with np.errstate(all="ignore"):
-        m = uv / np.where(usable, f, LD(1))[:, None]
-        rd = np.sqrt(m[:, 0] * m[:, 0] + m[:, 1] * m[:, 1])
-        rho = rd.copy()
-        active = usable & ((k1 != 0) | (k2 != 0))
-        for _ in range(200):
-            if not active.any():
-                break
-            r2 = rho * rho
-            dg = 1 + 3 * k1 * r2 + 5 * k2 * r2 * r2
-            bad = active & ~(dg > 0)
-            usable &= ~bad
-            active &= ~bad
-            nxt = rho - (rho * (1 + k1 * r2 + k2 * r2 * r2) - rd) / np.where(dg > 0, dg, LD(1))
-            done = active & ((np.abs(nxt - rho) <= 4 * np.finfo(LD).eps * np.abs(rho)) | ~np.isfinite(nxt))     # (a last-bit 2-cycle is convergence)
-            rho = np.where(active, nxt, rho)
-            active &= ~done
-        assert not active.any(), "Newton did not converge"
-        usable &= np.isfinite(rho)
-        s = np.where(rd == 0, LD(0), rho / np.where(rd == 0, LD(1), rd))
-        b = np.stack([m[:, 0] * s, m[:, 1] * s, -np.ones(n, dtype=LD)], axis=1)
         b = b / np.sqrt(np.sum(b * b, axis=1))[:, None]
     return b, usable
 

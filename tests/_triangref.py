@@ -33,12 +33,11 @@ def threshold(min_angle):
     return LD(1) - np.cos(LD(min_angle))
 
 
-def rays(cams15, uv, cam_of):
-    """(d [n_obs, 3] longdouble, usable [n_obs] bool): the unit ray of every observation in the world frame"""
-    cam = np.asarray(cams15).astype(LD)[cam_of]
+def undistorted_pixels(f, k1, k2, uv):
+    """(ray [n_obs, 3] longdouble, usable [n_obs] bool): every observed pixel's ray in its camera's frame, (m s, m s, -1)
+    with m = uv / f and s = rho / |m| the undistortion (rho (1 + k1 rho^2 + k2 rho^4) = |m| by Newton), not normalised"""
+    f, k1, k2 = (np.asarray(v).astype(LD) for v in (f, k1, k2))
     uv = np.asarray(uv).astype(LD).reshape(-1, 2)
-    n = len(cam_of)
-    f, k1, k2 = cam[:, 12], cam[:, 13], cam[:, 14]
     usable = (f != 0) & np.isfinite(f)
     with np.errstate(all="ignore"):
         m = uv / np.where(usable, f, LD(1))[:, None]
@@ -60,7 +59,15 @@ def rays(cams15, uv, cam_of):
         assert not active.any(), "Newton did not converge"
         usable &= np.isfinite(rho)
         s = np.where(rd == 0, LD(0), rho / np.where(rd == 0, LD(1), rd))
-        ray = np.stack([m[:, 0] * s, m[:, 1] * s, -np.ones(n, dtype=LD)], axis=1)
+        ray = np.stack([m[:, 0] * s, m[:, 1] * s, -np.ones(len(uv), dtype=LD)], axis=1)
+    return ray, usable
+
+
+def rays(cams15, uv, cam_of):
+    """(d [n_obs, 3] longdouble, usable [n_obs] bool): the unit ray of every observation in the world frame"""
+    cam = np.asarray(cams15).astype(LD)[cam_of]
+    ray, usable = undistorted_pixels(cam[:, 12], cam[:, 13], cam[:, 14], uv)
+    with np.errstate(all="ignore"):
         # cams15's R is column-major, Rm[i][j] = cam[3 j + i]; (R^T ray)_j = sum_i cam[3 j + i] ray_i
         d = np.stack([cam[:, 3 * j] * ray[:, 0] + cam[:, 3 * j + 1] * ray[:, 1] + cam[:, 3 * j + 2] * ray[:, 2] for j in range(3)], axis=1)
         d = d / np.sqrt(np.sum(d * d, axis=1))[:, None]
