@@ -101,6 +101,10 @@ TRI_DROP_OUTLIERS = 1      # C2B_TRI_DROP_OUTLIERS: compact the list by the inli
 # statuses of c2b_problem_resect_cameras / c2b_resect_rows (C2B_RES_*), the order of their counts
 RES_OK, RES_TOO_FEW, RES_DEGENERATE, RES_BEHIND, RES_CONSTANT = range(5)
 RES_STATUS = ("resected", "too_few", "degenerate", "behind", "constant")
+# c2b_problem_resect_consensus / c2b_resect_consensus_rows add one status (C2B_RES_NO_CONSENSUS) and one flag
+RES_NO_CONSENSUS = 5
+RES_CONSENSUS_STATUS = RES_STATUS + ("no_consensus",)
+RES_DROP_OUTLIERS = 1      # C2B_RES_DROP_OUTLIERS: compact the list by the inlier mask afterwards
 
 
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
@@ -136,6 +140,7 @@ SIGNATURES = {
     "c2b_triangulate_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "c2b_triangulate_consensus_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_resect_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp]),
+    "c2b_resect_consensus_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _int, _d, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_reprojection_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "c2b_add_noise_observations_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _d, _u64, _vp, _vp, _vp]),
     "c2b_jacobian_stream_policy": (_int, [_i64, _i64, _i64]),
@@ -172,6 +177,7 @@ SIGNATURES = {
     "c2b_problem_triangulate_points": (_int, [_vp, _d, _vp, _vp]),
     "c2b_problem_triangulate_consensus": (_int, [_vp, _d, _d, _int, _int, _int, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_resect_cameras": (_int, [_vp, _int, _d, _vp, _vp]),
+    "c2b_problem_resect_consensus": (_int, [_vp, _d, _int, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
     "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),

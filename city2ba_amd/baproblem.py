@@ -594,6 +594,44 @@ class BAProblem:
         return self._status_pass(L.lib().c2b_problem_resect_cameras, (int(min_points), float(min_gap)), self.num_cameras(),
                                  L.RES_STATUS, return_status)
 
+    def resect_cameras_robust(self, max_error, min_inliers=6, min_gap=1e-4, max_hypotheses=64, drop_outliers=False,
+                              return_status=False, return_inliers=False):
+        """Consensus resection on the device (c2b_problem_resect_consensus): resect_cameras for a list that
+        holds wrong matches.  Per camera, candidate poses are formed from triples of its observations (at most
+        max_hypotheses <= 64, widely spaced triples first, from the usable observations among the row's first 64; every
+        three-point solution of a triple is a candidate), each is scored by how many observations of the camera it
+        reprojects within max_error with the point in front (filter_observations' predicate with in_front), and the
+        camera is set to resect_cameras' fit over the best candidate's inliers -- if there are min_inliers (>= 6) of them
+        and that fit passes its own tests (min_gap, cheirality); otherwise it keeps its bits.  With drop_outliers the
+        observations of the resected cameras that are not inliers are then removed from the list as filter_observations
+        removes its own.  Returns dict(resected, too_few, degenerate, behind, constant, no_consensus, outliers, removed):
+        the number of cameras of each outcome, the zeros of the inlier mask and how many observations left the list; with
+        return_status also (status [n_cam] uint8 in the dict's order 0 .. 5, hyp [n_cam] int32 = the selected triple or
+        -1, n_inl [n_cam] int32 = its inlier count), with return_inliers also the mask [n_obs] uint8 over the list as it
+        was at the call.  The problem is in bal mode afterwards, as after resect_cameras."""
+        n_cam, n_obs = self.num_cameras(), self.num_observations()
+        counts = np.zeros(6, dtype=np.int64)
+        status = np.zeros(n_cam, dtype=np.uint8)
+        hyp = np.zeros(n_cam, dtype=np.int32)
+        n_inl = np.zeros(n_cam, dtype=np.int32)
+        inlier = np.ones(n_obs, dtype=np.uint8)
+        removed = C.c_int64()
+        L.check(L.lib().c2b_problem_resect_consensus(
+            self._h, float(max_error), int(min_inliers), float(min_gap), int(max_hypotheses), L.RES_DROP_OUTLIERS if drop_outliers else 0,
+            status.ctypes.data_as(C.c_void_p), hyp.ctypes.data_as(C.c_void_p), n_inl.ctypes.data_as(C.c_void_p),
+            inlier.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), C.byref(removed)))
+        if removed.value:
+            self._refresh_graph()
+        out = dict(zip(L.RES_CONSENSUS_STATUS, (int(v) for v in counts)))
+        out["outliers"] = int(n_obs - np.count_nonzero(inlier))
+        out["removed"] = int(removed.value)
+        ret = (out,)
+        if return_status:
+            ret += (status, hyp, n_inl)
+        if return_inliers:
+            ret += (inlier,)
+        return ret if len(ret) > 1 else out
+
     def subset(self, ci, pi):
         """BAProblem::subset (src/baproblem.rs:394-423): cameras ci and points pi in the given order; observations of
         dropped points disappear.  Host-side index shuffling; returns a NEW device problem."""

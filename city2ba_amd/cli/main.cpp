@@ -26,8 +26,9 @@
 //   city2ba triangulate IN OUT [--min-angle DEG] [--max-error X [--min-inliers N] [--max-hypotheses H] [--drop-outliers]]
 //                        (extension: the points from the cameras and observations, c2b_problem_triangulate_points; with
 //                         --max-error: from the rays that agree with each other, c2b_problem_triangulate_consensus)
-//   city2ba resect IN OUT [--min-points N] [--min-gap G]
-//                        (extension: the camera poses from the points and observations, c2b_problem_resect_cameras)
+//   city2ba resect IN OUT [--min-points N] [--min-gap G] [--max-error X [--min-inliers N] [--max-hypotheses H] [--drop-outliers]]
+//                        (extension: the camera poses from the points and observations, c2b_problem_resect_cameras; with
+//                         --max-error: from the observations that agree with each other, c2b_problem_resect_consensus)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -938,24 +939,48 @@ int run_triangulate(int argc, char **argv) {
 
 // `resect`: every camera pose of a .bal / .bbal from its points and observations by c2b_problem_resect_cameras (an
 // extension: the minimiser of the object-space error on the device; points, intrinsics and observations are written as they
-// were read).  Every argument is parsed before the device is touched.
+// were read).  Every argument is parsed before the device is touched.  --max-error X selects consensus resection
+// (c2b_problem_resect_consensus): candidate poses from triples of observations, the one most observations reproject within
+// X of, the same fit on those; --drop-outliers then removes the other observations of the resected cameras from the list.
 int run_resect(int argc, char **argv) {
-    const Args a = parse(argc, argv, 2, {}, {"min-points", "min-gap", "device"});
+    const Args a = parse(argc, argv, 2, {"drop-outliers"}, {"min-points", "min-gap", "device", "max-error", "min-inliers", "max-hypotheses"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
     const int64_t min_points = a.i("min-points", 6);
     const double min_gap = a.f("min-gap", 1e-4);
     const int device = (int)a.i("device", 0);
     if (min_points < 6 || min_points > 2147483647) die("Invalid value for '--min-points <N>': expected an integer of at least 6");
     if (!(min_gap >= 0.0 && min_gap < 1.0)) die("Invalid value for '--min-gap <G>': expected a number in 0 ... 1 (1 excluded)");
+    const bool robust = a.has("max-error");
+    const double max_error = a.f("max-error", 0.0);
+    const int64_t min_inliers = a.i("min-inliers", 6), max_hypotheses = a.i("max-hypotheses", 64);
+    if (robust && !(max_error >= 0.0 && std::isfinite(max_error))) die("Invalid value for '--max-error <X>': expected a finite number >= 0");
+    if (min_inliers < 6 || min_inliers > 2147483647) die("Invalid value for '--min-inliers <N>': expected an integer of at least 6");
+    if (max_hypotheses < 1 || max_hypotheses > 64) die("Invalid value for '--max-hypotheses <H>': expected an integer in 1 ... 64");
+    if (!robust && (a.has("min-inliers") || a.has("max-hypotheses") || a.has("drop-outliers")))
+        die("--min-inliers, --max-hypotheses and --drop-outliers need --max-error <X>");
+    if (robust && a.has("min-points")) die("--min-points does not go with --max-error <X>: --min-inliers <N> takes its place");
     PhaseTimer timer;
     int64_t nc = 0, np = 0, no = 0;
     c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
-    int64_t counts[5] = {0, 0, 0, 0, 0};
-    ck(c2b_problem_resect_cameras(p, (int)min_points, min_gap, nullptr, counts));
-    timer.mark("resect_cameras (device)");
-    std::printf("resected %lld cameras; kept: %lld too few observations, %lld degenerate, %lld behind a point, %lld constant\n",
-                (long long)counts[C2B_RES_OK], (long long)counts[C2B_RES_TOO_FEW], (long long)counts[C2B_RES_DEGENERATE],
-                (long long)counts[C2B_RES_BEHIND], (long long)counts[C2B_RES_CONSTANT]);
+    int64_t counts[6] = {0, 0, 0, 0, 0, 0};
+    if (robust) {
+        int64_t removed = 0;
+        std::vector<uint8_t> inlier((size_t)no);
+        ck(c2b_problem_resect_consensus(p, max_error, (int)min_inliers, min_gap, (int)max_hypotheses,
+                                        a.has("drop-outliers") ? C2B_RES_DROP_OUTLIERS : 0, nullptr, nullptr, nullptr, inlier.data(), counts, &removed));
+        timer.mark("resect_consensus (device)");
+        std::printf("resected %lld cameras; kept: %lld too few observations, %lld degenerate, %lld behind a point, %lld constant, "
+                    "%lld without consensus\n%lld outlier observations, %lld removed\n",
+                    (long long)counts[C2B_RES_OK], (long long)counts[C2B_RES_TOO_FEW], (long long)counts[C2B_RES_DEGENERATE],
+                    (long long)counts[C2B_RES_BEHIND], (long long)counts[C2B_RES_CONSTANT], (long long)counts[C2B_RES_NO_CONSENSUS],
+                    (long long)std::count(inlier.begin(), inlier.end(), (uint8_t)0), (long long)removed);
+    } else {
+        ck(c2b_problem_resect_cameras(p, (int)min_points, min_gap, nullptr, counts));
+        timer.mark("resect_cameras (device)");
+        std::printf("resected %lld cameras; kept: %lld too few observations, %lld degenerate, %lld behind a point, %lld constant\n",
+                    (long long)counts[C2B_RES_OK], (long long)counts[C2B_RES_TOO_FEW], (long long)counts[C2B_RES_DEGENERATE],
+                    (long long)counts[C2B_RES_BEHIND], (long long)counts[C2B_RES_CONSTANT]);
+    }
     close_problem(timer, p, a.positional[1]);
     return 0;
 }
@@ -1029,7 +1054,14 @@ const char *subcommand_help(const std::string &sub) {
         return "city2ba resect <FILE> <OUT>\n"
                "    --min-points <N> [6]      a camera with fewer usable observations keeps its pose (at least 6)\n"
                "    --min-gap <G> [1e-4]      degeneracy test: a camera whose points are so close to coplanar, or so little spread, that\n"
-               "                              lambda_2 < G lambda_9 keeps its pose\n";
+               "                              lambda_2 < G lambda_9 keeps its pose\n"
+               "    --max-error <X>           consensus resection for a list with wrong matches: candidate poses from triples of\n"
+               "                              observations, the one most observations reproject within X of (the point in front), the\n"
+               "                              same fit on those [off]\n"
+               "    --min-inliers <N> [6]     a camera whose best candidate has fewer inliers keeps its pose (at least 6; takes the\n"
+               "                              place of --min-points)\n"
+               "    --max-hypotheses <H> [64] candidates per camera, widest triples first (1 ... 64)\n"
+               "    --drop-outliers           then remove the observations of the resected cameras that are not inliers\n";
     return nullptr;
 }
 

@@ -39,6 +39,7 @@
 #include "triangulate_kernels.hpp"
 #include "triangulate_robust_kernels.hpp"
 #include "resect_kernels.hpp"
+#include "resect_robust_kernels.hpp"
 #include "cull_kernels.hpp"
 #include "cell_kernels.hpp"
 #include "text_kernels.hpp"

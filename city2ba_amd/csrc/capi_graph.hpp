@@ -433,6 +433,59 @@ int c2b_problem_triangulate_consensus(c2b_problem *p, double min_angle, double m
     C2B_API_END("problem_triangulate_consensus")
 }
 
+// Consensus resection: c2b_resect_consensus_rows over the row structure, in place on bal9 made the truth as
+// c2b_problem_resect_cameras makes it -- the cameras moved, so their caches go -- and, with C2B_RES_DROP_OUTLIERS, the filter's
+// compaction of the list by the pass's inlier mask, as c2b_problem_triangulate_consensus does it.  The cameras have moved by the
+// time the list is compacted.
+int c2b_problem_resect_consensus(c2b_problem *p, double max_error, int min_inliers, double min_gap, int max_hypotheses, int flags,
+                                 uint8_t *status, int32_t *hyp, int32_t *n_inl, uint8_t *inlier, int64_t *counts, int64_t *n_removed) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_resect_consensus");
+    if (!good_tri_max_error(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_consensus: max_error must be finite and >= 0");
+    if (min_inliers < kResMinPoints)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_consensus: min_inliers must be at least %d", kResMinPoints);
+    if (!good_min_gap(min_gap)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_consensus: min_gap must lie in [0, 1)");
+    if (max_hypotheses < 1 || max_hypotheses > kRrcSample)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_consensus: max_hypotheses must lie in [1, %d]", kRrcSample);
+    if (flags & ~C2B_RES_DROP_OUTLIERS)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_consensus: unknown flag bits 0x%x", (unsigned)(flags & ~C2B_RES_DROP_OUTLIERS));
+    if (p->shard_n_cam_global >= 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_resect_consensus: a shard is not resected alone");
+    if (n_removed) *n_removed = 0;
+    const int64_t nc = p->n_cam, n_old = p->n_obs;
+    StatusReport rep(kRrcKinds);
+    if (!n_old) {                                            // no observation: every camera has too few, nothing is read or written
+        if (hyp && nc) std::fill(hyp, hyp + nc, (int32_t)-1);
+        if (n_inl && nc) std::fill(n_inl, n_inl + nc, (int32_t)0);
+        return rep.all_have(kResTooFew, nc, status, counts);
+    }
+    int rc = ensure_rows(p);
+    if (rc) return rc;
+    DevBuf<uint8_t> d_inlier;
+    DevBuf<int32_t> d_hyp, d_ninl;
+    hipError_t e = rep.alloc(nc);
+    if (e == hipSuccess) e = d_inlier.alloc((size_t)n_old);
+    if (e == hipSuccess) e = d_hyp.alloc((size_t)nc);
+    if (e == hipSuccess) e = d_ninl.alloc((size_t)nc);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_resect_consensus: allocation: %s", hipGetErrorString(e));
+    hipStream_t st = p->stream;
+    if (!p->bal_valid && !p->bal9_fresh) {                   // state mode: the pass works on to_vec(cam15)
+        if ((rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st))) return rc;
+        p->bal9_fresh = true;
+    }
+    rc = c2b_resect_consensus_rows(p->bal9, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, n_old, max_error, min_inliers, min_gap, max_hypotheses,
+                                   p->cmask, rep.d_status, d_hyp, d_ninl, d_inlier, rep.d_counts, st);
+    if (!rc) rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
+    if (!rc && hyp) e = hipMemcpyAsync(hyp, d_hyp, sizeof(int32_t) * (size_t)nc, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess && n_inl) e = hipMemcpyAsync(n_inl, d_ninl, sizeof(int32_t) * (size_t)nc, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess && inlier) e = hipMemcpyAsync(inlier, d_inlier, (size_t)n_old, hipMemcpyDeviceToHost, st);
+    rc = rep.read_back("problem_resect_consensus", st, rc, e, nc, status, counts);
+    cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
+    p->bal_valid = true;
+    if (rc || !(flags & C2B_RES_DROP_OUTLIERS)) return rc;
+    return compact_and_install(p, "problem_resect_consensus", d_inlier, n_old, n_removed);     // the filter's compaction, by the inlier mask
+    C2B_API_END("problem_resect_consensus")
+}
+
 int c2b_problem_visibility_pairs_compact(c2b_problem *p, int64_t n_pairs, const uint32_t *cam_idx, const uint32_t *pt_idx,
                                          double max_dist, uint64_t *row_ptr) {
     C2B_API_BEGIN

@@ -1552,6 +1552,37 @@ int c2b_resect_rows(double *bal9, const double *pts4, const uint64_t *row_ptr, i
     C2B_API_END("resect_rows")
 }
 
+// ---- consensus resection (resect_robust_kernels.hpp) -------------------------------------------------------
+int c2b_resect_consensus_rows(double *bal9, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                              const double *uv_obs, int64_t n_obs, double max_error, int min_inliers, double min_gap, int max_hypotheses,
+                              const uint16_t *cam_mask, uint8_t *status, int32_t *hyp, int32_t *n_inl, uint8_t *inlier, int64_t *counts,
+                              void *stream) {
+    C2B_API_BEGIN
+    if (n_cam < 0 || n_cam > (int64_t)0x7fffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_consensus_rows: n_cam out of range");
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 64)        // (a row's length and its chunk offsets are ints in the kernel)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "resect_consensus_rows: n_obs out of range");
+    if (!good_tri_max_error(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_consensus_rows: max_error must be finite and >= 0");
+    if (min_inliers < kResMinPoints) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_consensus_rows: min_inliers must be at least %d", kResMinPoints);
+    if (!good_min_gap(min_gap)) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_consensus_rows: min_gap must lie in [0, 1)");
+    if (max_hypotheses < 1 || max_hypotheses > kRrcSample)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "resect_consensus_rows: max_hypotheses must lie in [1, %d]", kRrcSample);
+    if (!counts || (n_cam && (!bal9 || !row_ptr || !status))) return fail(C2B_ERR_INVALID_ARGUMENT, "resect_consensus_rows: NULL argument");
+    if (!aligned8(bal9) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(row_ptr) || !aligned8(counts) ||
+        (reinterpret_cast<uintptr_t>(pt_idx) & 3) || (reinterpret_cast<uintptr_t>(cam_mask) & 1) || (reinterpret_cast<uintptr_t>(hyp) & 3) ||
+        (reinterpret_cast<uintptr_t>(n_inl) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "resect_consensus_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kRrcKinds, st));
+    if (inlier && n_obs) HIP_TRY(hipMemsetAsync(inlier, 1, (size_t)n_obs, st));      // the kernel writes the zeros
+    if (!n_cam) return C2B_OK;
+    hipLaunchKernelGGL(k_resect_consensus, dim3(blocks_for(n_cam, kResWaves)), dim3(kResBlock), 0, st, bal9, reinterpret_cast<const double4 *>(pts4),
+                       row_ptr, n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs), max_error * max_error, min_inliers, min_gap,
+                       max_hypotheses, cam_mask, status, hyp, n_inl, inlier, reinterpret_cast<unsigned long long *>(counts));
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("resect_consensus_rows")
+}
+
 // grid of k_schur_cameras: one wave per kNormCamsPerWave cameras
 static unsigned schur_cameras_grid(int64_t n_cam) {
     const int64_t quads = (n_cam + kNormCamsPerWave - 1) / kNormCamsPerWave, waves = kNormBlock / 64;

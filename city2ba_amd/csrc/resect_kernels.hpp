@@ -89,11 +89,19 @@ C2B_DEV void res_jt(const double *R, const double *w, double o[3]) {
     }
 }
 
+// resect_camera's keep predicate of k_resect_cameras: every usable observation counts
+struct ResKeepAll {
+    __device__ __forceinline__ bool operator()(uint64_t, double, double, double) const { return true; }
+};
+
 // The pose of one camera by the wave that calls it (every lane returns the same status; R column-major and t are written
-// by lane 0 when it is kResOk).  cam = the camera's bal9 row, [b, e) its row of the observation list.
+// by lane 0 when it is kResOk).  cam = the camera's bal9 row, [b, e) its row of the observation list.  keep(j, x, y, z) is
+// asked about every usable observation j (of the point x y z) in each of the three walks: what it refuses is not in the list
+// as far as this routine goes (resect_robust_kernels.hpp restricts the fit to a pose's inliers that way).
+template <typename Keep>
 C2B_DEV int resect_camera(ResLds &W, const int lane, double *__restrict__ cam, const double4 *__restrict__ pts4, const uint64_t b,
                           const uint64_t e, const uint32_t *__restrict__ pt_idx, const double2 *__restrict__ uv_obs, const int min_points,
-                          const double min_gap) {
+                          const double min_gap, const Keep keep) {
     const ResIntrinsics in = {cam[6], cam[7], cam[8]};
     // ---- walk 1: the centroid of the usable points (lanes 0..2 own a component each and add in row order) ----
     double acc = 0.0;
@@ -102,7 +110,7 @@ C2B_DEV int resect_camera(ResLds &W, const int lane, double *__restrict__ cam, c
     for (uint64_t j0 = b; j0 < e; j0 += 64) {
         const uint64_t j = j0 + lane;
         double bx, by, bz, x = 0.0, y = 0.0, z = 0.0;
-        const bool use = j < e && res_observation(in, pts4, pt_idx, uv_obs, j, bx, by, bz, x, y, z);
+        const bool use = j < e && res_observation(in, pts4, pt_idx, uv_obs, j, bx, by, bz, x, y, z) && keep(j, x, y, z);
         W.stage[lane] = use ? x : 0.0;
         W.stage[kResPitch + lane] = use ? y : 0.0;
         W.stage[2 * kResPitch + lane] = use ? z : 0.0;
@@ -127,7 +135,7 @@ C2B_DEV int resect_camera(ResLds &W, const int lane, double *__restrict__ cam, c
     for (uint64_t j0 = b; j0 < e; j0 += 64) {
         const uint64_t j = j0 + lane;
         double bx = 0.0, by = 0.0, bz = 0.0, x = 0.0, y = 0.0, z = 0.0;
-        const bool use = j < e && res_observation(in, pts4, pt_idx, uv_obs, j, bx, by, bz, x, y, z);
+        const bool use = j < e && res_observation(in, pts4, pt_idx, uv_obs, j, bx, by, bz, x, y, z) && keep(j, x, y, z);
         const double y0 = x - cx, y1 = y - cy, y2 = z - cz;
         double *s = W.stage + lane;
         s[0] = use ? 1.0 : 0.0;
@@ -352,7 +360,7 @@ C2B_DEV int resect_camera(ResLds &W, const int lane, double *__restrict__ cam, c
     for (uint64_t j0 = b; j0 < e; j0 += 64) {
         const uint64_t j = j0 + lane;
         double bx, by, bz, x = 0.0, y = 0.0, z = 0.0;
-        const bool use = j < e && res_observation(in, pts4, pt_idx, uv_obs, j, bx, by, bz, x, y, z);
+        const bool use = j < e && res_observation(in, pts4, pt_idx, uv_obs, j, bx, by, bz, x, y, z) && keep(j, x, y, z);
         const double qz = ((R[2] * x + R[5] * y) + R[8] * z) + t2;
         behind = behind || __ballot(use && qz >= 0.0) != 0ull;
     }
@@ -380,7 +388,7 @@ __global__ __launch_bounds__(kResBlock) void k_resect_cameras(
     if (c < n_cam) {                                             // wave-uniform
         int st = kResConstant;
         if (!cam_mask || !(cam_mask[c] & 0x3f))                  // C2B_CONST_POSE
-            st = resect_camera(sW[wave], lane, bal9 + 9 * c, pts4, row_ptr[c], row_ptr[c + 1], pt_idx, uv_obs, min_points, min_gap);
+            st = resect_camera(sW[wave], lane, bal9 + 9 * c, pts4, row_ptr[c], row_ptr[c + 1], pt_idx, uv_obs, min_points, min_gap, ResKeepAll());
         if (lane == 0) {
             status[c] = (uint8_t)st;
             atomicAdd(&sCnt[st], 1u);

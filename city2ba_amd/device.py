@@ -314,6 +314,17 @@ def resect_rows(bal9, pts4, rows, pt_idx, uv, status, counts, min_points=6, min_
     return status, counts
 
 
+def resect_consensus_rows(bal9, pts4, rows, pt_idx, uv, status, counts, max_error, min_inliers=6, min_gap=1e-4, max_hypotheses=64,
+                          cam_mask=None, hyp=None, n_inl=None, inlier=None):
+    """consensus resection (c2b_resect_consensus_rows): resect_rows over the observations of a camera that agree with each
+    other; status [n_cam] uint8 (_lib.RES_CONSENSUS_STATUS order), counts [6] int64; hyp, n_inl [n_cam] int32 and inlier
+    [n_obs] uint8 (0 = an observation of a resected camera that is not an inlier) or None"""
+    L.check(L.lib().c2b_resect_consensus_rows(_p(bal9), _p(pts4), _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs, float(max_error),
+                                              int(min_inliers), float(min_gap), int(max_hypotheses), _p(cam_mask), _p(status), _p(hyp), _p(n_inl),
+                                              _p(inlier), _p(counts), _stream()))
+    return status, counts
+
+
 def residual_jacobian_rows(camblk, pts4, rows, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None, out_sum=None, obs_base=0,
                            n_obs=None):
     """residual + Jacobian (+ sum |r|^norm when ws is given: into out_sum, or into ws for error_sum_finish) of the

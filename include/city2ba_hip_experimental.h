@@ -421,6 +421,71 @@ int c2b_resect_rows(double *bal9, const double *pts4, const uint64_t *row_ptr, i
                     int min_points, double min_gap, const c2b_camera_mask *cam_mask, uint8_t *status, int64_t *counts, void *stream);
 int c2b_problem_resect_cameras(c2b_problem *p, int min_points, double min_gap, uint8_t *status, int64_t *counts);
 
+/* ---- consensus resection: camera poses from the observations that agree (three-point hypotheses, inlier mask, refit) ----
+ * c2b_resect_rows is a least-squares fit over every observation of a camera: one pixel matched to another point's
+ * coordinates (a wrong match, a joined landmark) drags the sixty sums, and the camera is rejected or placed wrongly.  This
+ * pass forms candidate poses from triples of observations, keeps the one most of the row agrees with, and refits on those.
+ * Notation as above: camera c's row of the list in ascending order, usable(o) = the ray of c2b_resect_rows exists and the
+ * point is finite, f, k1, k2 = bal9[c][6..8], E2 = max_error * max_error formed once on the host.  One wave per camera.  In
+ * this order:
+ *   C2B_RES_CONSTANT     the camera's mask word holds a pose bit (C2B_CONST_POSE); nothing of its row is read.
+ *   C2B_RES_TOO_FEW      the whole row has fewer than min_inliers usable observations (min_inliers >= 6: it is the refit's
+ *                        min_points too).
+ *   sample               the usable observations among the FIRST 64 ENTRIES of the row, in row order, numbered 0 .. m - 1.
+ *   hypotheses           triple number k = 0, 1, ...: the gap g runs from floor(m / 3) down to 1 and, per gap, i over 0 .. m - 1
+ *                        (when 3 g == m only i < g: each triple once); the triple is {i, (i + g) mod m, (i + 2 g) mod m} in
+ *                        ascending order.  The enumeration stops after max_hypotheses triples, 1 <= max_hypotheses <= 64.
+ *   three-point poses    for a triple with unit rays b1..b3 and points X1..X3 the solutions are the real (l1, l2, l3), every
+ *                        l > 0, with li^2 + lj^2 - 2 li lj (bi . bj) = |Xi - Xj|^2 for the three pairs.  Whatever finds the
+ *                        candidates, each is polished by Newton on the three equations (at most 8 steps, until
+ *                        max |step| <= 1e-14 max l) and counts when the last step was at most 1e-9 max l; a solution is NOT
+ *                        FORMED when |(X2 - X1) x (X3 - X1)|^2 < 1e-12 |X2 - X1|^2 |X3 - X1|^2 or when the equations'
+ *                        Jacobian J at it has |det J| <= 1e-5 (2 max l)^3; two solutions within 1e-9 max l of each other are
+ *                        one.  At most FOUR solutions are kept per triple, in the order they are found (the equations have
+ *                        no more than four with every l > 0, so the cap drops none); whether the determinant is tested
+ *                        before or after the merge is the same, merged solutions sharing it to 1e-9.  The pose: with the orthonormal frames of the triangles (li bi) and (Xi) -- e1 along 1 -> 2,
+ *                        e3 along e1 x (1 -> 3), e2 = e3 x e1 -- R = camera frame . (world frame)^T, t = l1 b1 - R X1.
+ *   C2B_RES_DEGENERATE   no hypothesis has a formed solution.
+ *   score                observation o of the row -- every entry, also past the 64th, also the triple itself -- is an inlier
+ *                        of a pose iff it is usable and c2b_residual_keep_rows with C2B_FILTER_IN_FRONT would keep it at a
+ *                        camera (R, t, f, k1, k2): du * du + dv * dv <= E2 (five unfused operations; NaN compares false)
+ *                        and q.z < 0.  The score is the integer inlier count.
+ *   select               the highest score, the LOWEST k among equal scores, the smallest l1 among that triple's solutions
+ *                        of that score; I* is its inlier set.
+ *   C2B_RES_NO_CONSENSUS |I*| < min_inliers.
+ *   refit                c2b_resect_rows' rule set on I* in ascending row order with min_points = min_inliers and min_gap:
+ *                        its C2B_RES_DEGENERATE or C2B_RES_BEHIND is the camera's status; C2B_RES_OK writes bal9[c][0..5]
+ *                        and keeps the bits of 6..8: bit for bit what c2b_resect_rows returns on the list restricted to I*.
+ * A camera whose status is not C2B_RES_OK keeps all nine entries.  Per camera also hyp = the selected k (not a solution
+ * number) and n_inl = |I*|, set once a hypothesis was selected, whatever the status after it; -1 and 0 under CONSTANT,
+ * TOO_FEW and when no solution was formed.  Per observation inlier[o] = 0 for the observations of a C2B_RES_OK camera
+ * outside I* (the unusable ones among them), 1 everywhere else -- nothing is claimed about a camera that was not resected.
+ * counts[6] is the histogram of the statuses.  No float atomics, no scratch memory, no workspace, no loss from the handle:
+ * the same inputs give the same bits whatever the launch shape.  max_error negative, NaN or infinite, min_inliers < 6,
+ * min_gap negative, NaN or >= 1, max_hypotheses outside [1, 64], an unknown flag bit: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_resect_consensus_rows: Level 0, stateless, asynchronous on `stream`.  The arguments of c2b_resect_rows, and n_obs, the
+ *   length of the list; hyp, n_inl [n_cam] (device int32) and inlier [n_obs] (device, one byte) may each be NULL; counts [6]
+ *   (device int64) is zeroed and inlier set to 1 before the kernel runs.
+ * c2b_problem_resect_consensus: Level 1, synchronous, with the preconditions and the cache story of
+ *   c2b_problem_resect_cameras: bal9 is made the truth, the pass runs over the problem's row structure with its camera
+ *   mask, the state is rebuilt from bal9 and the problem is in bal mode afterwards; a shard is refused; a problem without
+ *   observations returns C2B_RES_TOO_FEW for every camera and launches nothing.  status, hyp, n_inl [n_cam], inlier [n_obs,
+ *   in the list's order at call time] and counts [6] are host arrays and may be NULL.  flags = C2B_RES_DROP_OUTLIERS: the
+ *   list is then compacted by the inlier mask exactly as c2b_problem_triangulate_consensus compacts by its own (stable
+ *   inside every camera's row, nothing renumbered, what was derived from the list is rebuilt by its next user);
+ *   *n_removed (may be NULL) = how many went, and when it is 0 no cache is dropped.  Should the compaction fail (an
+ *   allocation), the cameras have already moved and the list has not: the status, the mask and the counts returned
+ *   describe the pass, and the call returns the error.  The constant masks, the loss, the preconditioner and a checkpoint
+ *   all stay.  Every refusal leaves the problem unchanged. */
+#define C2B_RES_NO_CONSENSUS 5
+#define C2B_RES_DROP_OUTLIERS 1
+int c2b_resect_consensus_rows(double *bal9, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                              const double *uv_obs, int64_t n_obs, double max_error, int min_inliers, double min_gap, int max_hypotheses,
+                              const c2b_camera_mask *cam_mask, uint8_t *status, int32_t *hyp, int32_t *n_inl, uint8_t *inlier,
+                              int64_t *counts, void *stream);
+int c2b_problem_resect_consensus(c2b_problem *p, double max_error, int min_inliers, double min_gap, int max_hypotheses, int flags,
+                                 uint8_t *status, int32_t *hyp, int32_t *n_inl, uint8_t *inlier, int64_t *counts, int64_t *n_removed);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
