@@ -17,7 +17,7 @@ ERR_OOM = -4
 ERR_NO_DEVICE = -5
 ERR_RCCL = -6
 COMM_ID_BYTES = 128
-ABI_VERSION = 9            # include/city2ba_hip.h: C2B_ABI_VERSION
+ABI_VERSION = 10           # include/city2ba_hip.h: C2B_ABI_VERSION
 CAMBLK_DOUBLES = 32
 STATS_DOUBLES = 20
 
@@ -190,6 +190,13 @@ SIGNATURES = {
     "c2b_problem_preconditioner_fallbacks": (_int, [_vp, C.POINTER(_i64)]),
     "c2b_problem_set_constant": (_int, [_vp, _vp, _vp]),
     "c2b_problem_get_constant": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "c2b_problem_set_priors": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_problem_get_priors": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "c2b_problem_prior_cost": (_int, [_vp, C.POINTER(_d)]),
+    "c2b_problem_prior_residual_jacobian": (_int, [_vp, _vp, _vp, _vp]),
+    "c2b_prior_cameras_rows": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_prior_points_rows": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_prior_model_rows": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_schur_jacobi_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _d, _vp, _vp]),
     "c2b_schur_jacobi_rows_loss": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _d, _vp, _int, _d, _vp]),
     "c2b_visibility_pairs": (_int, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp]),

@@ -358,6 +358,60 @@ class BAProblem:
         L.check(L.lib().c2b_problem_get_constant(self._h, _ptr(cm), _ptr(pm), None, None))
         return ((cm[:, None] >> np.arange(9, dtype=np.uint16)) & 1).astype(bool), pm.astype(bool)
 
+    def set_priors(self, camera_centers=None, camera_center_weights=None, intrinsics=None, intrinsics_weights=None, points=None,
+                   point_weights=None):
+        """Soft constraints beside the observations in normal_equations / solve_step / the LM loops (c2b_problem_set_priors):
+        r_C = w_C o (C - C0) on the cameras' world-frame centres, r_I = w_I o ((f, k1, k2) - I0) on their intrinsics and
+        r_X = w_X o (X - X0) on the points; the cost gains sum |r_prior|^2.  Each kind is a target [n, 3] and weights
+        [n, 3] >= 0 (1 / sigma in units of the observations' standard deviation; 0 switches a row off; a scalar or a
+        length-3 weight broadcasts over the rows).  A target left None under a given weight is the problem's current
+        value; a kind whose weight is None has no prior, and all None clears the priors.  No robust loss reweights a prior.
+        The priors belong to the handle exactly as the constant masks do: kept by apply_step, noise and an upload of the
+        same counts, dropped by whatever changes a count or renumbers the entities."""
+        nc, npt = self.num_cameras(), self.num_points()
+
+        def pair(target, w, n, current, name):
+            if w is None:
+                if target is not None:
+                    raise ValueError("set_priors: %s given without weights" % name)
+                return None, None
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), (n, 3)))
+            t = current() if target is None else _f64(target, (-1, 3))
+            if t.shape != (n, 3):
+                raise ValueError("set_priors: %s must have shape (%d, 3)" % (name, n))
+            return np.ascontiguousarray(t), w
+        c0, cw = pair(camera_centers, camera_center_weights, nc, self._camera_centers, "camera_centers")
+        i0, iw = pair(intrinsics, intrinsics_weights, nc, lambda: self.cameras_bal()[:, 6:9].copy(), "intrinsics")
+        x0, xw = pair(points, point_weights, npt, self.points, "points")
+        L.check(L.lib().c2b_problem_set_priors(self._h, _ptr(c0), _ptr(cw), _ptr(i0), _ptr(iw), _ptr(x0), _ptr(xw)))
+
+    @property
+    def priors(self):
+        """the priors in force (c2b_problem_get_priors): dict(camera_centers, camera_center_weights, intrinsics,
+        intrinsics_weights, points, point_weights -- [n, 3] each, zeros for a kind with none --, active = (cameras with a
+        centre row, cameras with an intrinsics row, points with a row) of positive weight)"""
+        nc, npt = self.num_cameras(), self.num_points()
+        a = [np.zeros((n, 3)) for n in (nc, nc, nc, nc, npt, npt)]
+        k = [C.c_int64(), C.c_int64(), C.c_int64()]
+        L.check(L.lib().c2b_problem_get_priors(self._h, *[_ptr(x) for x in a], *[C.byref(x) for x in k]))
+        names = ("camera_centers", "camera_center_weights", "intrinsics", "intrinsics_weights", "points", "point_weights")
+        out = dict(zip(names, a))
+        out["active"] = tuple(x.value for x in k)
+        return out
+
+    def prior_cost(self):
+        """sum |r_prior|^2 at the current state, on the device (c2b_problem_prior_cost); 0.0 without priors"""
+        s = C.c_double()
+        L.check(L.lib().c2b_problem_prior_cost(self._h, C.byref(s)))
+        return s.value
+
+    def prior_residual_jacobian(self):
+        """(r_cam [n_cam, 6] = (r_C, r_I), A_cam [n_cam, 3, 6] = diag(w_C) [dC/dw | -R^T], r_pt [n_pts, 3]) of the priors in
+        force (c2b_problem_prior_residual_jacobian); zeros where there is none.  The columns are those of residual_jacobian."""
+        r, A, rp = np.empty((self.num_cameras(), 6)), np.empty((self.num_cameras(), 3, 6)), np.empty((self.num_points(), 3))
+        L.check(L.lib().c2b_problem_prior_residual_jacobian(self._h, _ptr(r), _ptr(A), _ptr(rp)))
+        return r, A, rp
+
     def solve_step(self, lam, max_iters=100, rel_tol=1e-6, out=None):
         """One damped Gauss-Newton (Levenberg-Marquardt) step on the device (c2b_problem_solve_step): the solution of
         (J^T J + lam D) delta = -g, D = diag(min(max(diag(J^T J), 1e-6), 1e32)), by PCG on the Schur complement of the

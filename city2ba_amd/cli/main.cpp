@@ -20,7 +20,9 @@
 //   city2ba solve IN OUT [--iterations N --lambda X --pcg-iterations N --pcg-tol X --function-tol X --gradient-tol X
 //                         --parameter-tol X --loss squared|huber|cauchy|soft-l1 --loss-scale X
 //                         --preconditioner block-jacobi|schur-jacobi --fix-intrinsics --fix-first-camera
-//                         --filter-max-error X --filter-rounds N --filter-in-front]
+//                         --filter-max-error X --filter-rounds N --filter-in-front
+//                         --prior-from FILE [--prior-center-sigma S|SX,SY,SZ] [--prior-intrinsics-sigma SF,SK1,SK2]
+//                         [--prior-point-sigma S [--prior-point-every N]]]
 //                        (extension: Levenberg-Marquardt on the device, c2b_problem_levenberg_marquardt; with
 //                         --filter-max-error: N times solve + c2b_problem_filter_observations, then a solve without a loss)
 //   city2ba triangulate IN OUT [--min-angle DEG] [--max-error X [--min-inliers N] [--max-hypotheses H] [--drop-outliers]]
@@ -815,11 +817,55 @@ static void close_problem(PhaseTimer &timer, c2b_problem *p, const std::string &
 // problems).  The file is decoded into the resident problem, solved there and its image assembled there.  Every argument
 // is parsed before the device is touched.  --filter-max-error X: --filter-rounds times (solve, then drop the observations
 // whose residual exceeds X -- with --filter-in-front also those behind their camera), then one more solve with the loss
-// cleared; cameras and points keep their numbers, nothing is culled.
+// cleared; cameras and points keep their numbers, nothing is culled.  --prior-from FILE: priors (c2b_problem_set_priors)
+// whose targets are FILE's camera centres, intrinsics and points, weight 1 / sigma per component.
+
+// sigmas of a --prior-*-sigma flag: `want` numbers (or also one, when `or_one`), each > 0; returned as weights 1 / sigma
+static std::vector<double> prior_weights_of(const Args &a, const std::string &key, const char *shape, int want, bool or_one) {
+    std::vector<double> w;
+    const std::string &v = a.opt.at(key);
+    size_t at = 0;
+    while (at <= v.size()) {
+        const size_t comma = std::min(v.find(',', at), v.size());
+        const std::string part = v.substr(at, comma - at);
+        char *end = nullptr;
+        const double sigma = std::strtod(part.c_str(), &end);
+        if (part.empty() || end == part.c_str() || *end || !(sigma > 0.0) || !std::isfinite(sigma))
+            die("Invalid value for '--" + key + " <" + shape + ">': expected " + shape + " with every sigma a number > 0");
+        w.push_back(1.0 / sigma);
+        at = comma + 1;
+    }
+    if (!((int)w.size() == want || (or_one && w.size() == 1)))
+        die("Invalid value for '--" + key + " <" + shape + ">': expected " + shape + " with every sigma a number > 0");
+    if ((int)w.size() < want) w.assign((size_t)want, w[0]);
+    return w;
+}
+
+// n_cam and n_pts of a .bal / .bbal from its first line / header alone (no device, no parse of the body)
+static void peek_counts(const std::string &path, int64_t &n_cam, int64_t &n_pts) {
+    std::FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) die("Could not open " + path);
+    bool ok = false;
+    if (path.size() >= 5 && path.compare(path.size() - 5, 5, ".bbal") == 0) {
+        unsigned char b[16];
+        ok = std::fread(b, 1, 16, f) == 16;
+        uint64_t v[2] = {0, 0};
+        for (int k = 0; k < 16; ++k) v[k / 8] = (v[k / 8] << 8) | b[k];
+        n_cam = (int64_t)v[0]; n_pts = (int64_t)v[1];
+    } else {
+        long long c = 0, q = 0;
+        ok = std::fscanf(f, "%lld %lld", &c, &q) == 2;
+        n_cam = c; n_pts = q;
+    }
+    std::fclose(f);
+    if (!ok) die("Could not read the camera and point counts of " + path);
+}
+
 int run_solve(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera", "filter-in-front"},
                          {"iterations", "lambda", "pcg-iterations", "pcg-tol", "function-tol", "gradient-tol", "parameter-tol", "loss",
-                          "loss-scale", "preconditioner", "device", "filter-max-error", "filter-rounds"});
+                          "loss-scale", "preconditioner", "device", "filter-max-error", "filter-rounds", "prior-from",
+                          "prior-center-sigma", "prior-intrinsics-sigma", "prior-point-sigma", "prior-point-every"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
     c2b_lm_options opt;
     opt.max_iterations = (int32_t)std::min<int64_t>(a.i("iterations", 10), 1 << 20);
@@ -853,11 +899,68 @@ int run_solve(int argc, char **argv) {
         else if (v == "schur-jacobi") precond = C2B_PRECOND_SCHUR_JACOBI;
         else die("Invalid value for '--preconditioner <preconditioner>': expected block-jacobi or schur-jacobi");
     }
+    // priors: every flag and both files' counts are checked here, before a device exists
+    const bool prior = a.has("prior-from");
+    std::vector<double> w_center, w_intr, w_point;
+    int64_t point_every = 1;
+    for (const char *k : {"prior-center-sigma", "prior-intrinsics-sigma", "prior-point-sigma", "prior-point-every"})
+        if (a.has(k) && !prior) die(std::string("--") + k + " needs --prior-from <FILE>");
+    if (prior) {
+        if (a.has("prior-center-sigma")) w_center = prior_weights_of(a, "prior-center-sigma", "S|SX,SY,SZ", 3, true);
+        if (a.has("prior-intrinsics-sigma")) w_intr = prior_weights_of(a, "prior-intrinsics-sigma", "SF,SK1,SK2", 3, false);
+        if (a.has("prior-point-sigma")) w_point = prior_weights_of(a, "prior-point-sigma", "S", 3, true);
+        if (w_point.size() == 3 && a.opt.at("prior-point-sigma").find(',') != std::string::npos)
+            die("Invalid value for '--prior-point-sigma <S>': expected S with every sigma a number > 0");
+        if (w_center.empty() && w_intr.empty() && w_point.empty())
+            die("--prior-from <FILE> needs at least one of --prior-center-sigma, --prior-intrinsics-sigma, --prior-point-sigma");
+        if (a.has("prior-point-every")) {
+            if (w_point.empty()) die("--prior-point-every needs --prior-point-sigma <S>");
+            point_every = a.i("prior-point-every", 1);
+            if (point_every < 1) die("Invalid value for '--prior-point-every <N>': expected N >= 1");
+        }
+        int64_t in_cam = 0, in_pts = 0, from_cam = 0, from_pts = 0;
+        peek_counts(a.positional[0], in_cam, in_pts);
+        peek_counts(a.opt.at("prior-from"), from_cam, from_pts);
+        if (from_cam != in_cam)
+            die("--prior-from: " + a.opt.at("prior-from") + " has " + std::to_string(from_cam) + " cameras, " + a.positional[0] + " has " +
+                std::to_string(in_cam));
+        if (!w_point.empty() && from_pts != in_pts)
+            die("--prior-from: " + a.opt.at("prior-from") + " has " + std::to_string(from_pts) + " points, " + a.positional[0] + " has " +
+                std::to_string(in_pts) + " (a point prior needs the same points)");
+    }
     PhaseTimer timer;
     int64_t nc = 0, np = 0, no = 0;
     c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
     ck(c2b_problem_set_loss(p, loss, loss_scale));
     ck(c2b_problem_set_preconditioner(p, precond));
+    if (prior) {                                             // the targets: FILE's centres, intrinsics and points, as a problem holds them
+        c2b_problem *q = nullptr;
+        int64_t qc = 0, qp = 0, qo = 0;
+        ck(create_problem(device, &q));
+        ck(c2b_problem_read(q, a.opt.at("prior-from").c_str(), -1));
+        ck(c2b_problem_sizes(q, &qc, &qp, &qo));
+        if (qc != nc || (!w_point.empty() && qp != np)) die("--prior-from: the counts of " + a.opt.at("prior-from") + " are not those of " + a.positional[0]);
+        std::vector<double> c0((size_t)nc * 3 + 1), b9((size_t)nc * 9 + 1), x0((size_t)qp * 3 + 1), cams15((size_t)nc * 15 + 1);
+        ck(c2b_problem_centers(q, c0.data()));
+        ck(c2b_problem_download_bal(q, b9.data()));
+        ck(c2b_problem_download(q, cams15.data(), x0.data(), nullptr));
+        c2b_problem_destroy(q);
+        std::vector<double> i0((size_t)nc * 3 + 1), cw, iw, xw;
+        for (int64_t c = 0; c < nc; ++c)
+            for (int k = 0; k < 3; ++k) i0[(size_t)(3 * c + k)] = b9[(size_t)(9 * c + 6 + k)];
+        auto spread = [](const std::vector<double> &w3, int64_t n, int64_t every) {
+            std::vector<double> w((size_t)n * 3 + 1, 0.0);
+            for (int64_t i = 0; i < n; i += every)
+                for (int k = 0; k < 3; ++k) w[(size_t)(3 * i + k)] = w3[(size_t)k];
+            return w;
+        };
+        if (!w_center.empty()) cw = spread(w_center, nc, 1);
+        if (!w_intr.empty()) iw = spread(w_intr, nc, 1);
+        if (!w_point.empty()) xw = spread(w_point, np, point_every);
+        ck(c2b_problem_set_priors(p, cw.empty() ? nullptr : c0.data(), cw.empty() ? nullptr : cw.data(), iw.empty() ? nullptr : i0.data(),
+                                  iw.empty() ? nullptr : iw.data(), xw.empty() ? nullptr : x0.data(), xw.empty() ? nullptr : xw.data()));
+        timer.mark("priors (targets read on the device, c2b_problem_set_priors)");
+    }
     if (a.has("fix-intrinsics") || a.has("fix-first-camera")) {
         std::vector<c2b_camera_mask> cm((size_t)nc + 1, (c2b_camera_mask)(a.has("fix-intrinsics") ? C2B_CONST_INTRINSICS : 0));
         if (a.has("fix-first-camera") && nc) cm[0] |= C2B_CONST_POSE;
@@ -1041,7 +1144,12 @@ const char *subcommand_help(const std::string &sub) {
                "    --filter-max-error <X>    outlier rejection: solve, drop the observations whose reprojection residual exceeds X,\n"
                "                              then solve again without a loss [off]\n"
                "    --filter-rounds <N> [1]   solve + filter rounds before the last solve\n"
-               "    --filter-in-front         also drop observations whose point is not in front of its camera\n";
+               "    --filter-in-front         also drop observations whose point is not in front of its camera\n"
+               "    --prior-from <FILE>       priors whose targets are FILE's camera centres, intrinsics and points (a .bal / .bbal with\n"
+               "                              the same cameras; a point prior needs the same points); weight = 1 / sigma\n"
+               "    --prior-center-sigma <S|SX,SY,SZ>            on every camera's centre\n"
+               "    --prior-intrinsics-sigma <SF,SK1,SK2>        on every camera's f, k1, k2\n"
+               "    --prior-point-sigma <S>  [--prior-point-every <N> [1]]   on every N-th point\n";
     if (sub == "triangulate")
         return "city2ba triangulate <FILE> <OUT>\n"
                "    --min-angle <DEG> [1]     parallax test: a point whose rays are less than DEG degrees apart keeps its position\n"

@@ -36,6 +36,7 @@
 #include "kernels.hpp"
 #include "normal_kernels.hpp"
 #include "schur_kernels.hpp"
+#include "prior_kernels.hpp"
 #include "triangulate_kernels.hpp"
 #include "triangulate_robust_kernels.hpp"
 #include "resect_kernels.hpp"

@@ -214,6 +214,7 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
     p->cam15 = std::move(n_cam15); p->bal9 = std::move(n_bal9); p->camblk = std::move(n_camblk); p->cen4 = std::move(n_cen4);
     p->pts4 = std::move(n_pts4); p->n_cam = nc; p->n_pts = np;
     drop_constant(p);                                         // the survivors are renumbered
+    drop_priors(p);
     drop_lm_state(p);
     p->blk_valid = false;                                     // camblk is rebuilt on demand from the gathered cameras
     p->bal9_fresh = false;                                    // (bal9 was gathered only when it was the truth)
@@ -835,6 +836,7 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
     free_dense(p);
     drop_rows(p);
     drop_constant(p);
+    drop_priors(p);
     drop_lm_state(p);
     p->pts4 = std::move(out);
     p->n_pts = accepted;

@@ -1461,6 +1461,102 @@ int c2b_schur_points_rows_loss(const double *camblk, const double *pts4, int64_t
     C2B_API_END("schur_points_rows_loss")
 }
 
+// ---- priors on camera centres, intrinsics and points (prior_kernels.hpp) -----------------------------------
+// how many partials the three passes write: one per workgroup of kSchurBlock lanes
+static unsigned prior_cameras_grid(int64_t n_cam) { return blocks_for(9 * n_cam, kSchurBlock); }
+static unsigned prior_points_grid(int64_t n_pts) { return blocks_for(n_pts, kSchurBlock); }
+static unsigned prior_model_grid(int64_t n_cam, int64_t n_pts) { return blocks_for(std::max(n_cam, n_pts), kSchurBlock); }
+
+static int prior_cameras_rows_impl(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
+                                   const double *intr_w, double *U, double *gc, double *r, double *A, double *part, double *cost, void *stream) {
+    if (n_cam < 0 || n_cam > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_cameras_rows: n_cam out of range");
+    if (!center != !center_w || !intr != !intr_w) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_cameras_rows: a target and its weights go in pairs");
+    if ((n_cam && !camblk) || (cost && !part)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_cameras_rows: NULL argument");
+    for (const void *q : {(const void *)center, (const void *)center_w, (const void *)intr, (const void *)intr_w, (const void *)U, (const void *)gc,
+                          (const void *)r, (const void *)A, (const void *)part, (const void *)cost})
+        if (!aligned8(q)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_cameras_rows: misaligned pointer");
+    if (!aligned16(camblk)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_cameras_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    if (!n_cam) {
+        if (cost) HIP_TRY(hipMemsetAsync(cost, 0, sizeof(double), st));
+        return C2B_OK;
+    }
+    hipLaunchKernelGGL(k_prior_cameras, dim3(prior_cameras_grid(n_cam)), dim3(kSchurBlock), 0, st, 9 * n_cam, camblk, center, center_w, intr, intr_w,
+                       U, gc, r, A, part);
+    if (cost) fold_sum(st, part, (int)prior_cameras_grid(n_cam), cost);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
+static int prior_points_rows_impl(const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, double *V, double *gp, double *r,
+                                  double *part, double *cost, void *stream) {
+    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_points_rows: n_pts out of range");
+    if (!pt != !pt_w) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_points_rows: a target and its weights go in pairs");
+    if ((n_pts && !pts4) || (cost && !part)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_points_rows: NULL argument");
+    for (const void *q : {(const void *)pt, (const void *)pt_w, (const void *)V, (const void *)gp, (const void *)r, (const void *)part, (const void *)cost})
+        if (!aligned8(q)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_points_rows: misaligned pointer");
+    if (!aligned16(pts4)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_points_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    if (!n_pts) {
+        if (cost) HIP_TRY(hipMemsetAsync(cost, 0, sizeof(double), st));
+        return C2B_OK;
+    }
+    hipLaunchKernelGGL(k_prior_points, dim3(prior_points_grid(n_pts)), dim3(kSchurBlock), 0, st, n_pts, reinterpret_cast<const double4 *>(pts4), pt,
+                       pt_w, V, gp, r, part);
+    if (cost) fold_sum(st, part, (int)prior_points_grid(n_pts), cost);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
+static int prior_model_rows_impl(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
+                                 const double *intr_w, const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, const double *dc,
+                                 const double *dp, double *part_sq, double *part_md, double *sums, void *stream) {
+    if (n_cam < 0 || n_cam > (int64_t)0xffffffff || n_pts < 0 || n_pts > (int64_t)0xffffffff)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "prior_model_rows: count out of range");
+    if (!center != !center_w || !intr != !intr_w || !pt != !pt_w)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "prior_model_rows: a target and its weights go in pairs");
+    if (!part_sq || !part_md || !sums || (n_cam && (!camblk || !dc)) || (n_pts && (!pts4 || !dp)))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "prior_model_rows: NULL argument");
+    for (const void *q : {(const void *)center, (const void *)center_w, (const void *)intr, (const void *)intr_w, (const void *)pt, (const void *)pt_w,
+                          (const void *)dc, (const void *)dp, (const void *)part_sq, (const void *)part_md, (const void *)sums})
+        if (!aligned8(q)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_model_rows: misaligned pointer");
+    if (!aligned16(camblk) || !aligned16(pts4)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_model_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    if (!n_cam && !n_pts) {
+        HIP_TRY(hipMemsetAsync(sums, 0, 2 * sizeof(double), st));
+        return C2B_OK;
+    }
+    const unsigned grid = prior_model_grid(n_cam, n_pts);
+    hipLaunchKernelGGL(k_prior_model, dim3(grid), dim3(kSchurBlock), 0, st, n_cam, camblk, center, center_w, intr, intr_w, n_pts,
+                       reinterpret_cast<const double4 *>(pts4), pt, pt_w, dc, dp, part_sq, part_md);
+    fold_sum(st, part_sq, (int)grid, sums);
+    fold_sum(st, part_md, (int)grid, sums + 1);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
+int c2b_prior_cameras_rows(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
+                           const double *intr_w, double *U, double *gc, double *r, double *A, double *part, double *cost, void *stream) {
+    C2B_API_BEGIN
+    return prior_cameras_rows_impl(camblk, n_cam, center, center_w, intr, intr_w, U, gc, r, A, part, cost, stream);
+    C2B_API_END("prior_cameras_rows")
+}
+
+int c2b_prior_points_rows(const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, double *V, double *gp, double *r, double *part,
+                          double *cost, void *stream) {
+    C2B_API_BEGIN
+    return prior_points_rows_impl(pts4, n_pts, pt, pt_w, V, gp, r, part, cost, stream);
+    C2B_API_END("prior_points_rows")
+}
+
+int c2b_prior_model_rows(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
+                         const double *intr_w, const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, const double *dc,
+                         const double *dp, double *part_sq, double *part_md, double *sums, void *stream) {
+    C2B_API_BEGIN
+    return prior_model_rows_impl(camblk, n_cam, center, center_w, intr, intr_w, pts4, n_pts, pt, pt_w, dc, dp, part_sq, part_md, sums, stream);
+    C2B_API_END("prior_model_rows")
+}
+
 // ---- linear midpoint triangulation (triangulate_kernels.hpp) ------------------------------------------------
 // the parallax threshold 1 - cos(min_angle), evaluated once on the host as 2 sin^2(min_angle / 2): no cancellation at a small angle
 static bool good_min_angle(double a) { return a >= 0.0 && a <= 1.57079632679489661923; }

@@ -35,7 +35,14 @@ struct c2b_problem {
     std::vector<uint16_t> h_cmask;
     std::vector<uint8_t> h_pmask;
     int64_t const_n_cam = -1, const_n_pts = -1, const_params = 0, const_pts = 0;
-    bool bal_valid = false;     // bal9 still describes the cameras (no mutation since upload_bal)
+    // c2b_problem_set_priors: targets and weights [n][3] of the camera centres (pc0, pcw), the intrinsics
+    // (pi0, piw) and the points (px0, pxw), and the partials and scalars their sums go through (prior_part); the handle's,
+    // kept and dropped as the masks are (prior_n_cam, prior_n_pts: the counts they were set for).  A kind whose weights
+    // are all 0 has no array, and with none in force nothing is launched or allocated for priors.
+    DevBuf<double> pc0, pcw, pi0, piw, px0, pxw, prior_part;
+    std::vector<double> h_pc0, h_pcw, h_pi0, h_piw, h_px0, h_pxw;
+    int64_t prior_n_cam = -1, prior_n_pts = -1, prior_rows[3] = {0, 0, 0};
+    bool bal_valid = false;    // bal9 still describes the cameras (no mutation since upload_bal)
     bool blk_valid = false;     // camblk matches cam15 (and bal_valid mode)
     bool bal9_fresh = false;    // !bal_valid, but bal9 holds to_vec of the current cameras (the last write / download_bal computed it)
     // the row structure of the observation list for the *_rows launchers, rebuilt on demand after the list changed
@@ -83,6 +90,7 @@ struct c2b_problem {
 //   triangulate_consensus (6)  -            -          - / X - / X      - / X  -             -           -
 //   resect_cameras             X            truth      -     -          -      -             -           -
 //   resect_consensus (6)       X            truth      - / X - / X      - / X  -             -           -
+// The priors (c2b_problem_set_priors) share the masks' column: kept and dropped with them, by counts of their own.
 // (1) kept when both counts are those the masks were set for.  (2) gathered with the cameras while it is the truth; a merely
 // fresh bal9 (bal9_fresh: to_vec of the current cameras, filled by download_bal / write / apply_step) is dropped.  (3) on
 // entry, so also by a cull that fails later.  (4) one that removes nothing drops nothing.  (5) checkpoint is an apply_step
@@ -112,6 +120,15 @@ static void drop_constant(c2b_problem *p) {
     p->const_n_cam = p->const_n_pts = -1;
     p->const_params = p->const_pts = 0;
 }
+
+// the priors: no soft constraint any more (dropped wherever the masks are dropped for a count change or a renumbering)
+static void drop_priors(c2b_problem *p) {
+    p->pc0.reset(); p->pcw.reset(); p->pi0.reset(); p->piw.reset(); p->px0.reset(); p->pxw.reset(); p->prior_part.reset();
+    for (auto *v : {&p->h_pc0, &p->h_pcw, &p->h_pi0, &p->h_piw, &p->h_px0, &p->h_pxw}) v->clear();
+    p->prior_n_cam = p->prior_n_pts = -1;
+    p->prior_rows[0] = p->prior_rows[1] = p->prior_rows[2] = 0;
+}
+static bool has_priors(const c2b_problem *p) { return p->pcw || p->piw || p->pxw; }
 
 // the checkpoint and the LM scratch: no checkpoint describes the entities any more
 static void drop_lm_state(c2b_problem *p) {
@@ -172,6 +189,7 @@ void c2b_problem_destroy(c2b_problem *p) {
     (void)hipSetDevice(p->device);
     free_buffers(p);
     drop_constant(p);
+    drop_priors(p);
     for (int k = 0; k < c2b_problem::kJacSlots; ++k) {
         if (p->ev_done[k]) (void)hipEventDestroy(p->ev_done[k]);
         if (p->ev_free[k]) (void)hipEventDestroy(p->ev_free[k]);
@@ -202,6 +220,7 @@ static int alloc_problem(c2b_problem *p, int64_t n_cam, int64_t n_pts, int64_t n
     HIP_TRY(hipSetDevice(p->device));
     free_buffers(p);
     if (!same_entities || n_cam != p->const_n_cam || n_pts != p->const_n_pts) drop_constant(p);
+    if (!same_entities || n_cam != p->prior_n_cam || n_pts != p->prior_n_pts) drop_priors(p);
     HIP_TRY(p->cam15.alloc(15 * (size_t)n_cam));
     HIP_TRY(p->bal9.alloc(9 * (size_t)n_cam));
     HIP_TRY(p->camblk.alloc((size_t)cam_table_doubles(n_cam)));      // whole groups of 8 cameras

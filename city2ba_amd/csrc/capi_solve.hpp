@@ -90,6 +90,181 @@ static int constant_points(c2b_problem *p, double *V, double diag, double *t) {
     return C2B_OK;
 }
 
+// ---- priors on camera centres, intrinsics and points ------------------------------------------------------
+// one (target, weights) pair of n rows of 3, checked and copied to the host vectors; `rows` = rows with a weight > 0
+static int prior_pair(const char *what, int64_t n, const double *target, const double *w, std::vector<double> &ht, std::vector<double> &hw,
+                      int64_t &rows) {
+    rows = 0;
+    if (!target != !w) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_priors: %s targets and weights go in pairs (both or neither)", what);
+    if (!w) return C2B_OK;
+    for (int64_t i = 0; i < n; ++i) {
+        bool on = false;
+        for (int k = 0; k < 3; ++k) {
+            const double wk = w[3 * i + k];
+            if (!std::isfinite(wk) || wk < 0.0)
+                return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_priors: %s weight [%lld][%d] is negative or not finite", what, (long long)i, k);
+            if (wk > 0.0 && !std::isfinite(target[3 * i + k]))
+                return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_priors: %s target [%lld][%d] is not finite under a positive weight", what,
+                            (long long)i, k);
+            on = on || wk > 0.0;
+        }
+        rows += on;
+    }
+    if (rows) {                                              // all-zero weights are no prior, as an all-zero mask is no mask
+        ht.assign(target, target + 3 * n);
+        hw.assign(w, w + 3 * n);
+    }
+    return C2B_OK;
+}
+
+// prior_part, carved: two partial arrays [n_pp], n_pp = the camera pass's workgroups + the point pass's (the model pass has
+// fewer), then four scalars: the cameras' cost, the points' cost, the model pass's sum of squares and decrease
+struct PriorBufs {
+    double *pa, *pb, *sc;
+};
+enum { kPrCostCam = 0, kPrCostPts = 1, kPrSumSq = 2, kPrModel = 3, kPrSlots = 4 };
+static int64_t prior_parts(int64_t n_cam, int64_t n_pts) { return (int64_t)prior_cameras_grid(n_cam) + prior_points_grid(n_pts); }
+static PriorBufs prior_bufs(c2b_problem *p) {
+    const int64_t n_pp = prior_parts(p->n_cam, p->n_pts);
+    return PriorBufs{p->prior_part, p->prior_part + n_pp, p->prior_part + 2 * n_pp};
+}
+
+int c2b_problem_set_priors(c2b_problem *p, const double *cam_center, const double *cam_center_w, const double *cam_intr, const double *cam_intr_w,
+                           const double *pt, const double *pt_w) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_set_priors");
+    if (p->shard_n_cam_global >= 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_priors: a shard takes no priors (it cannot be solved alone)");
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    std::vector<double> h[6];
+    int64_t rows[3];
+    int rc = prior_pair("camera centre", nc, cam_center, cam_center_w, h[0], h[1], rows[0]);
+    if (!rc) rc = prior_pair("intrinsics", nc, cam_intr, cam_intr_w, h[2], h[3], rows[1]);
+    if (!rc) rc = prior_pair("point", np, pt, pt_w, h[4], h[5], rows[2]);
+    if (rc) return rc;
+    // the new device arrays first: a failure leaves the priors in force as they were
+    DevBuf<double> d[6], part;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 6 && e == hipSuccess; ++k) {
+        if (h[k].empty()) continue;
+        e = d[k].alloc(h[k].size());
+        if (e == hipSuccess) e = hipMemcpyAsync(d[k], h[k].data(), sizeof(double) * h[k].size(), hipMemcpyHostToDevice, p->stream);
+    }
+    const bool any = rows[0] || rows[1] || rows[2];
+    if (e == hipSuccess && any) e = part.alloc((size_t)(2 * prior_parts(nc, np) + kPrSlots));
+    const hipError_t es = hipStreamSynchronize(p->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(hip_code(e), "problem_set_priors: %s", hipGetErrorString(e));
+    drop_priors(p);
+    if (!any) return C2B_OK;
+    p->pc0 = std::move(d[0]); p->pcw = std::move(d[1]); p->pi0 = std::move(d[2]); p->piw = std::move(d[3]);
+    p->px0 = std::move(d[4]); p->pxw = std::move(d[5]); p->prior_part = std::move(part);
+    p->h_pc0.swap(h[0]); p->h_pcw.swap(h[1]); p->h_pi0.swap(h[2]); p->h_piw.swap(h[3]); p->h_px0.swap(h[4]); p->h_pxw.swap(h[5]);
+    p->prior_n_cam = nc; p->prior_n_pts = np;
+    for (int k = 0; k < 3; ++k) p->prior_rows[k] = rows[k];
+    return C2B_OK;
+    C2B_API_END("problem_set_priors")
+}
+
+int c2b_problem_get_priors(const c2b_problem *p, double *cam_center, double *cam_center_w, double *cam_intr, double *cam_intr_w, double *pt,
+                           double *pt_w, int64_t *n_center_rows, int64_t *n_intr_rows, int64_t *n_pt_rows) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_priors: problem is NULL");
+    if (!p->ws) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_priors: nothing uploaded");
+    auto give = [](const std::vector<double> &h, int64_t n, double *out) {
+        if (!out) return;
+        if (!h.empty()) std::copy(h.begin(), h.end(), out);
+        else std::fill(out, out + 3 * n, 0.0);
+    };
+    give(p->h_pc0, p->n_cam, cam_center); give(p->h_pcw, p->n_cam, cam_center_w);
+    give(p->h_pi0, p->n_cam, cam_intr); give(p->h_piw, p->n_cam, cam_intr_w);
+    give(p->h_px0, p->n_pts, pt); give(p->h_pxw, p->n_pts, pt_w);
+    if (n_center_rows) *n_center_rows = p->prior_rows[0];
+    if (n_intr_rows) *n_intr_rows = p->prior_rows[1];
+    if (n_pt_rows) *n_pt_rows = p->prior_rows[2];
+    return C2B_OK;
+    C2B_API_END("problem_get_priors")
+}
+
+// the priors' terms into blocks the passes filled (asynchronous; nothing is launched for a kind without priors): A^T A into
+// A9 [n_cam][9][9] = U or M and A^T r into gc (either may be NULL); with want_cost their cost into the kPrCostCam scalar ...
+static int prior_cameras(c2b_problem *p, double *A9, double *gc, bool want_cost) {
+    if ((!p->pcw && !p->piw) || !p->n_cam) return C2B_OK;
+    const PriorBufs P = prior_bufs(p);
+    return prior_cameras_rows_impl(p->camblk, p->n_cam, p->pc0, p->pcw, p->pi0, p->piw, A9, gc, nullptr, nullptr, want_cost ? P.pa : nullptr,
+                                   want_cost ? P.sc + kPrCostCam : nullptr, p->stream);
+}
+
+// ... diag(w^2) into V and w o r into gp (both may be NULL), the cost into the kPrCostPts scalar
+static int prior_points(c2b_problem *p, double *V, double *gp, bool want_cost) {
+    if (!p->pxw || !p->n_pts) return C2B_OK;
+    const PriorBufs P = prior_bufs(p);
+    return prior_points_rows_impl(p->pts4, p->n_pts, p->px0, p->pxw, V, gp, nullptr, want_cost ? P.pb : nullptr,
+                                  want_cost ? P.sc + kPrCostPts : nullptr, p->stream);
+}
+
+// the two costs queued to host[2] (asynchronous: valid after the stream is synchronised); prior_cost_of adds them
+static int prior_cost_queue(c2b_problem *p, double host[2]) {
+    host[0] = host[1] = 0.0;
+    const PriorBufs P = prior_bufs(p);
+    if ((p->pcw || p->piw) && p->n_cam)
+        HIP_TRY(hipMemcpyAsync(host, P.sc + kPrCostCam, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (p->pxw && p->n_pts) HIP_TRY(hipMemcpyAsync(host + 1, P.sc + kPrCostPts, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    return C2B_OK;
+}
+static double prior_cost_of(const double host[2]) { return host[0] + host[1]; }
+
+int c2b_problem_prior_cost(c2b_problem *p, double *cost) {
+    C2B_API_BEGIN
+    if (!p || !cost) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_prior_cost: NULL argument");
+    NEED_UPLOADED(p, "problem_prior_cost");
+    *cost = 0.0;
+    if (!has_priors(p)) return C2B_OK;
+    double h[2];
+    int rc = ensure_camblk(p);
+    if (!rc) rc = prior_cameras(p, nullptr, nullptr, true);
+    if (!rc) rc = prior_points(p, nullptr, nullptr, true);
+    if (!rc) rc = prior_cost_queue(p, h);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    *cost = prior_cost_of(h);
+    return C2B_OK;
+    C2B_API_END("problem_prior_cost")
+}
+
+int c2b_problem_prior_residual_jacobian(c2b_problem *p, double *r_cam, double *A_cam, double *r_pt) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_prior_residual_jacobian");
+    const int64_t nc = p->n_cam, np = p->n_pts;
+    const bool cams = (p->pcw || p->piw) && nc && (r_cam || A_cam), pts = p->pxw && np && r_pt;
+    if (!cams) {
+        if (r_cam) std::fill(r_cam, r_cam + 6 * nc, 0.0);
+        if (A_cam) std::fill(A_cam, A_cam + 18 * nc, 0.0);
+    }
+    if (!pts && r_pt) std::fill(r_pt, r_pt + 3 * np, 0.0);
+    if (!cams && !pts) return C2B_OK;
+    DevBuf<double> d_r, d_A, d_rp;
+    hipStream_t st = p->stream;
+    int rc = ensure_camblk(p);
+    if (rc) return rc;
+    if (cams) {
+        HIP_TRY(d_r.alloc(6 * (size_t)nc));
+        HIP_TRY(d_A.alloc(18 * (size_t)nc));
+        rc = prior_cameras_rows_impl(p->camblk, nc, p->pc0, p->pcw, p->pi0, p->piw, nullptr, nullptr, d_r, d_A, nullptr, nullptr, st);
+        if (!rc && r_cam) HIP_TRY(hipMemcpyAsync(r_cam, d_r, sizeof(double) * 6 * (size_t)nc, hipMemcpyDeviceToHost, st));
+        if (!rc && A_cam) HIP_TRY(hipMemcpyAsync(A_cam, d_A, sizeof(double) * 18 * (size_t)nc, hipMemcpyDeviceToHost, st));
+    }
+    if (!rc && pts) {
+        HIP_TRY(d_rp.alloc(3 * (size_t)np));
+        rc = prior_points_rows_impl(p->pts4, np, p->px0, p->pxw, nullptr, nullptr, d_rp, nullptr, nullptr, st);
+        if (!rc) HIP_TRY(hipMemcpyAsync(r_pt, d_rp, sizeof(double) * 3 * (size_t)np, hipMemcpyDeviceToHost, st));
+    }
+    const hipError_t es = hipStreamSynchronize(st);                  // (the temporaries are freed on return)
+    if (rc) return rc;
+    if (es != hipSuccess) return fail(C2B_ERR_HIP, "problem_prior_residual_jacobian: %s", hipGetErrorString(es));
+    return C2B_OK;
+    C2B_API_END("problem_prior_residual_jacobian")
+}
+
 // ---- robust loss -----------------------------------------------------------------------------------------
 int c2b_problem_set_loss(c2b_problem *p, int kind, double scale) {
     C2B_API_BEGIN
@@ -185,6 +360,9 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
     if (!rc) rc = ensure_rows(p);
     if (rc) return rc;
     const bool want_sum = sum_sq != nullptr;
+    // priors: after a kind's pass and before its constant zeros; their cost joins sum_sq.  None in force:
+    // every call below that names them returns without a launch
+    const bool pri = has_priors(p);
     if (U) {
         rc = normal_cameras_rows_impl(p->camblk, p->pts4, p->n_obs ? p->rows_ptr : nullptr, p->n_obs ? p->n_cam : 0, p->pt_idx, p->uv,
                                       p->n_obs, U, gc, want_sum ? p->ws : nullptr, want_sum ? p->scalar : nullptr, p->loss_kind,
@@ -193,7 +371,8 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
             HIP_TRY(hipMemsetAsync(U, 0, sizeof(double) * 81 * (size_t)p->n_cam, p->stream));
             HIP_TRY(hipMemsetAsync(gc, 0, sizeof(double) * 9 * (size_t)p->n_cam, p->stream));
         }
-        if (!rc && p->n_obs) rc = constant_cameras(p, U, 0.0, gc);
+        if (!rc && pri) rc = prior_cameras(p, U, gc, want_sum);
+        if (!rc && (p->n_obs || pri)) rc = constant_cameras(p, U, 0.0, gc);
     } else if (want_sum && p->loss_kind != kLossSquared && p->n_obs) {
         rc = robust_sum(p, true, p->scalar);                 // the weighted sum of squares without the blocks
     } else if (want_sum) {
@@ -202,22 +381,32 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
                       : (hipMemsetAsync(p->scalar, 0, sizeof(double), p->stream) == hipSuccess ? C2B_OK
                                                                                              : fail(C2B_ERR_HIP, "problem_normal_equations: memset"));
     }
+    if (!rc && pri && !U && want_sum) rc = prior_cameras(p, nullptr, nullptr, true);      // the cost without the blocks
     if (rc) return rc;
     if (V && p->n_pts) {
         if (p->n_obs) {
             rc = ensure_transpose(p);
             if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, V, gp, p->loss_kind,
                                                   p->loss_scale, p->stream);
+            if (!rc && pri) rc = prior_points(p, V, gp, want_sum);
             if (!rc) rc = constant_points(p, V, 0.0, gp);
             if (rc) return rc;
         } else {
             HIP_TRY(hipMemsetAsync(V, 0, sizeof(double) * 9 * (size_t)p->n_pts, p->stream));
             HIP_TRY(hipMemsetAsync(gp, 0, sizeof(double) * 3 * (size_t)p->n_pts, p->stream));
+            if (pri) {
+                rc = prior_points(p, V, gp, want_sum);
+                if (!rc) rc = constant_points(p, V, 0.0, gp);
+                if (rc) return rc;
+            }
         }
+    } else if (pri && want_sum) {
+        if ((rc = prior_points(p, nullptr, nullptr, true))) return rc;
     }
-    double s = 0.0;
+    double s = 0.0, hp[2] = {0.0, 0.0};
+    if (pri && want_sum && (rc = prior_cost_queue(p, hp))) return rc;
     if ((rc = scalars_to_host(p->stream, p->scalar, want_sum ? 1 : 0, &s))) return rc;
-    if (want_sum) *sum_sq = s;
+    if (want_sum) *sum_sq = pri ? s + prior_cost_of(hp) : s;
     return C2B_OK;
     C2B_API_END("problem_normal_equations")
 }
@@ -279,6 +468,8 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     hipStream_t st = p->stream;
     c2b_step_info out{0, 0, 0.0, 0.0, 0.0};
     p->precond_fallbacks = 0;
+    const bool pri = has_priors(p);
+    if (!no && pri) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: priors without a single observation are not solved (DESIGN 4.13)");
     if (!no) {                                               // no observation: g = 0, the step is 0
         if (nc) HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
         if (np) HIP_TRY(hipMemsetAsync(dp, 0, sizeof(double) * 3 * (size_t)np, st));
@@ -322,6 +513,9 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     rc = normal_cameras_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.gc, nullptr, nullptr, kind,
                                   p->loss_scale, st);
     if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, B.gp, kind, p->loss_scale, st);
+    // priors: from here on U, gc, V, gp are those of the stacked system, and so is the damping's diagonal
+    if (!rc && pri) rc = prior_cameras(p, B.U, B.gc, false);
+    if (!rc && pri) rc = prior_points(p, B.V, B.gp, false);
     if (rc) return rc;
     const bool schur_jacobi = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI;
     // constant parameters: from here on U, gc, V, gp are those of J~.  k_schur_jacobi first sees the constant
@@ -331,6 +525,7 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     if (rc) return rc;
     if (schur_jacobi) {                                      // M from U's diagonal and V, its factors, the fallbacks' count
         rc = schur_jacobi_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.V, lambda, B.M, kind, p->loss_scale, st);
+        if (!rc && pri) rc = prior_cameras(p, B.M, nullptr, false);      // k_schur_jacobi sums M from the observations, not from U
         if (!rc) rc = constant_cameras(p, B.M, lambda * 1e-6, nullptr);
         if (!rc) rc = constant_points(p, B.V, 0.0, nullptr);
         if (rc) return rc;
@@ -398,13 +593,21 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     });
     fold_sum(st, B.pa, (int)nbo, B.sc + kScSumSq);
     fold_sum(st, B.pb, (int)nbo, B.sc + kScModel);
+    double hpr[2] = {0.0, 0.0};                              // the priors' share of the two sums, beside k_schur_model's
+    if (pri) {
+        const PriorBufs P = prior_bufs(p);
+        if ((rc = prior_model_rows_impl(p->camblk, nc, p->pc0, p->pcw, p->pi0, p->piw, p->pts4, np, p->px0, p->pxw, dc, dp, P.pa, P.pb,
+                                        P.sc + kPrSumSq, st)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(hpr, P.sc + kPrSumSq, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
     if ((rc = fetch(schur_jacobi ? kScFallback + 1 : kScModel + 1))) return rc;
     if (schur_jacobi) p->precond_fallbacks = (int64_t)h[kScFallback];
     out.iterations = it;
     out.status = status;
     out.rel_residual = bb == 0.0 ? 0.0 : rnorm / bnorm;
-    out.sum_sq = h[kScSumSq];
-    out.model_decrease = h[kScModel];
+    out.sum_sq = pri ? h[kScSumSq] + hpr[0] : h[kScSumSq];
+    out.model_decrease = pri ? h[kScModel] + hpr[1] : h[kScModel];
     if (!std::isfinite(out.sum_sq) || !std::isfinite(out.model_decrease) || !std::isfinite(out.rel_residual)) {
         // a factorisation failed (a pivot <= 0 at the damping's low end) and a NaN reached the step: no step at all
         HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
@@ -632,12 +835,22 @@ static double libm_pow(double x, double y) {
 
 // the cost the loop compares: sum rho(|r|^2) under a loss, else the square of the root total_reprojection_error returns
 // (the numbers of city2ba_amd/solve.py's loop)
-static int lm_cost(c2b_problem *p, double *cost) {
+static int lm_cost_observations(c2b_problem *p, double *cost) {
     if (p->loss_kind != kLossSquared) return c2b_problem_robust_cost(p, cost);
     double e = 0.0;
     const int rc = c2b_problem_total_reprojection_error(p, 2.0, &e);
     if (rc) return rc;
     *cost = libm_pow(e, 2.0);
+    return C2B_OK;
+}
+
+// ... plus the priors' cost when any is in force, added in that order
+static int lm_cost(c2b_problem *p, double *cost) {
+    int rc = lm_cost_observations(p, cost);
+    if (rc || !has_priors(p)) return rc;
+    double pc = 0.0;
+    if ((rc = c2b_problem_prior_cost(p, &pc))) return rc;
+    *cost = *cost + pc;
     return C2B_OK;
 }
 
@@ -733,6 +946,8 @@ int c2b_problem_levenberg_marquardt(c2b_problem *p, const c2b_lm_options *opt, c
     NEED_UPLOADED(p, "problem_levenberg_marquardt");
     if (p->shard_n_cam_global >= 0)
         return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: a shard cannot be solved alone (the point-side sums span every rank)");
+    if (!p->n_obs && has_priors(p))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_levenberg_marquardt: priors without a single observation are not solved (DESIGN 4.13)");
     const int rc = lm_loop(p, *opt, history, summary);
     p->ck_valid = false;                                     // the checkpoint was the loop's
     return rc;

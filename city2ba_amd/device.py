@@ -452,6 +452,56 @@ def schur_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, lam, x, t, y, loss=Non
     return y
 
 
+def _prior_pair(target, w, n, name):
+    """a (target, weights) pair of a prior: both None, or both [n, 3] float64 on the device"""
+    if (target is None) != (w is None):
+        raise ValueError("%s: a prior's target and its weights go in pairs" % name)
+    for a in (target, w):
+        if a is not None:
+            _chk(a, torch.float64, name)
+            if tuple(a.shape) != (n, 3):
+                raise ValueError("%s must have shape (%d, 3)" % (name, n))
+    return _p(target), _p(w)
+
+
+def prior_cameras_rows(camblk, center=None, center_w=None, intr=None, intr_w=None, U=None, gc=None, r=None, A=None, part=None, cost=None):
+    """the camera priors' terms (c2b_prior_cameras_rows): U [n_cam,9,9] += A^T A, gc [n_cam,9] += A^T r for r_C = w_C o (C - C0)
+    (C the centre of the camera's record) and r_I = w_I o ((f, k1, k2) - I0); any of U, gc None skips it.  r [n_cam,6] and
+    A [n_cam,3,6] = diag(w_C) [dC/dw | -R^T] are written when given; part [ceil(9 n_cam / 256)] takes the cost's partials and
+    cost [1] their sum.  (center, center_w) and (intr, intr_w) are [n_cam,3] pairs, None together."""
+    n = _as_table(camblk).n_cam
+    c0, cw = _prior_pair(center, center_w, n, "center")
+    i0, iw = _prior_pair(intr, intr_w, n, "intr")
+    if part is not None and part.numel() < (9 * n + 255) // 256:
+        raise ValueError("prior_cameras_rows: part needs %d doubles" % ((9 * n + 255) // 256))
+    L.check(L.lib().c2b_prior_cameras_rows(_p(camblk), n, c0, cw, i0, iw, _p(U), _p(gc), _p(r), _p(A), _p(part), _p(cost), _stream()))
+    return U, gc
+
+
+def prior_points_rows(pts4, pt=None, pt_w=None, V=None, gp=None, r=None, part=None, cost=None):
+    """the point priors' terms (c2b_prior_points_rows): V [n_pts,3,3] += diag(w_X^2), gp [n_pts,3] += w_X o r_X, r_X = w_X o
+    (X - X0); r [n_pts,3], part [ceil(n_pts / 256)] and cost [1] as in prior_cameras_rows"""
+    n = pts4.shape[0]
+    x0, xw = _prior_pair(pt, pt_w, n, "pt")
+    if part is not None and part.numel() < (n + 255) // 256:
+        raise ValueError("prior_points_rows: part needs %d doubles" % ((n + 255) // 256))
+    L.check(L.lib().c2b_prior_points_rows(_p(pts4), n, x0, xw, _p(V), _p(gp), _p(r), _p(part), _p(cost), _stream()))
+    return V, gp
+
+
+def prior_model_rows(camblk, pts4, dc, dp, sums, center=None, center_w=None, intr=None, intr_w=None, pt=None, pt_w=None):
+    """the priors' part of a step's two sums (c2b_prior_model_rows): sums[0] = sum |r_prior|^2, sums[1] = sum (|r_prior|^2 -
+    |r_prior + A delta|^2) for the step dc [n_cam,9], dp [n_pts,3]; sums is a float64 device tensor of 2"""
+    nc, npt = _as_table(camblk).n_cam, pts4.shape[0]
+    c0, cw = _prior_pair(center, center_w, nc, "center")
+    i0, iw = _prior_pair(intr, intr_w, nc, "intr")
+    x0, xw = _prior_pair(pt, pt_w, npt, "pt")
+    part = torch.empty((2, (max(nc, npt) + 255) // 256 + 1), dtype=torch.float64, device=sums.device)
+    L.check(L.lib().c2b_prior_model_rows(_p(camblk), nc, c0, cw, i0, iw, _p(pts4), npt, x0, xw, _p(dc), _p(dp), _p(part[0]), _p(part[1]),
+                                         _p(sums), _stream()))
+    return sums
+
+
 def residual_jacobian(camblk, pts4, cam_idx, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None):
     """ws != None -> the same launch also folds sum |r|^norm into ws (see error_sum_finish)."""
     L.check(L.lib().c2b_residual_jacobian(_p(camblk), _p(pts4), _p(cam_idx), _p(pt_idx), _p(uv), cam_idx.shape[0],

@@ -1,8 +1,9 @@
 """Levenberg-Marquardt on a resident BAProblem: BAProblem.solve_step (the damped Gauss-Newton step by PCG on the
 cameras' Schur complement, on the device) and apply_step, with Nielsen's update of the damping; optionally under a
-robust loss (BAProblem.set_loss), by iteratively reweighted least squares, and with chosen camera parameters and points
-held constant (BAProblem.set_constant); and the usual pipeline around it (solve_filtered): a robust solve, the observations
-whose residual is still large dropped on the device (BAProblem.filter_observations), a last solve without a loss."""
+robust loss (BAProblem.set_loss), by iteratively reweighted least squares, with chosen camera parameters and points
+held constant (BAProblem.set_constant) and with priors on camera centres, intrinsics and points (BAProblem.set_priors);
+and the usual pipeline around it (solve_filtered): a robust solve, the observations whose residual is still large
+dropped on the device (BAProblem.filter_observations), a last solve without a loss."""
 
 LAMBDA_MIN, LAMBDA_MAX = 1e-20, 1e32                # the damping c2b_problem_solve_step accepts (C2B_STEP_LAMBDA_MIN / _MAX)
 # bits of a camera's constant mask (BAProblem.set_constant; C2B_CONST_*): parameter k of to_vec order is bit k
@@ -15,7 +16,8 @@ def _clamp(lam):
     return min(max(lam, LAMBDA_MIN), LAMBDA_MAX)
 
 
-def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0, preconditioner=None, constant=None):
+def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0, preconditioner=None, constant=None,
+                        priors=None):
     """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
     sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
     and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit); lam is held
@@ -32,7 +34,12 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     None leaves ba's as it is.  It changes how many PCG iterations a step takes, not what the step converges to.
     constant = (cameras, points) as BAProblem.set_constant takes them (which this calls: the masks stay on ba); None leaves
     ba's masks as they are.  Constant entries get a zero step and keep their bits through accepted and rejected iterations
-    (the restore after a rejected step is an upload of the same counts, which keeps the masks)."""
+    (the restore after a rejected step is an upload of the same counts, which keeps the masks).
+    priors = dict(...) of BAProblem.set_priors' keywords (which this calls: the priors stay on ba); None leaves ba's priors as
+    they are.  With priors in force the steps are those of the stacked system and the quantity compared -- 'error', 'cost',
+    'error_after' -- is the observations' cost + ba.prior_cost(), added in that order."""
+    if priors is not None:
+        ba.set_priors(**priors)
     if constant is not None:
         ba.set_constant(*constant)
     if preconditioner is not None:
@@ -46,11 +53,16 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     nu = 2.0
     lam = _clamp(lam)
     history = []
-    e0 = ba.robust_cost() if robust else ba.total_reprojection_error(2.0) ** 2
+    with_priors = any(ba.priors["active"])
+    cost = lambda: ba.robust_cost() if robust else ba.total_reprojection_error(2.0) ** 2
+    if with_priors:
+        observed = cost
+        cost = lambda: observed() + ba.prior_cost()
+    e0 = cost()
     for _ in range(int(iterations)):
         dc, dp, info = ba.solve_step(lam, max_iters=max_iters, rel_tol=rel_tol)
         ba.apply_step(dc, dp)
-        e1 = ba.robust_cost() if robust else ba.total_reprojection_error(2.0) ** 2
+        e1 = cost()
         md = info["model_decrease"]
         rho = (e0 - e1) / md if md > 0.0 else -1.0
         accepted = rho > 0.0 and e1 < e0
@@ -70,7 +82,7 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
 
 
 def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, function_tol=0.0, gradient_tol=0.0,
-                               parameter_tol=0.0, loss=None, loss_scale=1.0, preconditioner=None, constant=None):
+                               parameter_tol=0.0, loss=None, loss_scale=1.0, preconditioner=None, constant=None, priors=None):
     """levenberg_marquardt's loop inside the library (c2b_problem_levenberg_marquardt): the same steps, the same damping
     and the same numbers, with a device-side checkpoint and rollback where the loop above downloads and uploads, and with
     stopping tests.  Returns (history, summary).
@@ -83,10 +95,13 @@ def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_t
     gradient tolerance (gradient_max <= gradient_tol; the step is not applied), 3 = parameter tolerance (step_norm <=
     parameter_tol (x_norm + parameter_tol); the step is not applied), 4 = the cost or the gradient is not finite (the state
     is the last accepted one).  A tolerance of 0 disables its test: with all three at 0 this is levenberg_marquardt,
-    iteration for iteration.  loss, preconditioner and constant as there."""
+    iteration for iteration.  loss, preconditioner, constant and priors as there: with priors in force every cost is the
+    observations' cost + the priors', and the gradient test reads the gradient of the stacked system."""
     import ctypes as C
 
     from . import _lib as L
+    if priors is not None:
+        ba.set_priors(**priors)
     if constant is not None:
         ba.set_constant(*constant)
     if preconditioner is not None:

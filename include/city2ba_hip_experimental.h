@@ -209,6 +209,58 @@ int c2b_problem_set_constant(c2b_problem *p, const c2b_camera_mask *cam_mask, co
 int c2b_problem_get_constant(const c2b_problem *p, c2b_camera_mask *cam_mask, uint8_t *pt_mask, int64_t *n_const_cam_params,
                              int64_t *n_const_pts);
 
+/* ---- priors on camera centres, intrinsics and points in the step ----
+ * Optional residual rows beside the observations' (costs are sums of squares without a 1/2, g = J^T r):
+ *   camera c:  r_C = w_C o (C - C0), C = -R^T t the world-frame centre (3 rows);  r_I = w_I o ((f, k1, k2) - I0) (3 rows)
+ *   point p:   r_X = w_X o (X - X0) (3 rows)
+ * Weights are per component, finite and >= 0: 1 / sigma in units of the observations' standard deviation.  A weight of 0
+ * switches its row off, and its target is then ignored and may be anything.  No robust loss reweights a prior.  The stacked
+ * objective is (sum |r_obs|^2, or sum rho(|r_obs|^2)) + sum |r_prior|^2.  With the left-Jacobian convention of the Jacobian's
+ * rotation columns, dC/dw = -R^T [t]x J_l(w) and dC/dt = -R^T, from the camera's camblk record (so the prior refers to the w
+ * of the mode the problem is in); A = the 6x9 stack diag(w_C) [dC/dw | -R^T | 0], [0 | 0 | diag(w_I)].
+ * With priors in force c2b_problem_normal_equations and c2b_problem_solve_step are those of the stacked system: U_c += A^T A,
+ * gc_c += A^T r, V_p += diag(w_X^2), gp_p += w_X o r_X, added after the observations' passes and before the constant
+ * parameters' zeros (a constant parameter's prior column is zeroed like any other); the damping's diagonal, S, b, both
+ * preconditioners, sum_sq (+ sum |r_prior|^2) and model_decrease (+ sum |r_prior|^2 - |r_prior + A delta|^2) follow.
+ * c2b_problem_levenberg_marquardt's cost is the observations' cost + c2b_problem_prior_cost, added in that order.
+ * c2b_problem_total_reprojection_error, c2b_problem_robust_cost and c2b_problem_filter_observations stay observation-only.
+ * _set_priors: six HOST arrays of [n][3] doubles; a (target, weights) pair may be NULL (no prior of that kind), all NULL
+ *   clears the priors; a pair whose weights are all 0 is no prior.  A target without its weights (or the reverse), a negative
+ *   or non-finite weight, a non-finite target under a positive weight, or a shard: C2B_ERR_INVALID_ARGUMENT, and the priors
+ *   in force stay.  With none in force every entry launches and allocates exactly what it does without this entry.
+ * _get_priors: the arrays in force (zeros for a kind with none) and how many cameras / cameras / points have a centre / an
+ *   intrinsics / a point row with a positive weight; any output may be NULL.
+ * _prior_cost: sum |r_prior|^2 at the current state (the cameras' sum + the points' sum); 0 without priors.
+ * _prior_residual_jacobian: HOST out-buffers (any may be NULL), synchronous: r_cam [n_cam][6] = (r_C, r_I), A_cam [n_cam][3][6]
+ *   = diag(w_C) [dC/dw | -R^T], r_pt [n_pts][3]; zeros where no prior is in force.
+ * Lifetime: as the constant masks -- kept by c2b_problem_apply_step, the noise functions, _set_loss, _set_preconditioner,
+ *   _set_constant, checkpoint and rollback and an upload of the same counts; dropped by a cull, a read, a generator, an
+ *   upload of another size.
+ * Limits: priors in force and no observation at all: c2b_problem_solve_step and c2b_problem_levenberg_marquardt return
+ *   C2B_ERR_INVALID_ARGUMENT.  A camera with an empty row and a prior is ordinary: its block is the prior alone.
+ * Level 0, asynchronous on `stream`, device pointers, (target, weights) pairs [n][3] NULL together:
+ * _prior_cameras_rows: U [n_cam][9][9] += A^T A, gc [n_cam][9] += A^T r (either may be NULL: U may be the Schur-Jacobi M);
+ *   r [n_cam][6] and A [n_cam][3][6] (may be NULL) are written for every camera; part (may be NULL) takes one cost partial
+ *   per 256 rows of blocks, ceil(9 n_cam / 256) doubles, and cost (may be NULL, needs part) their sum in a fixed order.
+ * _prior_points_rows: V [n_pts][3][3] += diag(w_X^2), gp [n_pts][3] += w_X o r_X (both may be NULL), r [n_pts][3], part
+ *   [ceil(n_pts / 256)], cost likewise.
+ * _prior_model_rows: sums[0] = sum |r_prior|^2, sums[1] = sum (|r_prior|^2 - |r_prior + A delta|^2) for the step dc [n_cam][9],
+ *   dp [n_pts][3]; part_sq, part_md: ceil(max(n_cam, n_pts) / 256) doubles each.
+ * Deterministic: no float atomics; the same inputs give the same bits. */
+int c2b_problem_set_priors(c2b_problem *p, const double *cam_center, const double *cam_center_w, const double *cam_intr,
+                           const double *cam_intr_w, const double *pt, const double *pt_w);
+int c2b_problem_get_priors(const c2b_problem *p, double *cam_center, double *cam_center_w, double *cam_intr, double *cam_intr_w,
+                           double *pt, double *pt_w, int64_t *n_center_rows, int64_t *n_intr_rows, int64_t *n_pt_rows);
+int c2b_problem_prior_cost(c2b_problem *p, double *cost);
+int c2b_problem_prior_residual_jacobian(c2b_problem *p, double *r_cam, double *A_cam, double *r_pt);
+int c2b_prior_cameras_rows(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
+                           const double *intr_w, double *U, double *gc, double *r, double *A, double *part, double *cost, void *stream);
+int c2b_prior_points_rows(const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, double *V, double *gp, double *r,
+                          double *part, double *cost, void *stream);
+int c2b_prior_model_rows(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
+                         const double *intr_w, const double *pts4, int64_t n_pts, const double *pt, const double *pt_w,
+                         const double *dc, const double *dp, double *part_sq, double *part_md, double *sums, void *stream);
+
 /* ---- the Levenberg-Marquardt loop on the device: checkpoint, stopping tests ----
  * _checkpoint: takes the problem to bal mode exactly as c2b_problem_apply_step(p, NULL, NULL) does and copies bal9 and the
  *   points into two device buffers the problem owns (allocated on first use, reused while the counts stay).  Device to
