@@ -469,19 +469,14 @@ int c2b_problem_resect_consensus(c2b_problem *p, double max_error, int min_inlie
     if (e == hipSuccess) e = d_ninl.alloc((size_t)nc);
     if (e != hipSuccess) return fail(hip_code(e), "problem_resect_consensus: allocation: %s", hipGetErrorString(e));
     hipStream_t st = p->stream;
-    if (!p->bal_valid && !p->bal9_fresh) {                   // state mode: the pass works on to_vec(cam15)
-        if ((rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st))) return rc;
-        p->bal9_fresh = true;
-    }
+    if ((rc = bal9_edit_begin(p))) return rc;                // state mode: the pass works on to_vec(cam15)
     rc = c2b_resect_consensus_rows(p->bal9, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, n_old, max_error, min_inliers, min_gap, max_hypotheses,
                                    p->cmask, rep.d_status, d_hyp, d_ninl, d_inlier, rep.d_counts, st);
-    if (!rc) rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
+    rc = bal9_edit_end(p, rc);
     if (!rc && hyp) e = hipMemcpyAsync(hyp, d_hyp, sizeof(int32_t) * (size_t)nc, hipMemcpyDeviceToHost, st);
     if (!rc && e == hipSuccess && n_inl) e = hipMemcpyAsync(n_inl, d_ninl, sizeof(int32_t) * (size_t)nc, hipMemcpyDeviceToHost, st);
     if (!rc && e == hipSuccess && inlier) e = hipMemcpyAsync(inlier, d_inlier, (size_t)n_old, hipMemcpyDeviceToHost, st);
     rc = rep.read_back("problem_resect_consensus", st, rc, e, nc, status, counts);
-    cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
-    p->bal_valid = true;
     if (rc || !(flags & C2B_RES_DROP_OUTLIERS)) return rc;
     return compact_and_install(p, "problem_resect_consensus", d_inlier, n_old, n_removed);     // the filter's compaction, by the inlier mask
     C2B_API_END("problem_resect_consensus")

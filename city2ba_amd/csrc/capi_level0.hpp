@@ -1322,11 +1322,123 @@ static bool good_loss(int kind, double scale) { return kind == 0 || (kind >= 1 &
 #define NEED_LOSS(kind, scale, who) \
     if (!good_loss(kind, scale)) return fail(C2B_ERR_INVALID_ARGUMENT, who ": loss kind must be 0..3 and its scale finite and > 0")
 
-// the *_rows entries and their *_loss forms: kind 0 launches the squared-loss instance of a pass (the empty pack), any
-// other kind the weighted one (with_loss, normal_kernels.hpp)
-static int normal_cameras_rows_impl(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
-                                    const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
-                                    void *workspace, double *sum_sq, int kind, double scale, void *stream) {
+// ---- one launcher per observation pass of the solver --------------------------------------------------------------------
+// Each holds the only launch of its kernel: it picks the template instance (kind 0 the squared-loss one, the empty pack, any other
+// kind the weighted one: with_loss, normal_kernels.hpp) and the grid, asynchronous and unchecked like any launch in a sequence.  The
+// *_rows_loss entries below check a caller's arguments and call them; Level 1 calls them with the resident problem's own buffers.
+static const double4 *as4(const double *pts4) { return reinterpret_cast<const double4 *>(pts4); }
+static const double2 *as2(const double *uv) { return reinterpret_cast<const double2 *>(uv); }
+
+// grid of k_schur_cameras and k_schur_jacobi: one wave per kNormCamsPerWave cameras
+static unsigned schur_cameras_grid(int64_t n_cam) { return blocks_for(blocks_for(n_cam, kNormCamsPerWave), kNormBlock / 64); }
+
+// sum over the observations of rho(s) (weighted_sq: of w s) under a loss into out[0]: one partial per workgroup of 256
+// observations, the cameras per observation (cam_idx) or through the row structure (cam_idx NULL)
+static void launch_robust_cost(hipStream_t st, bool weighted_sq, const double *camblk, const double *pts4, const uint32_t *cam_idx,
+                               const uint64_t *row_ptr, int n_cam, const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, int kind, double scale,
+                               double *part, double *out) {
+    static_assert(kNormBlock == 256, "k_robust_cost's partials are sized by block_part_slots");
+    const unsigned nb = blocks_for(n_obs, kNormBlock);       // <= block_part_slots(n_obs): one partial per 4 tiles of 64
+    if (nb && weighted_sq)
+        hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, st, camblk, as4(pts4), cam_idx, row_ptr, n_cam, pt_idx, as2(uv_obs), n_obs,
+                           kind, scale * scale, part);
+    else if (nb)
+        hipLaunchKernelGGL(k_robust_cost<false>, dim3(nb), dim3(kNormBlock), 0, st, camblk, as4(pts4), cam_idx, row_ptr, n_cam, pt_idx, as2(uv_obs), n_obs,
+                           kind, scale * scale, part);
+    fold_sum(st, part, (int)nb, out);
+}
+
+// U and gc of n_cam > 0 cameras; with sum_sq the (weighted) sum of squares through the workspace's partials: the squared-loss
+// pass folds its own wave partials, under a loss the sum is a pass of its own (k_robust_cost)
+static void launch_normal_cameras(hipStream_t st, const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                                  const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc, void *workspace,
+                                  double *sum_sq, int kind, double scale) {
+    const unsigned grid = std::min(schur_cameras_grid(n_cam), (unsigned)kNormMaxGrid);
+    double *block_part = sum_sq ? reinterpret_cast<double *>(workspace) + kWsBlockPart : nullptr;
+    if (sum_sq && kind == kLossSquared) {
+        hipLaunchKernelGGL(k_normal_cameras<true>, dim3(grid), dim3(kNormBlock), 0, st, camblk, as4(pts4), row_ptr, (int)n_cam, pt_idx, as2(uv_obs), U, gc,
+                           block_part);
+        fold_sum(st, block_part, (int)(grid * (kNormBlock / 64)), sum_sq);
+        return;
+    }
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        hipLaunchKernelGGL((k_normal_cameras<false, decltype(loss)...>), dim3(grid), dim3(kNormBlock), 0, st, camblk, as4(pts4), row_ptr, (int)n_cam,
+                           pt_idx, as2(uv_obs), U, gc, (double *)nullptr, loss...);
+    });
+    if (sum_sq) launch_robust_cost(st, true, camblk, pts4, nullptr, row_ptr, (int)n_cam, pt_idx, uv_obs, n_obs, kind, scale, block_part, sum_sq);
+}
+
+static void launch_normal_points(hipStream_t st, const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                                 const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp, int kind, double scale) {
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        hipLaunchKernelGGL(k_normal_points<decltype(loss)...>, dim3(blocks_for(n_pts, kNormBlock)), dim3(kNormBlock), 0, st, camblk, as4(pts4), n_pts,
+                           pt_row_ptr, obs_of, cam_of, as2(uv_obs), V, gp, loss...);
+    });
+}
+
+// t = (neg ? -1 : 1) V_l^-1 (h + W^T x): neg picks the NEG instance
+static void launch_schur_points(hipStream_t st, const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                                const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda, const double *x,
+                                const double *h, double *t, bool neg, int kind, double scale) {
+    const dim3 grid(blocks_for(n_pts, kSchurBlock)), block(kSchurBlock);
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        if (neg)
+            hipLaunchKernelGGL((k_schur_points<true, decltype(loss)...>), grid, block, 0, st, camblk, as4(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
+                               as2(uv_obs), V, lambda, x, h, t, loss...);
+        else
+            hipLaunchKernelGGL((k_schur_points<false, decltype(loss)...>), grid, block, 0, st, camblk, as4(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
+                               as2(uv_obs), V, lambda, x, h, t, loss...);
+    });
+}
+
+// the camera pass of the Schur operator.  The pointers given name the mode, one instance each: h (with x NULL) is the
+// right-hand side's kSchurRhs, block_part the iteration's kSchurDot, x alone kSchurApply, none of them kSchurNoX
+static void launch_schur_cameras(hipStream_t st, const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                                 const uint32_t *pt_idx, const double *uv_obs, const double *U, double lambda, const double *x, const double *h,
+                                 const double *t, double *y, double *block_part, int kind, double scale) {
+    const dim3 grid(schur_cameras_grid(n_cam)), block(kNormBlock);
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        auto launch = [&](auto mode) {
+            hipLaunchKernelGGL((k_schur_cameras<decltype(mode)::value, decltype(loss)...>), grid, block, 0, st, camblk, as4(pts4), row_ptr, (int)n_cam,
+                               pt_idx, as2(uv_obs), U, lambda, x, h, t, y, block_part, loss...);
+        };
+        if (h) launch(std::integral_constant<int, kSchurRhs>());
+        else if (block_part) launch(std::integral_constant<int, kSchurDot>());
+        else if (x) launch(std::integral_constant<int, kSchurApply>());
+        else launch(std::integral_constant<int, kSchurNoX>());
+    });
+}
+
+// the Schur-Jacobi blocks M
+static void launch_schur_jacobi(hipStream_t st, const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                                const uint32_t *pt_idx, const double *uv_obs, const double *U, const double *V, double lambda, double *M, int kind,
+                                double scale) {
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        hipLaunchKernelGGL(k_schur_jacobi<decltype(loss)...>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, st, camblk, as4(pts4), row_ptr,
+                           (int)n_cam, pt_idx, as2(uv_obs), U, V, lambda, M, loss...);
+    });
+}
+
+// |r|^2 and the model decrease of the step (dc, dp) per observation, folded into sums[0] and sums[1]
+static void launch_schur_model(hipStream_t st, const double *camblk, const double *pts4, const uint32_t *cam_idx, const uint32_t *pt_idx,
+                               const double *uv_obs, int64_t n_obs, const double *dc, const double *dp, double *part_sq, double *part_md, double *sums,
+                               int kind, double scale) {
+    const unsigned nbo = blocks_for(n_obs, kSchurBlock);
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        hipLaunchKernelGGL(k_schur_model<decltype(loss)...>, dim3(nbo), dim3(kSchurBlock), 0, st, camblk, as4(pts4), cam_idx, pt_idx, as2(uv_obs), n_obs, dc,
+                           dp, part_sq, part_md, loss...);
+    });
+    fold_sum(st, part_sq, (int)nbo, sums);
+    fold_sum(st, part_md, (int)nbo, sums + 1);
+}
+
+// the *_rows_loss entries: the argument checks, then the pass's launcher; a *_rows entry is its *_loss form with kind 0, which
+// catches what there is to catch
+int c2b_normal_cameras_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
+                                 const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
+                                 void *workspace, double *sum_sq, int kind, double scale, void *stream) {
+    C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "normal_cameras_rows_loss");
     if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
         return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: count out of range");
     if (sum_sq && !workspace) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_cameras_rows: sum_sq needs a workspace");
@@ -1340,74 +1452,16 @@ static int normal_cameras_rows_impl(const double *camblk, const double *pts4, co
         if (sum_sq) HIP_TRY(hipMemsetAsync(sum_sq, 0, sizeof(double), st));
         return C2B_OK;
     }
-    const int64_t quads = (n_cam + kNormCamsPerWave - 1) / kNormCamsPerWave, waves = kNormBlock / 64;
-    const unsigned grid = (unsigned)((quads + waves - 1) / waves < kNormMaxGrid ? (quads + waves - 1) / waves : kNormMaxGrid);
-    const double4 *p4 = reinterpret_cast<const double4 *>(pts4);
-    const double2 *uv = reinterpret_cast<const double2 *>(uv_obs);
-    const double a2 = scale * scale;
-    double *block_part = sum_sq ? reinterpret_cast<double *>(workspace) + kWsBlockPart : nullptr;
-    if (sum_sq && kind == kLossSquared) {
-        hipLaunchKernelGGL(k_normal_cameras<true>, dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr, (int)n_cam, pt_idx, uv,
-                           U, gc, block_part);
-        fold_sum(st, block_part, (int)(grid * waves), sum_sq);
-    } else {
-        with_loss(kind, a2, [&](auto... loss) {
-            hipLaunchKernelGGL((k_normal_cameras<false, decltype(loss)...>), dim3(grid), dim3(kNormBlock), 0, st, camblk, p4, row_ptr,
-                               (int)n_cam, pt_idx, uv, U, gc, (double *)nullptr, loss...);
-        });
-        if (sum_sq) {                                        // under a loss: the weighted sum of squares, a pass of its own (k_robust_cost)
-            const unsigned nb = blocks_for(n_obs, kNormBlock);   // <= block_part_slots(n_obs): one partial per 4 tiles of 64
-            if (nb) hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, st, camblk, p4, (const uint32_t *)nullptr, row_ptr,
-                                       (int)n_cam, pt_idx, uv, n_obs, kind, a2, block_part);
-            fold_sum(st, block_part, (int)nb, sum_sq);
-        }
-    }
+    launch_normal_cameras(st, camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, gc, workspace, sum_sq, kind, scale);
     LAUNCH_CHECK();
     return C2B_OK;
+    C2B_API_END("normal_cameras_rows_loss")
 }
 
 int c2b_normal_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
                             const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
                             void *workspace, double *sum_sq, void *stream) {
-    C2B_API_BEGIN
-    return normal_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, gc, workspace, sum_sq, 0, 1.0, stream);
-    C2B_API_END("normal_cameras_rows")
-}
-
-int c2b_normal_cameras_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam,
-                                 const uint32_t *pt_idx, const double *uv_obs, int64_t n_obs, double *U, double *gc,
-                                 void *workspace, double *sum_sq, int kind, double scale, void *stream) {
-    C2B_API_BEGIN
-    NEED_LOSS(kind, scale, "normal_cameras_rows_loss");
-    return normal_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, gc, workspace, sum_sq, kind, scale, stream);
-    C2B_API_END("normal_cameras_rows_loss")
-}
-
-static int normal_points_rows_impl(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
-                                   const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
-                                   int kind, double scale, void *stream) {
-    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: n_pts out of range");
-    if (n_pts && (!camblk || !pts4 || !pt_row_ptr || !obs_of || !cam_of || !uv_obs || !V || !gp))
-        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: NULL argument");
-    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(V) || !aligned8(gp) ||
-        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
-        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: misaligned pointer");
-    if (!n_pts) return C2B_OK;
-    with_loss(kind, scale * scale, [&](auto... loss) {
-        hipLaunchKernelGGL(k_normal_points<decltype(loss)...>, dim3((unsigned)((n_pts + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0,
-                           S(stream), camblk, reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
-                           reinterpret_cast<const double2 *>(uv_obs), V, gp, loss...);
-    });
-    LAUNCH_CHECK();
-    return C2B_OK;
-}
-
-int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
-                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
-                           void *stream) {
-    C2B_API_BEGIN
-    return normal_points_rows_impl(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, gp, 0, 1.0, stream);
-    C2B_API_END("normal_points_rows")
+    return c2b_normal_cameras_rows_loss(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, gc, workspace, sum_sq, 0, 1.0, stream);
 }
 
 int c2b_normal_points_rows_loss(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
@@ -1415,17 +1469,34 @@ int c2b_normal_points_rows_loss(const double *camblk, const double *pts4, int64_
                                 int kind, double scale, void *stream) {
     C2B_API_BEGIN
     NEED_LOSS(kind, scale, "normal_points_rows_loss");
-    return normal_points_rows_impl(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, gp, kind, scale, stream);
+    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: n_pts out of range");
+    if (n_pts && (!camblk || !pts4 || !pt_row_ptr || !obs_of || !cam_of || !uv_obs || !V || !gp))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: NULL argument");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(V) || !aligned8(gp) ||
+        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "normal_points_rows: misaligned pointer");
+    if (!n_pts) return C2B_OK;
+    launch_normal_points(S(stream), camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, gp, kind, scale);
+    LAUNCH_CHECK();
+    return C2B_OK;
     C2B_API_END("normal_points_rows_loss")
+}
+
+int c2b_normal_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, double *V, double *gp,
+                           void *stream) {
+    return c2b_normal_points_rows_loss(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, gp, 0, 1.0, stream);
 }
 
 // ---- damped Gauss-Newton step: the implicit Schur complement's passes (schur_kernels.hpp) -----------------------
 // the damping range: inside it lambda * 1e-6 and lambda * 1e32 (the clamp's ends) stay normal doubles
 static bool good_lambda(double lam) { return lam >= C2B_STEP_LAMBDA_MIN && lam <= C2B_STEP_LAMBDA_MAX; }
 
-static int schur_points_rows_impl(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
-                                  const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
-                                  const double *x_cam, const double *h_pts, double *t_pts, int kind, double scale, void *stream) {
+int c2b_schur_points_rows_loss(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
+                               const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
+                               const double *x_cam, const double *h_pts, double *t_pts, int kind, double scale, void *stream) {
+    C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "schur_points_rows_loss");
     if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: n_pts out of range");
     if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: lambda must lie in [1e-20, 1e32]");
     if (n_pts && (!V || !t_pts || (x_cam && (!camblk || !pts4 || !pt_row_ptr || !obs_of || !cam_of || !uv_obs))))
@@ -1434,31 +1505,16 @@ static int schur_points_rows_impl(const double *camblk, const double *pts4, int6
         !aligned8(h_pts) || !aligned8(t_pts) || (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_points_rows: misaligned pointer");
     if (!n_pts) return C2B_OK;
-    with_loss(kind, scale * scale, [&](auto... loss) {
-        hipLaunchKernelGGL((k_schur_points<false, decltype(loss)...>), dim3(blocks_for(n_pts, kSchurBlock)), dim3(kSchurBlock), 0, S(stream),
-                           camblk, reinterpret_cast<const double4 *>(pts4), n_pts, pt_row_ptr, obs_of, cam_of,
-                           reinterpret_cast<const double2 *>(uv_obs), V, lambda, x_cam, h_pts, t_pts, loss...);
-    });
+    launch_schur_points(S(stream), camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, lambda, x_cam, h_pts, t_pts, false, kind, scale);
     LAUNCH_CHECK();
     return C2B_OK;
+    C2B_API_END("schur_points_rows_loss")
 }
 
 int c2b_schur_points_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
                           const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
                           const double *x_cam, const double *h_pts, double *t_pts, void *stream) {
-    C2B_API_BEGIN
-    return schur_points_rows_impl(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, lambda, x_cam, h_pts, t_pts, 0, 1.0, stream);
-    C2B_API_END("schur_points_rows")
-}
-
-int c2b_schur_points_rows_loss(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr,
-                               const uint32_t *obs_of, const uint32_t *cam_of, const double *uv_obs, const double *V, double lambda,
-                               const double *x_cam, const double *h_pts, double *t_pts, int kind, double scale, void *stream) {
-    C2B_API_BEGIN
-    NEED_LOSS(kind, scale, "schur_points_rows_loss");
-    return schur_points_rows_impl(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, lambda, x_cam, h_pts, t_pts, kind, scale,
-                                  stream);
-    C2B_API_END("schur_points_rows_loss")
+    return c2b_schur_points_rows_loss(camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, V, lambda, x_cam, h_pts, t_pts, 0, 1.0, stream);
 }
 
 // ---- priors on camera centres, intrinsics and points (prior_kernels.hpp) -----------------------------------
@@ -1467,8 +1523,9 @@ static unsigned prior_cameras_grid(int64_t n_cam) { return blocks_for(9 * n_cam,
 static unsigned prior_points_grid(int64_t n_pts) { return blocks_for(n_pts, kSchurBlock); }
 static unsigned prior_model_grid(int64_t n_cam, int64_t n_pts) { return blocks_for(std::max(n_cam, n_pts), kSchurBlock); }
 
-static int prior_cameras_rows_impl(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
+int c2b_prior_cameras_rows(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
                                    const double *intr_w, double *U, double *gc, double *r, double *A, double *part, double *cost, void *stream) {
+    C2B_API_BEGIN
     if (n_cam < 0 || n_cam > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_cameras_rows: n_cam out of range");
     if (!center != !center_w || !intr != !intr_w) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_cameras_rows: a target and its weights go in pairs");
     if ((n_cam && !camblk) || (cost && !part)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_cameras_rows: NULL argument");
@@ -1486,10 +1543,12 @@ static int prior_cameras_rows_impl(const double *camblk, int64_t n_cam, const do
     if (cost) fold_sum(st, part, (int)prior_cameras_grid(n_cam), cost);
     LAUNCH_CHECK();
     return C2B_OK;
+    C2B_API_END("prior_cameras_rows")
 }
 
-static int prior_points_rows_impl(const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, double *V, double *gp, double *r,
+int c2b_prior_points_rows(const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, double *V, double *gp, double *r,
                                   double *part, double *cost, void *stream) {
+    C2B_API_BEGIN
     if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_points_rows: n_pts out of range");
     if (!pt != !pt_w) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_points_rows: a target and its weights go in pairs");
     if ((n_pts && !pts4) || (cost && !part)) return fail(C2B_ERR_INVALID_ARGUMENT, "prior_points_rows: NULL argument");
@@ -1506,11 +1565,13 @@ static int prior_points_rows_impl(const double *pts4, int64_t n_pts, const doubl
     if (cost) fold_sum(st, part, (int)prior_points_grid(n_pts), cost);
     LAUNCH_CHECK();
     return C2B_OK;
+    C2B_API_END("prior_points_rows")
 }
 
-static int prior_model_rows_impl(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
+int c2b_prior_model_rows(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
                                  const double *intr_w, const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, const double *dc,
                                  const double *dp, double *part_sq, double *part_md, double *sums, void *stream) {
+    C2B_API_BEGIN
     if (n_cam < 0 || n_cam > (int64_t)0xffffffff || n_pts < 0 || n_pts > (int64_t)0xffffffff)
         return fail(C2B_ERR_INVALID_ARGUMENT, "prior_model_rows: count out of range");
     if (!center != !center_w || !intr != !intr_w || !pt != !pt_w)
@@ -1533,27 +1594,6 @@ static int prior_model_rows_impl(const double *camblk, int64_t n_cam, const doub
     fold_sum(st, part_md, (int)grid, sums + 1);
     LAUNCH_CHECK();
     return C2B_OK;
-}
-
-int c2b_prior_cameras_rows(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
-                           const double *intr_w, double *U, double *gc, double *r, double *A, double *part, double *cost, void *stream) {
-    C2B_API_BEGIN
-    return prior_cameras_rows_impl(camblk, n_cam, center, center_w, intr, intr_w, U, gc, r, A, part, cost, stream);
-    C2B_API_END("prior_cameras_rows")
-}
-
-int c2b_prior_points_rows(const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, double *V, double *gp, double *r, double *part,
-                          double *cost, void *stream) {
-    C2B_API_BEGIN
-    return prior_points_rows_impl(pts4, n_pts, pt, pt_w, V, gp, r, part, cost, stream);
-    C2B_API_END("prior_points_rows")
-}
-
-int c2b_prior_model_rows(const double *camblk, int64_t n_cam, const double *center, const double *center_w, const double *intr,
-                         const double *intr_w, const double *pts4, int64_t n_pts, const double *pt, const double *pt_w, const double *dc,
-                         const double *dp, double *part_sq, double *part_md, double *sums, void *stream) {
-    C2B_API_BEGIN
-    return prior_model_rows_impl(camblk, n_cam, center, center_w, intr, intr_w, pts4, n_pts, pt, pt_w, dc, dp, part_sq, part_md, sums, stream);
     C2B_API_END("prior_model_rows")
 }
 
@@ -1679,15 +1719,11 @@ int c2b_resect_consensus_rows(double *bal9, const double *pts4, const uint64_t *
     C2B_API_END("resect_consensus_rows")
 }
 
-// grid of k_schur_cameras: one wave per kNormCamsPerWave cameras
-static unsigned schur_cameras_grid(int64_t n_cam) {
-    const int64_t quads = (n_cam + kNormCamsPerWave - 1) / kNormCamsPerWave, waves = kNormBlock / 64;
-    return (unsigned)((quads + waves - 1) / waves);
-}
-
-static int schur_cameras_rows_impl(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
-                                   const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
-                                   const double *t_pts, double *y_cam, int kind, double scale, void *stream) {
+int c2b_schur_cameras_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                                const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
+                                const double *t_pts, double *y_cam, int kind, double scale, void *stream) {
+    C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "schur_cameras_rows_loss");
     if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: count out of range");
     if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: lambda must lie in [1e-20, 1e32]");
@@ -1697,43 +1733,23 @@ static int schur_cameras_rows_impl(const double *camblk, const double *pts4, con
         !aligned8(t_pts) || !aligned8(y_cam) || (reinterpret_cast<uintptr_t>(pt_idx) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_cameras_rows: misaligned pointer");
     if (!n_cam) return C2B_OK;
-    with_loss(kind, scale * scale, [&](auto... loss) {
-        if (x_cam)
-            hipLaunchKernelGGL((k_schur_cameras<kSchurApply, decltype(loss)...>), dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0,
-                               S(stream), camblk, reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx,
-                               reinterpret_cast<const double2 *>(uv_obs), U, lambda, x_cam, (const double *)nullptr, t_pts, y_cam,
-                               (double *)nullptr, loss...);
-        else
-            hipLaunchKernelGGL((k_schur_cameras<kSchurNoX, decltype(loss)...>), dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0,
-                               S(stream), camblk, reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx,
-                               reinterpret_cast<const double2 *>(uv_obs), U, lambda, (const double *)nullptr, (const double *)nullptr, t_pts,
-                               y_cam, (double *)nullptr, loss...);
-    });
+    launch_schur_cameras(S(stream), camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, U, lambda, x_cam, nullptr, t_pts, y_cam, nullptr, kind, scale);
     LAUNCH_CHECK();
     return C2B_OK;
+    C2B_API_END("schur_cameras_rows_loss")
 }
 
 int c2b_schur_cameras_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
                            const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
                            const double *t_pts, double *y_cam, void *stream) {
-    C2B_API_BEGIN
-    return schur_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, lambda, x_cam, t_pts, y_cam, 0, 1.0, stream);
-    C2B_API_END("schur_cameras_rows")
+    return c2b_schur_cameras_rows_loss(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, lambda, x_cam, t_pts, y_cam, 0, 1.0, stream);
 }
 
-int c2b_schur_cameras_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
-                                const double *uv_obs, int64_t n_obs, const double *U, double lambda, const double *x_cam,
-                                const double *t_pts, double *y_cam, int kind, double scale, void *stream) {
+int c2b_schur_jacobi_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                               const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
+                               int kind, double scale, void *stream) {
     C2B_API_BEGIN
-    NEED_LOSS(kind, scale, "schur_cameras_rows_loss");
-    return schur_cameras_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, lambda, x_cam, t_pts, y_cam, kind, scale, stream);
-    C2B_API_END("schur_cameras_rows_loss")
-}
-
-// the Schur-Jacobi blocks M (k_schur_jacobi, on the grid of k_schur_cameras)
-static int schur_jacobi_rows_impl(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
-                                  const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
-                                  int kind, double scale, void *stream) {
+    NEED_LOSS(kind, scale, "schur_jacobi_rows_loss");
     if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 4096 * 64 || n_cam < 0 || n_cam >= (int64_t)1 << 31)
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: count out of range");
     if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: lambda must lie in [1e-20, 1e32]");
@@ -1743,28 +1759,15 @@ static int schur_jacobi_rows_impl(const double *camblk, const double *pts4, cons
         !aligned8(M) || (reinterpret_cast<uintptr_t>(pt_idx) & 3))
         return fail(C2B_ERR_INVALID_ARGUMENT, "schur_jacobi_rows: misaligned pointer");
     if (!n_cam) return C2B_OK;
-    with_loss(kind, scale * scale, [&](auto... loss) {
-        hipLaunchKernelGGL(k_schur_jacobi<decltype(loss)...>, dim3(schur_cameras_grid(n_cam)), dim3(kNormBlock), 0, S(stream), camblk,
-                           reinterpret_cast<const double4 *>(pts4), row_ptr, (int)n_cam, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
-                           U, V, lambda, M, loss...);
-    });
+    launch_schur_jacobi(S(stream), camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, U, V, lambda, M, kind, scale);
     LAUNCH_CHECK();
     return C2B_OK;
+    C2B_API_END("schur_jacobi_rows_loss")
 }
 
 int c2b_schur_jacobi_rows(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
                           const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
                           void *stream) {
-    C2B_API_BEGIN
-    return schur_jacobi_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, V, lambda, M, 0, 1.0, stream);
-    C2B_API_END("schur_jacobi_rows")
+    return c2b_schur_jacobi_rows_loss(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, V, lambda, M, 0, 1.0, stream);
 }
 
-int c2b_schur_jacobi_rows_loss(const double *camblk, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
-                               const double *uv_obs, int64_t n_obs, const double *U, const double *V, double lambda, double *M,
-                               int kind, double scale, void *stream) {
-    C2B_API_BEGIN
-    NEED_LOSS(kind, scale, "schur_jacobi_rows_loss");
-    return schur_jacobi_rows_impl(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, V, lambda, M, kind, scale, stream);
-    C2B_API_END("schur_jacobi_rows_loss")
-}

@@ -185,24 +185,32 @@ int c2b_problem_get_priors(const c2b_problem *p, double *cam_center, double *cam
     C2B_API_END("problem_get_priors")
 }
 
-// the priors' terms into blocks the passes filled (asynchronous; nothing is launched for a kind without priors): A^T A into
-// A9 [n_cam][9][9] = U or M and A^T r into gc (either may be NULL); with want_cost their cost into the kPrCostCam scalar ...
-static int prior_cameras(c2b_problem *p, double *A9, double *gc, bool want_cost) {
-    if ((!p->pcw && !p->piw) || !p->n_cam) return C2B_OK;
-    const PriorBufs P = prior_bufs(p);
-    return prior_cameras_rows_impl(p->camblk, p->n_cam, p->pc0, p->pcw, p->pi0, p->piw, A9, gc, nullptr, nullptr, want_cost ? P.pa : nullptr,
-                                   want_cost ? P.sc + kPrCostCam : nullptr, p->stream);
+// What follows a kind's observation pass, in the one order the stacked system is assembled in, written here and
+// nowhere else: the kind's priors, then the zeros of its constant entries with `diag` on the blocks' diagonal.  Asynchronous; nothing
+// is launched for a kind without priors or with nothing constant.  The cameras: A^T A into A9 [n_cam][9][9] = U or M and A^T r
+// into gc (gc, or both, may be NULL); with want_cost the priors' cost into the kPrCostCam scalar ...
+static int stack_cameras(c2b_problem *p, double *A9, double *gc, double diag, bool want_cost) {
+    if ((p->pcw || p->piw) && p->n_cam && (A9 || want_cost)) {
+        const PriorBufs P = prior_bufs(p);
+        const int rc = c2b_prior_cameras_rows(p->camblk, p->n_cam, p->pc0, p->pcw, p->pi0, p->piw, A9, gc, nullptr, nullptr,
+                                               want_cost ? P.pa : nullptr, want_cost ? P.sc + kPrCostCam : nullptr, p->stream);
+        if (rc) return rc;
+    }
+    return A9 && (p->n_obs || has_priors(p)) ? constant_cameras(p, A9, diag, gc) : C2B_OK;
 }
 
-// ... diag(w^2) into V and w o r into gp (both may be NULL), the cost into the kPrCostPts scalar
-static int prior_points(c2b_problem *p, double *V, double *gp, bool want_cost) {
-    if (!p->pxw || !p->n_pts) return C2B_OK;
-    const PriorBufs P = prior_bufs(p);
-    return prior_points_rows_impl(p->pts4, p->n_pts, p->px0, p->pxw, V, gp, nullptr, want_cost ? P.pb : nullptr,
-                                  want_cost ? P.sc + kPrCostPts : nullptr, p->stream);
+// ... the points: diag(w^2) into V and w o r into gp (both may be NULL), the cost into the kPrCostPts scalar
+static int stack_points(c2b_problem *p, double *V, double *gp, double diag, bool want_cost) {
+    if (p->pxw && p->n_pts && (V || want_cost)) {
+        const PriorBufs P = prior_bufs(p);
+        const int rc = c2b_prior_points_rows(p->pts4, p->n_pts, p->px0, p->pxw, V, gp, nullptr, want_cost ? P.pb : nullptr,
+                                              want_cost ? P.sc + kPrCostPts : nullptr, p->stream);
+        if (rc) return rc;
+    }
+    return V && (p->n_obs || has_priors(p)) ? constant_points(p, V, diag, gp) : C2B_OK;
 }
 
-// the two costs queued to host[2] (asynchronous: valid after the stream is synchronised); prior_cost_of adds them
+// the two costs queued to host[2] (asynchronous: valid after the stream is synchronised); the priors' cost is their sum
 static int prior_cost_queue(c2b_problem *p, double host[2]) {
     host[0] = host[1] = 0.0;
     const PriorBufs P = prior_bufs(p);
@@ -211,7 +219,6 @@ static int prior_cost_queue(c2b_problem *p, double host[2]) {
     if (p->pxw && p->n_pts) HIP_TRY(hipMemcpyAsync(host + 1, P.sc + kPrCostPts, sizeof(double), hipMemcpyDeviceToHost, p->stream));
     return C2B_OK;
 }
-static double prior_cost_of(const double host[2]) { return host[0] + host[1]; }
 
 int c2b_problem_prior_cost(c2b_problem *p, double *cost) {
     C2B_API_BEGIN
@@ -221,12 +228,12 @@ int c2b_problem_prior_cost(c2b_problem *p, double *cost) {
     if (!has_priors(p)) return C2B_OK;
     double h[2];
     int rc = ensure_camblk(p);
-    if (!rc) rc = prior_cameras(p, nullptr, nullptr, true);
-    if (!rc) rc = prior_points(p, nullptr, nullptr, true);
+    if (!rc) rc = stack_cameras(p, nullptr, nullptr, 0.0, true);
+    if (!rc) rc = stack_points(p, nullptr, nullptr, 0.0, true);
     if (!rc) rc = prior_cost_queue(p, h);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(p->stream));
-    *cost = prior_cost_of(h);
+    *cost = h[0] + h[1];
     return C2B_OK;
     C2B_API_END("problem_prior_cost")
 }
@@ -249,13 +256,13 @@ int c2b_problem_prior_residual_jacobian(c2b_problem *p, double *r_cam, double *A
     if (cams) {
         HIP_TRY(d_r.alloc(6 * (size_t)nc));
         HIP_TRY(d_A.alloc(18 * (size_t)nc));
-        rc = prior_cameras_rows_impl(p->camblk, nc, p->pc0, p->pcw, p->pi0, p->piw, nullptr, nullptr, d_r, d_A, nullptr, nullptr, st);
+        rc = c2b_prior_cameras_rows(p->camblk, nc, p->pc0, p->pcw, p->pi0, p->piw, nullptr, nullptr, d_r, d_A, nullptr, nullptr, st);
         if (!rc && r_cam) HIP_TRY(hipMemcpyAsync(r_cam, d_r, sizeof(double) * 6 * (size_t)nc, hipMemcpyDeviceToHost, st));
         if (!rc && A_cam) HIP_TRY(hipMemcpyAsync(A_cam, d_A, sizeof(double) * 18 * (size_t)nc, hipMemcpyDeviceToHost, st));
     }
     if (!rc && pts) {
         HIP_TRY(d_rp.alloc(3 * (size_t)np));
-        rc = prior_points_rows_impl(p->pts4, np, p->px0, p->pxw, nullptr, nullptr, d_rp, nullptr, nullptr, st);
+        rc = c2b_prior_points_rows(p->pts4, np, p->px0, p->pxw, nullptr, nullptr, d_rp, nullptr, nullptr, st);
         if (!rc) HIP_TRY(hipMemcpyAsync(r_pt, d_rp, sizeof(double) * 3 * (size_t)np, hipMemcpyDeviceToHost, st));
     }
     const hipError_t es = hipStreamSynchronize(st);                  // (the temporaries are freed on return)
@@ -317,19 +324,8 @@ int c2b_problem_preconditioner_fallbacks(const c2b_problem *p, int64_t *n) {
 static int robust_sum(c2b_problem *p, bool weighted_sq, double *out) {
     const int rc = ensure_camblk(p);
     if (rc) return rc;
-    static_assert(kNormBlock == 256, "k_robust_cost's partials are sized by block_part_slots");
-    const unsigned nb = blocks_for(p->n_obs, kNormBlock);
-    double *part = reinterpret_cast<double *>(p->ws.ptr) + kWsBlockPart;
-    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4.ptr);
-    const double2 *uv = reinterpret_cast<const double2 *>(p->uv.ptr);
-    const double a2 = p->loss_scale * p->loss_scale;
-    if (weighted_sq)
-        hipLaunchKernelGGL(k_robust_cost<true>, dim3(nb), dim3(kNormBlock), 0, p->stream, p->camblk, p4, (const uint32_t *)p->cam_idx,
-                           (const uint64_t *)nullptr, 0, (const uint32_t *)p->pt_idx, uv, p->n_obs, p->loss_kind, a2, part);
-    else
-        hipLaunchKernelGGL(k_robust_cost<false>, dim3(nb), dim3(kNormBlock), 0, p->stream, p->camblk, p4, (const uint32_t *)p->cam_idx,
-                           (const uint64_t *)nullptr, 0, (const uint32_t *)p->pt_idx, uv, p->n_obs, p->loss_kind, a2, part);
-    fold_sum(p->stream, part, (int)nb, out);
+    launch_robust_cost(p->stream, weighted_sq, p->camblk, p->pts4, p->cam_idx, nullptr, 0, p->pt_idx, p->uv, p->n_obs, p->loss_kind,
+                       p->loss_scale, reinterpret_cast<double *>(p->ws.ptr) + kWsBlockPart, out);
     HIP_TRY(launch_error());
     return C2B_OK;
 }
@@ -349,6 +345,47 @@ int c2b_problem_robust_cost(c2b_problem *p, double *cost) {
     C2B_API_END("problem_robust_cost")
 }
 
+// ---- the stacked system: a kind's observation pass (zeros without a list), then stack_cameras / stack_points ----
+// The camera side: U and gc (both NULL: the cost alone).  want_cost: the observations' sum of squares (weighted under a
+// loss) into p->scalar and the camera priors' cost into its scalar (prior_cost_queue).  After ensure_camblk and ensure_rows.
+static int assemble_cameras(c2b_problem *p, double *U, double *gc, double diag, bool want_cost) {
+    hipStream_t st = S(p->stream);
+    if (!U && !want_cost) return C2B_OK;
+    if (!p->n_obs) {                                         // no list: every camera's block is empty
+        if (U && p->n_cam) {
+            HIP_TRY(hipMemsetAsync(U, 0, sizeof(double) * 81 * (size_t)p->n_cam, st));
+            HIP_TRY(hipMemsetAsync(gc, 0, sizeof(double) * 9 * (size_t)p->n_cam, st));
+        }
+        if (want_cost) HIP_TRY(hipMemsetAsync(p->scalar, 0, sizeof(double), st));
+    } else if (U) {
+        launch_normal_cameras(st, p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->pt_idx, p->uv, p->n_obs, U, gc, p->ws,
+                              want_cost ? p->scalar.ptr : nullptr, p->loss_kind, p->loss_scale);
+        LAUNCH_CHECK();
+    } else {                                                 // the (weighted) sum of squares without the blocks
+        const int rc = p->loss_kind != kLossSquared
+                           ? robust_sum(p, true, p->scalar)
+                           : c2b_reprojection_error_sum_rows(p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->rows_tiles, p->pt_idx, p->uv,
+                                                             p->n_obs, 2.0, p->ws, p->scalar, st);
+        if (rc) return rc;
+    }
+    return stack_cameras(p, U, gc, diag, want_cost);
+}
+
+// The point side: V and gp (both NULL: the cost alone, of the point priors)
+static int assemble_points(c2b_problem *p, double *V, double *gp, double diag, bool want_cost) {
+    hipStream_t st = S(p->stream);
+    if (!p->n_pts || (!V && !want_cost)) return C2B_OK;
+    if (V && p->n_obs) {
+        if (const int rc = ensure_transpose(p)) return rc;
+        launch_normal_points(st, p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, V, gp, p->loss_kind, p->loss_scale);
+        LAUNCH_CHECK();
+    } else if (V) {
+        HIP_TRY(hipMemsetAsync(V, 0, sizeof(double) * 9 * (size_t)p->n_pts, st));
+        HIP_TRY(hipMemsetAsync(gp, 0, sizeof(double) * 3 * (size_t)p->n_pts, st));
+    }
+    return stack_points(p, V, gp, diag, want_cost);
+}
+
 int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *V, double *gp, double *sum_sq) {
     C2B_API_BEGIN
     if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: problem is NULL");
@@ -356,57 +393,16 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
     for (const void *q : {(const void *)U, (const void *)gc, (const void *)V, (const void *)gp, (const void *)sum_sq})
         if (reinterpret_cast<uintptr_t>(q) & 7) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_normal_equations: misaligned pointer");
     NEED_UPLOADED(p, "problem_normal_equations");
+    const bool want_sum = sum_sq != nullptr, pri = has_priors(p);
     int rc = ensure_camblk(p);
     if (!rc) rc = ensure_rows(p);
+    if (!rc) rc = assemble_cameras(p, U, gc, 0.0, want_sum);
+    if (!rc) rc = assemble_points(p, V, gp, 0.0, want_sum);
+    double s = 0.0, hp[2] = {0.0, 0.0};                      // the priors' cost joins sum_sq
+    if (!rc && pri && want_sum) rc = prior_cost_queue(p, hp);
+    if (!rc) rc = scalars_to_host(p->stream, p->scalar, want_sum ? 1 : 0, &s);
     if (rc) return rc;
-    const bool want_sum = sum_sq != nullptr;
-    // priors: after a kind's pass and before its constant zeros; their cost joins sum_sq.  None in force:
-    // every call below that names them returns without a launch
-    const bool pri = has_priors(p);
-    if (U) {
-        rc = normal_cameras_rows_impl(p->camblk, p->pts4, p->n_obs ? p->rows_ptr : nullptr, p->n_obs ? p->n_cam : 0, p->pt_idx, p->uv,
-                                      p->n_obs, U, gc, want_sum ? p->ws : nullptr, want_sum ? p->scalar : nullptr, p->loss_kind,
-                                      p->loss_scale, p->stream);
-        if (!rc && !p->n_obs && p->n_cam) {                   // no list: every camera's block is empty
-            HIP_TRY(hipMemsetAsync(U, 0, sizeof(double) * 81 * (size_t)p->n_cam, p->stream));
-            HIP_TRY(hipMemsetAsync(gc, 0, sizeof(double) * 9 * (size_t)p->n_cam, p->stream));
-        }
-        if (!rc && pri) rc = prior_cameras(p, U, gc, want_sum);
-        if (!rc && (p->n_obs || pri)) rc = constant_cameras(p, U, 0.0, gc);
-    } else if (want_sum && p->loss_kind != kLossSquared && p->n_obs) {
-        rc = robust_sum(p, true, p->scalar);                 // the weighted sum of squares without the blocks
-    } else if (want_sum) {
-        rc = p->n_obs ? c2b_reprojection_error_sum_rows(p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->rows_tiles, p->pt_idx, p->uv,
-                                                        p->n_obs, 2.0, p->ws, p->scalar, p->stream)
-                      : (hipMemsetAsync(p->scalar, 0, sizeof(double), p->stream) == hipSuccess ? C2B_OK
-                                                                                             : fail(C2B_ERR_HIP, "problem_normal_equations: memset"));
-    }
-    if (!rc && pri && !U && want_sum) rc = prior_cameras(p, nullptr, nullptr, true);      // the cost without the blocks
-    if (rc) return rc;
-    if (V && p->n_pts) {
-        if (p->n_obs) {
-            rc = ensure_transpose(p);
-            if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, V, gp, p->loss_kind,
-                                                  p->loss_scale, p->stream);
-            if (!rc && pri) rc = prior_points(p, V, gp, want_sum);
-            if (!rc) rc = constant_points(p, V, 0.0, gp);
-            if (rc) return rc;
-        } else {
-            HIP_TRY(hipMemsetAsync(V, 0, sizeof(double) * 9 * (size_t)p->n_pts, p->stream));
-            HIP_TRY(hipMemsetAsync(gp, 0, sizeof(double) * 3 * (size_t)p->n_pts, p->stream));
-            if (pri) {
-                rc = prior_points(p, V, gp, want_sum);
-                if (!rc) rc = constant_points(p, V, 0.0, gp);
-                if (rc) return rc;
-            }
-        }
-    } else if (pri && want_sum) {
-        if ((rc = prior_points(p, nullptr, nullptr, true))) return rc;
-    }
-    double s = 0.0, hp[2] = {0.0, 0.0};
-    if (pri && want_sum && (rc = prior_cost_queue(p, hp))) return rc;
-    if ((rc = scalars_to_host(p->stream, p->scalar, want_sum ? 1 : 0, &s))) return rc;
-    if (want_sum) *sum_sq = pri ? s + prior_cost_of(hp) : s;
+    if (want_sum) *sum_sq = pri ? s + (hp[0] + hp[1]) : s;
     return C2B_OK;
     C2B_API_END("problem_normal_equations")
 }
@@ -453,6 +449,122 @@ static int ensure_solver(c2b_problem *p) {
     return C2B_OK;
 }
 
+// ---- the phases of c2b_problem_solve_step, in the order it runs them (the set-up is the stacked system above) -----------
+// The Schur operator's application, written once: the point pass t = +-V_l^-1 (hp + W^T x) with t = 0 for the constant
+// points, then -- y given -- the camera pass over t in the mode its pointers name (launch_schur_cameras) and y's constant
+// entries to 0.  Asynchronous; the right-hand side, the iteration and the back-substitution are calls of it.
+static int schur_apply(c2b_problem *p, const SolveBufs &B, double lambda, const double *x, const double *hp, double *t, bool neg,
+                       const double *hc, double *y, double *part) {
+    launch_schur_points(p->stream, p->camblk, p->pts4, p->n_pts, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, lambda, x, hp, t, neg,
+                        p->loss_kind, p->loss_scale);
+    const int rc = constant_points(p, nullptr, 0.0, t);
+    if (rc || !y) return rc;
+    launch_schur_cameras(p->stream, p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->pt_idx, p->uv, B.U, lambda, x, hc, t, y, part,
+                         p->loss_kind, p->loss_scale);
+    return constant_cameras(p, nullptr, 0.0, y);
+}
+
+// The preconditioner's factors Lf: of U_l's blocks, or (B.M) of the Schur-Jacobi blocks M with the fallbacks' count queued.
+// k_schur_jacobi sums M from the observations, not from U, so the camera priors and the constant zeros follow it as they
+// follow the camera pass (stack_cameras).  It sees the constant points' V as kConstPointV, under which their observations
+// add Jc^T Jc as they do with Jp = 0; from here on that V is 0.
+static int step_preconditioner(c2b_problem *p, const SolveBufs &B, double lambda) {
+    hipStream_t st = p->stream;
+    const int64_t nc = p->n_cam;
+    const unsigned nbc = blocks_for(nc, kSchurBlock);
+    if (!B.M) {
+        hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
+        return C2B_OK;
+    }
+    launch_schur_jacobi(st, p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, B.U, B.V, lambda, B.M, p->loss_kind, p->loss_scale);
+    int rc = stack_cameras(p, B.M, nullptr, lambda * 1e-6, false);
+    if (!rc) rc = constant_points(p, B.V, 0.0, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_schur_factor_blocks, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.M, (const double *)B.U, lambda,
+                       B.Lf, B.pa);
+    fold_sum(st, B.pa, (int)nbc, B.sc + kScFallback);
+    return C2B_OK;
+}
+
+// PCG on the reduced system from x = 0 (x is dc), its right-hand side b in B.r: the iterations run, the status (0 converged,
+// 1 max_iters reached, 2 a breakdown or a non-finite number), |b|^2 and the last |r|.  One read-back per iteration.
+struct PcgResult {
+    int iterations, status;
+    double bb, rnorm;
+};
+static int schur_pcg(c2b_problem *p, const SolveBufs &B, double lambda, int max_iters, double rel_tol, double *dc, PcgResult *res) {
+    hipStream_t st = p->stream;
+    const int64_t nc = p->n_cam;
+    const unsigned nbc = blocks_for(nc, kSchurBlock);
+    double h[kScSlots];                                      // what each read-back brings: the scalars up to kScRz1, after all queued work
+    int rc;
+    hipLaunchKernelGGL(k_pcg_update<true>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc, 0, dc,
+                       B.r, B.pv, (const double *)nullptr, B.z, B.pa, B.pb);
+    fold_sum(st, B.pa, (int)nbc, B.sc + kScRr);
+    fold_sum(st, B.pb, (int)nbc, B.sc + kScRz0);
+    HIP_TRY(launch_error());
+    if ((rc = scalars_to_host(st, B.sc, kScRz1 + 1, h))) return rc;
+    const double bb = h[kScRr], bnorm = std::sqrt(bb);
+    double rnorm = bnorm;
+    int it = 0, status = 1;
+    if (!std::isfinite(bb) || !std::isfinite(h[kScRz0])) {
+        status = 2;
+    } else if (rnorm <= rel_tol * bnorm) {                   // b = 0 (or rel_tol >= 1)
+        status = 0;
+    } else {
+        while (it < max_iters) {
+            const int cur = (it & 1) ? kScRz1 : kScRz0, nxt = (it & 1) ? kScRz0 : kScRz1;
+            // q = S p and the p.q partials (p's constant entries are 0: they need no correction)
+            if ((rc = schur_apply(p, B, lambda, B.pv, nullptr, B.t, false, nullptr, B.q, B.pa))) return rc;
+            fold_sum(st, B.pa, (int)(schur_cameras_grid(nc) * (kNormBlock / 64)), B.sc + kScPq);
+            hipLaunchKernelGGL(k_pcg_update<false>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc,
+                               cur, dc, B.r, B.pv, (const double *)B.q, B.z, B.pa, B.pb);
+            fold_sum(st, B.pa, (int)nbc, B.sc + kScRr);
+            fold_sum(st, B.pb, (int)nbc, B.sc + nxt);
+            HIP_TRY(launch_error());
+            if ((rc = scalars_to_host(st, B.sc, kScRz1 + 1, h))) return rc;
+            const double pq = h[kScPq], rz = h[cur], alpha = rz / pq;
+            if (!(pq > 0.0) || !std::isfinite(alpha)) { status = 2; break; }     // k_pcg_update left x as it was
+            ++it;
+            const double rr = h[kScRr], rzn = h[nxt];
+            if (!std::isfinite(rr) || !std::isfinite(rzn)) { status = 2; break; }
+            rnorm = std::sqrt(rr);
+            if (rnorm <= rel_tol * bnorm) { status = 0; break; }
+            if (it == max_iters) break;
+            hipLaunchKernelGGL(k_pcg_direction, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, rzn / rz,
+                               (const double *)B.z, B.pv);
+        }
+    }
+    *res = PcgResult{it, status, bb, rnorm};
+    return C2B_OK;
+}
+
+// dp = -V_l^-1 (gp + W^T dc); then |r|^2 and the model decrease from J, per observation, and the priors' share of the two
+// sums beside k_schur_model's; the step's last read-back, which also brings the Schur-Jacobi fallbacks' count
+static int step_model(c2b_problem *p, const SolveBufs &B, double lambda, const double *dc, double *dp, double *sum_sq, double *model) {
+    hipStream_t st = p->stream;
+    const bool pri = has_priors(p);
+    int rc = schur_apply(p, B, lambda, dc, B.gp, dp, true, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    launch_schur_model(st, p->camblk, p->pts4, p->cam_idx, p->pt_idx, p->uv, p->n_obs, dc, dp, B.pa, B.pb, B.sc + kScSumSq,
+                       p->loss_kind, p->loss_scale);
+    static_assert(kScModel == kScSumSq + 1, "launch_schur_model folds into two neighbouring scalars");
+    double h[kScSlots], hpr[2] = {0.0, 0.0};
+    if (pri) {
+        const PriorBufs P = prior_bufs(p);
+        if ((rc = c2b_prior_model_rows(p->camblk, p->n_cam, p->pc0, p->pcw, p->pi0, p->piw, p->pts4, p->n_pts, p->px0, p->pxw, dc, dp, P.pa,
+                                        P.pb, P.sc + kPrSumSq, st)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(hpr, P.sc + kPrSumSq, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(launch_error());
+    if ((rc = scalars_to_host(st, B.sc, B.M ? kScFallback + 1 : kScModel + 1, h))) return rc;
+    if (B.M) p->precond_fallbacks = (int64_t)h[kScFallback];
+    *sum_sq = pri ? h[kScSumSq] + hpr[0] : h[kScSumSq];
+    *model = pri ? h[kScModel] + hpr[1] : h[kScModel];
+    return C2B_OK;
+}
+
 int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double rel_tol, double *dc, double *dp, c2b_step_info *info) {
     C2B_API_BEGIN
     if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: problem is NULL");
@@ -468,8 +580,7 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     hipStream_t st = p->stream;
     c2b_step_info out{0, 0, 0.0, 0.0, 0.0};
     p->precond_fallbacks = 0;
-    const bool pri = has_priors(p);
-    if (!no && pri) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: priors without a single observation are not solved (DESIGN 4.13)");
+    if (!no && has_priors(p)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: priors without a single observation are not solved (DESIGN 4.13)");
     if (!no) {                                               // no observation: g = 0, the step is 0
         if (nc) HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
         if (np) HIP_TRY(hipMemsetAsync(dp, 0, sizeof(double) * 3 * (size_t)np, st));
@@ -483,131 +594,19 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     if (!rc) rc = ensure_solver(p);
     if (rc) return rc;
     const SolveBufs B = solve_bufs(p);
-    const double4 *p4 = reinterpret_cast<const double4 *>(p->pts4.ptr);
-    const double2 *uv = reinterpret_cast<const double2 *>(p->uv.ptr);
-    const unsigned cgrid = schur_cameras_grid(nc), nbc = blocks_for(nc, kSchurBlock), nbo = blocks_for(no, kSchurBlock);
-    const int n_cpart = (int)(cgrid * (kNormBlock / 64));
-    const int kind = p->loss_kind;                           // 0: every launch below is the squared-loss kernel it always was
-    const double a2 = p->loss_scale * p->loss_scale;
-    auto points = [&](const double *x, const double *h, double *t, bool neg) {
-        with_loss(kind, a2, [&](auto... loss) {
-            if (neg)
-                hipLaunchKernelGGL((k_schur_points<true, decltype(loss)...>), dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st,
-                                   p->camblk, p4, np, p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, loss...);
-            else
-                hipLaunchKernelGGL((k_schur_points<false, decltype(loss)...>), dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st,
-                                   p->camblk, p4, np, p->nt_ptr, p->nt_obs, p->nt_cam, uv, B.V, lambda, x, h, t, loss...);
-        });
-        if (p->pmask) (void)constant_points(p, nullptr, 0.0, t);        // t = 0 for the constant points (fetch sees a launch error)
-    };
-    auto mask_y = [&](double *y) {                           // after a camera pass: y's constant entries to 0
-        if (p->cmask) (void)constant_cameras(p, nullptr, 0.0, y);
-    };
-    double h[kScSlots];
-    auto fetch = [&](int slots) -> int {                     // the first `slots` scalars to the host, after all queued work
-        HIP_TRY(launch_error());
-        return scalars_to_host(st, B.sc, slots, h);
-    };
-
-    // U, gc, V, gp; the preconditioner; b = -gc + W V_l^-1 gp into r
-    rc = normal_cameras_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.gc, nullptr, nullptr, kind,
-                                  p->loss_scale, st);
-    if (!rc) rc = normal_points_rows_impl(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, B.V, B.gp, kind, p->loss_scale, st);
-    // priors: from here on U, gc, V, gp are those of the stacked system, and so is the damping's diagonal
-    if (!rc && pri) rc = prior_cameras(p, B.U, B.gc, false);
-    if (!rc && pri) rc = prior_points(p, B.V, B.gp, false);
+    // U, gc, V, gp of the stacked system: with priors and constant parameters they are those of J~
+    // from here on, and so is the damping's diagonal.  The constant points' V: see step_preconditioner
+    PcgResult pcg{0, 1, 0.0, 0.0};
+    rc = assemble_cameras(p, B.U, B.gc, 0.0, false);
+    if (!rc) rc = assemble_points(p, B.V, B.gp, B.M ? kConstPointV : 0.0, false);
+    if (!rc) rc = step_preconditioner(p, B, lambda);
+    if (!rc) rc = schur_apply(p, B, lambda, nullptr, B.gp, B.t, false, B.gc, B.r, nullptr);      // b = -gc + W V_l^-1 gp into r
+    if (!rc) rc = schur_pcg(p, B, lambda, max_iters, rel_tol, dc, &pcg);
+    if (!rc) rc = step_model(p, B, lambda, dc, dp, &out.sum_sq, &out.model_decrease);
     if (rc) return rc;
-    const bool schur_jacobi = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI;
-    // constant parameters: from here on U, gc, V, gp are those of J~.  k_schur_jacobi first sees the constant
-    // points' V as kConstPointV, under which their observations add Jc^T Jc as they do with Jp = 0
-    rc = constant_cameras(p, B.U, 0.0, B.gc);
-    if (!rc) rc = constant_points(p, B.V, schur_jacobi ? kConstPointV : 0.0, B.gp);
-    if (rc) return rc;
-    if (schur_jacobi) {                                      // M from U's diagonal and V, its factors, the fallbacks' count
-        rc = schur_jacobi_rows_impl(p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, no, B.U, B.V, lambda, B.M, kind, p->loss_scale, st);
-        if (!rc && pri) rc = prior_cameras(p, B.M, nullptr, false);      // k_schur_jacobi sums M from the observations, not from U
-        if (!rc) rc = constant_cameras(p, B.M, lambda * 1e-6, nullptr);
-        if (!rc) rc = constant_points(p, B.V, 0.0, nullptr);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_schur_factor_blocks, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.M, (const double *)B.U,
-                           lambda, B.Lf, B.pa);
-        fold_sum(st, B.pa, (int)nbc, B.sc + kScFallback);
-    } else {
-        hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
-    }
-    points(nullptr, B.gp, B.t, false);
-    with_loss(kind, a2, [&](auto... loss) {
-        hipLaunchKernelGGL((k_schur_cameras<kSchurRhs, decltype(loss)...>), dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4, p->rows_ptr,
-                           (int)nc, p->pt_idx, uv, (const double *)B.U, lambda, (const double *)nullptr, (const double *)B.gc,
-                           (const double *)B.t, B.r, (double *)nullptr, loss...);
-    });
-    mask_y(B.r);
-    hipLaunchKernelGGL(k_pcg_update<true>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc, 0, dc,
-                       B.r, B.pv, (const double *)nullptr, B.z, B.pa, B.pb);
-    fold_sum(st, B.pa, (int)nbc, B.sc + kScRr);
-    fold_sum(st, B.pb, (int)nbc, B.sc + kScRz0);
-    if ((rc = fetch(kScRz1 + 1))) return rc;
-
-    // PCG from x = 0 (x is dc)
-    const double bb = h[kScRr], bnorm = std::sqrt(bb);
-    double rnorm = bnorm;
-    int it = 0, status = 1;
-    if (!std::isfinite(bb) || !std::isfinite(h[kScRz0])) {
-        status = 2;
-    } else if (rnorm <= rel_tol * bnorm) {                   // b = 0 (or rel_tol >= 1)
-        status = 0;
-    } else {
-        while (it < max_iters) {
-            const int cur = (it & 1) ? kScRz1 : kScRz0, nxt = (it & 1) ? kScRz0 : kScRz1;
-            points(B.pv, nullptr, B.t, false);
-            with_loss(kind, a2, [&](auto... loss) {
-                hipLaunchKernelGGL((k_schur_cameras<kSchurDot, decltype(loss)...>), dim3(cgrid), dim3(kNormBlock), 0, st, p->camblk, p4,
-                                   p->rows_ptr, (int)nc, p->pt_idx, uv, (const double *)B.U, lambda, (const double *)B.pv,
-                                   (const double *)nullptr, (const double *)B.t, B.q, B.pa, loss...);
-            });
-            mask_y(B.q);                                     // p's constant entries are 0: the p.q partials need no correction
-            fold_sum(st, B.pa, n_cpart, B.sc + kScPq);
-            hipLaunchKernelGGL(k_pcg_update<false>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc,
-                               cur, dc, B.r, B.pv, (const double *)B.q, B.z, B.pa, B.pb);
-            fold_sum(st, B.pa, (int)nbc, B.sc + kScRr);
-            fold_sum(st, B.pb, (int)nbc, B.sc + nxt);
-            if ((rc = fetch(kScRz1 + 1))) return rc;
-            const double pq = h[kScPq], rz = h[cur], alpha = rz / pq;
-            if (!(pq > 0.0) || !std::isfinite(alpha)) { status = 2; break; }     // k_pcg_update left x as it was
-            ++it;
-            const double rr = h[kScRr], rzn = h[nxt];
-            if (!std::isfinite(rr) || !std::isfinite(rzn)) { status = 2; break; }
-            rnorm = std::sqrt(rr);
-            if (rnorm <= rel_tol * bnorm) { status = 0; break; }
-            if (it == max_iters) break;
-            hipLaunchKernelGGL(k_pcg_direction, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, rzn / rz,
-                               (const double *)B.z, B.pv);
-        }
-    }
-
-    // dp = -V_l^-1 (gp + W^T dc); then |r|^2 and the model decrease from J, per observation
-    points(dc, B.gp, dp, true);
-    with_loss(kind, a2, [&](auto... loss) {
-        hipLaunchKernelGGL(k_schur_model<decltype(loss)...>, dim3(nbo), dim3(kSchurBlock), 0, st, p->camblk, p4, (const uint32_t *)p->cam_idx,
-                           (const uint32_t *)p->pt_idx, uv, no, (const double *)dc, (const double *)dp, B.pa, B.pb, loss...);
-    });
-    fold_sum(st, B.pa, (int)nbo, B.sc + kScSumSq);
-    fold_sum(st, B.pb, (int)nbo, B.sc + kScModel);
-    double hpr[2] = {0.0, 0.0};                              // the priors' share of the two sums, beside k_schur_model's
-    if (pri) {
-        const PriorBufs P = prior_bufs(p);
-        if ((rc = prior_model_rows_impl(p->camblk, nc, p->pc0, p->pcw, p->pi0, p->piw, p->pts4, np, p->px0, p->pxw, dc, dp, P.pa, P.pb,
-                                        P.sc + kPrSumSq, st)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(hpr, P.sc + kPrSumSq, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    if ((rc = fetch(schur_jacobi ? kScFallback + 1 : kScModel + 1))) return rc;
-    if (schur_jacobi) p->precond_fallbacks = (int64_t)h[kScFallback];
-    out.iterations = it;
-    out.status = status;
-    out.rel_residual = bb == 0.0 ? 0.0 : rnorm / bnorm;
-    out.sum_sq = pri ? h[kScSumSq] + hpr[0] : h[kScSumSq];
-    out.model_decrease = pri ? h[kScModel] + hpr[1] : h[kScModel];
+    out.iterations = pcg.iterations;
+    out.status = pcg.status;
+    out.rel_residual = pcg.bb == 0.0 ? 0.0 : pcg.rnorm / std::sqrt(pcg.bb);
     if (!std::isfinite(out.sum_sq) || !std::isfinite(out.model_decrease) || !std::isfinite(out.rel_residual)) {
         // a factorisation failed (a pivot <= 0 at the damping's low end) and a NaN reached the step: no step at all
         HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
@@ -622,25 +621,35 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     C2B_API_END("problem_solve_step")
 }
 
+// ---- bal9 made the truth (the apply_step / rollback / resect rows of the table above cameras_mutated) -------------------
+// Before bal9 is edited in place: in state mode it becomes to_vec of the cameras, unless it already is (bal9_fresh) ...
+static int bal9_edit_begin(c2b_problem *p) {
+    return p->bal_valid || p->bal9_fresh ? C2B_OK : c2b_cameras_to_bal(p->cam15, p->n_cam, p->bal9, p->stream);
+}
+
+// ... and after the edit returned rc: the cameras from bal9 by the kernel that builds them at upload_bal (the same bits),
+// every cache of the cameras dropped (cameras_mutated), bal9 the truth
+static int bal9_edit_end(c2b_problem *p, int rc) {
+    if (!rc) rc = c2b_cameras_from_bal(p->bal9, p->n_cam, p->cam15, p->stream);
+    cameras_mutated(p);
+    p->bal_valid = true;
+    return rc;
+}
+
 int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
     C2B_API_BEGIN
     NEED_UPLOADED(p, "problem_apply_step");
     if (!aligned8(dc) || !aligned8(dp)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_apply_step: misaligned pointer");
     const int64_t nc = p->n_cam, np = p->n_pts;
     hipStream_t st = p->stream;
-    if (nc) {
-        if (!p->bal_valid && !p->bal9_fresh) {               // state mode: the columns of dc refer to to_vec(cam15)
-            const int rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st);
-            if (rc) return rc;
-        }
-        if (dc && p->cmask)                                  // a constant entry keeps its bits
-            hipLaunchKernelGGL(k_add_free, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc,
-                               (const uint16_t *)p->cmask, p->bal9);
-        else if (dc) hipLaunchKernelGGL(k_add_f64, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc, p->bal9);
-        LAUNCH_CHECK();
-        const int rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
-        if (rc) return rc;
-    }
+    int rc = bal9_edit_begin(p);                             // state mode: the columns of dc refer to to_vec(cam15)
+    if (rc) return rc;
+    if (dc && nc && p->cmask)                                // a constant entry keeps its bits
+        hipLaunchKernelGGL(k_add_free, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc,
+                           (const uint16_t *)p->cmask, p->bal9);
+    else if (dc && nc) hipLaunchKernelGGL(k_add_f64, dim3(blocks_for(9 * nc, kSchurBlock)), dim3(kSchurBlock), 0, st, 9 * nc, dc, p->bal9);
+    LAUNCH_CHECK();
+    if ((rc = bal9_edit_end(p, C2B_OK))) return rc;
     if (dp && np) {
         if (p->pmask)
             hipLaunchKernelGGL(k_points_add_free, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp,
@@ -649,8 +658,6 @@ int c2b_problem_apply_step(c2b_problem *p, const double *dc, const double *dp) {
             hipLaunchKernelGGL(k_points_add, dim3(blocks_for(np, kSchurBlock)), dim3(kSchurBlock), 0, st, np, dp, reinterpret_cast<double4 *>(p->pts4.ptr));
         LAUNCH_CHECK();
     }
-    cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
-    p->bal_valid = true;
     HIP_TRY(hipStreamSynchronize(st));
     return C2B_OK;
     C2B_API_END("problem_apply_step")
@@ -739,16 +746,10 @@ int c2b_problem_resect_cameras(c2b_problem *p, int min_points, double min_gap, u
     const hipError_t e = rep.alloc(nc);
     if (e != hipSuccess) return fail(hip_code(e), "problem_resect_cameras: allocation: %s", hipGetErrorString(e));
     hipStream_t st = p->stream;
-    if (!p->bal_valid && !p->bal9_fresh) {                   // state mode: the pass works on to_vec(cam15)
-        if ((rc = c2b_cameras_to_bal(p->cam15, nc, p->bal9, st))) return rc;
-        p->bal9_fresh = true;
-    }
+    if ((rc = bal9_edit_begin(p))) return rc;                // state mode: the pass works on to_vec(cam15)
     rc = c2b_resect_rows(p->bal9, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, min_points, min_gap, p->cmask, rep.d_status, rep.d_counts, st);
-    if (!rc) rc = c2b_cameras_from_bal(p->bal9, nc, p->cam15, st);
-    rc = rep.read_back("problem_resect_cameras", st, rc, hipSuccess, nc, status, counts);
-    cameras_mutated(p);                                      // every cache of the cameras; then bal9 is the truth
-    p->bal_valid = true;
-    return rc;
+    rc = bal9_edit_end(p, rc);
+    return rep.read_back("problem_resect_cameras", st, rc, hipSuccess, nc, status, counts);
     C2B_API_END("problem_resect_cameras")
 }
 
@@ -779,14 +780,10 @@ int c2b_problem_rollback(c2b_problem *p) {
     NEED_UPLOADED(p, "problem_rollback");
     if (!p->ck_valid) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_rollback: the problem holds no checkpoint");
     hipStream_t st = p->stream;
-    if (p->n_cam) {
-        HIP_TRY(hipMemcpyAsync(p->bal9, p->ck_bal9, sizeof(double) * 9 * (size_t)p->n_cam, hipMemcpyDeviceToDevice, st));
-        const int rc = c2b_cameras_from_bal(p->bal9, p->n_cam, p->cam15, st);      // the kernel that built cam15: the same bits
-        if (rc) return rc;
-    }
+    if (p->n_cam) HIP_TRY(hipMemcpyAsync(p->bal9, p->ck_bal9, sizeof(double) * 9 * (size_t)p->n_cam, hipMemcpyDeviceToDevice, st));
+    const int rc = bal9_edit_end(p, C2B_OK);                 // the cameras' caches only: rows, transpose, solve buffers, masks stay
+    if (rc) return rc;
     if (p->n_pts) HIP_TRY(hipMemcpyAsync(p->pts4, p->ck_pts4, sizeof(double) * 4 * (size_t)p->n_pts, hipMemcpyDeviceToDevice, st));
-    cameras_mutated(p);                                      // the cameras' caches only: rows, transpose, solve buffers, masks stay
-    p->bal_valid = true;
     HIP_TRY(hipStreamSynchronize(st));
     return C2B_OK;
     C2B_API_END("problem_rollback")
