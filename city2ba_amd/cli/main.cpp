@@ -131,6 +131,24 @@ Args parse(int argc, char **argv, int first, const std::vector<std::string> &fla
     return a;
 }
 
+// "a,b,c" -> its tokens, empty ones included ("" is one empty token); what a token must be is the caller's to check
+std::vector<std::string> split_commas(const std::string &s) {
+    std::vector<std::string> tok;
+    for (size_t pos = 0; pos <= s.size();) {
+        const size_t comma = std::min(s.find(',', pos), s.size());
+        tok.push_back(s.substr(pos, comma - pos));
+        pos = comma + 1;
+    }
+    return tok;
+}
+
+// --seed, or the reference's unseeded thread_rng()
+uint64_t seed_of(const Args &a) {
+    if (a.has("seed")) return (uint64_t)a.i("seed", 0);
+    std::random_device rd;
+    return ((uint64_t)rd() << 32) ^ rd();
+}
+
 // The library takes its behaviour switches as c2b_problem_options, not from the environment; this program -- a caller of
 // the C ABI like any other -- keeps its environment variables (README.md) and turns them into those options for every
 // problem it makes.
@@ -163,37 +181,47 @@ struct PhaseTimer {
 };
 
 struct HostProblem {
-    int64_t n_cam = 0, n_pts = 0;
-    std::vector<double> cams15, pts, uv;
+    int64_t n_cam = 0, n_pts = 0, n_obs = 0;
+    std::vector<double> cams15, pts, uv;                                  // each with one spare element, so that data() is never null
     std::vector<uint64_t> row_ptr, pt_idx;
 };
 
 // the resident problem (cameras as in-memory records, points, graph, observations) on the host
 void download_problem(c2b_problem *p, HostProblem &hp) {
-    int64_t n_obs = 0;
-    ck(c2b_problem_sizes(p, &hp.n_cam, &hp.n_pts, &n_obs));
+    ck(c2b_problem_sizes(p, &hp.n_cam, &hp.n_pts, &hp.n_obs));
     hp.cams15.assign((size_t)hp.n_cam * 15 + 1, 0.0);
     hp.pts.assign((size_t)hp.n_pts * 3 + 1, 0.0);
-    hp.uv.assign((size_t)n_obs * 2 + 1, 0.0);
+    hp.uv.assign((size_t)hp.n_obs * 2 + 1, 0.0);
     hp.row_ptr.assign((size_t)hp.n_cam + 1, 0);
-    hp.pt_idx.assign((size_t)n_obs + 1, 0);
+    hp.pt_idx.assign((size_t)hp.n_obs + 1, 0);
     ck(c2b_problem_download(p, hp.cams15.data(), hp.pts.data(), hp.uv.data()));
     ck(c2b_problem_download_graph(p, hp.row_ptr.data(), hp.pt_idx.data()));
-    hp.cams15.resize((size_t)hp.n_cam * 15);
-    hp.pts.resize((size_t)hp.n_pts * 3);
-    hp.uv.resize((size_t)n_obs * 2);
-    hp.pt_idx.resize((size_t)n_obs);
 }
 
-void display_and_write(c2b_problem *p, const HostProblem &hp, const std::string &out) {
-    PhaseTimer timer;
-    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)hp.n_cam,
-                (long long)hp.n_pts, (long long)hp.pt_idx.size());
-    std::vector<double> bal9((size_t)hp.n_cam * 9);
-    ck(c2b_problem_download_bal(p, bal9.data()));
-    timer.mark("to_vec + download");
-    ck(c2b_bal_write(out.c_str(), hp.n_cam, bal9.data(), hp.n_pts, hp.pts.data(), hp.row_ptr.data(), hp.pt_idx.data(), hp.uv.data()));
-    timer.mark("write");
+// the report lines: BAProblem's Display, and run_noise's three (src/bin/city2ba.rs:283-287, :342-354)
+void print_problem(int64_t n_cam, int64_t n_pts, int64_t n_obs) {
+    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)n_cam, (long long)n_pts, (long long)n_obs);
+}
+void print_initial_error(double l1, double l2) { std::printf("Initial error: %s (L1) %s (L2)\n", sci2(l1).c_str(), sci2(l2).c_str()); }
+void print_correspondences(int64_t n_cam, int64_t n_pts, int64_t n_obs) {
+    std::printf("BA Problem with %lld cameras, %lld points, %lld correspondences\n", (long long)n_cam, (long long)n_pts, (long long)n_obs);
+}
+void print_final_error(double l1, double l2) { std::printf("Final error: %s (L1) %s (L2)\n", sci2(l1).c_str(), sci2(l2).c_str()); }
+
+// A problem on `device` decoded from `file` there; and its end: written to `file` from the device, destroyed.
+c2b_problem *read_problem(PhaseTimer &timer, int device, const std::string &file) {
+    c2b_problem *p = nullptr;
+    ck(create_problem(device, &p));
+    timer.mark("problem_create (HIP runtime start)");
+    ck(c2b_problem_read(p, file.c_str(), -1));
+    timer.mark("read (c2b_problem_read: decoded on the device)");
+    return p;
+}
+
+void close_problem(PhaseTimer &timer, c2b_problem *p, const std::string &file) {
+    ck(c2b_problem_write(p, file.c_str(), -1));
+    timer.mark("write (c2b_problem_write: the file image is built on the device)");
+    c2b_problem_destroy(p);
 }
 
 // synthetic_grid / synthetic_line (src/synthetic.rs:163-300, :313-381) and the tail of their subcommands
@@ -207,7 +235,13 @@ struct Layout {
     double L = 0, inset = 0, cam_h = 0, pt_h = 0, length = 0, point_offset = 0;
 };
 
-void generate_cull_write(c2b_problem *p, const Layout &lay, double max_dist, const std::string &out, PhaseTimer &timer) {
+int generate_cull_write(const Args &a, const Layout &lay) {
+    PhaseTimer timer;
+    c2b_problem *p = nullptr;
+    ck(create_problem((int)a.i("device", 0), &p));
+    timer.mark("problem_create (HIP runtime start)");
+    const double max_dist = a.f("max-dist", 10);
+    const std::string &out = a.positional[0];
     const bool host_route = std::getenv("C2B_HOST_CANDIDATES") != nullptr;
     const bool occlusion = lay.grid;
     const double L = lay.grid ? lay.L : 1.0, inset = lay.grid ? lay.inset : 0.0;
@@ -246,14 +280,20 @@ void generate_cull_write(c2b_problem *p, const Layout &lay, double max_dist, con
         HostProblem hp;
         download_problem(p, hp);
         timer.mark("download");
-        display_and_write(p, hp, out);
-        return;
+        print_problem(hp.n_cam, hp.n_pts, hp.n_obs);
+        std::vector<double> bal9((size_t)hp.n_cam * 9);
+        ck(c2b_problem_download_bal(p, bal9.data()));
+        timer.mark("to_vec + download");
+        ck(c2b_bal_write(out.c_str(), hp.n_cam, bal9.data(), hp.n_pts, hp.pts.data(), hp.row_ptr.data(), hp.pt_idx.data(), hp.uv.data()));
+        timer.mark("write");
+        c2b_problem_destroy(p);
+    } else {
+        int64_t nc = 0, np = 0, no = 0;
+        ck(c2b_problem_sizes(p, &nc, &np, &no));
+        print_problem(nc, np, no);
+        close_problem(timer, p, out);
     }
-    int64_t nc = 0, np = 0, no = 0;
-    ck(c2b_problem_sizes(p, &nc, &np, &no));
-    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
-    ck(c2b_problem_write(p, out.c_str(), -1));
-    timer.mark("write (c2b_problem_write: the file image is built on the device)");
+    return 0;
 }
 
 int run_synthetic(int argc, char **argv) {
@@ -264,13 +304,7 @@ int run_synthetic(int argc, char **argv) {
     lay.cpb = a.i("cameras-per-block", 10); lay.ppb = a.i("points-per-block", 10); lay.blocks = a.i("blocks", 5);
     lay.cam_h = a.f("camera-height", 1); lay.pt_h = a.f("point-height", 1);
     lay.inset = a.f("block-inset", 1); lay.L = a.f("block-length", 20);
-    PhaseTimer timer;
-    c2b_problem *p = nullptr;
-    ck(create_problem((int)a.i("device", 0), &p));
-    timer.mark("problem_create (HIP runtime start)");
-    generate_cull_write(p, lay, a.f("max-dist", 10), a.positional[0], timer);
-    c2b_problem_destroy(p);
-    return 0;
+    return generate_cull_write(a, lay);
 }
 
 int run_synthetic_line(int argc, char **argv) {
@@ -282,13 +316,135 @@ int run_synthetic_line(int argc, char **argv) {
     lay.n_cam = a.i("cameras", 10); lay.n_pts = a.i("points", 10);
     lay.length = a.f("length", 20); lay.point_offset = a.f("point-offset", 1);
     lay.cam_h = a.f("camera-height", 1); lay.pt_h = a.f("point-height", 1);
-    PhaseTimer timer;
-    c2b_problem *p = nullptr;
-    ck(create_problem((int)a.i("device", 0), &p));
-    timer.mark("problem_create (HIP runtime start)");
-    generate_cull_write(p, lay, a.f("max-dist", 10), a.positional[0], timer);
-    c2b_problem_destroy(p);
-    return 0;
+    return generate_cull_write(a, lay);
+}
+
+// Every option of `noise`, converted before a device exists or the input is opened; a worker thread sees only this.  (Not
+// looked at, as no route reads it: --sin-frequency without --sin-strength, --gpus beside --devices, --device when sharded.)
+struct NoiseOptions {
+    uint64_t seed = 0;
+    double drop = 1, join = 0, split = 0, mismatch = 0, drift_strength = 0, drift_angle = 0, drift_std = 0, sin_strength = 0, sin_frequency = 1;
+    double translation_std = 0, rotation_std = 0, point_std = 0, observation_std = 0;
+    bool fixed_drift = false;
+    int device = 0;                // the GPU of the unsharded routes
+    std::vector<int> devices;      // --gpus N / --devices a,b,...: the sharded route when not empty
+    bool reshapes() const { return drop < 1.0 || join > 0.0 || split > 0.0; }
+};
+
+NoiseOptions noise_options(const Args &a) {
+    NoiseOptions o;
+    o.seed = seed_of(a);
+    o.drop = a.f("drop-features", 1.0); o.join = a.f("join-landmarks", 0.0); o.split = a.f("split-landmarks", 0.0);
+    o.mismatch = a.f("mismatch-chance", 0.0);
+    o.fixed_drift = a.has("fixed-drift");
+    o.drift_strength = a.f("drift-strength", 0); o.drift_angle = a.f("drift-angle", 0); o.drift_std = a.f("drift-std", 0);
+    o.sin_strength = a.f("sin-strength", 0);
+    if (o.sin_strength > 0.0) o.sin_frequency = a.f("sin-frequency", 1);
+    o.translation_std = a.f("translation-std", 0); o.rotation_std = a.f("rotation-std", 0);
+    o.point_std = a.f("point-std", 0); o.observation_std = a.f("observation-std", 0);
+    if (!a.has("devices") && !a.has("gpus")) {
+        o.device = (int)a.i("device", 0);
+        return o;
+    }
+    if (!a.has("devices"))
+        for (int64_t k = 0; k < a.i("gpus", 1); ++k) o.devices.push_back((int)k);
+    else
+        for (const std::string &tok : split_commas(a.opt.at("devices"))) {
+            char *end = nullptr;
+            const long v = std::strtol(tok.c_str(), &end, 10);
+            if (tok.empty() || *end || v < 0) die("Invalid value for '--devices <devices>': expected a,b,c");
+            o.devices.push_back((int)v);
+        }
+    if (o.devices.size() < 1 || o.devices.size() > 64) die("Invalid value for '--gpus <gpus>': expected 1..64");
+    return o;
+}
+
+// A problem on the host as a .bal holds it: cameras as 9-vectors, points, the camera-major observation list.
+struct HostBal {
+    int64_t n_cam = 0, n_pts = 0, n_obs = 0;
+    size_t pts_cap = 0;            // points `pts` has room for: split_landmarks appends
+    std::vector<double> bal9, pts, uv;
+    std::vector<uint64_t> row_ptr, pt_idx;
+};
+
+HostBal read_bal(const std::string &path, double split = 0.0) {
+    HostBal h;
+    c2b_balfile *f = nullptr;
+    ck(c2b_bal_read(path.c_str(), &f));
+    ck(c2b_bal_sizes(f, &h.n_cam, &h.n_pts, &h.n_obs));
+    h.pts_cap = (size_t)h.n_pts + (split > 0.0 ? (size_t)(std::min(split, 1.0) * (double)h.n_pts) + 1 : 0);
+    h.bal9.resize((size_t)h.n_cam * 9 + 1); h.pts.resize(h.pts_cap * 3 + 1); h.uv.resize((size_t)h.n_obs * 2 + 1);
+    h.row_ptr.resize((size_t)h.n_cam + 1); h.pt_idx.resize((size_t)h.n_obs + 1);
+    ck(c2b_bal_copy(f, h.bal9.data(), h.pts.data(), h.row_ptr.data(), h.pt_idx.data(), h.uv.data()));
+    c2b_bal_close(f);
+    return h;
+}
+
+int upload_bal(c2b_problem *p, const HostBal &h) {
+    return c2b_problem_upload_bal(p, h.n_cam, h.bal9.data(), h.n_pts, h.pts.data(), h.row_ptr.data(), h.pt_idx.data(), h.uv.data());
+}
+void write_bal(const std::string &path, const HostBal &h) {
+    ck(c2b_bal_write(path.c_str(), h.n_cam, h.bal9.data(), h.n_pts, h.pts.data(), h.row_ptr.data(), h.pt_idx.data(), h.uv.data()));
+}
+
+// The index-corruption passes on the host arrays, each followed by cull() (src/bin/city2ba.rs:288-303); camera rows stay
+// 9-vectors (cull treats them as opaque).  Returns whether anything was reshaped.
+bool reshape(HostBal &h, const NoiseOptions &o) {
+    bool reshaped = false;
+    auto cull = [&]() {
+        ck(c2b_cull(&h.n_cam, h.bal9.data(), 9, &h.n_pts, h.pts.data(), h.row_ptr.data(), h.pt_idx.data(), h.uv.data(), 1));
+        h.n_obs = (int64_t)h.row_ptr[(size_t)h.n_cam];
+        reshaped = true;
+    };
+    if (o.drop < 1.0) {
+        ck(c2b_drop_features(h.n_cam, h.row_ptr.data(), h.pt_idx.data(), h.uv.data(), o.drop, o.seed + 2));
+        cull();
+    }
+    if (o.join > 0.0) {
+        // the reference passes opt.split_landmarks as the fraction here (src/bin/city2ba.rs:296)
+        ck(c2b_join_landmarks(h.n_pts, h.pts.data(), (int64_t)h.row_ptr[(size_t)h.n_cam], h.pt_idx.data(), o.split, o.seed + 3));
+        cull();
+    }
+    if (o.split > 0.0) {
+        ck(c2b_split_landmarks(&h.n_pts, h.pts.data(), (int64_t)h.pts_cap, (int64_t)h.row_ptr[(size_t)h.n_cam], h.pt_idx.data(), o.split, o.seed + 4));
+        cull();
+    }
+    // (the sharded route refuses an empty input here as well: there is nothing to cut into ranges)
+    if ((reshaped || !o.devices.empty()) && (h.n_cam == 0 || h.n_pts == 0)) die("EmptyProblem: nothing remains after culling");
+    return reshaped;
+}
+
+// add_incorrect_correspondences on the host arrays (src/bin/city2ba.rs:341)
+void scramble(HostBal &h, const NoiseOptions &o) {
+    ck(c2b_add_incorrect_correspondences(h.n_cam, h.row_ptr.data(), h.pt_idx.data(), h.uv.data(), o.mismatch, o.seed + 5));
+}
+
+// The arithmetic chain of run_noise on one problem (comm == nullptr) or on one shard of it (the collective *_sharded
+// entries).  Returns the first failing call's status and never dies: shard workers call it.
+int perturb(c2b_problem *p, c2b_comm *comm, const NoiseOptions &o, double *l1, double *l2) {
+    int rc = C2B_OK;
+    double stats[C2B_STATS_DOUBLES];
+    const double *dir = nullptr;                                         // src/bin/city2ba.rs:305-316: drift is ALWAYS applied, even with zero strength
+    if (o.fixed_drift) {
+        if ((rc = comm ? c2b_problem_stats_sharded(p, comm, stats) : c2b_problem_stats(p, stats))) return rc;
+        dir = stats + 3;
+    }
+    if (comm) rc = c2b_problem_add_drift_sharded(p, comm, o.drift_strength, o.drift_angle, o.drift_std, dir, o.seed);
+    else if (dir) rc = c2b_problem_add_drift(p, o.drift_strength, o.drift_angle, o.drift_std, dir, o.seed);
+    else rc = c2b_problem_add_drift_normalized(p, o.drift_strength, o.drift_angle, o.drift_std, o.seed);
+    if (rc) return rc;
+    if (o.sin_strength > 0.0) {                                          // :318-333
+        const double dx[3] = {1, 0, 0}, dz[3] = {0, 0, 1}, up[3] = {0, 1, 0};
+        for (const double *d : {dx, dz}) {
+            rc = comm ? c2b_problem_add_sin_noise_sharded(p, comm, d, up, o.sin_strength, o.sin_frequency)
+                      : c2b_problem_add_sin_noise(p, d, up, o.sin_strength, o.sin_frequency);
+            if (rc) return rc;
+        }
+    }
+    // :334-340 (always) fused with the final errors of :350-354: the observation pass draws, perturbs, stores, projects
+    // and folds both norms in one launch (per shard).  With --mismatch-chance the errors are evaluated again after the scramble.
+    return comm ? c2b_problem_add_noise_errors_l1_l2_sharded(p, comm, o.translation_std, o.rotation_std, o.point_std, o.observation_std, o.seed + 1, l1, l2)
+                : c2b_problem_add_noise_errors_l1_l2(p, o.translation_std, o.rotation_std, o.point_std, o.observation_std, o.seed + 1, l1, l2);
 }
 
 // `noise --gpus N` (or --devices a,b,...): run_noise (src/bin/city2ba.rs:280-357) with the problem sharded over N GPUs of
@@ -299,27 +455,10 @@ int run_synthetic_line(int argc, char **argv) {
 // collective Level-1 calls (c2b_problem_*_sharded: statistics and errors go through RCCL, c2b_comm_init_all).  Draws
 // are keyed by global indices, so the written file is the same for every N up to rounding: the statistics that scale
 // the perturbations (mean, std) are sums of per-rank shares, whose last bits depend on how the cameras were cut.
-int run_noise_sharded(const Args &a, uint64_t seed, int64_t n_cam, int64_t n_pts, int64_t n_obs, std::vector<double> &bal9,
-                      std::vector<double> &pts, size_t pts_cap, std::vector<double> &uv, std::vector<uint64_t> &row_ptr,
-                      std::vector<uint64_t> &pt_idx) {
-    std::vector<int> devs;
-    if (a.has("devices")) {
-        const std::string &sv = a.opt.at("devices");
-        size_t pos = 0;
-        while (pos <= sv.size()) {
-            const size_t comma = std::min(sv.find(',', pos), sv.size());
-            const std::string tok = sv.substr(pos, comma - pos);
-            char *end = nullptr;
-            const long v = std::strtol(tok.c_str(), &end, 10);
-            if (tok.empty() || *end || v < 0) die("Invalid value for '--devices <devices>': expected a,b,c");
-            devs.push_back((int)v);
-            pos = comma + 1;
-        }
-    } else {
-        for (int64_t k = 0; k < a.i("gpus", 1); ++k) devs.push_back((int)k);
-    }
+// On return `h` holds the noised problem; the caller writes it.
+void run_noise_sharded(const NoiseOptions &o, HostBal &h) {
+    const std::vector<int> &devs = o.devices;
     const int N = (int)devs.size();
-    if (N < 1 || N > 64) die("Invalid value for '--gpus <gpus>': expected 1..64");
     int visible = 0;
     ck(c2b_device_count(&visible));
     for (int d : devs) if (d >= visible) die("--gpus / --devices: device " + std::to_string(d) + " is not visible (" + std::to_string(visible) + " devices)");
@@ -334,19 +473,19 @@ int run_noise_sharded(const Args &a, uint64_t seed, int64_t n_cam, int64_t n_pts
     // error, download.
     auto pass = [&](bool with_initial, bool with_noise) {
         std::vector<int64_t> bounds((size_t)N + 1);
-        ck(c2b_partition_cameras(row_ptr.data(), n_cam, N, bounds.data()));
+        ck(c2b_partition_cameras(h.row_ptr.data(), h.n_cam, N, bounds.data()));
         int nonempty = 0;
         for (int k = 0; k < N; ++k) nonempty += bounds[(size_t)k + 1] > bounds[(size_t)k];
         if (nonempty < N)
-            die("--gpus " + std::to_string(N) + ": the problem's " + std::to_string(n_cam) + " cameras (" + std::to_string(n_obs) +
+            die("--gpus " + std::to_string(N) + ": the problem's " + std::to_string(h.n_cam) + " cameras (" + std::to_string(h.n_obs) +
                 " observations) cut into only " + std::to_string(nonempty) + " non-empty ranges; use --gpus " + std::to_string(std::max(1, nonempty)));
         std::vector<std::string> failures((size_t)N);
         if (with_noise) {
             std::fprintf(stderr, "noise on %d GPU%s through %s; observations per GPU:", N, N == 1 ? "" : "s", c2b_comm_backend());
             for (int k = 0; k < N; ++k)
-                std::fprintf(stderr, " %llu", (unsigned long long)(row_ptr[(size_t)bounds[(size_t)k + 1]] - row_ptr[(size_t)bounds[(size_t)k]]));
+                std::fprintf(stderr, " %llu", (unsigned long long)(h.row_ptr[(size_t)bounds[(size_t)k + 1]] - h.row_ptr[(size_t)bounds[(size_t)k]]));
             std::fprintf(stderr, "\n");
-            pts_out.assign((size_t)n_pts * 3 + 1, 0.0);
+            pts_out.assign((size_t)h.n_pts * 3 + 1, 0.0);
         }
         std::vector<std::thread> workers;
         for (int k = 0; k < N; ++k) {
@@ -357,13 +496,13 @@ int run_noise_sharded(const Args &a, uint64_t seed, int64_t n_cam, int64_t n_pts
                 auto ck = [&](int rc) { if (rc != C2B_OK) throw std::runtime_error(c2b_last_error()); };
                 try {
                 const int64_t lo = bounds[(size_t)k], hi = bounds[(size_t)k + 1], nc = hi - lo;
-                const uint64_t o0 = row_ptr[(size_t)lo];
+                const uint64_t o0 = h.row_ptr[(size_t)lo];
                 std::vector<uint64_t> rp((size_t)nc + 1);
-                for (int64_t c = 0; c <= nc; ++c) rp[(size_t)c] = row_ptr[(size_t)(lo + c)] - o0;
+                for (int64_t c = 0; c <= nc; ++c) rp[(size_t)c] = h.row_ptr[(size_t)(lo + c)] - o0;
                 c2b_problem *p = nullptr;
                 ck(create_problem(devs[(size_t)k], &p));
-                ck(c2b_problem_upload_bal(p, nc, bal9.data() + 9 * lo, n_pts, pts.data(), rp.data(), pt_idx.data() + o0, uv.data() + 2 * o0));
-                ck(c2b_problem_set_shard(p, lo, n_cam, (int64_t)o0));
+                ck(c2b_problem_upload_bal(p, nc, h.bal9.data() + 9 * lo, h.n_pts, h.pts.data(), rp.data(), h.pt_idx.data() + o0, h.uv.data() + 2 * o0));
+                ck(c2b_problem_set_shard(p, lo, h.n_cam, (int64_t)o0));
                 c2b_comm *comm = comms[(size_t)k];
                 double l1, l2;
                 if (with_initial) {           // both norms from one pass, ONE 2-element all-reduce (src/bin/city2ba.rs:283-287)
@@ -371,27 +510,12 @@ int run_noise_sharded(const Args &a, uint64_t seed, int64_t n_cam, int64_t n_pts
                     if (k == 0) { err[0] = l1; err[1] = l2; }
                 }
                 if (with_noise) {
-                    // src/bin/city2ba.rs:305-316: drift is ALWAYS applied, even with zero strength
-                    if (a.has("fixed-drift")) {
-                        double stats[C2B_STATS_DOUBLES];
-                        ck(c2b_problem_stats_sharded(p, comm, stats));
-                        ck(c2b_problem_add_drift_sharded(p, comm, a.f("drift-strength", 0), a.f("drift-angle", 0), a.f("drift-std", 0), stats + 3, seed));
-                    } else {
-                        ck(c2b_problem_add_drift_sharded(p, comm, a.f("drift-strength", 0), a.f("drift-angle", 0), a.f("drift-std", 0), nullptr, seed));
-                    }
-                    if (a.f("sin-strength", 0) > 0.0) {        // :318-333
-                        const double dx[3] = {1, 0, 0}, dz[3] = {0, 0, 1}, up[3] = {0, 1, 0};
-                        ck(c2b_problem_add_sin_noise_sharded(p, comm, dx, up, a.f("sin-strength", 0), a.f("sin-frequency", 1)));
-                        ck(c2b_problem_add_sin_noise_sharded(p, comm, dz, up, a.f("sin-strength", 0), a.f("sin-frequency", 1)));
-                    }
-                    // :334-340 (always) and :350-354: the observation pass and both final errors in one launch per shard
-                    ck(c2b_problem_add_noise_errors_l1_l2_sharded(p, comm, a.f("translation-std", 0), a.f("rotation-std", 0),
-                                                                  a.f("point-std", 0), a.f("observation-std", 0), seed + 1, &l1, &l2));
+                    ck(perturb(p, comm, o, &l1, &l2));
                     if (k == 0) { err[2] = l1; err[3] = l2; }
                     // every shard's cameras and observations go back to their rows of the host arrays; the points
                     // (identical on every GPU) come from rank 0
-                    ck(c2b_problem_download(p, nullptr, k == 0 ? pts_out.data() : nullptr, uv.data() + 2 * o0));
-                    ck(c2b_problem_download_bal(p, bal9.data() + 9 * lo));
+                    ck(c2b_problem_download(p, nullptr, k == 0 ? pts_out.data() : nullptr, h.uv.data() + 2 * o0));
+                    ck(c2b_problem_download_bal(p, h.bal9.data() + 9 * lo));
                 }
                 c2b_problem_destroy(p);
                 } catch (const std::exception &e) { failures[(size_t)k] = e.what(); }
@@ -404,46 +528,24 @@ int run_noise_sharded(const Args &a, uint64_t seed, int64_t n_cam, int64_t n_pts
 
     // host-side index corruption + cull, exactly as in the single-GPU path (src/bin/city2ba.rs:288-303): the reference
     // prints the initial error BEFORE these passes, so when any of them is requested the problem visits the GPUs twice
-    const double split = a.f("split-landmarks", 0.0);
-    const bool reshapes = a.f("drop-features", 1.0) < 1.0 || a.f("join-landmarks", 0.0) > 0.0 || split > 0.0;
-    if (reshapes) pass(true, false);
-    auto cull = [&]() {
-        ck(c2b_cull(&n_cam, bal9.data(), 9, &n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data(), 1));
-        n_obs = (int64_t)row_ptr[(size_t)n_cam];
-    };
-    if (a.f("drop-features", 1.0) < 1.0) {
-        ck(c2b_drop_features(n_cam, row_ptr.data(), pt_idx.data(), uv.data(), a.f("drop-features", 1.0), seed + 2));
-        cull();
-    }
-    if (a.f("join-landmarks", 0.0) > 0.0) {
-        ck(c2b_join_landmarks(n_pts, pts.data(), (int64_t)row_ptr[(size_t)n_cam], pt_idx.data(), split, seed + 3));
-        cull();
-    }
-    if (split > 0.0) {
-        ck(c2b_split_landmarks(&n_pts, pts.data(), (int64_t)pts_cap, (int64_t)row_ptr[(size_t)n_cam], pt_idx.data(), split, seed + 4));
-        cull();
-    }
-    if (n_cam == 0 || n_pts == 0) die("EmptyProblem: nothing remains after culling");
-    pass(!reshapes, true);
+    if (o.reshapes()) pass(true, false);
+    reshape(h, o);
+    pass(!o.reshapes(), true);
     for (c2b_comm *c : comms) c2b_comm_destroy(c);
-    std::copy(pts_out.begin(), pts_out.begin() + (size_t)n_pts * 3, pts.begin());
-    std::printf("Initial error: %s (L1) %s (L2)\n", sci2(err[0]).c_str(), sci2(err[1]).c_str());
-    if (a.f("mismatch-chance", 0.0) > 0.0)                               // :341, on the noised image positions (host arrays)
-        ck(c2b_add_incorrect_correspondences(n_cam, row_ptr.data(), pt_idx.data(), uv.data(), a.f("mismatch-chance", 0.0), seed + 5));
-    std::printf("BA Problem with %lld cameras, %lld points, %lld correspondences\n", (long long)n_cam, (long long)n_pts,
-                (long long)n_obs);
-    if (a.f("mismatch-chance", 0.0) > 0.0) {
+    std::copy(pts_out.begin(), pts_out.begin() + (size_t)h.n_pts * 3, h.pts.begin());
+    print_initial_error(err[0], err[1]);
+    if (o.mismatch > 0.0) scramble(h, o);                                // :341, on the noised image positions (host arrays)
+    print_correspondences(h.n_cam, h.n_pts, h.n_obs);
+    if (o.mismatch > 0.0) {
         // the reference reports the error AFTER the correspondences were scrambled: one more sharded pass would need a
         // re-upload; the single-GPU evaluation of the final arrays gives the same number
         c2b_problem *p = nullptr;
         ck(create_problem(devs[0], &p));
-        ck(c2b_problem_upload_bal(p, n_cam, bal9.data(), n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
+        ck(upload_bal(p, h));
         ck(c2b_problem_total_reprojection_errors_l1_l2(p, &err[2], &err[3]));
         c2b_problem_destroy(p);
     }
-    std::printf("Final error: %s (L1) %s (L2)\n", sci2(err[2]).c_str(), sci2(err[3]).c_str());
-    ck(c2b_bal_write(a.positional[1].c_str(), n_cam, bal9.data(), n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
-    return 0;
+    print_final_error(err[2], err[3]);
 }
 
 int run_noise(int argc, char **argv) {
@@ -452,128 +554,55 @@ int run_noise(int argc, char **argv) {
                           "drift-angle", "mismatch-chance", "drop-features", "split-landmarks", "join-landmarks",
                           "sin-strength", "sin-frequency", "seed", "device", "gpus", "devices"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
-    uint64_t seed;
-    if (a.has("seed")) seed = (uint64_t)a.i("seed", 0);
-    else { std::random_device rd; seed = ((uint64_t)rd() << 32) ^ rd(); }   // the reference: unseeded thread_rng()
+    const NoiseOptions o = noise_options(a);                             // every value is converted before the device is touched
+    const std::string &in = a.positional[0], &out = a.positional[1];
+    double l1, l2;
 
     // The common case -- no index-corruption pass (src/bin/city2ba.rs:288-303, :341), one GPU -- never leaves the device:
     // the file is decoded into the resident problem (c2b_problem_read), the whole chain of src/bin/city2ba.rs:280-357 runs
     // on it, and the output file's image is assembled there (c2b_problem_write).  Both error pairs cost one pass each, the
     // second one fused with add_noise's observation pass.
-    const bool reshapes_any = a.f("drop-features", 1.0) < 1.0 || a.f("join-landmarks", 0.0) > 0.0 || a.f("split-landmarks", 0.0) > 0.0;
-    if (!reshapes_any && !(a.f("mismatch-chance", 0.0) > 0.0) && !a.has("gpus") && !a.has("devices") && !std::getenv("C2B_HOST_IO")) {
+    if (!o.reshapes() && !(o.mismatch > 0.0) && o.devices.empty() && !std::getenv("C2B_HOST_IO")) {
         PhaseTimer timer;
-        c2b_problem *p = nullptr;
-        ck(create_problem((int)a.i("device", 0), &p));
-        timer.mark("problem_create (HIP runtime start)");
-        ck(c2b_problem_read(p, a.positional[0].c_str(), -1));
-        timer.mark("read (c2b_problem_read: decoded on the device)");
-        double l1, l2;
+        c2b_problem *p = read_problem(timer, o.device, in);
         ck(c2b_problem_total_reprojection_errors_l1_l2(p, &l1, &l2));
-        std::printf("Initial error: %s (L1) %s (L2)\n", sci2(l1).c_str(), sci2(l2).c_str());
-        if (a.has("fixed-drift")) {                                      // :305-316: drift is ALWAYS applied
-            double stats[C2B_STATS_DOUBLES];
-            ck(c2b_problem_stats(p, stats));
-            ck(c2b_problem_add_drift(p, a.f("drift-strength", 0), a.f("drift-angle", 0), a.f("drift-std", 0), stats + 3, seed));
-        } else {
-            ck(c2b_problem_add_drift_normalized(p, a.f("drift-strength", 0), a.f("drift-angle", 0), a.f("drift-std", 0), seed));
-        }
-        if (a.f("sin-strength", 0) > 0.0) {                              // :318-333
-            const double dx[3] = {1, 0, 0}, dz[3] = {0, 0, 1}, up[3] = {0, 1, 0};
-            ck(c2b_problem_add_sin_noise(p, dx, up, a.f("sin-strength", 0), a.f("sin-frequency", 1)));
-            ck(c2b_problem_add_sin_noise(p, dz, up, a.f("sin-strength", 0), a.f("sin-frequency", 1)));
-        }
-        ck(c2b_problem_add_noise_errors_l1_l2(p, a.f("translation-std", 0), a.f("rotation-std", 0), a.f("point-std", 0),
-                                              a.f("observation-std", 0), seed + 1, &l1, &l2));      // :334-340 + :350-354
+        print_initial_error(l1, l2);
+        ck(perturb(p, nullptr, o, &l1, &l2));
         int64_t nc = 0, np = 0, no = 0;
         ck(c2b_problem_sizes(p, &nc, &np, &no));
-        std::printf("BA Problem with %lld cameras, %lld points, %lld correspondences\n", (long long)nc, (long long)np, (long long)no);
-        std::printf("Final error: %s (L1) %s (L2)\n", sci2(l1).c_str(), sci2(l2).c_str());
+        print_correspondences(nc, np, no);
+        print_final_error(l1, l2);
         timer.mark("errors + drift + noise (device)");
-        ck(c2b_problem_write(p, a.positional[1].c_str(), -1));
-        timer.mark("write (c2b_problem_write: the file image is built on the device)");
-        c2b_problem_destroy(p);
+        close_problem(timer, p, out);
         return 0;
     }
 
-    c2b_balfile *f = nullptr;
-    ck(c2b_bal_read(a.positional[0].c_str(), &f));
-    int64_t n_cam, n_pts, n_obs;
-    ck(c2b_bal_sizes(f, &n_cam, &n_pts, &n_obs));
-    const double split = a.f("split-landmarks", 0.0);
-    // room for the landmarks split_landmarks appends
-    const size_t pts_cap = (size_t)n_pts + (split > 0.0 ? (size_t)(std::min(split, 1.0) * (double)n_pts) + 1 : 0);
-    std::vector<double> bal9((size_t)n_cam * 9 + 1), pts(pts_cap * 3 + 1), uv((size_t)n_obs * 2 + 1);
-    std::vector<uint64_t> row_ptr((size_t)n_cam + 1), pt_idx((size_t)n_obs + 1);
-    ck(c2b_bal_copy(f, bal9.data(), pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
-    c2b_bal_close(f);
-
-    if (a.has("gpus") || a.has("devices"))
-        return run_noise_sharded(a, seed, n_cam, n_pts, n_obs, bal9, pts, pts_cap, uv, row_ptr, pt_idx);
+    HostBal h = read_bal(in, o.split);
+    if (!o.devices.empty()) {
+        run_noise_sharded(o, h);
+        write_bal(out, h);
+        return 0;
+    }
 
     c2b_problem *p = nullptr;
-    ck(create_problem((int)a.i("device", 0), &p));
-    ck(c2b_problem_upload_bal(p, n_cam, bal9.data(), n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
-    double l1, l2;
+    ck(create_problem(o.device, &p));
+    ck(upload_bal(p, h));
     ck(c2b_problem_total_reprojection_errors_l1_l2(p, &l1, &l2));        // src/bin/city2ba.rs:283-287: both norms, one pass
-    std::printf("Initial error: %s (L1) %s (L2)\n", sci2(l1).c_str(), sci2(l2).c_str());
-
-    // index-corruption passes on the host arrays, each followed by cull() (src/bin/city2ba.rs:288-303); camera rows
-    // stay 9-vectors (cull treats them as opaque)
-    bool reshaped = false;
-    auto cull = [&]() {
-        ck(c2b_cull(&n_cam, bal9.data(), 9, &n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data(), 1));
-        n_obs = (int64_t)row_ptr[(size_t)n_cam];
-        reshaped = true;
-    };
-    if (a.f("drop-features", 1.0) < 1.0) {
-        ck(c2b_drop_features(n_cam, row_ptr.data(), pt_idx.data(), uv.data(), a.f("drop-features", 1.0), seed + 2));
-        cull();
-    }
-    if (a.f("join-landmarks", 0.0) > 0.0) {
-        // the reference passes opt.split_landmarks as the fraction here (src/bin/city2ba.rs:296)
-        ck(c2b_join_landmarks(n_pts, pts.data(), (int64_t)row_ptr[(size_t)n_cam], pt_idx.data(), split, seed + 3));
-        cull();
-    }
-    if (split > 0.0) {
-        ck(c2b_split_landmarks(&n_pts, pts.data(), (int64_t)pts_cap, (int64_t)row_ptr[(size_t)n_cam], pt_idx.data(), split, seed + 4));
-        cull();
-    }
-    if (reshaped) {
-        if (n_cam == 0 || n_pts == 0) die("EmptyProblem: nothing remains after culling");
-        ck(c2b_problem_upload_bal(p, n_cam, bal9.data(), n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
-    }
-
-    // src/bin/city2ba.rs:305-316: drift is ALWAYS applied, even with zero strength
-    if (a.has("fixed-drift")) {
-        double stats[C2B_STATS_DOUBLES];
-        ck(c2b_problem_stats(p, stats));
-        ck(c2b_problem_add_drift(p, a.f("drift-strength", 0), a.f("drift-angle", 0), a.f("drift-std", 0), stats + 3, seed));
-    } else {
-        ck(c2b_problem_add_drift_normalized(p, a.f("drift-strength", 0), a.f("drift-angle", 0), a.f("drift-std", 0), seed));
-    }
-    if (a.f("sin-strength", 0) > 0.0) {        // :318-333
-        const double dx[3] = {1, 0, 0}, dz[3] = {0, 0, 1}, up[3] = {0, 1, 0};
-        ck(c2b_problem_add_sin_noise(p, dx, up, a.f("sin-strength", 0), a.f("sin-frequency", 1)));
-        ck(c2b_problem_add_sin_noise(p, dz, up, a.f("sin-strength", 0), a.f("sin-frequency", 1)));
-    }
-    // :334-340 (always) fused with the final errors of :350-354: the observation pass draws, perturbs, stores, projects
-    // and folds both norms in one launch.  With --mismatch-chance the errors are re-evaluated after the scramble below.
-    ck(c2b_problem_add_noise_errors_l1_l2(p, a.f("translation-std", 0), a.f("rotation-std", 0), a.f("point-std", 0),
-                                          a.f("observation-std", 0), seed + 1, &l1, &l2));
-    ck(c2b_problem_download(p, nullptr, pts.data(), uv.data()));
-    if (a.f("mismatch-chance", 0.0) > 0.0) {                             // :341, on the noised image positions
-        std::vector<double> cams15((size_t)n_cam * 15 + 1);
+    print_initial_error(l1, l2);
+    if (reshape(h, o)) ck(upload_bal(p, h));
+    ck(perturb(p, nullptr, o, &l1, &l2));
+    ck(c2b_problem_download(p, nullptr, h.pts.data(), h.uv.data()));
+    if (o.mismatch > 0.0) {                                              // :341, on the noised image positions
+        std::vector<double> cams15((size_t)h.n_cam * 15 + 1);
         ck(c2b_problem_download(p, cams15.data(), nullptr, nullptr));
-        ck(c2b_add_incorrect_correspondences(n_cam, row_ptr.data(), pt_idx.data(), uv.data(), a.f("mismatch-chance", 0.0), seed + 5));
-        ck(c2b_problem_upload(p, n_cam, cams15.data(), n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
+        scramble(h, o);
+        ck(c2b_problem_upload(p, h.n_cam, cams15.data(), h.n_pts, h.pts.data(), h.row_ptr.data(), h.pt_idx.data(), h.uv.data()));
         ck(c2b_problem_total_reprojection_errors_l1_l2(p, &l1, &l2));
     }
-    std::printf("BA Problem with %lld cameras, %lld points, %lld correspondences\n", (long long)n_cam, (long long)n_pts,
-                (long long)n_obs);
-    std::printf("Final error: %s (L1) %s (L2)\n", sci2(l1).c_str(), sci2(l2).c_str());
-    ck(c2b_problem_download_bal(p, bal9.data()));
-    ck(c2b_bal_write(a.positional[1].c_str(), n_cam, bal9.data(), n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
+    print_correspondences(h.n_cam, h.n_pts, h.n_obs);
+    print_final_error(l1, l2);
+    ck(c2b_problem_download_bal(p, h.bal9.data()));
+    write_bal(out, h);
     c2b_problem_destroy(p);
     return 0;
 }
@@ -582,16 +611,12 @@ int run_noise(int argc, char **argv) {
 void parse_vec3(const Args &a, const std::string &k, double out[3]) {
     auto it = a.opt.find(k);
     if (it == a.opt.end()) return;
-    const std::string &s = it->second;
-    size_t pos = 0;
-    for (int c = 0; c < 3; ++c) {
-        const size_t comma = c < 2 ? s.find(',', pos) : s.size();
-        if (comma == std::string::npos) die("Invalid value for '--" + k + " <" + k + ">': expected x,y,z");
-        const std::string tok = s.substr(pos, comma - pos);
+    const std::vector<std::string> tok = split_commas(it->second);
+    for (size_t c = 0; c < 3; ++c) {                                     // a missing comma is met before the number in front of it
+        if (c < 2 && tok.size() < c + 2) die("Invalid value for '--" + k + " <" + k + ">': expected x,y,z");
         char *end = nullptr;
-        out[c] = std::strtod(tok.c_str(), &end);
-        if (end == tok.c_str() || *end) die("Invalid value for '--" + k + " <" + k + ">': invalid float literal");
-        pos = comma + 1;
+        out[c] = std::strtod(tok[c].c_str(), &end);
+        if (end == tok[c].c_str() || *end || (c == 2 && tok.size() > 3)) die("Invalid value for '--" + k + " <" + k + ">': invalid float literal");
     }
 }
 
@@ -618,9 +643,7 @@ int run_generate(int argc, char **argv) {
     double istart[3] = {1, 0, 0}, iend[3] = {1, 0, 0};
     parse_vec3(a, "intrinsics-start", istart);
     parse_vec3(a, "intrinsics-end", iend);
-    uint64_t seed;
-    if (a.has("seed")) seed = (uint64_t)a.i("seed", 0);
-    else { std::random_device rd; seed = ((uint64_t)rd() << 32) ^ rd(); }   // the reference: unseeded thread_rng()
+    const uint64_t seed = seed_of(a);
 
     PhaseTimer timer;
     // Everything that needs only the file runs on a second thread while this one starts the HIP runtime (c2b_problem_create:
@@ -776,41 +799,23 @@ int run_generate(int argc, char **argv) {
 int run_ply(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {}, {"device"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
-    c2b_balfile *f = nullptr;
-    ck(c2b_bal_read(a.positional[0].c_str(), &f));
-    int64_t n_cam, n_pts, n_obs;
-    ck(c2b_bal_sizes(f, &n_cam, &n_pts, &n_obs));
-    std::vector<double> bal9((size_t)n_cam * 9 + 1), pts((size_t)n_pts * 3 + 1), uv((size_t)n_obs * 2 + 1);
-    std::vector<uint64_t> row_ptr((size_t)n_cam + 1), pt_idx((size_t)n_obs + 1);
-    ck(c2b_bal_copy(f, bal9.data(), pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
-    c2b_bal_close(f);
+    const HostBal h = read_bal(a.positional[0]);
     c2b_problem *p = nullptr;
     ck(create_problem((int)a.i("device", 0), &p));
-    ck(c2b_problem_upload_bal(p, n_cam, bal9.data(), n_pts, pts.data(), row_ptr.data(), pt_idx.data(), uv.data()));
-    std::vector<double> centers((size_t)n_cam * 3 + 1);
+    ck(upload_bal(p, h));
+    std::vector<double> centers((size_t)h.n_cam * 3 + 1);
     ck(c2b_problem_centers(p, centers.data()));
     c2b_problem_destroy(p);
-    ck(c2b_ply_write(a.positional[1].c_str(), n_cam, centers.data(), n_pts, pts.data(), row_ptr.data(), pt_idx.data()));
+    ck(c2b_ply_write(a.positional[1].c_str(), h.n_cam, centers.data(), h.n_pts, h.pts.data(), h.row_ptr.data(), h.pt_idx.data()));
     return 0;
 }
 
-// The head and the tail `solve`, `triangulate` and `resect` share: a problem on `device` read from `file`, its sizes printed;
-// the problem written to `file` and destroyed.
+// The head `solve`, `triangulate` and `resect` share: read_problem, and the sizes printed (close_problem is their tail)
 static c2b_problem *open_problem(PhaseTimer &timer, int device, const std::string &file, int64_t &nc, int64_t &np, int64_t &no) {
-    c2b_problem *p = nullptr;
-    ck(create_problem(device, &p));
-    timer.mark("problem_create (HIP runtime start)");
-    ck(c2b_problem_read(p, file.c_str(), -1));
-    timer.mark("read (c2b_problem_read: decoded on the device)");
+    c2b_problem *p = read_problem(timer, device, file);
     ck(c2b_problem_sizes(p, &nc, &np, &no));
-    std::printf("Bundle Adjustment Problem with %lld cameras, %lld points, and %lld observations\n", (long long)nc, (long long)np, (long long)no);
+    print_problem(nc, np, no);
     return p;
-}
-
-static void close_problem(PhaseTimer &timer, c2b_problem *p, const std::string &file) {
-    ck(c2b_problem_write(p, file.c_str(), -1));
-    timer.mark("write (c2b_problem_write: the file image is built on the device)");
-    c2b_problem_destroy(p);
 }
 
 // `solve`: bundle adjustment of a .bal / .bbal by c2b_problem_levenberg_marquardt (an extension: the reference only makes
@@ -823,20 +828,14 @@ static void close_problem(PhaseTimer &timer, c2b_problem *p, const std::string &
 // sigmas of a --prior-*-sigma flag: `want` numbers (or also one, when `or_one`), each > 0; returned as weights 1 / sigma
 static std::vector<double> prior_weights_of(const Args &a, const std::string &key, const char *shape, int want, bool or_one) {
     std::vector<double> w;
-    const std::string &v = a.opt.at(key);
-    size_t at = 0;
-    while (at <= v.size()) {
-        const size_t comma = std::min(v.find(',', at), v.size());
-        const std::string part = v.substr(at, comma - at);
+    const std::string bad = "Invalid value for '--" + key + " <" + shape + ">': expected " + shape + " with every sigma a number > 0";
+    for (const std::string &part : split_commas(a.opt.at(key))) {
         char *end = nullptr;
         const double sigma = std::strtod(part.c_str(), &end);
-        if (part.empty() || end == part.c_str() || *end || !(sigma > 0.0) || !std::isfinite(sigma))
-            die("Invalid value for '--" + key + " <" + shape + ">': expected " + shape + " with every sigma a number > 0");
+        if (end == part.c_str() || *end || !(sigma > 0.0) || !std::isfinite(sigma)) die(bad);
         w.push_back(1.0 / sigma);
-        at = comma + 1;
     }
-    if (!((int)w.size() == want || (or_one && w.size() == 1)))
-        die("Invalid value for '--" + key + " <" + shape + ">': expected " + shape + " with every sigma a number > 0");
+    if (!((int)w.size() == want || (or_one && w.size() == 1))) die(bad);
     if ((int)w.size() < want) w.assign((size_t)want, w[0]);
     return w;
 }
@@ -995,6 +994,37 @@ int run_solve(int argc, char **argv) {
     return 0;
 }
 
+// The consensus flags `triangulate` and `resect` share, parsed and cross-checked: --min-inliers is at least `least`, `dflt`
+// when absent.
+struct Consensus { bool on, drop_outliers; double max_error; int min_inliers, max_hypotheses; };
+
+static Consensus consensus_of(const Args &a, int64_t least, int64_t dflt) {
+    Consensus c = {a.has("max-error"), a.has("drop-outliers"), a.f("max-error", 0.0), 0, 0};
+    const int64_t min_inliers = a.i("min-inliers", dflt), max_hypotheses = a.i("max-hypotheses", 64);
+    if (c.on && !(c.max_error >= 0.0 && std::isfinite(c.max_error))) die("Invalid value for '--max-error <X>': expected a finite number >= 0");
+    if (min_inliers < least || min_inliers > 2147483647) die("Invalid value for '--min-inliers <N>': expected an integer of at least " + std::to_string(least));
+    if (max_hypotheses < 1 || max_hypotheses > 64) die("Invalid value for '--max-hypotheses <H>': expected an integer in 1 ... 64");
+    if (!c.on && (a.has("min-inliers") || a.has("max-hypotheses") || c.drop_outliers))
+        die("--min-inliers, --max-hypotheses and --drop-outliers need --max-error <X>");
+    c.min_inliers = (int)min_inliers; c.max_hypotheses = (int)max_hypotheses;
+    return c;
+}
+
+// What a start-up pass did, from its counts: "<did> N <what>; kept: ..." -- with `inlier` (consensus) also the count
+// without consensus and a second line.  C2B_TRI_* and C2B_RES_* number the outcomes alike.
+static_assert(C2B_TRI_OK == C2B_RES_OK && C2B_TRI_TOO_FEW == C2B_RES_TOO_FEW && C2B_TRI_DEGENERATE == C2B_RES_DEGENERATE &&
+              C2B_TRI_BEHIND == C2B_RES_BEHIND && C2B_TRI_CONSTANT == C2B_RES_CONSTANT && C2B_TRI_NO_CONSENSUS == C2B_RES_NO_CONSENSUS, "");
+static void print_summary(const char *did, const char *what, const char *behind, const int64_t counts[6], const std::vector<uint8_t> *inlier,
+                          int64_t removed) {
+    std::printf("%s %lld %s; kept: %lld too few observations, %lld degenerate, %lld behind a %s, %lld constant", did, (long long)counts[C2B_TRI_OK],
+                what, (long long)counts[C2B_TRI_TOO_FEW], (long long)counts[C2B_TRI_DEGENERATE], (long long)counts[C2B_TRI_BEHIND], behind,
+                (long long)counts[C2B_TRI_CONSTANT]);
+    if (inlier)
+        std::printf(", %lld without consensus\n%lld outlier observations, %lld removed", (long long)counts[C2B_TRI_NO_CONSENSUS],
+                    (long long)std::count(inlier->begin(), inlier->end(), (uint8_t)0), (long long)removed);
+    std::printf("\n");
+}
+
 // `triangulate`: every point of a .bal / .bbal from its cameras and observations by c2b_problem_triangulate_points (an
 // extension: linear midpoint triangulation on the device; cameras and observations are written as they were read).  Every
 // argument is parsed before the device is touched.  --max-error X selects consensus triangulation
@@ -1006,36 +1036,18 @@ int run_triangulate(int argc, char **argv) {
     const double min_angle_deg = a.f("min-angle", 1.0);
     const int device = (int)a.i("device", 0);
     if (!(min_angle_deg >= 0.0 && min_angle_deg <= 90.0)) die("Invalid value for '--min-angle <DEG>': expected a number in 0 ... 90");
-    const bool robust = a.has("max-error");
-    const double max_error = a.f("max-error", 0.0);
-    const int64_t min_inliers = a.i("min-inliers", 3), max_hypotheses = a.i("max-hypotheses", 64);
-    if (robust && !(max_error >= 0.0 && std::isfinite(max_error))) die("Invalid value for '--max-error <X>': expected a finite number >= 0");
-    if (min_inliers < 2 || min_inliers > 2147483647) die("Invalid value for '--min-inliers <N>': expected an integer of at least 2");
-    if (max_hypotheses < 1 || max_hypotheses > 64) die("Invalid value for '--max-hypotheses <H>': expected an integer in 1 ... 64");
-    if (!robust && (a.has("min-inliers") || a.has("max-hypotheses") || a.has("drop-outliers")))
-        die("--min-inliers, --max-hypotheses and --drop-outliers need --max-error <X>");
+    const double min_angle = min_angle_deg * (3.14159265358979323846 / 180.0);
+    const Consensus c = consensus_of(a, 2, 3);
     PhaseTimer timer;
     int64_t nc = 0, np = 0, no = 0;
     c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
-    int64_t counts[6] = {0, 0, 0, 0, 0, 0};
-    if (robust) {
-        int64_t removed = 0;
-        std::vector<uint8_t> inlier((size_t)no);
-        ck(c2b_problem_triangulate_consensus(p, min_angle_deg * (3.14159265358979323846 / 180.0), max_error, (int)min_inliers, (int)max_hypotheses,
-                                             a.has("drop-outliers") ? C2B_TRI_DROP_OUTLIERS : 0, nullptr, nullptr, inlier.data(), counts, &removed));
-        timer.mark("triangulate_consensus (device)");
-        std::printf("triangulated %lld points; kept: %lld too few observations, %lld degenerate, %lld behind a camera, %lld constant, "
-                    "%lld without consensus\n%lld outlier observations, %lld removed\n",
-                    (long long)counts[C2B_TRI_OK], (long long)counts[C2B_TRI_TOO_FEW], (long long)counts[C2B_TRI_DEGENERATE],
-                    (long long)counts[C2B_TRI_BEHIND], (long long)counts[C2B_TRI_CONSTANT], (long long)counts[C2B_TRI_NO_CONSENSUS],
-                    (long long)std::count(inlier.begin(), inlier.end(), (uint8_t)0), (long long)removed);
-    } else {
-        ck(c2b_problem_triangulate_points(p, min_angle_deg * (3.14159265358979323846 / 180.0), nullptr, counts));
-        timer.mark("triangulate_points (device)");
-        std::printf("triangulated %lld points; kept: %lld too few observations, %lld degenerate, %lld behind a camera, %lld constant\n",
-                    (long long)counts[C2B_TRI_OK], (long long)counts[C2B_TRI_TOO_FEW], (long long)counts[C2B_TRI_DEGENERATE],
-                    (long long)counts[C2B_TRI_BEHIND], (long long)counts[C2B_TRI_CONSTANT]);
-    }
+    int64_t counts[6] = {0, 0, 0, 0, 0, 0}, removed = 0;
+    std::vector<uint8_t> inlier((size_t)(c.on ? no : 0));
+    ck(c.on ? c2b_problem_triangulate_consensus(p, min_angle, c.max_error, c.min_inliers, c.max_hypotheses, c.drop_outliers ? C2B_TRI_DROP_OUTLIERS : 0,
+                                                nullptr, nullptr, inlier.data(), counts, &removed)
+            : c2b_problem_triangulate_points(p, min_angle, nullptr, counts));
+    timer.mark(c.on ? "triangulate_consensus (device)" : "triangulate_points (device)");
+    print_summary("triangulated", "points", "camera", counts, c.on ? &inlier : nullptr, removed);
     close_problem(timer, p, a.positional[1]);
     return 0;
 }
@@ -1053,37 +1065,18 @@ int run_resect(int argc, char **argv) {
     const int device = (int)a.i("device", 0);
     if (min_points < 6 || min_points > 2147483647) die("Invalid value for '--min-points <N>': expected an integer of at least 6");
     if (!(min_gap >= 0.0 && min_gap < 1.0)) die("Invalid value for '--min-gap <G>': expected a number in 0 ... 1 (1 excluded)");
-    const bool robust = a.has("max-error");
-    const double max_error = a.f("max-error", 0.0);
-    const int64_t min_inliers = a.i("min-inliers", 6), max_hypotheses = a.i("max-hypotheses", 64);
-    if (robust && !(max_error >= 0.0 && std::isfinite(max_error))) die("Invalid value for '--max-error <X>': expected a finite number >= 0");
-    if (min_inliers < 6 || min_inliers > 2147483647) die("Invalid value for '--min-inliers <N>': expected an integer of at least 6");
-    if (max_hypotheses < 1 || max_hypotheses > 64) die("Invalid value for '--max-hypotheses <H>': expected an integer in 1 ... 64");
-    if (!robust && (a.has("min-inliers") || a.has("max-hypotheses") || a.has("drop-outliers")))
-        die("--min-inliers, --max-hypotheses and --drop-outliers need --max-error <X>");
-    if (robust && a.has("min-points")) die("--min-points does not go with --max-error <X>: --min-inliers <N> takes its place");
+    const Consensus c = consensus_of(a, 6, 6);
+    if (c.on && a.has("min-points")) die("--min-points does not go with --max-error <X>: --min-inliers <N> takes its place");
     PhaseTimer timer;
     int64_t nc = 0, np = 0, no = 0;
     c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
-    int64_t counts[6] = {0, 0, 0, 0, 0, 0};
-    if (robust) {
-        int64_t removed = 0;
-        std::vector<uint8_t> inlier((size_t)no);
-        ck(c2b_problem_resect_consensus(p, max_error, (int)min_inliers, min_gap, (int)max_hypotheses,
-                                        a.has("drop-outliers") ? C2B_RES_DROP_OUTLIERS : 0, nullptr, nullptr, nullptr, inlier.data(), counts, &removed));
-        timer.mark("resect_consensus (device)");
-        std::printf("resected %lld cameras; kept: %lld too few observations, %lld degenerate, %lld behind a point, %lld constant, "
-                    "%lld without consensus\n%lld outlier observations, %lld removed\n",
-                    (long long)counts[C2B_RES_OK], (long long)counts[C2B_RES_TOO_FEW], (long long)counts[C2B_RES_DEGENERATE],
-                    (long long)counts[C2B_RES_BEHIND], (long long)counts[C2B_RES_CONSTANT], (long long)counts[C2B_RES_NO_CONSENSUS],
-                    (long long)std::count(inlier.begin(), inlier.end(), (uint8_t)0), (long long)removed);
-    } else {
-        ck(c2b_problem_resect_cameras(p, (int)min_points, min_gap, nullptr, counts));
-        timer.mark("resect_cameras (device)");
-        std::printf("resected %lld cameras; kept: %lld too few observations, %lld degenerate, %lld behind a point, %lld constant\n",
-                    (long long)counts[C2B_RES_OK], (long long)counts[C2B_RES_TOO_FEW], (long long)counts[C2B_RES_DEGENERATE],
-                    (long long)counts[C2B_RES_BEHIND], (long long)counts[C2B_RES_CONSTANT]);
-    }
+    int64_t counts[6] = {0, 0, 0, 0, 0, 0}, removed = 0;
+    std::vector<uint8_t> inlier((size_t)(c.on ? no : 0));
+    ck(c.on ? c2b_problem_resect_consensus(p, c.max_error, c.min_inliers, min_gap, c.max_hypotheses, c.drop_outliers ? C2B_RES_DROP_OUTLIERS : 0,
+                                           nullptr, nullptr, nullptr, inlier.data(), counts, &removed)
+            : c2b_problem_resect_cameras(p, (int)min_points, min_gap, nullptr, counts));
+    timer.mark(c.on ? "resect_consensus (device)" : "resect_cameras (device)");
+    print_summary("resected", "cameras", "point", counts, c.on ? &inlier : nullptr, removed);
     close_problem(timer, p, a.positional[1]);
     return 0;
 }

@@ -56,3 +56,16 @@ def test_argument_errors_do_not_need_a_device(cli, tmp_path):
     assert r.returncode != 0 and "Could not open file" in r.stderr
     r = run(cli, "noise", tmp_path / "none.bal", tmp_path / "o.bal")
     assert r.returncode != 0
+
+
+def test_noise_values_are_refused_before_the_input_is_opened(cli, tmp_path):
+    """`noise` converts every option before it creates a device or opens its input: on a machine without a GPU, and with
+    an input that does not exist, a malformed value is still what the message names."""
+    missing, out = tmp_path / "missing.bal", tmp_path / "o.bal"
+    r = run(cli, "noise", missing, out, "--rotation-std", "x")
+    assert r.returncode != 0 and "invalid float literal" in r.stderr
+    assert not out.exists()
+    r = run(cli, "noise", missing, out, "--seed", "-1")
+    assert r.returncode != 0 and "invalid digit found in string" in r.stderr
+    r = run(cli, "noise", missing, out, "--devices", "0,,1")
+    assert r.returncode != 0 and "expected a,b,c" in r.stderr
