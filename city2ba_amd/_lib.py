@@ -106,6 +106,10 @@ RES_NO_CONSENSUS = 5
 RES_CONSENSUS_STATUS = RES_STATUS + ("no_consensus",)
 RES_DROP_OUTLIERS = 1      # C2B_RES_DROP_OUTLIERS: compact the list by the inlier mask afterwards
 
+# statuses of c2b_merge_partner_rows (C2B_MERGE_*), the order of its counts
+MERGE_NONE, MERGE_CHOSEN, MERGE_UNOBSERVED, MERGE_HELD = range(4)
+MERGE_STATUS = ("none", "chosen", "unobserved", "held")
+
 
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
 SIGNATURES = {
@@ -141,6 +145,7 @@ SIGNATURES = {
     "c2b_triangulate_consensus_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_resect_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp]),
     "c2b_resect_consensus_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _int, _d, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_merge_partner_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "c2b_reprojection_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "c2b_add_noise_observations_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _d, _u64, _vp, _vp, _vp]),
     "c2b_jacobian_stream_policy": (_int, [_i64, _i64, _i64]),
@@ -178,6 +183,7 @@ SIGNATURES = {
     "c2b_problem_triangulate_consensus": (_int, [_vp, _d, _d, _int, _int, _int, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_resect_cameras": (_int, [_vp, _int, _d, _vp, _vp]),
     "c2b_problem_resect_consensus": (_int, [_vp, _d, _int, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "c2b_problem_merge_points": (_int, [_vp, _d, _d, _int, _vp, C.POINTER(_i64), C.POINTER(_int)]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
     "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),

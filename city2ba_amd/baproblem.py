@@ -580,6 +580,27 @@ class BAProblem:
             self._refresh_graph()
         return n.value
 
+    def merge_points(self, radius, max_error, rounds=1, return_map=False):
+        """Duplicate landmarks merged in place, on the device (c2b_problem_merge_points): the repair of
+        split_landmarks and of broken tracks.  Per round every observed point that is neither constant nor tied to a point
+        prior picks the nearest other such point within `radius` that shares no camera with it and whose merged position
+        -- between the two, weighted by their observation counts -- reprojects every observation of both within max_error
+        in front of its camera (filter_observations' predicate with in_front); pairs that pick each other are merged onto
+        the lower index.  Up to `rounds` rounds, each on the state the last one left; a round that merges nothing is the
+        last.  Cameras and points are not renumbered and uv, the row pointer and the order inside every camera's list
+        stay, so the constant masks, the priors, the loss, the preconditioner and a checkpoint stay too.  The absorbed
+        points are NOT culled: they stay in the table as unobserved points (the LM step leaves them where they are);
+        cull() is the caller's call.  Returns dict(merged, rounds): the number of points absorbed and of rounds run; with
+        return_map also the int32 map [n_pts]: the point each point's observations ended on (itself when not absorbed)."""
+        merged, run = C.c_int64(), C.c_int()
+        into = np.zeros(self.num_points(), dtype=np.int32) if return_map else None
+        L.check(L.lib().c2b_problem_merge_points(self._h, float(radius), float(max_error), int(rounds),
+                                                 into.ctypes.data_as(C.c_void_p) if return_map else None, C.byref(merged), C.byref(run)))
+        if merged.value:
+            self._refresh_graph()
+        out = dict(merged=int(merged.value), rounds=int(run.value))
+        return (out, into) if return_map else out
+
     def _status_pass(self, entry, args, n, names, return_status):
         """entry(handle, *args, status, counts) over n entities: the counts as a dict under `names`, and the status bytes"""
         counts = np.zeros(len(names), dtype=np.int64)

@@ -31,6 +31,9 @@
 //   city2ba resect IN OUT [--min-points N] [--min-gap G] [--max-error X [--min-inliers N] [--max-hypotheses H] [--drop-outliers]]
 //                        (extension: the camera poses from the points and observations, c2b_problem_resect_cameras; with
 //                         --max-error: from the observations that agree with each other, c2b_problem_resect_consensus)
+//   city2ba merge IN OUT --radius R --max-error X [--rounds N]
+//                        (extension: duplicate landmarks merged, the repair of --split-landmarks, c2b_problem_merge_points;
+//                         the absorbed points stay in the file as unobserved points, nothing is culled)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -1081,6 +1084,30 @@ int run_resect(int argc, char **argv) {
     return 0;
 }
 
+// `merge`: duplicate landmarks of a .bal / .bbal merged by c2b_problem_merge_points (an extension: the repair of
+// `noise --split-landmarks` and of broken tracks; cameras and observed pixels are written as they were read).  Every argument
+// is parsed before the device is touched.  The absorbed points stay in the file as unobserved points: nothing is culled.
+int run_merge(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {}, {"radius", "max-error", "rounds", "device"});
+    if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
+    if (!a.has("radius") || !a.has("max-error")) die("The following required arguments were not provided:\n    --radius <R> --max-error <X>");
+    const double radius = a.f("radius", 0.0), max_error = a.f("max-error", 0.0);
+    const int64_t rounds = a.i("rounds", 1);
+    const int device = (int)a.i("device", 0);
+    if (!(radius >= 0.0 && std::isfinite(radius))) die("Invalid value for '--radius <R>': expected a finite number >= 0");
+    if (!(max_error >= 0.0 && std::isfinite(max_error))) die("Invalid value for '--max-error <X>': expected a finite number >= 0");
+    if (rounds < 1 || rounds > 1000) die("Invalid value for '--rounds <N>': expected an integer in 1 ... 1000");
+    PhaseTimer timer;
+    int64_t nc = 0, np = 0, no = 0, merged = 0;
+    int run = 0;
+    c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
+    ck(c2b_problem_merge_points(p, radius, max_error, (int)rounds, nullptr, &merged, &run));
+    timer.mark("merge_points (device)");
+    std::printf("merged %lld points in %d rounds; they stay in the file as unobserved points\n", (long long)merged, run);
+    close_problem(timer, p, a.positional[1]);
+    return 0;
+}
+
 void usage() {
     std::printf("city2ba (MI355X build, %s)\nTools for generating synthetic bundle adjustment problems.\n\n"
                 "USAGE:\n    city2ba <SUBCOMMAND>\n\nSUBCOMMANDS:\n"
@@ -1091,7 +1118,8 @@ void usage() {
                 "    ply               Convert a .bal or .bbal to a .ply for visualization.\n"
                 "    solve             Bundle-adjust a .bal or .bbal by Levenberg-Marquardt on the device.\n"
                 "    triangulate       Set the points of a .bal or .bbal from its cameras and observations.\n"
-                "    resect            Set the camera poses of a .bal or .bbal from its points and observations.\n",
+                "    resect            Set the camera poses of a .bal or .bbal from its points and observations.\n"
+                "    merge             Merge the duplicate landmarks of a .bal or .bbal (the repair of noise --split-landmarks).\n",
                 c2b_version());
 }
 
@@ -1163,6 +1191,13 @@ const char *subcommand_help(const std::string &sub) {
                "                              place of --min-points)\n"
                "    --max-hypotheses <H> [64] candidates per camera, widest triples first (1 ... 64)\n"
                "    --drop-outliers           then remove the observations of the resected cameras that are not inliers\n";
+    if (sub == "merge")
+        return "city2ba merge <FILE> <OUT>\n"
+               "    --radius <R>              two points at most R apart are candidates for one landmark (required)\n"
+               "    --max-error <X>           they are merged when no camera sees both and every observation of both reprojects\n"
+               "                              within X of the merged position, in front of its camera (required)\n"
+               "    --rounds <N> [1]          rounds, each on the result of the last; a round that merges nothing is the last\n"
+               "                              The absorbed points are not culled: they stay in the file as unobserved points.\n";
     return nullptr;
 }
 
@@ -1188,5 +1223,6 @@ int main(int argc, char **argv) {
     if (sub == "solve") return run_solve(argc, argv);
     if (sub == "triangulate") return run_triangulate(argc, argv);
     if (sub == "resect") return run_resect(argc, argv);
+    if (sub == "merge") return run_merge(argc, argv);
     die("The subcommand '" + sub + "' wasn't recognized");
 }

@@ -43,6 +43,7 @@
 #include "resect_robust_kernels.hpp"
 #include "cull_kernels.hpp"
 #include "cell_kernels.hpp"
+#include "merge_kernels.hpp"
 #include "text_kernels.hpp"
 #include "comm_rccl.hpp"
 

@@ -565,6 +565,168 @@ static int build_cell_list(hipStream_t st, const char *who, const double4 *pos4,
     return C2B_OK;
 }
 
+// ---- landmark merging (merge_kernels.hpp) --------------------------------------------------------------------
+static bool good_merge_length(double v) { return v >= 0.0 && std::isfinite(v); }       // (a NaN fails the first)
+
+// the double whose merge_order_key is k
+static double merge_key_value(unsigned long long k) {
+    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double v;
+    std::memcpy(&v, &u, sizeof v);
+    return v;
+}
+
+// One round's partner choice over a point-major transpose: the cell list over x / z is built here, from the extent of the
+// finite points, with cells of radius (1 + 2^-20) doubled as cell_grid_from_stats doubles them -- the result does not depend
+// on the grid.  The temporaries are freed on return, so the call synchronises `stream` as a scan does.
+int c2b_merge_partner_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                           const uint32_t *cam_of, const double *uv_obs, int64_t n_obs, double radius, double max_error,
+                           const uint8_t *pt_held, int32_t *partner, uint8_t *status, int64_t *counts, void *stream) {
+    C2B_API_BEGIN
+    if (!good_merge_length(radius)) return fail(C2B_ERR_INVALID_ARGUMENT, "merge_partner_rows: radius must be finite and >= 0");
+    if (!good_merge_length(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "merge_partner_rows: max_error must be finite and >= 0");
+    if (n_pts < 0 || n_pts >= ((int64_t)1 << 31)) return fail(C2B_ERR_INVALID_ARGUMENT, "merge_partner_rows: n_pts out of range");
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 64)        // (a row's length and its chunk offsets are ints in the kernel)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "merge_partner_rows: n_obs out of range");
+    if (!counts || (n_pts && (!pts4 || !pt_row_ptr || !partner || !status))) return fail(C2B_ERR_INVALID_ARGUMENT, "merge_partner_rows: NULL argument");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(pt_row_ptr) || !aligned8(counts) ||
+        (reinterpret_cast<uintptr_t>(obs_of) & 3) || (reinterpret_cast<uintptr_t>(cam_of) & 3) || (reinterpret_cast<uintptr_t>(partner) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "merge_partner_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kMergeKinds, st));
+    if (!n_pts) return C2B_OK;
+    const double4 *pos4 = reinterpret_cast<const double4 *>(pts4);
+    // the extent of the points -> the cell grid
+    DevBuf<unsigned long long> ext;
+    const unsigned long long ext0[4] = {~0ull, ~0ull, 0ull, 0ull};
+    unsigned long long ext_h[4] = {0, 0, 0, 0};
+    HIP_TRY(ext.alloc(4));
+    HIP_TRY(hipMemcpyAsync(ext.ptr, ext0, sizeof ext0, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_merge_extent, dim3(std::min(blocks_of(n_pts, 256), 1024u)), dim3(256), 0, st, pos4, n_pts, ext.ptr);
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(ext_h, ext.ptr, sizeof ext_h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    double stats[C2B_STATS_DOUBLES] = {0.0};
+    if (ext_h[2] != 0ull) {                                  // (no finite point: one cell at the origin, and no pair)
+        stats[6] = merge_key_value(ext_h[0]); stats[8] = merge_key_value(ext_h[1]);
+        stats[9] = merge_key_value(ext_h[2]); stats[11] = merge_key_value(ext_h[3]);
+    }
+    CellGrid g;
+    int64_t n_cells = 0;
+    int rc = cell_grid_from_stats(stats, radius, "merge_partner_rows", &g, &n_cells);
+    if (rc) return rc;
+    DevArena arena;
+    DevBuf<uint32_t> cell_of, cnt, startb, sorted, tiles, total;
+    auto temporaries = [&](auto &&each) {
+        each(cell_of, (size_t)n_pts); each(cnt, (size_t)(n_cells + 1)); each(startb, (size_t)(n_cells + 1));
+        each(sorted, (size_t)n_pts); each(tiles, (size_t)((n_cells + 1) / kScanTile + 2)); each(total, (size_t)1);
+    };
+    size_t arena_bytes = 0;
+    temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
+    const hipError_t ea = arena.reserve(arena_bytes);
+    if (ea != hipSuccess) return fail(hip_code(ea), "merge_partner_rows: %s", hipGetErrorString(ea));
+    temporaries([&](auto &b, size_t n) { arena.carve(b, n); });
+    HIP_TRY(hipMemsetAsync(cnt.ptr, 0, 4 * (size_t)(n_cells + 1), st));
+    rc = build_cell_list(st, "merge_partner_rows", pos4, n_pts, g, n_cells, cell_of, cnt, startb, sorted, tiles, total);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    hipLaunchKernelGGL(k_merge_partner, dim3(blocks_for(n_pts, kMrgWaves)), dim3(kMrgBlock), 0, st, camblk, pos4, n_pts, pt_row_ptr, obs_of,
+                       cam_of, reinterpret_cast<const double2 *>(uv_obs), g, (const uint32_t *)startb, (const uint32_t *)sorted,
+                       radius * radius, max_error * max_error, pt_held, partner, status, reinterpret_cast<unsigned long long *>(counts));
+    const hipError_t el = launch_error(), es = hipStreamSynchronize(st);          // the arena is freed on return
+    if (el != hipSuccess || es != hipSuccess)
+        return fail(hip_code(el != hipSuccess ? el : es), "merge_partner_rows: %s", hipGetErrorString(el != hipSuccess ? el : es));
+    return C2B_OK;
+    C2B_API_END("merge_partner_rows")
+}
+
+// Merging on the resident problem: per round the partner pass over the cached transpose, the mutual pairs
+// applied to pts4, and pt_idx rewritten through the round's map.  The entities do not move and nothing is renumbered: cameras,
+// both counts, the masks, the priors, the loss, the preconditioner, the checkpoint and the LM scratch stay; after a round
+// that merged, what was derived from the list (drop_rows) goes, as after a filter that removed something.
+int c2b_problem_merge_points(c2b_problem *p, double radius, double max_error, int rounds, int32_t *merged_into, int64_t *n_merged,
+                             int *rounds_run) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_merge_points");
+    if (!good_merge_length(radius)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_merge_points: radius must be finite and >= 0");
+    if (!good_merge_length(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_merge_points: max_error must be finite and >= 0");
+    if (rounds < 1) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_merge_points: rounds must be at least 1");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_merge_points: a shard is not merged alone (a point's observations span every rank)");
+    const int64_t np = p->n_pts;
+    if (np >= ((int64_t)1 << 31)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_merge_points: too many points");
+    if (n_merged) *n_merged = 0;
+    if (rounds_run) *rounds_run = 0;
+    if (merged_into)
+        for (int64_t i = 0; i < np; ++i) merged_into[i] = (int32_t)i;
+    if (!p->n_obs || !np) return C2B_OK;                     // no observation: every point is unobserved, nothing is launched
+    hipStream_t st = p->stream;
+    DevBuf<uint8_t> held, status;
+    DevBuf<int32_t> partner;
+    DevBuf<uint32_t> into, map;
+    DevBuf<int64_t> counts;
+    DevBuf<unsigned long long> moved;
+    const bool any_held = p->pmask || p->pxw;
+    hipError_t e = status.alloc((size_t)np);
+    if (e == hipSuccess) e = partner.alloc((size_t)np);
+    if (e == hipSuccess) e = into.alloc((size_t)np);
+    if (e == hipSuccess) e = counts.alloc(kMergeKinds);
+    if (e == hipSuccess) e = moved.alloc(1);
+    if (e == hipSuccess && any_held) e = held.alloc((size_t)np);
+    if (e == hipSuccess && merged_into) e = map.alloc((size_t)np);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_merge_points: allocation: %s", hipGetErrorString(e));
+    if (any_held) {
+        hipLaunchKernelGGL(k_merge_held, dim3(blocks_of(np, 256)), dim3(256), 0, st, np, (const uint8_t *)p->pmask, (const double *)p->pxw, held.ptr);
+        LAUNCH_CHECK();
+    }
+    int64_t total = 0;
+    int run = 0;
+    int rc = C2B_OK;
+    while (run < rounds) {
+        rc = ensure_camblk(p);
+        if (!rc) rc = ensure_rows(p);
+        if (!rc) rc = ensure_transpose(p);
+        if (!rc) rc = c2b_merge_partner_rows(p->camblk, p->pts4, np, p->nt_ptr, p->nt_obs, p->nt_cam, p->uv, p->n_obs, radius, max_error,
+                                             any_held ? held.ptr : nullptr, partner, status, counts, st);
+        if (rc) break;
+        unsigned long long m = 0;
+        e = hipMemsetAsync(moved.ptr, 0, 8, st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_merge_apply, dim3(blocks_of(np, 256)), dim3(256), 0, st, reinterpret_cast<double4 *>(p->pts4.ptr), np,
+                               (const uint64_t *)p->nt_ptr, (const int32_t *)partner, into.ptr, moved.ptr);
+            e = launch_error();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&m, moved.ptr, 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        ++run;
+        if (!m) break;                                       // nothing merged: the list, the points and every cache are as they were
+        hipLaunchKernelGGL(k_merge_remap, dim3(blocks_of(p->n_obs, 256)), dim3(256), 0, st, p->pt_idx.ptr, p->n_obs, (const uint32_t *)into);
+        if (merged_into) {
+            if (!total) e = hipMemcpyAsync(map.ptr, into.ptr, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToDevice, st);
+            else hipLaunchKernelGGL(k_merge_remap, dim3(blocks_of(np, 256)), dim3(256), 0, st, map.ptr, np, (const uint32_t *)into);
+        }
+        const hipError_t el = launch_error();
+        if (e == hipSuccess) e = el;
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = es;
+        drop_rows(p);                                        // pt_idx changed: rows' tiles, the transpose and the solve buffers go
+        if (e != hipSuccess) break;
+        total += (int64_t)m;
+    }
+    if (!rc && e == hipSuccess && merged_into && total)
+        e = hipMemcpy(merged_into, map.ptr, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost);
+    if (rc || e != hipSuccess) (void)hipStreamSynchronize(st);
+    if (n_merged) *n_merged = total;
+    if (rounds_run) *rounds_run = run;
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(hip_code(e), "problem_merge_points: %s", hipGetErrorString(e));
+    return C2B_OK;
+    C2B_API_END("problem_merge_points")
+}
+
 // The generators' whole visibility loop (src/synthetic.rs:268-297, :353-378) on the device: candidates by a cell list
 // (rstar's locate_within_distance), the sight line against the buildings (hits_building), the predicate, and the kept
 // (point, uv) lists compacted per camera in ascending point index -- csrc/cell_kernels.hpp.  The result becomes the

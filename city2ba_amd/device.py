@@ -325,6 +325,17 @@ def resect_consensus_rows(bal9, pts4, rows, pt_idx, uv, status, counts, max_erro
     return status, counts
 
 
+def merge_partner_rows(camblk, pts4, prows, uv, partner, status, counts, radius, max_error, pt_held=None):
+    """one round's partner choice of landmark merging (c2b_merge_partner_rows): partner [n_pts] int32 = the nearest other
+    point within `radius` that shares no camera with the point and whose merged position reprojects every observation of
+    both within max_error in front of its camera, or -1; status [n_pts] uint8 (_lib.MERGE_STATUS order), counts [4] int64;
+    pt_held [n_pts] uint8 (1 = takes no part) or None.  pts4 is only read.  Synchronises the stream."""
+    L.check(L.lib().c2b_merge_partner_rows(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of),
+                                           _p(uv), prows.n_obs, float(radius), float(max_error), _p(pt_held), _p(partner), _p(status),
+                                           _p(counts), _stream()))
+    return partner, status, counts
+
+
 def residual_jacobian_rows(camblk, pts4, rows, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None, out_sum=None, obs_base=0,
                            n_obs=None):
     """residual + Jacobian (+ sum |r|^norm when ws is given: into out_sum, or into ws for error_sum_finish) of the

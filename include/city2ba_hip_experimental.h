@@ -538,6 +538,61 @@ int c2b_resect_consensus_rows(double *bal9, const double *pts4, const uint64_t *
 int c2b_problem_resect_consensus(c2b_problem *p, double max_error, int min_inliers, double min_gap, int max_hypotheses, int flags,
                                  uint8_t *status, int32_t *hyp, int32_t *n_inl, uint8_t *inlier, int64_t *counts, int64_t *n_removed);
 
+/* ---- landmark merging: two points that are one landmark put back together (the repair of split_landmarks) ----
+ * split_landmarks, like a matcher that breaks a track, leaves two points where one belongs, with the observations dealt
+ * between them.  This pass finds such pairs and joins them: the two points are close, no camera sees both, and one position
+ * explains every observation of both.  Notation: point p's row of the transpose (every entry counts, usable or not), R2 =
+ * radius * radius and E2 = max_error * max_error each formed once on the host.  One ROUND on a state (cameras, points, the
+ * camera-major list and its transpose):
+ *   C2B_MERGE_HELD       p is constant under pt_held (Level 1: under the point mask, or it carries a point prior with a
+ *                        non-zero weight); it takes no part: it is nobody's candidate and gets no partner.
+ *   C2B_MERGE_UNOBSERVED p's row is empty; it takes no part either.
+ *   candidates of p      every other point q that takes part with d2(p, q) <= R2, where d2 = (dx * dx + dy * dy) + dz * dz
+ *                        (five unfused operations; dx and -dx square alike, so d2(p, q) and d2(q, p) are the same bits; a
+ *                        NaN compares false), ordered by (d2, q) ascending -- d2 >= 0, its bit pattern orders it.
+ *   verified pair        with a = min(p, q), b = max(p, q), na and nb the lengths of their rows:
+ *                        (i)  no camera index occurs in both rows;
+ *                        (ii) with f = nb / (na + nb) and per coordinate m = a + (b - a) * f (a subtraction, a product, a
+ *                             sum, unfused, the lower index first: twins with equal bits give m == a exactly), EVERY entry of
+ *                             both rows is one that c2b_residual_keep_rows with C2B_FILTER_IN_FRONT would keep at m: du * du +
+ *                             dv * dv <= E2 && q.z < 0 (a NaN fails).
+ *   C2B_MERGE_CHOSEN     partner[p] = the first verified candidate in that order;
+ *   C2B_MERGE_NONE       there is none: partner[p] = -1 (also under HELD and UNOBSERVED).
+ *   merge                for every pair with partner[partner[p]] == p, a < b: pts[a].xyz = m, the fourth lane keeps its value;
+ *                        every pt_idx == b becomes a; pts[b] keeps its bits and is now unobserved.  Nothing is renumbered
+ *                        and no count changes: uv, the row pointer and the order inside every camera's row stay bit for bit.
+ * Only mutual choices merge, so the result does not depend on the launch shape or on the order the points are visited, and
+ * a chain a-b-c is never merged in one round; the closest verified pair of all is always mutual, so a round that can merge
+ * does.  No float atomics, no scratch memory.  The cost is that of the neighbourhoods: all points within one radius of each
+ * other cost O(n_pts^2) candidate tests, and nothing bounds that.
+ * c2b_merge_partner_rows: Level 0, the partner choice of one round.  camblk, pts4 and the transpose as c2b_triangulate_rows
+ *   takes them (pts4 is only read), n_obs the length of the list obs_of indexes; pt_held (device, one byte per point) may be
+ *   NULL; partner [n_pts] (device int32), status [n_pts] (device, one byte), counts [4] (device int64, indexed by status,
+ *   zeroed and then summed by integer atomics).  The pass builds its own cell list over x / z from the extent of the points
+ *   (cells of radius (1 + 2^-20), doubled until there are at most 2^24: the result does not depend on the grid), frees it
+ *   and therefore SYNCHRONISES `stream` before it returns.  radius = 0 is valid (exact twins have d2 = 0); n_pts = 0 launches
+ *   nothing.  radius or max_error negative, NaN or infinite, n_pts >= 2^31: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_problem_merge_points: Level 1, synchronous: rounds >= 1 rounds on the resident problem, each on the state the last one
+ *   left with the transpose rebuilt; a round that merges nothing ends the loop (and counts in *rounds_run).  The preconditions
+ *   and caches follow c2b_problem_triangulate_consensus with C2B_TRI_DROP_OUTLIERS: a shard is refused; a bad argument (also
+ *   rounds < 1) is refused with the problem unchanged; a problem without observations merges nothing and launches nothing;
+ *   after a round that merged, what was derived from the list is rebuilt by its next user and nothing else goes -- cameras,
+ *   masks, priors, loss, preconditioner, checkpoint and LM scratch stay, as c2b_problem_filter_observations leaves them;
+ *   after a round that merged nothing no cache is dropped.  merged_into [n_pts] (host, may be NULL): the point that p's
+ *   observations ended on, composed over the rounds, p itself when p was not absorbed; *n_merged (may be NULL) = how many
+ *   points were absorbed; *rounds_run (may be NULL).  Absorbed points STAY in the table as unobserved points (the LM step
+ *   gives them a zero step); nothing is culled here, because a cull renumbers and drops the masks: c2b_problem_cull is the
+ *   caller's call. */
+#define C2B_MERGE_NONE 0
+#define C2B_MERGE_CHOSEN 1
+#define C2B_MERGE_UNOBSERVED 2
+#define C2B_MERGE_HELD 3
+int c2b_merge_partner_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                           const uint32_t *cam_of, const double *uv_obs, int64_t n_obs, double radius, double max_error,
+                           const uint8_t *pt_held, int32_t *partner, uint8_t *status, int64_t *counts, void *stream);
+int c2b_problem_merge_points(c2b_problem *p, double radius, double max_error, int rounds, int32_t *merged_into, int64_t *n_merged,
+                             int *rounds_run);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
