@@ -110,6 +110,10 @@ RES_DROP_OUTLIERS = 1      # C2B_RES_DROP_OUTLIERS: compact the list by the inli
 MERGE_NONE, MERGE_CHOSEN, MERGE_UNOBSERVED, MERGE_HELD = range(4)
 MERGE_STATUS = ("none", "chosen", "unobserved", "held")
 
+# statuses of c2b_rematch_rows (C2B_REMATCH_*), the order of its counts
+REMATCH_FITS, REMATCH_SKIPPED, REMATCH_REASSIGNED, REMATCH_REMOVED = range(4)
+REMATCH_STATUS = ("fits", "skipped", "reassigned", "removed")
+
 
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
 SIGNATURES = {
@@ -146,6 +150,7 @@ SIGNATURES = {
     "c2b_resect_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp]),
     "c2b_resect_consensus_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _int, _d, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_merge_partner_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_rematch_rows": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp]),
     "c2b_reprojection_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "c2b_add_noise_observations_error_sums2_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _d, _u64, _vp, _vp, _vp]),
     "c2b_jacobian_stream_policy": (_int, [_i64, _i64, _i64]),
@@ -184,6 +189,7 @@ SIGNATURES = {
     "c2b_problem_resect_cameras": (_int, [_vp, _int, _d, _vp, _vp]),
     "c2b_problem_resect_consensus": (_int, [_vp, _d, _int, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_merge_points": (_int, [_vp, _d, _d, _int, _vp, C.POINTER(_i64), C.POINTER(_int)]),
+    "c2b_problem_rematch_observations": (_int, [_vp, _d, _d, _int, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
     "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),

@@ -601,6 +601,28 @@ class BAProblem:
         out = dict(merged=int(merged.value), rounds=int(run.value))
         return (out, into) if return_map else out
 
+    def rematch_observations(self, radius, max_error, min_fits=2, return_status=False):
+        """Wrong matches relabelled in place, on the device (c2b_problem_rematch_observations): the repair of
+        add_incorrect_correspondences and join_landmarks that keeps the measurement.  An observation that fits its point
+        (filter_observations' predicate with in_front at max_error) stays; so does one whose point fewer than min_fits
+        observations fit or that is not finite (skipped: nothing is judged about such a point, and nothing assigned to it).
+        Every other observation gives its label up and takes the trusted point it fits best among the points within `radius`
+        of the one it named and the labels the other failing observations of its camera gave up, unless an observation of
+        that camera that stays already names it; of two observations of a camera that want one point the better fit gets it.
+        Whoever is left without a point is removed, as the filter would remove it.  Cameras and points neither move nor are
+        renumbered, the survivors keep their order and the bits of their pixels, and the constant masks, the priors, the
+        loss, the preconditioner and a checkpoint stay.  Returns dict(fits, skipped, reassigned, removed); with
+        return_status also the uint8 status [n_obs before the call] (_lib.REMATCH_STATUS order)."""
+        status = np.zeros(self.num_observations(), dtype=np.uint8)
+        reassigned, removed = C.c_int64(), C.c_int64()
+        L.check(L.lib().c2b_problem_rematch_observations(self._h, float(radius), float(max_error), int(min_fits),
+                                                         status.ctypes.data_as(C.c_void_p), C.byref(reassigned), C.byref(removed)))
+        if reassigned.value or removed.value:
+            self._refresh_graph()
+        out = dict(zip(L.REMATCH_STATUS, (int(v) for v in np.bincount(status, minlength=4))))
+        assert (out["reassigned"], out["removed"]) == (reassigned.value, removed.value)
+        return (out, status) if return_status else out
+
     def _status_pass(self, entry, args, n, names, return_status):
         """entry(handle, *args, status, counts) over n entities: the counts as a dict under `names`, and the status bytes"""
         counts = np.zeros(len(names), dtype=np.int64)

@@ -34,6 +34,9 @@
 //   city2ba merge IN OUT --radius R --max-error X [--rounds N]
 //                        (extension: duplicate landmarks merged, the repair of --split-landmarks, c2b_problem_merge_points;
 //                         the absorbed points stay in the file as unobserved points, nothing is culled)
+//   city2ba rematch IN OUT --radius R --max-error X [--min-fits N]
+//                        (extension: wrong point indices put right, the repair of --mismatch-chance and --join-landmarks that
+//                         keeps the observation, c2b_problem_rematch_observations; whoever fits no point is removed)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -1108,6 +1111,29 @@ int run_merge(int argc, char **argv) {
     return 0;
 }
 
+// `rematch`: the wrong point indices of a .bal / .bbal put right by c2b_problem_rematch_observations (an extension: the repair
+// of `noise --mismatch-chance` and `--join-landmarks` that keeps the measurement; cameras, points and the surviving pixels are
+// written as they were read).  Every argument is parsed before the device is touched.  Nothing is culled.
+int run_rematch(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {}, {"radius", "max-error", "min-fits", "device"});
+    if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
+    if (!a.has("radius") || !a.has("max-error")) die("The following required arguments were not provided:\n    --radius <R> --max-error <X>");
+    const double radius = a.f("radius", 0.0), max_error = a.f("max-error", 0.0);
+    const int64_t min_fits = a.i("min-fits", 2);
+    const int device = (int)a.i("device", 0);
+    if (!(radius >= 0.0 && std::isfinite(radius))) die("Invalid value for '--radius <R>': expected a finite number >= 0");
+    if (!(max_error >= 0.0 && std::isfinite(max_error))) die("Invalid value for '--max-error <X>': expected a finite number >= 0");
+    if (min_fits > 1000000) die("Invalid value for '--min-fits <N>': expected an integer in 0 ... 1000000");      // (the parser refuses a negative one)
+    PhaseTimer timer;
+    int64_t nc = 0, np = 0, no = 0, reassigned = 0, removed = 0;
+    c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
+    ck(c2b_problem_rematch_observations(p, radius, max_error, (int)min_fits, nullptr, &reassigned, &removed));
+    timer.mark("rematch_observations (device)");
+    std::printf("reassigned %lld observations and removed %lld of %lld; nothing is culled\n", (long long)reassigned, (long long)removed, (long long)no);
+    close_problem(timer, p, a.positional[1]);
+    return 0;
+}
+
 void usage() {
     std::printf("city2ba (MI355X build, %s)\nTools for generating synthetic bundle adjustment problems.\n\n"
                 "USAGE:\n    city2ba <SUBCOMMAND>\n\nSUBCOMMANDS:\n"
@@ -1119,7 +1145,8 @@ void usage() {
                 "    solve             Bundle-adjust a .bal or .bbal by Levenberg-Marquardt on the device.\n"
                 "    triangulate       Set the points of a .bal or .bbal from its cameras and observations.\n"
                 "    resect            Set the camera poses of a .bal or .bbal from its points and observations.\n"
-                "    merge             Merge the duplicate landmarks of a .bal or .bbal (the repair of noise --split-landmarks).\n",
+                "    merge             Merge the duplicate landmarks of a .bal or .bbal (the repair of noise --split-landmarks).\n"
+                "    rematch           Put the wrong point indices of a .bal or .bbal right (the repair of noise --mismatch-chance).\n",
                 c2b_version());
 }
 
@@ -1198,6 +1225,14 @@ const char *subcommand_help(const std::string &sub) {
                "                              within X of the merged position, in front of its camera (required)\n"
                "    --rounds <N> [1]          rounds, each on the result of the last; a round that merges nothing is the last\n"
                "                              The absorbed points are not culled: they stay in the file as unobserved points.\n";
+    if (sub == "rematch")
+        return "city2ba rematch <FILE> <OUT>\n"
+               "    --radius <R>              an observation that does not fit its point may take a point at most R from it, or a\n"
+               "                              point that another such observation of the same camera gives up (required)\n"
+               "    --max-error <X>           an observation fits a point when it reprojects within X of it, in front of its camera\n"
+               "                              (required)\n"
+               "    --min-fits <N> [2]        points that fewer than N observations fit are neither judged nor assigned\n"
+               "                              An observation that fits no such point is removed.  Nothing is culled.\n";
     return nullptr;
 }
 
@@ -1224,5 +1259,6 @@ int main(int argc, char **argv) {
     if (sub == "triangulate") return run_triangulate(argc, argv);
     if (sub == "resect") return run_resect(argc, argv);
     if (sub == "merge") return run_merge(argc, argv);
+    if (sub == "rematch") return run_rematch(argc, argv);
     die("The subcommand '" + sub + "' wasn't recognized");
 }

@@ -44,6 +44,7 @@
 #include "cull_kernels.hpp"
 #include "cell_kernels.hpp"
 #include "merge_kernels.hpp"
+#include "rematch_kernels.hpp"
 #include "text_kernels.hpp"
 #include "comm_rccl.hpp"
 

@@ -576,9 +576,55 @@ static double merge_key_value(unsigned long long k) {
     return v;
 }
 
-// One round's partner choice over a point-major transpose: the cell list over x / z is built here, from the extent of the
-// finite points, with cells of radius (1 + 2^-20) doubled as cell_grid_from_stats doubles them -- the result does not depend
-// on the grid.  The temporaries are freed on return, so the call synchronises `stream` as a scan does.
+// The x / z cell list of a point table for a search within `radius` (merging, re-matching): the grid comes from the extent of
+// the finite points, with cells of radius (1 + 2^-20) doubled as cell_grid_from_stats doubles them, so a result never depends
+// on it.  Its temporaries and whatever else the caller names in `extra` (called with the each(buffer, count) of the arena's two
+// passes) are ONE allocation, freed with the object: the caller synchronises before it lets go of it.
+extern "C++" {
+struct PointCells {
+    CellGrid g;
+    DevArena arena;
+    DevBuf<uint32_t> cell_of, cnt, start, sorted, tiles, total;
+    DevBuf<unsigned long long> ext;
+};
+template <class Extra>
+static int build_point_cells(hipStream_t st, const char *who, const double4 *pos4, int64_t n_pts, double radius, PointCells &pc, Extra &&extra) {
+    // the extent of the points -> the cell grid
+    const unsigned long long ext0[4] = {~0ull, ~0ull, 0ull, 0ull};
+    unsigned long long ext_h[4] = {0, 0, 0, 0};
+    HIP_TRY(pc.ext.alloc(4));
+    HIP_TRY(hipMemcpyAsync(pc.ext.ptr, ext0, sizeof ext0, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_merge_extent, dim3(std::min(blocks_of(n_pts, 256), 1024u)), dim3(256), 0, st, pos4, n_pts, pc.ext.ptr);
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(ext_h, pc.ext.ptr, sizeof ext_h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    double stats[C2B_STATS_DOUBLES] = {0.0};
+    if (ext_h[2] != 0ull) {                                  // (no finite point: one cell at the origin, and no pair)
+        stats[6] = merge_key_value(ext_h[0]); stats[8] = merge_key_value(ext_h[1]);
+        stats[9] = merge_key_value(ext_h[2]); stats[11] = merge_key_value(ext_h[3]);
+    }
+    int64_t n_cells = 0;
+    int rc = cell_grid_from_stats(stats, radius, who, &pc.g, &n_cells);
+    if (rc) return rc;
+    auto temporaries = [&](auto &&each) {
+        each(pc.cell_of, (size_t)n_pts); each(pc.cnt, (size_t)(n_cells + 1)); each(pc.start, (size_t)(n_cells + 1));
+        each(pc.sorted, (size_t)n_pts); each(pc.tiles, (size_t)((n_cells + 1) / kScanTile + 2)); each(pc.total, (size_t)1);
+        extra(each);
+    };
+    size_t arena_bytes = 0;
+    temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
+    const hipError_t ea = pc.arena.reserve(arena_bytes);
+    if (ea != hipSuccess) return fail(hip_code(ea), "%s: %s", who, hipGetErrorString(ea));
+    temporaries([&](auto &b, size_t n) { pc.arena.carve(b, n); });
+    HIP_TRY(hipMemsetAsync(pc.cnt.ptr, 0, 4 * (size_t)(n_cells + 1), st));
+    rc = build_cell_list(st, who, pos4, n_pts, pc.g, n_cells, pc.cell_of, pc.cnt, pc.start, pc.sorted, pc.tiles, pc.total);
+    if (rc) (void)hipStreamSynchronize(st);
+    return rc;
+}
+}  // extern "C++"
+
+// One round's partner choice over a point-major transpose: the cell list over x / z is built here (build_point_cells).  The
+// temporaries are freed on return, so the call synchronises `stream` as a scan does.
 int c2b_merge_partner_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
                            const uint32_t *cam_of, const double *uv_obs, int64_t n_obs, double radius, double max_error,
                            const uint8_t *pt_held, int32_t *partner, uint8_t *status, int64_t *counts, void *stream) {
@@ -596,42 +642,11 @@ int c2b_merge_partner_rows(const double *camblk, const double *pts4, int64_t n_p
     HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kMergeKinds, st));
     if (!n_pts) return C2B_OK;
     const double4 *pos4 = reinterpret_cast<const double4 *>(pts4);
-    // the extent of the points -> the cell grid
-    DevBuf<unsigned long long> ext;
-    const unsigned long long ext0[4] = {~0ull, ~0ull, 0ull, 0ull};
-    unsigned long long ext_h[4] = {0, 0, 0, 0};
-    HIP_TRY(ext.alloc(4));
-    HIP_TRY(hipMemcpyAsync(ext.ptr, ext0, sizeof ext0, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_merge_extent, dim3(std::min(blocks_of(n_pts, 256), 1024u)), dim3(256), 0, st, pos4, n_pts, ext.ptr);
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(ext_h, ext.ptr, sizeof ext_h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    double stats[C2B_STATS_DOUBLES] = {0.0};
-    if (ext_h[2] != 0ull) {                                  // (no finite point: one cell at the origin, and no pair)
-        stats[6] = merge_key_value(ext_h[0]); stats[8] = merge_key_value(ext_h[1]);
-        stats[9] = merge_key_value(ext_h[2]); stats[11] = merge_key_value(ext_h[3]);
-    }
-    CellGrid g;
-    int64_t n_cells = 0;
-    int rc = cell_grid_from_stats(stats, radius, "merge_partner_rows", &g, &n_cells);
+    PointCells cells;
+    const int rc = build_point_cells(st, "merge_partner_rows", pos4, n_pts, radius, cells, [](auto &&) {});
     if (rc) return rc;
-    DevArena arena;
-    DevBuf<uint32_t> cell_of, cnt, startb, sorted, tiles, total;
-    auto temporaries = [&](auto &&each) {
-        each(cell_of, (size_t)n_pts); each(cnt, (size_t)(n_cells + 1)); each(startb, (size_t)(n_cells + 1));
-        each(sorted, (size_t)n_pts); each(tiles, (size_t)((n_cells + 1) / kScanTile + 2)); each(total, (size_t)1);
-    };
-    size_t arena_bytes = 0;
-    temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
-    const hipError_t ea = arena.reserve(arena_bytes);
-    if (ea != hipSuccess) return fail(hip_code(ea), "merge_partner_rows: %s", hipGetErrorString(ea));
-    temporaries([&](auto &b, size_t n) { arena.carve(b, n); });
-    HIP_TRY(hipMemsetAsync(cnt.ptr, 0, 4 * (size_t)(n_cells + 1), st));
-    rc = build_cell_list(st, "merge_partner_rows", pos4, n_pts, g, n_cells, cell_of, cnt, startb, sorted, tiles, total);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
+    const CellGrid g = cells.g;
+    const DevBuf<uint32_t> &startb = cells.start, &sorted = cells.sorted;
     hipLaunchKernelGGL(k_merge_partner, dim3(blocks_for(n_pts, kMrgWaves)), dim3(kMrgBlock), 0, st, camblk, pos4, n_pts, pt_row_ptr, obs_of,
                        cam_of, reinterpret_cast<const double2 *>(uv_obs), g, (const uint32_t *)startb, (const uint32_t *)sorted,
                        radius * radius, max_error * max_error, pt_held, partner, status, reinterpret_cast<unsigned long long *>(counts));
@@ -725,6 +740,147 @@ int c2b_problem_merge_points(c2b_problem *p, double radius, double max_error, in
     if (e != hipSuccess) return fail(hip_code(e), "problem_merge_points: %s", hipGetErrorString(e));
     return C2B_OK;
     C2B_API_END("problem_merge_points")
+}
+
+// ---- guided re-matching (rematch_kernels.hpp) ------------------------------------------------------------------
+// The choice and its resolution over a camera-major list, given the filter's mask of it (`fits`) and the points that may be
+// judged or assigned (`pt_trusted`; NULL: every finite point).  The cell list over x / z is built here (build_point_cells);
+// the temporaries are freed on return, so the call synchronises `stream` as c2b_merge_partner_rows does.
+int c2b_rematch_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                     const double *uv_obs, int64_t n_obs, const uint8_t *fits, const uint8_t *pt_trusted, double radius, double max_error,
+                     int32_t *choice, uint8_t *status, int64_t *counts, void *stream) {
+    C2B_API_BEGIN
+    if (!good_merge_length(radius)) return fail(C2B_ERR_INVALID_ARGUMENT, "rematch_rows: radius must be finite and >= 0");
+    if (!good_merge_length(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "rematch_rows: max_error must be finite and >= 0");
+    if (n_pts < 0 || n_pts >= ((int64_t)1 << 31)) return fail(C2B_ERR_INVALID_ARGUMENT, "rematch_rows: n_pts out of range");
+    if (n_cam < 0 || n_cam >= ((int64_t)1 << 32)) return fail(C2B_ERR_INVALID_ARGUMENT, "rematch_rows: n_cam out of range");
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 64)        // (a row's length and its chunk offsets are ints in the kernel)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "rematch_rows: n_obs out of range");
+    if (n_obs && (!n_pts || !n_cam)) return fail(C2B_ERR_INVALID_ARGUMENT, "rematch_rows: observations without points or cameras");
+    if (!counts || (n_obs && (!camblk || !pts4 || !row_ptr || !pt_idx || !uv_obs || !fits || !choice || !status)))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "rematch_rows: NULL argument");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(row_ptr) || !aligned8(counts) ||
+        (reinterpret_cast<uintptr_t>(pt_idx) & 3) || (reinterpret_cast<uintptr_t>(choice) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "rematch_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kRematchKinds, st));
+    if (!n_obs) return C2B_OK;
+    const double4 *pos4 = reinterpret_cast<const double4 *>(pts4);
+    PointCells cells;
+    DevBuf<unsigned long long> r2bits;
+    DevBuf<uint8_t> finite;
+    const int rc = build_point_cells(st, "rematch_rows", pos4, n_pts, radius, cells, [&](auto &&each) {
+        each(r2bits, (size_t)n_obs);
+        if (!pt_trusted) each(finite, (size_t)n_pts);
+    });
+    if (rc) return rc;
+    if (!pt_trusted) {
+        hipLaunchKernelGGL(k_rematch_trusted, dim3(blocks_of(n_pts, 256)), dim3(256), 0, st, pos4, n_pts, (const uint64_t *)nullptr,
+                           (const uint32_t *)nullptr, (const uint8_t *)nullptr, 0, finite.ptr);
+        pt_trusted = finite.ptr;
+    }
+    hipLaunchKernelGGL(k_rematch_choose, dim3(blocks_for(n_cam, kRmtWaves)), dim3(kRmtBlock), 0, st, camblk, pos4, row_ptr, n_cam, pt_idx,
+                       reinterpret_cast<const double2 *>(uv_obs), fits, pt_trusted, cells.g, (const uint32_t *)cells.start.ptr,
+                       (const uint32_t *)cells.sorted.ptr, radius * radius, max_error * max_error, choice, r2bits.ptr, status);
+    hipLaunchKernelGGL(k_rematch_resolve, dim3(blocks_for(n_cam, kRmtWaves)), dim3(kRmtBlock), 0, st, row_ptr, n_cam, (const int32_t *)choice,
+                       (const unsigned long long *)r2bits.ptr, status, reinterpret_cast<unsigned long long *>(counts));
+    const hipError_t el = launch_error(), es = hipStreamSynchronize(st);          // the arena is freed on return
+    if (el != hipSuccess || es != hipSuccess)
+        return fail(hip_code(el != hipSuccess ? el : es), "rematch_rows: %s", hipGetErrorString(el != hipSuccess ? el : es));
+    return C2B_OK;
+    C2B_API_END("rematch_rows")
+}
+
+// Re-matching on the resident problem: the filter's mask, the trusted points over the cached transpose, the
+// choice, and -- when something was reassigned or removed -- the new labels in a list of their own, compacted by the keep mask
+// as the filter compacts and swapped in (install_observations).  The entities do not move: cameras, points, both counts, the
+// masks, the priors, the loss, the preconditioner, the checkpoint and the LM scratch stay; what was derived from the list
+// (drop_rows) goes, and only after a call that changed it.  A failure leaves the problem as it was.
+int c2b_problem_rematch_observations(c2b_problem *p, double radius, double max_error, int min_fits, uint8_t *status_out,
+                                     int64_t *n_reassigned, int64_t *n_removed) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_rematch_observations");
+    if (!good_merge_length(radius)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_rematch_observations: radius must be finite and >= 0");
+    if (!good_merge_length(max_error)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_rematch_observations: max_error must be finite and >= 0");
+    if (min_fits < 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_rematch_observations: min_fits must be >= 0");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_rematch_observations: a shard is not re-matched alone (a point's observations span every rank)");
+    const int64_t np = p->n_pts, n_old = p->n_obs;
+    if (np >= ((int64_t)1 << 31)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_rematch_observations: too many points");
+    if (n_reassigned) *n_reassigned = 0;
+    if (n_removed) *n_removed = 0;
+    if (!n_old) return C2B_OK;                               // no observation: nothing is launched
+    int rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (!rc) rc = ensure_transpose(p);
+    if (rc) return rc;
+    hipStream_t st = p->stream;
+    DevArena arena;
+    DevBuf<uint8_t> fits, trusted, status, keep;
+    DevBuf<int32_t> choice;
+    DevBuf<int64_t> counts;
+    auto temporaries = [&](auto &&each) {
+        each(counts, (size_t)kRematchKinds); each(choice, (size_t)n_old); each(fits, (size_t)n_old); each(status, (size_t)n_old);
+        each(keep, (size_t)n_old); each(trusted, (size_t)np);
+    };
+    size_t arena_bytes = 0;
+    temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
+    hipError_t e = arena.reserve(arena_bytes);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_rematch_observations: allocation: %s", hipGetErrorString(e));
+    temporaries([&](auto &b, size_t n) { arena.carve(b, n); });
+    rc = c2b_residual_keep_rows(p->camblk, p->pts4, p->rows_ptr, p->n_cam, p->rows_tiles, p->pt_idx, p->uv, n_old, max_error, C2B_FILTER_IN_FRONT,
+                                fits, st);
+    if (!rc) {
+        hipLaunchKernelGGL(k_rematch_trusted, dim3(blocks_of(np, 256)), dim3(256), 0, st, reinterpret_cast<const double4 *>(p->pts4.ptr), np,
+                           (const uint64_t *)p->nt_ptr.ptr, (const uint32_t *)p->nt_obs.ptr, (const uint8_t *)fits.ptr, min_fits, trusted.ptr);
+        rc = c2b_rematch_rows(p->camblk, p->pts4, np, p->rows_ptr, p->n_cam, p->pt_idx, p->uv, n_old, fits, trusted, radius, max_error, choice,
+                              status, counts, st);
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    int64_t cnt[kRematchKinds] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, counts.ptr, sizeof cnt, hipMemcpyDeviceToHost, st));
+    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status.ptr, (size_t)n_old, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_reassigned) *n_reassigned = cnt[kRematchReassigned];
+    if (n_removed) *n_removed = cnt[kRematchRemoved];
+    if (!cnt[kRematchReassigned] && !cnt[kRematchRemoved]) return C2B_OK;          // the list and every cache are as they were
+    DevBuf<uint32_t> pt_new;
+    e = pt_new.alloc((size_t)n_old);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_rematch_apply, dim3(blocks_of(n_old, 256)), dim3(256), 0, st, (const uint32_t *)p->pt_idx.ptr, n_old,
+                           (const int32_t *)choice.ptr, (const uint8_t *)status.ptr, pt_new.ptr, keep.ptr);
+        e = launch_error();
+    }
+    if (e == hipSuccess && !cnt[kRematchRemoved]) {          // labels alone: the new list takes the old one's place
+        e = hipStreamSynchronize(st);
+        if (e == hipSuccess) {
+            p->pt_idx = std::move(pt_new);
+            drop_rows(p);
+            return C2B_OK;
+        }
+    }
+    DevBuf<uint64_t> row_new;
+    DevBuf<uint32_t> pt_kept;
+    DevBuf<double> uv_kept;
+    std::vector<uint64_t> row_host((size_t)p->n_cam + 1);
+    int64_t w = 0;
+    if (e == hipSuccess) e = compact_rows_on_device(p, p->rows_ptr, keep, pt_new, p->uv, p->n_cam, row_host.data(), row_new, pt_kept, uv_kept, &w);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        if (n_reassigned) *n_reassigned = 0;
+        if (n_removed) *n_removed = 0;
+        return fail(hip_code(e), "problem_rematch_observations: %s", hipGetErrorString(e));
+    }
+    rc = install_observations(p, "problem_rematch_observations", w, uv_kept, pt_kept, nullptr, row_new, nothing_more);
+    if (rc) {
+        if (n_reassigned) *n_reassigned = 0;
+        if (n_removed) *n_removed = 0;
+    }
+    return rc;
+    C2B_API_END("problem_rematch_observations")
 }
 
 // The generators' whole visibility loop (src/synthetic.rs:268-297, :353-378) on the device: candidates by a cell list

@@ -91,11 +91,13 @@ struct c2b_problem {
 //   resect_cameras             X            truth      -     -          -      -             -           -
 //   resect_consensus (6)       X            truth      - / X - / X      - / X  -             -           -
 //   merge_points (7)           -            -          - / X - / X      - / X  -             -           -
+//   rematch_observations (8)   -            -          - / X - / X      - / X  -             -           -
 // The priors (c2b_problem_set_priors) share the masks' column: kept and dropped with them, by counts of their own.
 // (1) kept when both counts are those the masks were set for.  (2) gathered with the cameras while it is the truth; a merely
 // fresh bal9 (bal9_fresh: to_vec of the current cameras, filled by download_bal / write / apply_step) is dropped.  (3) on
 // entry, so also by a cull that fails later.  (4) one that removes nothing drops nothing.  (5) checkpoint is an apply_step
-// of no step, then the copy.  (6) with C2B_TRI_DROP_OUTLIERS / C2B_RES_DROP_OUTLIERS and something removed: as the filter.  (7) after every round that merged: as the filter.  A new visibility result
+// of no step, then the copy.  (6) with C2B_TRI_DROP_OUTLIERS / C2B_RES_DROP_OUTLIERS and something removed: as the filter.  (7) after every round that merged: as the filter.
+// (8) after a call that reassigned or removed something: as the filter.  A new visibility result
 // (pairs_compact, within_distance, dense) replaces the pending one only.
 // the cameras moved: every cache of them (apply_step / rollback then make bal9 the truth)
 static void cameras_mutated(c2b_problem *p) { p->bal_valid = false; p->blk_valid = false; p->bal9_fresh = false; }

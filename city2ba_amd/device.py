@@ -336,6 +336,20 @@ def merge_partner_rows(camblk, pts4, prows, uv, partner, status, counts, radius,
     return partner, status, counts
 
 
+def rematch_rows(camblk, pts4, rows, pt_idx, uv, fits, choice, status, counts, radius, max_error, pt_trusted=None):
+    """guided re-matching's choice (c2b_rematch_rows): for every observation that does not fit the point it names -- fits
+    [n_obs] uint8, residual_keep_rows(..., in_front=True) at the same max_error -- and whose point is trusted, choice [n_obs]
+    int32 = the trusted point it fits best among the neighbours of the named point within `radius` and the labels the
+    camera's other failing observations give up, not held by an observation of the camera that stays, or -1; status [n_obs]
+    uint8 (_lib.REMATCH_STATUS order) after the conflicts inside each camera are resolved, counts [4] int64; pt_trusted
+    [n_pts] uint8 or None (every finite point).  Nothing is applied: pts4, pt_idx and uv are only read.  Synchronises the
+    stream."""
+    n_pts = pts4.shape[0]
+    L.check(L.lib().c2b_rematch_rows(_p(camblk), _p(pts4), n_pts, _p(rows.row_ptr), rows.n_cam, _p(pt_idx), _p(uv), rows.n_obs, _p(fits),
+                                     _p(pt_trusted), float(radius), float(max_error), _p(choice), _p(status), _p(counts), _stream()))
+    return choice, status, counts
+
+
 def residual_jacobian_rows(camblk, pts4, rows, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None, out_sum=None, obs_base=0,
                            n_obs=None):
     """residual + Jacobian (+ sum |r|^norm when ws is given: into out_sum, or into ws for error_sum_finish) of the

@@ -593,6 +593,65 @@ int c2b_merge_partner_rows(const double *camblk, const double *pts4, int64_t n_p
 int c2b_problem_merge_points(c2b_problem *p, double radius, double max_error, int rounds, int32_t *merged_into, int64_t *n_merged,
                              int *rounds_run);
 
+/* ---- guided re-matching: an observation with a wrong point index is given the index it fits (the repair of
+ * add_incorrect_correspondences and join_landmarks that keeps the measurement) ----
+ * Both corruptions leave the pixel right and only pt_idx wrong; the filter and C2B_TRI_DROP_OUTLIERS can only remove such an
+ * observation.  This pass finds, for an observation that does not fit the point it names, the nearby point it does fit, and
+ * relabels it.  Notation: E2 = max_error * max_error and R2 = radius * radius, each formed once on the host in double;
+ * fit(o, q) = the predicate of c2b_residual_keep_rows with C2B_FILTER_IN_FRONT for observation o at point q through o's camera:
+ * r2(o, q) = du * du + dv * dv <= E2 && q.z < 0 (unfused; libm's pow when k2 != 0; a NaN fails).  The rules:
+ *   1 fits       fits[o] = fit(o, pt_idx[o]): exactly the byte c2b_residual_keep_rows(..., C2B_FILTER_IN_FRONT) writes.
+ *   2 trusted    nfit[p] = the number of fitting observations of point p; trusted[p] = x, y, z finite && nfit[p] >= min_fits
+ *                (min_fits >= 0; with 0 every finite point is trusted).  Nothing is judged about, or assigned to, a point that
+ *                too few observations agree on.
+ *   3 classes    observation o of camera c with label p = pt_idx[o]: C2B_REMATCH_FITS if fits[o]; else C2B_REMATCH_SKIPPED if
+ *                !trusted[p] -- untouched and kept --; else it is FAILING.  FITS and SKIPPED observations stay, and their
+ *                labels are HELD in c.
+ *   4 candidates of a failing o: every q with trusted[q], q != p, q not held in c, fit(o, q), and one of
+ *                  d2(p, q) = (dx * dx + dy * dy) + dz * dz <= R2 (unfused; the join case: a neighbour of the named point), or
+ *                  q is the label of a failing observation of c (the swap case: failing observations give their labels up,
+ *                  so a swap or a longer cycle inside one camera resolves in one call; it holds also at radius = 0).
+ *   5 choice     choice[o] = the candidate with the smallest key (bits of r2(o, q), q) -- r2 >= 0, its bit pattern orders it --;
+ *                choice[o] = -1 when there is none, and for every observation that is not failing.
+ *   6 conflicts  among the failing observations of c with the same choice the smallest (bits of r2, o) wins and is
+ *                C2B_REMATCH_REASSIGNED; the others, and those without a choice, are C2B_REMATCH_REMOVED.  A loser is not
+ *                offered its second candidate.
+ *   7 apply      (Level 1) pt_idx[o] = choice[o] for REASSIGNED; the list is then compacted by keep = (status != REMOVED)
+ *                exactly as c2b_problem_filter_observations compacts: stable inside every row, nothing renumbered, uv of the
+ *                survivors keeps its bits.  Unplaced observations are always removed: their labels may now belong to a
+ *                winner, and keeping them would let a camera see a point twice.  A list in which no camera sees a point
+ *                twice stays so.
+ *   8 counts     counts[4] = the histogram of the statuses, by integer atomics.
+ *   9            cameras are independent; nothing depends on the launch shape, on the cell grid or on the arrival order of
+ *                the cell fill.
+ * No float atomics, no scratch memory.  The cost is that of the neighbourhoods: one scan of the 3 x 3 cells around the named
+ * point and of the row's failing labels, with a projection per candidate that survives the distance test, for every failing
+ * observation, and a walk of the row for a fitting candidate; nothing bounds that, and a radius of the order of the scene
+ * is the wrong input.
+ * c2b_rematch_rows: Level 0, stateless, on `stream`: rules 3 - 6 and 8.  camblk and pts4 as c2b_residual_keep_rows takes them
+ *   (only read), row_ptr [n_cam + 1] the camera rows of the list pt_idx / uv_obs [n_obs]; fits [n_obs] (device, one byte, rule 1:
+ *   the caller's c2b_residual_keep_rows at the same max_error); pt_trusted [n_pts] (device, one byte per point, rule 2, taken as
+ *   given; NULL: every finite point).  It writes choice [n_obs] (device int32), status [n_obs] (device, one byte) and counts [4]
+ *   (device int64, indexed by status, zeroed and then summed).  It builds its own cell list over x / z as
+ *   c2b_merge_partner_rows does, frees it and therefore SYNCHRONISES `stream` before it returns.  radius = 0 is valid (the swap
+ *   case alone, and exact twins); n_obs = 0 launches nothing.  radius or max_error negative, NaN or infinite, n_pts >= 2^31,
+ *   n_obs > 2^31 - 65: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_problem_rematch_observations: Level 1, synchronous: rules 1 - 8 on the resident problem.  radius or max_error negative,
+ *   NaN or infinite, min_fits < 0 and a shard are refused with the problem unchanged; a problem without observations launches
+ *   nothing and its counts are zero.  status_out [n_obs before the call] (host, may be NULL); *n_reassigned, *n_removed (may
+ *   be NULL).  A call that reassigned or removed something drops what was derived from the list and nothing else -- cameras,
+ *   points, masks, priors, loss, preconditioner, checkpoint and LM scratch stay, as c2b_problem_filter_observations leaves
+ *   them --; a call that changes nothing drops no cache.  A failure leaves the problem as it was. */
+#define C2B_REMATCH_FITS 0
+#define C2B_REMATCH_SKIPPED 1
+#define C2B_REMATCH_REASSIGNED 2
+#define C2B_REMATCH_REMOVED 3
+int c2b_rematch_rows(const double *camblk, const double *pts4, int64_t n_pts, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
+                     const double *uv_obs, int64_t n_obs, const uint8_t *fits, const uint8_t *pt_trusted, double radius, double max_error,
+                     int32_t *choice, uint8_t *status, int64_t *counts, void *stream);
+int c2b_problem_rematch_observations(c2b_problem *p, double radius, double max_error, int min_fits, uint8_t *status_out,
+                                     int64_t *n_reassigned, int64_t *n_removed);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
