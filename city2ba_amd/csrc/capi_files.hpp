@@ -136,9 +136,9 @@ int c2b_problem_write(c2b_problem *p, const char *path, int format) {
         char head[80];
         const int head_len = std::snprintf(head, sizeof head, "%lld %lld %lld\n", (long long)n_cam, (long long)n_pts, (long long)n_obs);
         DevBuf<uint32_t> tl;                                 // the tiles' byte counts
-        DevBuf<uint64_t> tb, total;                          // their bases in the image; its size
+        DevBuf<uint64_t> tb, total;                          // their bases in the image (+ the scan's scratch); its size
         hipError_t e = tl.alloc((size_t)(n_tiles + 1));
-        if (e == hipSuccess) e = tb.alloc((size_t)(n_tiles + 1));
+        if (e == hipSuccess) e = tb.alloc((size_t)(n_tiles + 1) + scan_scratch_count(n_tiles));
         if (e == hipSuccess) e = total.alloc(1);
         if (e != hipSuccess) return fail(hip_code(e), "problem_write: %s", hipGetErrorString(e));
         const uint32_t *ci = (const uint32_t *)p->cam_idx, *pi = (const uint32_t *)p->pt_idx;
@@ -149,7 +149,7 @@ int c2b_problem_write(c2b_problem *p, const char *path, int format) {
                                       tl + t_obs, (const uint64_t *)nullptr, (char *)nullptr);
         if (t_pts) hipLaunchKernelGGL((k_text_vals<false>), dim3((unsigned)t_pts), dim3(kTextTile), 0, st, (const double *)p->pts4, n_pts, 3, 4, T,
                                       tl + t_obs + t_cam, (const uint64_t *)nullptr, (char *)nullptr);
-        hipLaunchKernelGGL(k_text_tile_bases, dim3(1), dim3(1024), 0, st, (const uint32_t *)tl, n_tiles, (uint64_t)head_len, tb, total);
+        scan_tiled(st, (const uint32_t *)tl, n_tiles, (uint64_t)head_len, tb.ptr, total.ptr, tb.ptr + n_tiles + 1);
         e = launch_error();
         uint64_t bytes = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&bytes, total.ptr, 8, hipMemcpyDeviceToHost, st);
@@ -332,7 +332,7 @@ static int read_text_device(c2b_problem *p, const char *path, bool *handled) {
     DevBuf<double> t_uv, t_bal, t_pts;
     hipError_t e = raw.alloc(padded);
     if (e == hipSuccess) e = cnt.alloc((size_t)n_tiles);
-    if (e == hipSuccess) e = base.alloc((size_t)n_tiles);
+    if (e == hipSuccess) e = base.alloc((size_t)n_tiles + scan_scratch_count(n_tiles));         // the tiles' first token + the scan's scratch
     if (e == hipSuccess) e = total.alloc(1);
     if (e == hipSuccess) e = flags.alloc(4);
     if (e == hipSuccess) e = t_cam.alloc((size_t)no);
@@ -349,7 +349,7 @@ static int read_text_device(c2b_problem *p, const char *path, bool *handled) {
     if (io == 1) return fail(C2B_ERR_HIP, "problem_read: host-to-device copy failed");
     if (io) return C2B_OK;                                   // unreadable: the host path says so
     hipLaunchKernelGGL(k_text_count_tokens, dim3((unsigned)n_tiles), dim3(kTextTile), 0, st, raw, (int64_t)bytes, cnt);
-    hipLaunchKernelGGL(k_text_tile_bases, dim3(1), dim3(1024), 0, st, cnt, n_tiles, (uint64_t)0, base, total);
+    scan_tiled(st, (const uint32_t *)cnt, n_tiles, (uint64_t)0, base.ptr, total.ptr, base.ptr + n_tiles);
     e = launch_error();
     uint64_t n_tokens = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&n_tokens, total.ptr, 8, hipMemcpyDeviceToHost, st);
@@ -377,7 +377,7 @@ static int read_text_device(c2b_problem *p, const char *path, bool *handled) {
         if (e == hipSuccess) e = v2.alloc((size_t)n);
         if (e == hipSuccess) e = hist.alloc((size_t)n_hist);
         if (e == hipSuccess) e = offs.alloc((size_t)n_hist);
-        if (e == hipSuccess) e = tiles.alloc((size_t)(n_hist / kScanTile + 2));
+        if (e == hipSuccess) e = tiles.alloc(scan_scratch_count(n_hist));
         if (e == hipSuccess) e = total32.alloc(1);
         if (e == hipSuccess) e = s_cam.alloc((size_t)n);
         if (e == hipSuccess) e = s_pt.alloc((size_t)n);

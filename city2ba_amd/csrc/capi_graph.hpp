@@ -44,13 +44,11 @@ namespace {
 
 unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
 
-// exclusive scan of n 0/1 flags into pos; *total_host = number of set flags.  Synchronises.
+// exclusive scan of n flags or counts into pos (the tiled form; tile_scratch: scan_scratch_count(n) words); *total_host =
+// their sum.  Synchronises.
 hipError_t scan_flags(hipStream_t st, const uint32_t *flags, int64_t n, uint32_t *pos, uint32_t *tile_scratch, uint32_t *d_total,
                       uint32_t *total_host) {
-    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
-    if (n > 0) hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)tiles), dim3(kScanBlock), 0, st, flags, n, pos, tile_scratch);
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, st, tile_scratch, tiles, d_total);
-    if (n > 0) hipLaunchKernelGGL(k_scan_add, dim3((unsigned)tiles), dim3(kScanBlock), 0, st, pos, n, (const uint32_t *)tile_scratch);
+    scan_tiled(st, flags, n, 0u, pos, d_total, tile_scratch);
     hipError_t e = launch_error();
     if (e == hipSuccess) e = hipMemcpyAsync(total_host, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -114,7 +112,7 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
         each(parent, (size_t)nodes0); each(sets, (size_t)nodes0); each(size, (size_t)nodes0);
         each(keep_c, (size_t)nc0); each(keep_p, (size_t)np0); each(keep_o, (size_t)no0);
         each(pos_c, (size_t)nc0); each(pos_p, (size_t)np0); each(pos_o, (size_t)no0);
-        each(tiles, (size_t)(big0 / kScanTile + 2)); each(best, (size_t)1); each(total, (size_t)1); each(deg, (size_t)nc0); each(cnt, (size_t)np0);
+        each(tiles, scan_scratch_count(big0)); each(best, (size_t)1); each(total, (size_t)1); each(deg, (size_t)nc0); each(cnt, (size_t)np0);
     };
     size_t arena_bytes = 0;
     temporaries([&](auto &b, size_t n) { arena_bytes += DevArena::room(b, n); });
@@ -323,7 +321,7 @@ static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_o
     if (e != hipSuccess) return e;
     const unsigned row_blocks = (unsigned)((n_cam + 3) / 4);
     if (n_cam) hipLaunchKernelGGL(k_keep_row_counts, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, d_keep, n_cam, d_tot);
-    hipLaunchKernelGGL(k_dense_cam_scan, dim3(1), dim3(256), 0, p->stream, (const uint64_t *)d_tot, n_cam, row_new);
+    scan_short(p->stream, (const uint64_t *)d_tot, n_cam, (uint64_t)0, row_new.ptr, row_new.ptr + n_cam);      // cameras: one workgroup
     e = hipMemcpyAsync(row_ptr_host, row_new, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     if (e != hipSuccess) return e;
@@ -558,7 +556,7 @@ static int build_cell_list(hipStream_t st, const char *who, const double4 *pos4,
     if (e == hipSuccess && (int64_t)n_sorted != n) return fail(C2B_ERR_HIP, "%s: cell counts do not add up", who);
     if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 4 * (size_t)(n_cells + 1), st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_cells_fill, dim3(blocks_of(n, 256)), dim3(256), 0, st, (const uint32_t *)cell_of, n, (const uint32_t *)start, counts, sorted);
+        hipLaunchKernelGGL(k_bucket_fill<uint32_t>, dim3(blocks_of(n, 256)), dim3(256), 0, st, (const uint32_t *)cell_of, n, n_cells, (const uint32_t *)start, counts, sorted);
         e = launch_error();
     }
     if (e != hipSuccess) return fail(hip_code(e), "%s: %s", who, hipGetErrorString(e));
@@ -608,7 +606,7 @@ static int build_point_cells(hipStream_t st, const char *who, const double4 *pos
     if (rc) return rc;
     auto temporaries = [&](auto &&each) {
         each(pc.cell_of, (size_t)n_pts); each(pc.cnt, (size_t)(n_cells + 1)); each(pc.start, (size_t)(n_cells + 1));
-        each(pc.sorted, (size_t)n_pts); each(pc.tiles, (size_t)((n_cells + 1) / kScanTile + 2)); each(pc.total, (size_t)1);
+        each(pc.sorted, (size_t)n_pts); each(pc.tiles, scan_scratch_count(n_cells + 1)); each(pc.total, (size_t)1);
         extra(each);
     };
     size_t arena_bytes = 0;
@@ -932,7 +930,7 @@ int c2b_problem_visibility_within_distance(c2b_problem *p, double max_dist, int 
     const int64_t big = std::max(n_cells + 1, n_cam + 1);
     auto temporaries = [&](auto &&each) {
         each(cell_of, (size_t)n_pts); each(counts, (size_t)(n_cells + 1)); each(cursor, (size_t)(n_cells + 1));
-        each(sorted, (size_t)n_pts); each(tiles, (size_t)(big / kScanTile + 2)); each(total, (size_t)1);
+        each(sorted, (size_t)n_pts); each(tiles, scan_scratch_count(big)); each(total, (size_t)1);
         each(cam_count, (size_t)(n_cam + 1)); each(pos, (size_t)(n_cam + 1)); each(sum64, (size_t)1); each(max32, (size_t)1);
     };
     size_t arena_bytes = 0;
@@ -1101,7 +1099,7 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
     if (e == hipSuccess) e = counts.alloc((size_t)(n_cells + 1));
     if (e == hipSuccess) e = startb.alloc((size_t)(n_cells + 1));
     if (e == hipSuccess) e = sorted.alloc((size_t)n_cam);
-    if (e == hipSuccess) e = tiles.alloc((size_t)(big / kScanTile + 2));
+    if (e == hipSuccess) e = tiles.alloc(scan_scratch_count(big));
     if (e == hipSuccess) e = total.alloc(1);
     if (e == hipSuccess) e = cand.alloc((size_t)chunk);
     if (e == hipSuccess) e = ok.alloc((size_t)chunk);

@@ -1247,9 +1247,9 @@ int c2b_visibility_dense_count(const double *camblk, int64_t n_cam, const double
                        reinterpret_cast<const double4 *>(pts4), n_pts, n_tiles, max_dist, tile_counts,
                        (const uint64_t *)nullptr, (uint32_t *)nullptr, (double2 *)nullptr);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_dense_row_scan, dim3((unsigned)n_cam), dim3(256), 0, S(stream), tile_counts, n_tiles, cam_total);
+    hipLaunchKernelGGL(k_dense_row_scan, dim3((unsigned)n_cam), dim3(kScanBlock), 0, S(stream), tile_counts, n_tiles, cam_total);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_dense_cam_scan, dim3(1), dim3(256), 0, S(stream), (const uint64_t *)cam_total, n_cam, row_ptr);
+    scan_short(S(stream), (const uint64_t *)cam_total, n_cam, (uint64_t)0, row_ptr, row_ptr + n_cam);      // cameras: one workgroup
     LAUNCH_CHECK();
     return C2B_OK;
     C2B_API_END("visibility_dense_count")
@@ -1278,11 +1278,13 @@ int c2b_visibility_dense_fill(const double *camblk, int64_t n_cam, const double 
 
 
 // ---- Gauss-Newton diagonal blocks (normal_kernels.hpp) -----------------------------------------------------------
-// temp of c2b_normal_transpose: [cursor: n_pts u32, padded to 16 B] [slots: n_obs u32]
+// temp of c2b_normal_transpose: [tile sums of the scan over the points: nt_scan_words(n_pts) u64, an even number]
+//                               [counts, then cursors: n_pts u32, padded to 16 B] [slots: n_obs u32]
+static int64_t nt_scan_words(int64_t n_pts) { return ((int64_t)scan_scratch_count(n_pts) + 1) / 2 * 2; }
 int64_t c2b_normal_transpose_temp_bytes(int64_t n_obs, int64_t n_pts) {
     if (n_obs < 0) n_obs = 0;
     if (n_pts < 0) n_pts = 0;
-    return ((n_pts + 3) / 4 * 4 + n_obs + 4) * (int64_t)sizeof(uint32_t);
+    return nt_scan_words(n_pts) * (int64_t)sizeof(uint64_t) + ((n_pts + 3) / 4 * 4 + n_obs + 4) * (int64_t)sizeof(uint32_t);
 }
 
 int c2b_normal_transpose(const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx, int64_t n_obs, int64_t n_pts,
@@ -1301,13 +1303,15 @@ int c2b_normal_transpose(const uint64_t *row_ptr, int64_t n_cam, const uint32_t 
         HIP_TRY(hipMemsetAsync(pt_row_ptr, 0, sizeof(uint64_t) * (size_t)(n_pts + 1), st));
         return C2B_OK;
     }
-    uint32_t *cursor = reinterpret_cast<uint32_t *>(temp);
+    uint64_t *tile_sums = reinterpret_cast<uint64_t *>(temp);
+    uint32_t *cursor = reinterpret_cast<uint32_t *>(tile_sums + nt_scan_words(n_pts));
     uint32_t *slots = cursor + (n_pts + 3) / 4 * 4;
     HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(uint32_t) * (size_t)n_pts, st));
     const unsigned go = (unsigned)((n_obs + 255) / 256);
     hipLaunchKernelGGL(k_nt_count, dim3(go), dim3(256), 0, st, pt_idx, n_obs, n_pts, cursor);
-    hipLaunchKernelGGL(k_nt_scan, dim3(1), dim3(kNtScanThreads), 0, st, cursor, n_pts, pt_row_ptr);
-    hipLaunchKernelGGL(k_nt_fill, dim3(go), dim3(256), 0, st, pt_idx, n_obs, n_pts, cursor, slots);
+    scan_tiled(st, (const uint32_t *)cursor, n_pts, (uint64_t)0, pt_row_ptr, pt_row_ptr + n_pts, tile_sums);      // the row-pointer form
+    HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(uint32_t) * (size_t)n_pts, st));
+    hipLaunchKernelGGL(k_bucket_fill<uint64_t>, dim3(go), dim3(256), 0, st, pt_idx, n_obs, n_pts, (const uint64_t *)pt_row_ptr, cursor, slots);
     hipLaunchKernelGGL(k_nt_rank, dim3(go), dim3(256), 0, st, pt_idx, (const uint64_t *)pt_row_ptr, n_pts, (const uint32_t *)slots,
                        row_ptr, (int)n_cam, obs_of, cam_of);
     LAUNCH_CHECK();

@@ -44,14 +44,18 @@ __global__ __launch_bounds__(256) void k_cells_assign(const double4 *__restrict_
     atomicAdd(counts + c, 1u);
 }
 
-// the cell-sorted point list (order inside a cell = arrival order of the atomics; k_rows_rank_sort makes the result
-// independent of it)
-__global__ __launch_bounds__(256) void k_cells_fill(const uint32_t *__restrict__ cell_of, int64_t n, const uint32_t *__restrict__ start,
-                                                   uint32_t *__restrict__ cursor, uint32_t *__restrict__ sorted) {
+// The fill of every count / scan / fill bucket list: element j joins bucket bucket_of[j] at start[bucket] + its arrival
+// number (`cursor` zeroed by the caller); an element whose bucket is not below n_buckets joins none.  The cell-sorted point
+// list (order inside a cell = arrival order of the atomics; k_rows_rank_sort makes the result independent of it) and the
+// slots of the point-major transpose (normal_kernels.hpp; k_nt_rank puts them into the stable order).
+template <class Start>
+__global__ __launch_bounds__(256) void k_bucket_fill(const uint32_t *__restrict__ bucket_of, int64_t n, int64_t n_buckets,
+                                                    const Start *__restrict__ start, uint32_t *__restrict__ cursor,
+                                                    uint32_t *__restrict__ sorted) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
-    const uint32_t c = cell_of[j];
-    sorted[start[c] + atomicAdd(cursor + c, 1u)] = (uint32_t)j;
+    const uint32_t b = bucket_of[j];
+    if (b < (uint64_t)n_buckets) sorted[start[b] + atomicAdd(cursor + b, 1u)] = (uint32_t)j;
 }
 
 // ---- hits_building, src/synthetic.rs:52-124, as csrc/host_synthetic.hpp restates it (same operations, same order) ----

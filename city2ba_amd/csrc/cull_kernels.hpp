@@ -8,18 +8,14 @@
 //                       smallest member -- the tie-break of the host version), sizes by atomic counters, arg-max of
 //                       (size, smallest root) packed in one 64-bit atomicMax;
 //   singletons        : per-camera / per-point observation counts by atomic counters;
-//   renumbering       : exclusive scans of the keep flags (cameras, points, observations) -- order preserving, so the
-//                       result equals the sequential version's element for element.
+//   renumbering       : exclusive scans of the keep flags (cameras, points, observations; scan_kernels.hpp) -- order
+//                       preserving, so the result equals the sequential version's element for element.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 namespace c2b {
-
-constexpr int kScanBlock = 256;                 // threads
-constexpr int kScanPer = 4;                     // elements per thread
-constexpr int kScanTile = kScanBlock * kScanPer;
 
 // Every link points at a SMALLER index (k_uf_union hooks the larger root under the smaller), so a walk always terminates,
 // a component's root is its smallest member, and a stale view of `parent` is harmless: a node that looked like a root
@@ -139,68 +135,6 @@ __global__ void k_singleton_flags(const uint32_t *__restrict__ deg_cam, const ui
     if (i < n_cam) keep_cam[i] = deg_cam[i] > 3u;
     if (i < n_pts) keep_pt[i] = cnt_pt[i] > 1u;
     if (i < n_obs) keep_obs[i] = (deg_cam[cam_idx[i]] > 3u && cnt_pt[pt_idx[i]] > 1u) ? 1u : 0u;
-}
-
-// ---- exclusive scan of 0/1 flags (uint32), three kernels: tile sums, scan of the tile sums, final offsets ----------
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *sWave, uint32_t &block_total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) sWave[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; ++w) base += sWave[w];
-    block_total = (sWave[0] + sWave[1]) + (sWave[2] + sWave[3]);
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_scan_tiles(const uint32_t *__restrict__ flags, int64_t n, uint32_t *__restrict__ out,
-                                                          uint32_t *__restrict__ tile_sum) {
-    __shared__ uint32_t sWave[kScanBlock / 64];
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
-    uint32_t f[kScanPer], s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) { f[k] = base + k < n ? flags[base + k] : 0u; s += f[k]; }
-    uint32_t total;
-    uint32_t ex = block_excl_scan(s, sWave, total);
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) {
-        if (base + k < n) out[base + k] = ex;
-        ex += f[k];
-    }
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-// one workgroup: tile_sum -> exclusive offsets in place; total[0] = grand total
-__global__ __launch_bounds__(kScanBlock) void k_scan_tile_sums(uint32_t *__restrict__ tile_sum, int64_t n_tiles, uint32_t *__restrict__ total) {
-    __shared__ uint32_t sWave[kScanBlock / 64];
-    __shared__ uint32_t sCarry;
-    if (threadIdx.x == 0) sCarry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n_tiles; base += kScanBlock) {
-        const int64_t i = base + threadIdx.x;
-        const uint32_t v = i < n_tiles ? tile_sum[i] : 0u;
-        uint32_t chunk;
-        const uint32_t ex = block_excl_scan(v, sWave, chunk);
-        const uint32_t carry = sCarry;
-        if (i < n_tiles) tile_sum[i] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) sCarry = carry + chunk;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) total[0] = sCarry;
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_scan_add(uint32_t *__restrict__ out, int64_t n, const uint32_t *__restrict__ tile_off) {
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
-    const uint32_t off = tile_off[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k)
-        if (base + k < n) out[base + k] += off;
 }
 
 // ---- renumbering: survivors move to their scanned positions, remembering where they came from -----------------------

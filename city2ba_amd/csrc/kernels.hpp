@@ -18,6 +18,7 @@
 //     (no float atomics: run-to-run reproducible).
 #pragma once
 #include "camera_math.hpp"
+#include "scan_kernels.hpp"
 #include "xcd_cuts.hpp"
 
 namespace c2b {
@@ -1715,17 +1716,6 @@ constexpr int kDenseTile = 64 * kDensePPL;         // points per wave tile
 constexpr int kDenseWPB = 4;                       // waves per workgroup
 constexpr int kDenseCamTile = 64;                  // granularity of the camera chunks of blockIdx.y
 
-C2B_DEV int wave_excl_scan(int v, int lane, int &total) {
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += t;
-    }
-    total = __shfl(inc, 63, 64);
-    return inc - v;
-}
-
 template <bool FILL>
 __global__ __launch_bounds__(kDenseWPB * 64) void k_visibility_dense(
     const double *__restrict__ camblk, int64_t n_cam, int64_t cams_per_chunk, const double4 *__restrict__ pts4,
@@ -1828,29 +1818,12 @@ __global__ __launch_bounds__(kDenseWPB * 64) void k_visibility_dense(
 }
 
 // per camera: exclusive scan of its row of tile counts (in place) + row total
-__global__ __launch_bounds__(256) void k_dense_row_scan(uint32_t *__restrict__ tile_counts, int64_t n_tiles,
-                                                       uint64_t *__restrict__ cam_total) {
-    __shared__ int sWave[4];
-    __shared__ int sCarry;
+__global__ __launch_bounds__(kScanBlock) void k_dense_row_scan(uint32_t *__restrict__ tile_counts, int64_t n_tiles,
+                                                              uint64_t *__restrict__ cam_total) {
+    __shared__ uint32_t sWave[kScanBlock / 64];
     uint32_t *row = tile_counts + (int64_t)blockIdx.x * n_tiles;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) sCarry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n_tiles; base += 256) {
-        const int64_t i = base + threadIdx.x;
-        const int v = i < n_tiles ? (int)row[i] : 0;
-        int total;
-        const int ex = wave_excl_scan(v, lane, total);
-        if (lane == 0) sWave[wave] = total;
-        __syncthreads();
-        int off = sCarry;
-        for (int w = 0; w < wave; ++w) off += sWave[w];
-        if (i < n_tiles) row[i] = (uint32_t)(off + ex);
-        __syncthreads();
-        if (threadIdx.x == 0) sCarry += (sWave[0] + sWave[1]) + (sWave[2] + sWave[3]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) cam_total[blockIdx.x] = (uint64_t)sCarry;
+    const uint32_t total = block_scan_array((const uint32_t *)row, n_tiles, 0u, row, sWave);
+    if (threadIdx.x == 0) cam_total[blockIdx.x] = (uint64_t)total;
 }
 
 // row_ptr[0..n_cam] of a non-decreasing camera index list: row_ptr[c] = first position whose camera is >= c
@@ -1898,35 +1871,6 @@ __global__ __launch_bounds__(256) void k_keep_row_scatter(const uint64_t *__rest
         }
         dst += (uint64_t)__popcll(m);
     }
-}
-
-// row_ptr[0..n_cam] = exclusive scan of cam_total (one workgroup; n_cam is small next to n_cam * n_tiles)
-__global__ __launch_bounds__(256) void k_dense_cam_scan(const uint64_t *__restrict__ cam_total, int64_t n_cam,
-                                                       uint64_t *__restrict__ row_ptr) {
-    __shared__ long long sWave[4];
-    __shared__ long long sCarry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) sCarry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n_cam; base += 256) {
-        const int64_t i = base + threadIdx.x;
-        const long long v = i < n_cam ? (long long)cam_total[i] : 0;
-        long long inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const long long t = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += t;
-        }
-        if (lane == 63) sWave[wave] = inc;
-        __syncthreads();
-        long long off = sCarry;
-        for (int w = 0; w < wave; ++w) off += sWave[w];
-        if (i < n_cam) row_ptr[i] = (uint64_t)(off + inc - v);
-        __syncthreads();
-        if (threadIdx.x == 0) sCarry += (sWave[0] + sWave[1]) + (sWave[2] + sWave[3]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) row_ptr[n_cam] = (uint64_t)sCarry;
 }
 
 }  // namespace c2b

@@ -12,8 +12,9 @@
 //     would spill in this kernel).
 //   * k_normal_points: point-major through the transpose below.  One lane owns one point and walks its observations in
 //     ascending observation index: the order depends on the point's list alone.
-//   * transpose (k_nt_*): pt_row_ptr / obs_of / cam_of from pt_idx and row_ptr.  An integer histogram, a one-workgroup
-//     scan, a fill through integer atomic cursors (arbitrary order), then each slot's final place by rank within its
+//   * transpose (k_nt_count, the shared scan, k_bucket_fill, k_nt_rank): pt_row_ptr / obs_of / cam_of from pt_idx and
+//     row_ptr.  An integer histogram, its scan (scan_kernels.hpp), the fill every bucket list uses (cell_kernels.hpp:
+//     integer atomic cursors, arbitrary order), then each slot's final place by rank within its
 //     point's list (observation indices are unique, so the rank is a permutation): the result is exactly the stable
 //     argsort of pt_idx.  The rank step costs k^2 loads for a point of k observations (cached; k is tens here).
 //   * robust losses: iteratively reweighted least squares.  An observation's weight w = rho'(s),
@@ -33,7 +34,6 @@ constexpr int kNormBlock = 256;
 constexpr int kNormMaxGrid = 1024;                // x 4 wave partials <= the workspace's partial slots (block_part_slots)
 constexpr int kNormSym = 45;                      // distinct entries of a symmetric 9x9
 constexpr int kNormAcc = kNormSym + 9;            // + the gradient
-constexpr int kNtScanThreads = 1024;
 
 // A camblk record read in place through the blocked table, shaped like a pointer for jacobian_obs (which indexes cam[j]
 // and takes cam + kJl): every index is a constant after inlining, so the layout arithmetic folds away.
@@ -101,38 +101,6 @@ __global__ __launch_bounds__(256) void k_nt_count(const uint32_t *__restrict__ p
     if (o >= n_obs) return;
     const uint32_t p = pt_idx[o];
     if (p < (uint64_t)n_pts) atomicAdd(cnt + p, 1u);
-}
-
-// one workgroup: pt_row_ptr[0] = 0, pt_row_ptr[p + 1] = cnt[0] + ... + cnt[p]; cnt[p] becomes the fill cursor pt_row_ptr[p]
-__global__ __launch_bounds__(kNtScanThreads) void k_nt_scan(uint32_t *__restrict__ cnt, int64_t n_pts, uint64_t *__restrict__ pt_row_ptr) {
-    __shared__ uint64_t sPart[kNtScanThreads];
-    const int64_t chunk = (n_pts + kNtScanThreads - 1) / kNtScanThreads;
-    const int64_t lo = threadIdx.x * chunk, hi = lo + chunk < n_pts ? lo + chunk : n_pts;
-    uint64_t s = 0;
-    for (int64_t p = lo; p < hi; ++p) s += cnt[p];
-    sPart[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t run = 0;
-        for (int i = 0; i < kNtScanThreads; ++i) { const uint64_t v = sPart[i]; sPart[i] = run; run += v; }
-        pt_row_ptr[0] = 0;
-    }
-    __syncthreads();
-    uint64_t run = sPart[threadIdx.x];
-    for (int64_t p = lo; p < hi; ++p) {
-        const uint32_t c = cnt[p];
-        cnt[p] = (uint32_t)run;
-        run += c;
-        pt_row_ptr[p + 1] = run;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_nt_fill(const uint32_t *__restrict__ pt_idx, int64_t n_obs, int64_t n_pts,
-                                                 uint32_t *__restrict__ cursor, uint32_t *__restrict__ slots) {
-    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (o >= n_obs) return;
-    const uint32_t p = pt_idx[o];
-    if (p < (uint64_t)n_pts) slots[atomicAdd(cursor + p, 1u)] = (uint32_t)o;
 }
 
 // slot j holds some observation o of point p (in fill order); its place in the stable order is b + #{k in [b, e): slots[k] < o}

@@ -3,7 +3,7 @@
 //
 // Writing.  A line's position in the file is the sum of the lengths of every line before it, so the image is made in
 // two passes over tiles of 256 units (an observation line, or one value of a camera / point line with the space or
-// newline behind it): pass 1 leaves each tile's byte count, one small kernel turns the counts into 64-bit tile bases,
+// newline behind it): pass 1 leaves each tile's byte count, the shared scan (scan_kernels.hpp) turns the counts into 64-bit tile bases,
 // pass 2 recomputes its tile's lengths, scans them inside the workgroup and writes the characters.  Nothing per line
 // is stored between the passes; the digits are simply found twice (a few hundred integer operations per value).
 // The characters of a tile are one contiguous piece of the file: they are written into LDS first -- at the offset
@@ -14,8 +14,9 @@
 #include <cstdint>
 
 #include "decimal.hpp"
+#include "scan_kernels.hpp"
 
-constexpr int kTextTile = 256;
+constexpr int kTextTile = c2b::kScanBlock;            // one unit per thread: a tile is scanned by c2b::block_excl_scan
 constexpr int kEmitCap = 24 * 1024;                   // LDS window of one tile's characters
 
 typedef __attribute__((address_space(3))) char *lds_char;
@@ -24,28 +25,6 @@ typedef unsigned int text_u4 __attribute__((ext_vector_type(4)));      // a plai
 typedef __attribute__((address_space(3))) text_u4 *lds_u4;
 
 __device__ c2b_dec::Tables g_dec_tables;              // filled once per device (capi_problem.hpp: device_dec_tables)
-
-// exclusive scan of one value per thread over a workgroup of kTextTile threads; *total = the tile's sum (every thread)
-__device__ __forceinline__ uint32_t text_tile_scan(uint32_t v, uint32_t *sh, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kTextTile / 64; ++w) {
-        const uint32_t s = sh[w];
-        if (w < wave) base += s;
-        all += s;
-    }
-    *total = all;
-    return base + inc - v;
-}
 
 // out[shift + k] -> dst[k] for k < total, where shift = (address of dst) mod 16: whole aligned 16-byte stores, the ragged
 // ends byte by byte
@@ -90,7 +69,7 @@ __global__ __launch_bounds__(kTextTile) void k_text_obs(const uint32_t *__restri
         len = lc + 1 + lp + 1 + tu.len + 1 + tv.len + 1;
     }
     uint32_t total;
-    const uint32_t at = text_tile_scan(len, sh, &total);
+    const uint32_t at = c2b::block_excl_scan(len, sh, total);
     if (!EMIT) {
         if (threadIdx.x == 0) tile_len[blockIdx.x] = total;
         return;
@@ -125,7 +104,7 @@ __global__ __launch_bounds__(kTextTile) void k_text_vals(const double *__restric
         len = t.len + 1;
     }
     uint32_t total;
-    const uint32_t at = text_tile_scan(len, sh, &total);
+    const uint32_t at = c2b::block_excl_scan(len, sh, total);
     if (!EMIT) {
         if (threadIdx.x == 0) tile_len[blockIdx.x] = total;
         return;
@@ -148,30 +127,10 @@ __global__ __launch_bounds__(kTextTile) void k_text_vals(const double *__restric
     }
 }
 
-// tile byte counts -> 64-bit tile bases (exclusive, starting at `first`); total[0] = first + every tile.  One workgroup:
-// thread t owns a contiguous run of tiles.
-__global__ __launch_bounds__(1024) void k_text_tile_bases(const uint32_t *__restrict__ tile_len, int64_t n_tiles, uint64_t first,
-                                                          uint64_t *__restrict__ tile_base, uint64_t *__restrict__ total) {
-    __shared__ uint64_t part[1024];
-    const int64_t per = (n_tiles + 1023) / 1024, a = (int64_t)threadIdx.x * per, b = a + per < n_tiles ? a + per : n_tiles;
-    uint64_t s = 0;
-    for (int64_t k = a; k < b; ++k) s += tile_len[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t run = first;
-        for (int t = 0; t < 1024; ++t) { const uint64_t v = part[t]; part[t] = run; run += v; }
-        total[0] = run;
-    }
-    __syncthreads();
-    uint64_t run = part[threadIdx.x];
-    for (int64_t k = a; k < b; ++k) { tile_base[k] = run; run += tile_len[k]; }
-}
-
 // ---- reading ---------------------------------------------------------------------------------------------------------
 // from_file_text (src/baproblem.rs:580-629) is a positional grammar over whitespace-separated tokens: 3 counts, 4 per
 // observation, 9 per camera, 3 per point.  A token's meaning is its index, and its index is the number of token starts
-// before it: pass 1 counts the starts in every tile of kParseTile bytes, k_text_tile_bases turns the counts into tile
+// before it: pass 1 counts the starts in every tile of kParseTile bytes, the shared scan turns the counts into tile
 // bases, pass 2 finds its starts again, ranks them inside the workgroup, parses each token where it stands
 // (decimal.hpp: correctly rounded, or `unsure`) and stores the value where that index belongs.  flags[0] counts tokens
 // the device declines (another spelling, more than 19 digits, an undecided rounding) -- the caller then gives the file
@@ -204,7 +163,7 @@ __global__ __launch_bounds__(kTextTile) void k_text_count_tokens(const char *__r
     uint32_t starts = 0;
     if (at < n) starts = text_starts(*reinterpret_cast<const text_u4 *>(raw + at), at == 0 ? true : text_ws((uint32_t)(uint8_t)raw[at - 1]), at, n);
     uint32_t total;
-    (void)text_tile_scan((uint32_t)__builtin_popcount(starts), sh, &total);
+    (void)c2b::block_excl_scan((uint32_t)__builtin_popcount(starts), sh, total);
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
 }
 
@@ -236,7 +195,7 @@ __global__ __launch_bounds__(kTextTile) void k_text_parse(const char *__restrict
     const bool prev_ws = threadIdx.x > 0 ? text_ws((uint32_t)(uint8_t)text[here - 1]) : (at == 0 ? true : text_ws((uint32_t)(uint8_t)raw[at - 1]));
     uint32_t starts = at < n ? text_starts(mine, prev_ws, at, n) : 0u;
     uint32_t total;
-    uint32_t rank = text_tile_scan((uint32_t)__builtin_popcount(starts), sh, &total);
+    uint32_t rank = c2b::block_excl_scan((uint32_t)__builtin_popcount(starts), sh, total);
     // Where the tile's tokens start, in token order: the parsing below takes ONE token per lane and trip, whatever the
     // spacing of the file (16 bytes per lane hold 0-8 tokens: parsing them where they were found left most lanes idle
     // behind the fullest one), and deals the tokens of a group of 256 so that each wave sees ONE kind: consecutive

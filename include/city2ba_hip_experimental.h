@@ -51,7 +51,8 @@ int c2b_calib_copy(const void *src, void *dst, int64_t bytes, void *stream);
  * _transpose: the point-major order of the list -- pt_row_ptr [n_pts + 1] (u64), obs_of [n_obs] the observations of
  * each point in ascending order (= a stable argsort of pt_idx), cam_of [n_obs] the camera of obs_of[j]; temp is
  * c2b_normal_transpose_temp_bytes(n_obs, n_pts) bytes of device memory (16-byte aligned), free once the stream passed
- * the call.  Every pt_idx must be < n_pts.
+ * the call: the counts / cursors of the points, the fill's slots and the tile sums of the scan over the points (about
+ * 8 bytes per 1024 points) -- ask for the size, never compute it.  Every pt_idx must be < n_pts.
  * _cameras_rows: U [n_cam][9][9], gc [n_cam][9] (both required); with a workspace and sum_sq != NULL (device pointer)
  * the same launch folds sum |r|^2 into sum_sq[0].
  * _points_rows: V [n_pts][3][3], gp [n_pts][3] from the transpose.
