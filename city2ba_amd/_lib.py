@@ -70,6 +70,12 @@ class LmOptions(C.Structure):
                 ("function_tol", C.c_double), ("gradient_tol", C.c_double), ("parameter_tol", C.c_double)]
 
 
+class RefineOptions(C.Structure):
+    """c2b_refine_options (include/city2ba_hip_experimental.h)"""
+    _fields_ = [("max_rounds", C.c_int32), ("reserved", C.c_int32), ("lambda0", C.c_double), ("function_tol", C.c_double),
+                ("gradient_tol", C.c_double), ("parameter_tol", C.c_double)]
+
+
 class LmIteration(C.Structure):
     """c2b_lm_iteration"""
     _fields_ = [("cost", C.c_double), ("cost_trial", C.c_double), ("lam", C.c_double), ("model_decrease", C.c_double),
@@ -97,6 +103,11 @@ TRI_STATUS = ("triangulated", "too_few", "degenerate", "behind", "constant")
 TRI_NO_CONSENSUS = 5
 TRI_CONSENSUS_STATUS = TRI_STATUS + ("no_consensus",)
 TRI_DROP_OUTLIERS = 1      # C2B_TRI_DROP_OUTLIERS: compact the list by the inlier mask afterwards
+
+# statuses of c2b_problem_refine_points / c2b_refine_points_rows (C2B_REFINE_*); their counts hold one more entry, `moved`
+REFINE_CONVERGED, REFINE_MAX_ROUNDS, REFINE_UNOBSERVED, REFINE_FAILED, REFINE_CONSTANT = range(5)
+REFINE_STATUS = ("converged", "max_rounds", "unobserved", "failed", "constant")
+REFINE_COUNTS = REFINE_STATUS + ("moved",)
 
 # statuses of c2b_problem_resect_cameras / c2b_resect_rows (C2B_RES_*), the order of their counts
 RES_OK, RES_TOO_FEW, RES_DEGENERATE, RES_BEHIND, RES_CONSTANT = range(5)
@@ -146,6 +157,7 @@ SIGNATURES = {
     "c2b_visibility_rows_bits": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
     "c2b_residual_keep_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _d, _int, _vp, _vp]),
     "c2b_triangulate_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "c2b_refine_points_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_triangulate_consensus_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_resect_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp]),
     "c2b_resect_consensus_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _int, _d, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -185,6 +197,9 @@ SIGNATURES = {
     "c2b_problem_levenberg_marquardt": (_int, [_vp, _vp, _vp, _int, _vp]),
     "c2b_problem_filter_observations": (_int, [_vp, _d, _int, C.POINTER(_i64)]),
     "c2b_problem_triangulate_points": (_int, [_vp, _d, _vp, _vp]),
+    "c2b_problem_refine_points": (_int, [_vp, _vp, _vp, _vp]),
+    "c2b_problem_set_inner_iterations": (_int, [_vp, _int]),
+    "c2b_problem_get_inner_iterations": (_int, [_vp, C.POINTER(_int)]),
     "c2b_problem_triangulate_consensus": (_int, [_vp, _d, _d, _int, _int, _int, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_resect_cameras": (_int, [_vp, _int, _d, _vp, _vp]),
     "c2b_problem_resect_consensus": (_int, [_vp, _d, _int, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),

@@ -642,6 +642,33 @@ class BAProblem:
         return self._status_pass(L.lib().c2b_problem_triangulate_points, (float(np.deg2rad(float(min_angle_deg))),),
                                  self.num_points(), L.TRI_STATUS, return_status)
 
+    def refine_points(self, rounds=10, lam=1e-4, function_tol=0.0, gradient_tol=0.0, parameter_tol=0.0, return_status=False):
+        """Per-point Levenberg-Marquardt on the device (c2b_problem_refine_points): every point is re-minimised
+        by itself against the cameras as they are, with its own damping (from `lam`) and its own acceptance, for up to
+        `rounds` rounds -- structure-only refinement in one launch.  A point's cost is sum rho(|r|^2) over its observations
+        under the handle's loss plus its point prior's; it stops when a tolerance is met (0 disables a test; they are
+        levenberg_marquardt_device's, per point).  A point is written only when its cost fell; constant points, points
+        with neither an observation nor a prior and points whose start cost is not finite keep their bits.  Masks, priors,
+        loss, preconditioner and a checkpoint stay.  Returns dict(converged, max_rounds, unobserved, failed, constant,
+        moved): the number of points of each status and of points written; with return_status also the uint8 status per
+        point (the dict's order: 0 .. 4)."""
+        opt = L.RefineOptions(int(rounds), 0, float(lam), float(function_tol), float(gradient_tol), float(parameter_tol))
+        return self._status_pass(L.lib().c2b_problem_refine_points, (C.cast(C.pointer(opt), C.c_void_p),), self.num_points(),
+                                 L.REFINE_COUNTS, return_status)
+
+    def set_inner_iterations(self, n):
+        """Inner iterations of the LM loops (c2b_problem_set_inner_iterations): with n > 0 solve.levenberg_marquardt and
+        levenberg_marquardt_device run refine_points(rounds=n) after every step they apply, before they take the step's cost.
+        0 = off, the default.  The setting is the handle's, like the loss: it stays until it is set again (the loops'
+        inner_iterations= argument sets it when given and leaves it alone when None)."""
+        L.check(L.lib().c2b_problem_set_inner_iterations(self._h, int(n)))
+
+    def inner_iterations(self):
+        """the inner iterations in force (set_inner_iterations)"""
+        n = C.c_int()
+        L.check(L.lib().c2b_problem_get_inner_iterations(self._h, C.byref(n)))
+        return n.value
+
     def triangulate_points_robust(self, max_error, min_angle_deg=1.0, min_inliers=3, max_hypotheses=64, drop_outliers=False,
                                   return_status=False, return_inliers=False):
         """Consensus triangulation on the device (c2b_problem_triangulate_consensus): triangulate_points for a

@@ -19,7 +19,7 @@
 //   city2ba ply IN OUT
 //   city2ba solve IN OUT [--iterations N --lambda X --pcg-iterations N --pcg-tol X --function-tol X --gradient-tol X
 //                         --parameter-tol X --loss squared|huber|cauchy|soft-l1 --loss-scale X
-//                         --preconditioner block-jacobi|schur-jacobi --fix-intrinsics --fix-first-camera
+//                         --preconditioner block-jacobi|schur-jacobi --inner-iterations N --fix-intrinsics --fix-first-camera
 //                         --filter-max-error X --filter-rounds N --filter-in-front
 //                         --prior-from FILE [--prior-center-sigma S|SX,SY,SZ] [--prior-intrinsics-sigma SF,SK1,SK2]
 //                         [--prior-point-sigma S [--prior-point-every N]]]
@@ -37,6 +37,10 @@
 //   city2ba rematch IN OUT --radius R --max-error X [--min-fits N]
 //                        (extension: wrong point indices put right, the repair of --mismatch-chance and --join-landmarks that
 //                         keeps the observation, c2b_problem_rematch_observations; whoever fits no point is removed)
+//   city2ba refine IN OUT [--rounds N] [--lambda L] [--loss KIND --loss-scale A] [--function-tol T] [--gradient-tol T]
+//                         [--parameter-tol T]
+//                        (extension: every point re-minimised by itself with the cameras held, per-point Levenberg-Marquardt,
+//                         c2b_problem_refine_points)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -866,10 +870,21 @@ static void peek_counts(const std::string &path, int64_t &n_cam, int64_t &n_pts)
     if (!ok) die("Could not read the camera and point counts of " + path);
 }
 
+// --loss, which `solve` and `refine` share: the kind (C2B loss kinds 0 .. 3)
+static int loss_kind_of(const Args &a) {
+    if (!a.has("loss")) return 0;
+    const std::string &v = a.opt.at("loss");
+    if (v == "squared") return 0;
+    if (v == "huber") return 1;
+    if (v == "cauchy") return 2;
+    if (v == "soft-l1") return 3;
+    die("Invalid value for '--loss <loss>': expected squared, huber, cauchy or soft-l1");
+}
+
 int run_solve(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera", "filter-in-front"},
                          {"iterations", "lambda", "pcg-iterations", "pcg-tol", "function-tol", "gradient-tol", "parameter-tol", "loss",
-                          "loss-scale", "preconditioner", "device", "filter-max-error", "filter-rounds", "prior-from",
+                          "loss-scale", "preconditioner", "inner-iterations", "device", "filter-max-error", "filter-rounds", "prior-from",
                           "prior-center-sigma", "prior-intrinsics-sigma", "prior-point-sigma", "prior-point-every"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
     c2b_lm_options opt;
@@ -889,21 +904,16 @@ int run_solve(int argc, char **argv) {
     if (filter && !(filter_max_error >= 0.0)) die("Invalid value for '--filter-max-error <X>': expected a number >= 0");
     if (filter_rounds > 1000) die("Invalid value for '--filter-rounds <N>': expected 0 ... 1000");
     if (!filter && (a.has("filter-rounds") || a.has("filter-in-front"))) die("--filter-rounds and --filter-in-front need --filter-max-error <X>");
-    int loss = 0, precond = C2B_PRECOND_BLOCK_JACOBI;
-    if (a.has("loss")) {
-        const std::string &v = a.opt.at("loss");
-        if (v == "squared") loss = 0;
-        else if (v == "huber") loss = 1;
-        else if (v == "cauchy") loss = 2;
-        else if (v == "soft-l1") loss = 3;
-        else die("Invalid value for '--loss <loss>': expected squared, huber, cauchy or soft-l1");
-    }
+    const int loss = loss_kind_of(a);
+    int precond = C2B_PRECOND_BLOCK_JACOBI;
     if (a.has("preconditioner")) {
         const std::string &v = a.opt.at("preconditioner");
         if (v == "block-jacobi") precond = C2B_PRECOND_BLOCK_JACOBI;
         else if (v == "schur-jacobi") precond = C2B_PRECOND_SCHUR_JACOBI;
         else die("Invalid value for '--preconditioner <preconditioner>': expected block-jacobi or schur-jacobi");
     }
+    const int64_t inner_iterations = a.i("inner-iterations", 0);
+    if (inner_iterations > 1000) die("Invalid value for '--inner-iterations <N>': expected an integer in 0 ... 1000");
     // priors: every flag and both files' counts are checked here, before a device exists
     const bool prior = a.has("prior-from");
     std::vector<double> w_center, w_intr, w_point;
@@ -938,6 +948,7 @@ int run_solve(int argc, char **argv) {
     c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
     ck(c2b_problem_set_loss(p, loss, loss_scale));
     ck(c2b_problem_set_preconditioner(p, precond));
+    ck(c2b_problem_set_inner_iterations(p, (int)inner_iterations));
     if (prior) {                                             // the targets: FILE's centres, intrinsics and points, as a problem holds them
         c2b_problem *q = nullptr;
         int64_t qc = 0, qp = 0, qo = 0;
@@ -1134,6 +1145,37 @@ int run_rematch(int argc, char **argv) {
     return 0;
 }
 
+// `refine`: every point of a .bal / .bbal re-minimised by itself against the cameras as they are, by
+// c2b_problem_refine_points (an extension: per-point Levenberg-Marquardt on the device; cameras and observations are written as
+// they were read).  Every argument is parsed before the device is touched.
+int run_refine(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {}, {"rounds", "lambda", "loss", "loss-scale", "function-tol", "gradient-tol", "parameter-tol", "device"});
+    if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
+    const int64_t rounds = a.i("rounds", 10);
+    if (rounds > 1000000) die("Invalid value for '--rounds <N>': expected an integer in 0 ... 1000000");
+    c2b_refine_options opt = {(int32_t)rounds, 0, a.f("lambda", 1e-4), a.f("function-tol", 0.0), a.f("gradient-tol", 0.0), a.f("parameter-tol", 0.0)};
+    if (!(opt.lambda0 >= C2B_STEP_LAMBDA_MIN && opt.lambda0 <= C2B_STEP_LAMBDA_MAX)) die("Invalid value for '--lambda <L>': expected a number in 1e-20 ... 1e32");
+    const std::pair<const char *, double> tols[] = {{"function-tol", opt.function_tol}, {"gradient-tol", opt.gradient_tol}, {"parameter-tol", opt.parameter_tol}};
+    for (const auto &t : tols)
+        if (!(t.second >= 0.0 && std::isfinite(t.second))) die(std::string("Invalid value for '--") + t.first + " <T>': expected a finite number >= 0");
+    const int loss = loss_kind_of(a);
+    const double loss_scale = a.f("loss-scale", 1.0);
+    if (!(loss_scale > 0.0 && std::isfinite(loss_scale))) die("Invalid value for '--loss-scale <A>': expected a finite number > 0");
+    const int device = (int)a.i("device", 0);
+    PhaseTimer timer;
+    int64_t nc = 0, np = 0, no = 0;
+    c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
+    ck(c2b_problem_set_loss(p, loss, loss_scale));
+    int64_t counts[6] = {0, 0, 0, 0, 0, 0};
+    ck(c2b_problem_refine_points(p, &opt, nullptr, counts));
+    timer.mark("refine_points (device)");
+    std::printf("refined %lld points: %lld converged, %lld at the round limit; kept: %lld unobserved, %lld with a cost that is not finite, %lld constant\n",
+                (long long)counts[5], (long long)counts[C2B_REFINE_CONVERGED], (long long)counts[C2B_REFINE_MAX_ROUNDS],
+                (long long)counts[C2B_REFINE_UNOBSERVED], (long long)counts[C2B_REFINE_FAILED], (long long)counts[C2B_REFINE_CONSTANT]);
+    close_problem(timer, p, a.positional[1]);
+    return 0;
+}
+
 void usage() {
     std::printf("city2ba (MI355X build, %s)\nTools for generating synthetic bundle adjustment problems.\n\n"
                 "USAGE:\n    city2ba <SUBCOMMAND>\n\nSUBCOMMANDS:\n"
@@ -1146,7 +1188,8 @@ void usage() {
                 "    triangulate       Set the points of a .bal or .bbal from its cameras and observations.\n"
                 "    resect            Set the camera poses of a .bal or .bbal from its points and observations.\n"
                 "    merge             Merge the duplicate landmarks of a .bal or .bbal (the repair of noise --split-landmarks).\n"
-                "    rematch           Put the wrong point indices of a .bal or .bbal right (the repair of noise --mismatch-chance).\n",
+                "    rematch           Put the wrong point indices of a .bal or .bbal right (the repair of noise --mismatch-chance).\n"
+                "    refine            Refine every point of a .bal or .bbal by itself, the cameras held (per-point Levenberg-Marquardt).\n",
                 c2b_version());
 }
 
@@ -1187,6 +1230,8 @@ const char *subcommand_help(const std::string &sub) {
                "    --function-tol <X> [0]  --gradient-tol <X> [0]  --parameter-tol <X> [0]   stopping tests (0: off)\n"
                "    --loss <squared|huber|cauchy|soft-l1> [squared]   --loss-scale <X> [1]\n"
                "    --preconditioner <block-jacobi|schur-jacobi> [block-jacobi]\n"
+               "    --inner-iterations <N> [0] after every step, N rounds of per-point refinement of the points against the moved cameras,\n"
+               "                              before the step's cost is taken (0: off)\n"
                "    --fix-intrinsics          hold f, k1, k2 of every camera constant\n"
                "    --fix-first-camera        hold the pose of camera 0 constant\n"
                "    --filter-max-error <X>    outlier rejection: solve, drop the observations whose reprojection residual exceeds X,\n"
@@ -1233,6 +1278,14 @@ const char *subcommand_help(const std::string &sub) {
                "                              (required)\n"
                "    --min-fits <N> [2]        points that fewer than N observations fit are neither judged nor assigned\n"
                "                              An observation that fits no such point is removed.  Nothing is culled.\n";
+    if (sub == "refine")
+        return "city2ba refine <FILE> <OUT>\n"
+               "    --rounds <N> [10]         rounds of per-point Levenberg-Marquardt: every point by itself, its own damping and acceptance,\n"
+               "                              the cameras held (0: report only)\n"
+               "    --lambda <L> [1e-4]       every point's initial damping\n"
+               "    --loss <squared|huber|cauchy|soft-l1> [squared]   --loss-scale <A> [1]\n"
+               "    --function-tol <T> [0]  --gradient-tol <T> [0]  --parameter-tol <T> [0]   per-point stopping tests (0: off)\n"
+               "                              A point is written only when its cost fell.\n";
     return nullptr;
 }
 
@@ -1260,5 +1313,6 @@ int main(int argc, char **argv) {
     if (sub == "resect") return run_resect(argc, argv);
     if (sub == "merge") return run_merge(argc, argv);
     if (sub == "rematch") return run_rematch(argc, argv);
+    if (sub == "refine") return run_refine(argc, argv);
     die("The subcommand '" + sub + "' wasn't recognized");
 }

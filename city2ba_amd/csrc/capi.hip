@@ -38,6 +38,7 @@
 #include "schur_kernels.hpp"
 #include "prior_kernels.hpp"
 #include "triangulate_kernels.hpp"
+#include "refine_kernels.hpp"
 #include "triangulate_robust_kernels.hpp"
 #include "resect_kernels.hpp"
 #include "resect_robust_kernels.hpp"

@@ -1637,6 +1637,43 @@ int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, cons
     C2B_API_END("triangulate_rows")
 }
 
+// ---- per-point Levenberg-Marquardt (refine_kernels.hpp) ------------------------------------------------------
+// what both refinement entries ask of the options
+static int check_refine_options(const char *who, const c2b_refine_options *o) {
+    if (!o) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: options is NULL", who);
+    if (o->max_rounds < 0 || o->reserved != 0) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: max_rounds must be >= 0 and reserved 0", who);
+    if (!good_lambda(o->lambda0)) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: lambda0 must lie in [1e-20, 1e32]", who);
+    for (const double t : {o->function_tol, o->gradient_tol, o->parameter_tol})
+        if (!(t >= 0.0) || !std::isfinite(t)) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: tolerances must be finite and >= 0", who);
+    return C2B_OK;
+}
+
+int c2b_refine_points_rows(const double *camblk, double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                           const uint32_t *cam_of, const double *uv_obs, int loss_kind, double loss_a2, const double *prior_pt,
+                           const double *prior_pt_w, const c2b_refine_options *opt, const uint8_t *pt_mask, uint8_t *status,
+                           int64_t *counts, void *stream) {
+    C2B_API_BEGIN
+    const int bad = check_tri_rows_args("refine_points_rows", camblk, pts4, n_pts, pt_row_ptr, obs_of, cam_of, uv_obs, 0.0, status, counts);
+    if (bad) return bad;
+    if (const int rc = check_refine_options("refine_points_rows", opt)) return rc;
+    if (loss_kind < kLossSquared || loss_kind > kLossSoftL1 || (loss_kind != kLossSquared && (!(loss_a2 > 0.0) || !std::isfinite(loss_a2))))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "refine_points_rows: loss kind must be 0..3 and its squared scale finite and > 0");
+    if (!prior_pt != !prior_pt_w) return fail(C2B_ERR_INVALID_ARGUMENT, "refine_points_rows: prior targets and weights go in pairs (both or neither)");
+    if (!aligned8(prior_pt) || !aligned8(prior_pt_w)) return fail(C2B_ERR_INVALID_ARGUMENT, "refine_points_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kRefCounts, st));
+    if (!n_pts) return C2B_OK;
+    auto tol = [](double t) { return t > 0.0 ? t : std::numeric_limits<double>::quiet_NaN(); };        // (RefOptions: 0 = disabled = NaN)
+    const RefOptions o{opt->max_rounds, opt->lambda0, tol(opt->function_tol), tol(opt->gradient_tol), tol(opt->parameter_tol)};
+    hipLaunchKernelGGL(k_refine_points, dim3(blocks_for(n_pts, kRefBlock)), dim3(kRefBlock), 0, st, camblk, reinterpret_cast<double4 *>(pts4),
+                       n_pts, pt_row_ptr, obs_of, cam_of, reinterpret_cast<const double2 *>(uv_obs), loss_kind,
+                       loss_kind == kLossSquared ? 1.0 : loss_a2, prior_pt, prior_pt_w, o, pt_mask, status,
+                       reinterpret_cast<unsigned long long *>(counts));
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("refine_points_rows")
+}
+
 // ---- consensus triangulation (triangulate_robust_kernels.hpp) ----------------------------------------------
 static bool good_tri_max_error(double e) { return e >= 0.0 && std::isfinite(e); }   // (a NaN fails the first)
 

@@ -23,6 +23,8 @@ struct c2b_problem {
     // 3 soft-L1) and its scale; the handle's too
     int loss_kind = 0;
     double loss_scale = 1.0;
+    // c2b_problem_set_inner_iterations: rounds of c2b_problem_refine_points after every step the LM loop applies (0 = off); the handle's too
+    int inner_rounds = 0;
     // c2b_problem_set_preconditioner: what c2b_problem_solve_step's PCG is preconditioned with (0 block-Jacobi on U,
     // 1 Schur-Jacobi), the handle's too; and how many cameras' Schur-Jacobi factors fell back in the last solve
     int precond_kind = 0;
@@ -87,6 +89,7 @@ struct c2b_problem {
 //   apply_step, rollback (5)   X            truth      -     -          -      -             -           -
 //   noise (drift, noise, sin)  X            X          -     -          -      -             -           -
 //   triangulate_points         -            -          -     -          -      -             -           -
+//   refine_points              -            -          -     -          -      -             -           -
 //   triangulate_consensus (6)  -            -          - / X - / X      - / X  -             -           -
 //   resect_cameras             X            truth      -     -          -      -             -           -
 //   resect_consensus (6)       X            truth      - / X - / X      - / X  -             -           -

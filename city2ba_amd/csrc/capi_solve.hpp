@@ -726,6 +726,63 @@ int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *st
     C2B_API_END("problem_triangulate_points")
 }
 
+// ---- per-point Levenberg-Marquardt --------------------------------------------------------------------
+// The resident points re-minimised one by one against the resident cameras: c2b_refine_points_rows over the cached transpose,
+// under the handle's loss, point mask and point priors.  Only pts4 changes, so the handle is left as triangulation leaves
+// it: the list, the row structure, the transpose, the solve buffers, the masks, the loss, the preconditioner, the priors
+// and a checkpoint all stay.  Without a single observation a point has its prior alone: an empty transpose stands in.
+// the launch over the resident buffers, which the entry below and lm_loop's inner iterations share: status and counts stay on
+// the device (asynchronous); `ptr` is the transpose's row pointer (an all-zero one when the problem has no observation)
+static int refine_resident(c2b_problem *p, const c2b_refine_options *opt, const uint64_t *ptr, uint8_t *d_status, int64_t *d_counts) {
+    const bool obs = p->n_obs > 0;
+    return c2b_refine_points_rows(p->camblk, p->pts4, p->n_pts, ptr, obs ? p->nt_obs.ptr : nullptr, obs ? p->nt_cam.ptr : nullptr, p->uv,
+                                  p->loss_kind, p->loss_scale * p->loss_scale, p->pxw ? p->px0.ptr : nullptr, p->pxw ? p->pxw.ptr : nullptr, opt,
+                                  p->pmask, d_status, d_counts, p->stream);
+}
+
+int c2b_problem_refine_points(c2b_problem *p, const c2b_refine_options *opt, uint8_t *status, int64_t *counts) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_refine_points");
+    if (const int bad = check_refine_options("problem_refine_points", opt)) return bad;
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_refine_points: a shard is not refined alone (a point's observations span every rank)");
+    const int64_t np = p->n_pts;
+    StatusReport rep(kRefCounts);
+    if (!np) return rep.all_have(kRefUnobserved, 0, status, counts);
+    DevBuf<uint64_t> empty_ptr;
+    int rc = ensure_camblk(p);
+    if (!rc && p->n_obs) rc = ensure_rows(p);
+    if (!rc && p->n_obs) rc = ensure_transpose(p);
+    if (rc) return rc;
+    hipError_t e = rep.alloc(np);
+    if (e == hipSuccess && !p->n_obs) {
+        e = empty_ptr.alloc((size_t)np + 1);
+        if (e == hipSuccess) e = hipMemsetAsync(empty_ptr, 0, sizeof(uint64_t) * ((size_t)np + 1), p->stream);
+    }
+    if (e != hipSuccess) return fail(hip_code(e), "problem_refine_points: allocation: %s", hipGetErrorString(e));
+    rc = refine_resident(p, opt, p->n_obs ? p->nt_ptr.ptr : empty_ptr.ptr, rep.d_status, rep.d_counts);
+    return rep.read_back("problem_refine_points", p->stream, rc, hipSuccess, np, status, counts);
+    C2B_API_END("problem_refine_points")
+}
+
+// inner iterations of the LM loop: the handle's state, like the loss (it survives uploads and reads)
+int c2b_problem_set_inner_iterations(c2b_problem *p, int rounds) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_inner_iterations: problem is NULL");
+    if (rounds < 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_inner_iterations: rounds must be >= 0, not %d", rounds);
+    p->inner_rounds = rounds;
+    return C2B_OK;
+    C2B_API_END("problem_set_inner_iterations")
+}
+
+int c2b_problem_get_inner_iterations(c2b_problem *p, int *rounds) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_inner_iterations: problem is NULL");
+    if (rounds) *rounds = p->inner_rounds;
+    return C2B_OK;
+    C2B_API_END("problem_get_inner_iterations")
+}
+
 // ---- camera resection ---------------------------------------------------------------------------------
 // The resident cameras' poses from the resident points and observations: c2b_resect_rows over the row structure, in place
 // on bal9, which is made the truth first as c2b_problem_apply_step makes it (state mode: to_vec of the cameras) and stays
@@ -798,9 +855,12 @@ int c2b_problem_drop_checkpoint(c2b_problem *p) {
 }
 
 // c2b_problem::lm, carved: dc [n_cam][9], dp [n_pts][3], the partials of k_lm_norms (kLmSums x grid; k_lm_gradient_max
-// uses the first 2 x grid of them after those were summed), the device scalars: the four sums, then the two maxima
+// uses the first 2 x grid of them after those were summed), the device scalars: the four sums, then the two maxima; then what
+// the inner iterations' refinement reports and nobody reads: its six counts and a status byte per point
 struct LmBufs {
     double *dc, *dp, *part, *sc;
+    int64_t *inner_counts;
+    uint8_t *inner_status;
     unsigned grid;
 };
 enum { kLmScGradCam = kLmSums, kLmScGradPts = kLmSums + 1, kLmScSlots = 8 };
@@ -812,12 +872,15 @@ static LmBufs lm_bufs(c2b_problem *p) {
     b.dp = b.dc + 9 * p->n_cam;
     b.part = b.dp + 3 * p->n_pts;
     b.sc = b.part + (int64_t)kLmSums * b.grid;
+    b.inner_counts = reinterpret_cast<int64_t *>(b.sc + kLmScSlots);
+    b.inner_status = reinterpret_cast<uint8_t *>(b.inner_counts + kRefCounts);
     return b;
 }
 
 static int ensure_lm(c2b_problem *p) {
     if (p->lm) return C2B_OK;                                // (dropped whenever a count changes)
-    const int64_t n = 9 * p->n_cam + 3 * p->n_pts + (int64_t)kLmSums * lm_grid(std::max<int64_t>(9 * p->n_cam, 3 * p->n_pts)) + kLmScSlots;
+    const int64_t n = 9 * p->n_cam + 3 * p->n_pts + (int64_t)kLmSums * lm_grid(std::max<int64_t>(9 * p->n_cam, 3 * p->n_pts)) + kLmScSlots +
+                      kRefCounts + (p->n_pts + 7) / 8;
     const hipError_t e = p->lm.alloc((size_t)n);
     if (e != hipSuccess) return fail(hip_code(e), "problem_levenberg_marquardt: allocation: %s", hipGetErrorString(e));
     return C2B_OK;
@@ -901,6 +964,11 @@ static int lm_loop(c2b_problem *p, const c2b_lm_options &o, c2b_lm_iteration *hi
             break;
         }
         if ((rc = c2b_problem_apply_step(p, L.dc, L.dp))) return rc;
+        if (p->inner_rounds && p->n_obs) {                   // inner iterations: the points against the moved cameras,
+            const c2b_refine_options inner{p->inner_rounds, 0, 1e-4, 0.0, 0.0, 0.0};       // queued like any pass: no allocation, no read-back
+            if ((rc = ensure_camblk(p))) return rc;          // (the rows and the transpose are the solve's)
+            if ((rc = refine_resident(p, &inner, p->nt_ptr, L.inner_status, L.inner_counts))) return rc;
+        }
         double e1 = 0.0;
         if ((rc = lm_cost(p, &e1))) return rc;
         it.cost_trial = e1;

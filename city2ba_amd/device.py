@@ -293,6 +293,20 @@ def triangulate_rows(camblk, pts4, prows, uv, status, counts, min_angle, pt_mask
     return status, counts
 
 
+def refine_points_rows(camblk, pts4, prows, uv, status, counts, rounds=10, lam=1e-4, function_tol=0.0, gradient_tol=0.0, parameter_tol=0.0,
+                       loss=None, loss_scale=1.0, prior_pt=None, prior_pt_w=None, pt_mask=None):
+    """per-point Levenberg-Marquardt (c2b_refine_points_rows): pts4 [n_pts,4] in place, every point re-minimised
+    by itself over its observations (PointRows) with the cameras held; status [n_pts] uint8 (_lib.REFINE_STATUS order),
+    counts [6] int64 (_lib.REFINE_COUNTS: the five statuses, then the points written); loss by name with its scale;
+    prior_pt / prior_pt_w [n_pts,3] (in pairs) and pt_mask [n_pts] uint8 (1 = constant) or None"""
+    import ctypes as C
+    opt = L.RefineOptions(int(rounds), 0, float(lam), float(function_tol), float(gradient_tol), float(parameter_tol))
+    L.check(L.lib().c2b_refine_points_rows(_p(camblk), _p(pts4), prows.n_pts, _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of),
+                                           _p(uv), L.loss_kind(loss), float(loss_scale) * float(loss_scale), _p(prior_pt), _p(prior_pt_w),
+                                           C.cast(C.pointer(opt), C.c_void_p), _p(pt_mask), _p(status), _p(counts), _stream()))
+    return status, counts
+
+
 def triangulate_consensus_rows(camblk, pts4, prows, uv, status, counts, min_angle, max_error, min_inliers=3, max_hypotheses=64,
                                pt_mask=None, hyp=None, n_inl=None, inlier=None):
     """consensus triangulation (c2b_triangulate_consensus_rows): triangulate_rows over the rays of a point that agree with

@@ -17,7 +17,7 @@ def _clamp(lam):
 
 
 def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0, preconditioner=None, constant=None,
-                        priors=None):
+                        priors=None, inner_iterations=None):
     """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
     sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
     and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit); lam is held
@@ -37,7 +37,15 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     (the restore after a rejected step is an upload of the same counts, which keeps the masks).
     priors = dict(...) of BAProblem.set_priors' keywords (which this calls: the priors stay on ba); None leaves ba's priors as
     they are.  With priors in force the steps are those of the stacked system and the quantity compared -- 'error', 'cost',
-    'error_after' -- is the observations' cost + ba.prior_cost(), added in that order."""
+    'error_after' -- is the observations' cost + ba.prior_cost(), added in that order.
+    inner_iterations = n (BAProblem.set_inner_iterations, which this calls: it stays on ba); None leaves ba's setting as it
+    is.  With n > 0 in force, after a step is applied and before its cost is taken, every point is re-minimised against the
+    moved cameras by ba.refine_points(rounds=n) (Ceres' inner iterations with the points as the inner block).
+    The cost compared is the one after the refinement, so the gain ratio may exceed 1; a rejected step restores the points
+    as before."""
+    if inner_iterations is not None:
+        ba.set_inner_iterations(inner_iterations)
+    n_inner = ba.inner_iterations()
     if priors is not None:
         ba.set_priors(**priors)
     if constant is not None:
@@ -62,6 +70,8 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     for _ in range(int(iterations)):
         dc, dp, info = ba.solve_step(lam, max_iters=max_iters, rel_tol=rel_tol)
         ba.apply_step(dc, dp)
+        if n_inner:
+            ba.refine_points(rounds=n_inner)
         e1 = cost()
         md = info["model_decrease"]
         rho = (e0 - e1) / md if md > 0.0 else -1.0
@@ -82,7 +92,8 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
 
 
 def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, function_tol=0.0, gradient_tol=0.0,
-                               parameter_tol=0.0, loss=None, loss_scale=1.0, preconditioner=None, constant=None, priors=None):
+                               parameter_tol=0.0, loss=None, loss_scale=1.0, preconditioner=None, constant=None, priors=None,
+                               inner_iterations=None):
     """levenberg_marquardt's loop inside the library (c2b_problem_levenberg_marquardt): the same steps, the same damping
     and the same numbers, with a device-side checkpoint and rollback where the loop above downloads and uploads, and with
     stopping tests.  Returns (history, summary).
@@ -96,7 +107,8 @@ def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_t
     parameter_tol (x_norm + parameter_tol); the step is not applied), 4 = the cost or the gradient is not finite (the state
     is the last accepted one).  A tolerance of 0 disables its test: with all three at 0 this is levenberg_marquardt,
     iteration for iteration.  loss, preconditioner, constant and priors as there: with priors in force every cost is the
-    observations' cost + the priors', and the gradient test reads the gradient of the stacked system."""
+    observations' cost + the priors', and the gradient test reads the gradient of the stacked system.
+    inner_iterations as there: set on the handle when given, left as it is when None; the library's loop honours the handle's."""
     import ctypes as C
 
     from . import _lib as L
@@ -108,6 +120,8 @@ def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_t
         ba.set_preconditioner(preconditioner)
     if loss is not None:
         ba.set_loss(loss, loss_scale)
+    if inner_iterations is not None:
+        ba.set_inner_iterations(inner_iterations)
     n = int(iterations)
     opt = L.LmOptions(n, int(max_iters), float(lam), float(rel_tol), float(function_tol), float(gradient_tol), float(parameter_tol))
     entries = (L.LmIteration * max(n, 1))()
@@ -129,7 +143,8 @@ def solve_filtered(ba, max_error, rounds=1, in_front=False, **lm):
     """Robust solve, reject outliers, solve again -- all on the resident problem.  `rounds` times
     levenberg_marquardt_device(ba, **lm) followed by ba.filter_observations(max_error, in_front), then a last
     levenberg_marquardt_device with loss="squared", which clears the loss (it stays cleared on ba).  **lm is what
-    levenberg_marquardt_device takes (iterations, lam, tolerances, loss, loss_scale, preconditioner, constant); the last
+    levenberg_marquardt_device takes (iterations, lam, tolerances, loss, loss_scale, preconditioner, constant,
+    inner_iterations); the last
     solve takes the same arguments but for the loss.  Returns (solves, removed): solves = the (history, summary) of every
     solve, rounds + 1 of them, removed = the observations each round's filter dropped.
     A filter can leave cameras or points with too few observations to constrain them (a camera needs more than 3, a point

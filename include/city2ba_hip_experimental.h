@@ -376,6 +376,65 @@ int c2b_triangulate_rows(const double *camblk, double *pts4, int64_t n_pts, cons
                          int64_t *counts, void *stream);
 int c2b_problem_triangulate_points(c2b_problem *p, double min_angle, uint8_t *status, int64_t *counts);
 
+/* ---- per-point Levenberg-Marquardt: every point refined by itself, the cameras held (one lane per point) ----
+ * Point p's observations are walked in ascending observation index through the point-major transpose, as triangulation
+ * walks them.  A walk evaluates at one position X, all in registers:
+ *   F = sum_o rho(|r_o|^2) + |w_X o (X - X0)|^2     rho of the loss (kind 0: s itself), then the point prior, in that order;
+ *   V = sum_o w Jp^T Jp + diag(w_X^2), g = sum_o w Jp^T r + w_X o r_X, w = rho'(|r_o|^2) at X (IRLS): r and Jp are those of
+ *   the step kernel, scaled by sqrt(w) before the products as every weighted pass scales them.
+ * A prior component of weight 0 contributes nothing and its target is never read (it may be NaN).  Walk 0 is at the start.
+ * Round k, per point, with mu = lambda0 and nu = 2 at the start:
+ *   the gradient test: max |g_i| <= gradient_tol -> converged;
+ *   (V + mu diag(d)) delta = -g by the 3x3 Cholesky, d_i = min(max(V_ii, 1e-6), 1e32); a pivot <= 0 or a non-finite delta
+ *     is a rejection (below);
+ *   the parameter test: |delta| <= parameter_tol (|X| + parameter_tol) -> converged, the step not applied;
+ *   a walk at X + delta gives F', V', g'; model = -(2 g.delta + delta^T V delta); gain = (F - F') / model if model > 0, else -1;
+ *   accepted iff gain > 0, F' < F and F' is finite: X, F, V, g become the trial's, mu *= max(1/3, 1 - (2 gain - 1)^3),
+ *     nu = 2, and the function test: F - F' <= function_tol F -> converged;
+ *   rejected: mu *= nu, nu *= 2.  mu is held in [C2B_STEP_LAMBDA_MIN, C2B_STEP_LAMBDA_MAX].
+ * A tolerance of 0 disables its test.  Status, one byte per point:
+ *   C2B_REFINE_CONVERGED   a tolerance test was met;
+ *   C2B_REFINE_MAX_ROUNDS  max_rounds rounds were run (max_rounds = 0: no round at all, nothing moves);
+ *   C2B_REFINE_UNOBSERVED  no observation and no prior weight; untouched;
+ *   C2B_REFINE_FAILED      the start cost is not finite; untouched;
+ *   C2B_REFINE_CONSTANT    constant under pt_mask / c2b_problem_set_constant; nothing of it is read; untouched.
+ * pts4[p].xyz is written only if the point's cost fell strictly; the fourth lane keeps its value.  counts [6]: the five
+ * statuses, then `moved`, the number of points written.  A point's result depends on its own list, its cameras and the
+ * options alone; there are no float atomics: the same inputs give the same bits.  The pass uses no scratch memory.
+ * max_rounds < 0, reserved != 0, lambda0 outside the damping range, a negative or non-finite tolerance:
+ * C2B_ERR_INVALID_ARGUMENT.
+ * c2b_refine_points_rows: Level 0, stateless, asynchronous on `stream`.  The arguments of c2b_triangulate_rows; loss_a2 is
+ *   the loss's squared scale (ignored for kind 0); prior_pt / prior_pt_w (device, [n_pts][3], in pairs) and pt_mask may be
+ *   NULL; counts [6] (device int64) is zeroed and then summed by integer atomics.
+ * c2b_problem_refine_points: Level 1, synchronous, with the preconditions and the cache story of
+ *   c2b_problem_triangulate_points: the resident cameras in the mode the problem is in, the cached transpose (built when
+ *   absent), only the points change, a shard is refused.  It honours the handle's loss, point mask and point priors; the
+ *   list, the row structure, the transpose, the solve buffers, the masks, the loss, the preconditioner, the priors and a
+ *   checkpoint all stay.  status (host, [n_pts]) and counts (host, [6]) may be NULL.  With no observation at all every
+ *   unmasked point without a prior is C2B_REFINE_UNOBSERVED.
+ * c2b_problem_set_inner_iterations: the handle's state, with the lifetime of the loss.  With rounds > 0 the loop of
+ *   c2b_problem_levenberg_marquardt calls c2b_problem_refine_points with {rounds, 0, 1e-4, 0, 0, 0} directly after it
+ *   applied a step and before it takes the trial cost (Ceres' inner iterations with the points as the inner block):
+ *   cost_trial is the cost after the refinement, so the gain ratio may exceed 1; acceptance, the lambda update and the
+ *   rollback are otherwise unchanged, and a rejected step rolls the points back through the checkpoint.  rounds = 0 (the
+ *   default) issues exactly the launches the loop issued without it.  rounds < 0: C2B_ERR_INVALID_ARGUMENT. */
+#define C2B_REFINE_CONVERGED 0
+#define C2B_REFINE_MAX_ROUNDS 1
+#define C2B_REFINE_UNOBSERVED 2
+#define C2B_REFINE_FAILED 3
+#define C2B_REFINE_CONSTANT 4
+typedef struct {
+    int32_t max_rounds, reserved;
+    double lambda0, function_tol, gradient_tol, parameter_tol;
+} c2b_refine_options;
+int c2b_refine_points_rows(const double *camblk, double *pts4, int64_t n_pts, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                           const uint32_t *cam_of, const double *uv_obs, int loss_kind, double loss_a2, const double *prior_pt,
+                           const double *prior_pt_w, const c2b_refine_options *opt, const uint8_t *pt_mask, uint8_t *status,
+                           int64_t *counts, void *stream);
+int c2b_problem_refine_points(c2b_problem *p, const c2b_refine_options *opt, uint8_t *status, int64_t *counts);
+int c2b_problem_set_inner_iterations(c2b_problem *p, int rounds);
+int c2b_problem_get_inner_iterations(c2b_problem *p, int *rounds);
+
 /* ---- consensus triangulation: points from the rays that agree (two-ray hypotheses, inlier mask, refit) ----
  * c2b_triangulate_rows is a least-squares midpoint over every ray of a point: one ray that belongs to another point (a
  * wrong match, a joined landmark) drags it arbitrarily far.  This pass forms candidates from pairs of rays, keeps the
