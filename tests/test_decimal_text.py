@@ -9,19 +9,7 @@ import numpy as np
 
 from city2ba_amd.baproblem import format_f64
 
-
-def rust_display(x):
-    x = float(x)
-    if x != x:
-        return "NaN"
-    if math.isinf(x):
-        return "inf" if x > 0 else "-inf"
-    s = format(Decimal(repr(x)), "f")
-    if "." in s:
-        s = s.rstrip("0").rstrip(".")
-    if s in ("0", "-0"):
-        return "-0" if math.copysign(1.0, x) < 0 else "0"
-    return s
+from _textref import rust_display
 
 
 def test_known_texts():
