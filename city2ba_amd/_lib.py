@@ -125,6 +125,10 @@ MERGE_STATUS = ("none", "chosen", "unobserved", "held")
 REMATCH_FITS, REMATCH_SKIPPED, REMATCH_REASSIGNED, REMATCH_REMOVED = range(4)
 REMATCH_STATUS = ("fits", "skipped", "reassigned", "removed")
 
+# flags of c2b_problem_subset / c2b_problem_window
+SUBSET_CARRY = 1           # C2B_SUBSET_CARRY: the child takes the parent's handle state and, for repeat-free lists, an origin
+WINDOW_HALO = 1            # C2B_WINDOW_HALO: halo cameras held constant; 0 = no halo cameras, shared points held constant
+
 
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
 SIGNATURES = {
@@ -205,6 +209,10 @@ SIGNATURES = {
     "c2b_problem_resect_consensus": (_int, [_vp, _d, _int, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_merge_points": (_int, [_vp, _d, _d, _int, _vp, C.POINTER(_i64), C.POINTER(_int)]),
     "c2b_problem_rematch_observations": (_int, [_vp, _d, _d, _int, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "c2b_problem_subset": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp]),
+    "c2b_problem_window": (_int, [_vp, _vp, _int, _vp]),
+    "c2b_problem_get_origin": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "c2b_problem_write_back": (_int, [_vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
     "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),

@@ -756,29 +756,76 @@ class BAProblem:
             ret += (inlier,)
         return ret if len(ret) > 1 else out
 
-    def subset(self, ci, pi):
-        """BAProblem::subset (src/baproblem.rs:394-423): cameras ci and points pi in the given order; observations of
-        dropped points disappear.  Host-side index shuffling; returns a NEW device problem."""
+    def subset(self, ci, pi, carry=False):
+        """BAProblem::subset (src/baproblem.rs:394-423) on the device (c2b_problem_subset): cameras ci and points pi in the
+        given order, repeats allowed (a repeated point appears twice and its observations name its last slot);
+        observations of dropped points disappear.  Only the two index lists cross PCIe.  Returns a NEW device problem in
+        this problem's camera mode, holding this problem's bits: cameras(), points(), row_ptr, pt_idx and observations()
+        are the same arrays in either mode.  carry=False: the child's handle state is a new problem's.  carry=True: it
+        takes this problem's options, loss, preconditioner, inner iterations, and its constant masks and priors gathered
+        by the lists; when neither list repeats an index it also records an origin() and can write_back()."""
         ci = np.asarray(ci, dtype=np.int64).reshape(-1)
         pi = np.asarray(pi, dtype=np.int64).reshape(-1)
         n_cam, n_pts = self.num_cameras(), self.num_points()
         if (len(ci) and (ci.min() < 0 or ci.max() >= n_cam)) or (len(pi) and (pi.min() < 0 or pi.max() >= n_pts)):
             raise L.City2baError(L.ERR_INDEX_OUT_OF_RANGE, "subset: index out of range")
-        cams, pts, uv = self.cameras(), self.points(), self.observations()
-        new_of = np.full(n_pts, -1, dtype=np.int64)
-        new_of[pi] = np.arange(len(pi))                       # HashMap::from_iter: a repeated point keeps its last slot
-        rows, cols, vals = [0], [], []
-        for c in ci:
-            a, b = int(self._row_ptr[c]), int(self._row_ptr[c + 1])
-            p_new = new_of[self._pt_idx[a:b].astype(np.int64)]
-            k = p_new >= 0
-            cols.append(p_new[k])
-            vals.append(uv[a:b][k])
-            rows.append(rows[-1] + int(k.sum()))
-        cols = np.concatenate(cols).astype(np.uint64) if cols else np.zeros(0, np.uint64)
-        vals = np.concatenate(vals) if vals else np.zeros((0, 2))
-        return BAProblem.from_visibility(cams[ci], pts[pi], np.array(rows, dtype=np.uint64), cols, vals.reshape(-1, 2),
-                                         self._device)
+        c32, p32 = np.ascontiguousarray(ci, dtype=np.uint32), np.ascontiguousarray(pi, dtype=np.uint32)
+        child = BAProblem(self._device)
+        try:
+            L.check(L.lib().c2b_problem_subset(self._h, _ptr(c32) if len(c32) else None, len(c32), _ptr(p32) if len(p32) else None,
+                                               len(p32), L.SUBSET_CARRY if carry else 0, child._h))
+        except Exception:
+            child.close()
+            raise
+        return child._refresh_graph()
+
+    def window(self, cameras, halo=True):
+        """A window of this problem as a problem of its own (c2b_problem_window): the seed cameras (`cameras`: an index
+        list or a bool mask [n_cam]), the points P they see, and the rim held constant -- with halo, every other camera
+        that sees a point of P, all nine parameters constant, with its observations of P; without, no further camera, and
+        the points of P seen from outside the window constant.  Every residual that depends on a free variable is in the
+        child, so a solve of the child is block-coordinate descent on this problem's cost.  The child carries this
+        problem's handle state (masks OR the roles, priors, loss, preconditioner, inner iterations, options) and an
+        origin(); write_back() puts its free entities back."""
+        n_cam = self.num_cameras()
+        a = np.asarray(cameras)
+        if a.dtype == np.bool_:
+            if a.shape != (n_cam,):
+                raise ValueError("window: a bool mask must have shape (%d,)" % n_cam)
+            seed = np.ascontiguousarray(a, dtype=np.uint8)
+        else:
+            idx = np.asarray(a, dtype=np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= n_cam):
+                raise L.City2baError(L.ERR_INDEX_OUT_OF_RANGE, "window: camera index out of range")
+            seed = np.zeros(n_cam, dtype=np.uint8)
+            seed[idx] = 1
+        child = BAProblem(self._device)
+        try:
+            L.check(L.lib().c2b_problem_window(self._h, _ptr(seed), L.WINDOW_HALO if halo else 0, child._h))
+        except Exception:
+            child.close()
+            raise
+        return child._refresh_graph()
+
+    def origin(self):
+        """where a child of subset(carry=True) / window came from (c2b_problem_get_origin): dict(cam_of [n_cam], pt_of
+        [n_pts]: the parent's index of every camera / point; cam_role: 0 seed, 1 halo; pt_role: 1 = shared), or None"""
+        n_cam, n_pts, _ = self._sizes()
+        out = dict(cam_of=np.zeros(n_cam, dtype=np.uint32), pt_of=np.zeros(n_pts, dtype=np.uint32),
+                   cam_role=np.zeros(n_cam, dtype=np.uint8), pt_role=np.zeros(n_pts, dtype=np.uint8))
+        if L.lib().c2b_problem_get_origin(self._h, _ptr(out["cam_of"]), _ptr(out["pt_of"]), _ptr(out["cam_role"]), _ptr(out["pt_role"])):
+            return None
+        return out
+
+    def write_back(self, parent):
+        """This child's cameras and points over the parent's (c2b_problem_write_back), component by component where this
+        child's masks leave them free now; everything else of the parent keeps its bits.  Both are in bal mode afterwards,
+        as after apply_step.  Refused when this problem has no origin, when `parent` is not the problem it was taken from,
+        or when the parent's entities were replaced or renumbered since.  Returns dict(cameras, points): cameras with at
+        least one free parameter, and free points."""
+        a, b = C.c_int64(), C.c_int64()
+        L.check(L.lib().c2b_problem_write_back(self._h, parent._h, C.byref(a), C.byref(b)))
+        return dict(cameras=a.value, points=b.value)
 
     def _refresh_graph(self):
         """host mirrors of the graph (row_ptr, pt_idx) after a device-side change"""

@@ -22,9 +22,10 @@
 //                         --preconditioner block-jacobi|schur-jacobi --inner-iterations N --fix-intrinsics --fix-first-camera
 //                         --filter-max-error X --filter-rounds N --filter-in-front
 //                         --prior-from FILE [--prior-center-sigma S|SX,SY,SZ] [--prior-intrinsics-sigma SF,SK1,SK2]
-//                         [--prior-point-sigma S [--prior-point-every N]]]
+//                         [--prior-point-sigma S [--prior-point-every N]] [--window LO:HI [--no-halo]]]
 //                        (extension: Levenberg-Marquardt on the device, c2b_problem_levenberg_marquardt; with
-//                         --filter-max-error: N times solve + c2b_problem_filter_observations, then a solve without a loss)
+//                         --filter-max-error: N times solve + c2b_problem_filter_observations, then a solve without a loss;
+//                         with --window: cameras LO .. HI-1 alone, c2b_problem_window + c2b_problem_write_back)
 //   city2ba triangulate IN OUT [--min-angle DEG] [--max-error X [--min-inliers N] [--max-hypotheses H] [--drop-outliers]]
 //                        (extension: the points from the cameras and observations, c2b_problem_triangulate_points; with
 //                         --max-error: from the rays that agree with each other, c2b_problem_triangulate_consensus)
@@ -882,10 +883,10 @@ static int loss_kind_of(const Args &a) {
 }
 
 int run_solve(int argc, char **argv) {
-    const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera", "filter-in-front"},
+    const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera", "filter-in-front", "no-halo"},
                          {"iterations", "lambda", "pcg-iterations", "pcg-tol", "function-tol", "gradient-tol", "parameter-tol", "loss",
                           "loss-scale", "preconditioner", "inner-iterations", "device", "filter-max-error", "filter-rounds", "prior-from",
-                          "prior-center-sigma", "prior-intrinsics-sigma", "prior-point-sigma", "prior-point-every"});
+                          "prior-center-sigma", "prior-intrinsics-sigma", "prior-point-sigma", "prior-point-every", "window"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
     c2b_lm_options opt;
     opt.max_iterations = (int32_t)std::min<int64_t>(a.i("iterations", 10), 1 << 20);
@@ -914,6 +915,27 @@ int run_solve(int argc, char **argv) {
     }
     const int64_t inner_iterations = a.i("inner-iterations", 0);
     if (inner_iterations > 1000) die("Invalid value for '--inner-iterations <N>': expected an integer in 0 ... 1000");
+    // --window LO:HI: cameras LO .. HI - 1 are solved with their rim held constant; the range is checked against the file's
+    // camera count here, before a device exists
+    const bool window = a.has("window");
+    int64_t win_lo = 0, win_hi = 0;
+    if (a.has("no-halo") && !window) die("--no-halo needs --window <LO:HI>");
+    if (window) {
+        const std::string &v = a.opt.at("window");
+        const std::string bad = "Invalid value for '--window <LO:HI>': expected two integers LO:HI with 0 <= LO < HI <= the number of cameras";
+        const size_t colon = v.find(':');
+        if (colon == std::string::npos || colon == 0 || colon + 1 == v.size()) die(bad);
+        for (size_t k = 0; k < v.size(); ++k)
+            if (k != colon && (v[k] < '0' || v[k] > '9')) die(bad);
+        if (colon > 18 || v.size() - colon - 1 > 18) die(bad);
+        win_lo = std::stoll(v.substr(0, colon));
+        win_hi = std::stoll(v.substr(colon + 1));
+        if (win_lo >= win_hi) die(bad);
+        int64_t in_cam = 0, in_pts = 0;
+        peek_counts(a.positional[0], in_cam, in_pts);
+        if (win_hi > in_cam)
+            die("--window: " + a.positional[0] + " has " + std::to_string(in_cam) + " cameras, the window ends at " + std::to_string(win_hi));
+    }
     // priors: every flag and both files' counts are checked here, before a device exists
     const bool prior = a.has("prior-from");
     std::vector<double> w_center, w_intr, w_point;
@@ -982,6 +1004,20 @@ int run_solve(int argc, char **argv) {
         if (a.has("fix-first-camera") && nc) cm[0] |= C2B_CONST_POSE;
         ck(c2b_problem_set_constant(p, cm.data(), nullptr));
     }
+    // the window: a child of the problem that carries everything set above (the rim's masks on top); it is what is solved
+    c2b_problem *whole = p;
+    if (window) {
+        std::vector<uint8_t> seed((size_t)nc + 1, 0);
+        for (int64_t c = win_lo; c < win_hi && c < nc; ++c) seed[(size_t)c] = 1;
+        c2b_problem *child = nullptr;
+        ck(create_problem(device, &child));
+        ck(c2b_problem_window(whole, seed.data(), a.has("no-halo") ? 0 : C2B_WINDOW_HALO, child));
+        p = child;
+        ck(c2b_problem_sizes(p, &nc, &np, &no));
+        timer.mark("window (device)");
+        std::printf("window %lld:%lld: %lld cameras, %lld points, %lld observations\n", (long long)win_lo, (long long)win_hi, (long long)nc,
+                    (long long)np, (long long)no);
+    }
     std::vector<c2b_lm_iteration> hist((size_t)opt.max_iterations + 1);
     static const char *const why[] = {"iteration limit reached", "function tolerance reached", "gradient tolerance reached",
                                       "parameter tolerance reached", "cost or gradient not finite"};
@@ -1007,6 +1043,14 @@ int run_solve(int argc, char **argv) {
         ck(c2b_problem_set_loss(p, 0, 1.0));
     }
     solve_once();
+    if (window) {                                            // the child's free cameras and points back into the whole problem
+        int64_t wc = 0, wp = 0;
+        ck(c2b_problem_write_back(p, whole, &wc, &wp));
+        c2b_problem_destroy(p);
+        p = whole;
+        timer.mark("write_back (device)");
+        std::printf("written back: %lld cameras, %lld points\n", (long long)wc, (long long)wp);
+    }
     close_problem(timer, p, a.positional[1]);
     return 0;
 }
@@ -1234,6 +1278,11 @@ const char *subcommand_help(const std::string &sub) {
                "                              before the step's cost is taken (0: off)\n"
                "    --fix-intrinsics          hold f, k1, k2 of every camera constant\n"
                "    --fix-first-camera        hold the pose of camera 0 constant\n"
+               "    --window <LO:HI>          solve cameras LO ... HI-1 and the points they see alone, with everything at the rim of the\n"
+               "                              window held constant, and put the result back; the whole problem is written.  Every other\n"
+               "                              flag applies to the window [off]\n"
+               "    --no-halo                 with --window: take no cameras from outside the window; the points also seen from outside\n"
+               "                              are held constant instead of the outside cameras that see the window's points\n"
                "    --filter-max-error <X>    outlier rejection: solve, drop the observations whose reprojection residual exceeds X,\n"
                "                              then solve again without a loss [off]\n"
                "    --filter-rounds <N> [1]   solve + filter rounds before the last solve\n"

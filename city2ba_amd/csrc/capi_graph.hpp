@@ -212,6 +212,7 @@ static int cull_impl(c2b_problem *p, int faithful, int mode) {
     p->cam15 = std::move(n_cam15); p->bal9 = std::move(n_bal9); p->camblk = std::move(n_camblk); p->cen4 = std::move(n_cen4);
     p->pts4 = std::move(n_pts4); p->n_cam = nc; p->n_pts = np;
     drop_constant(p);                                         // the survivors are renumbered
+    entities_replaced(p);
     drop_priors(p);
     drop_lm_state(p);
     p->blk_valid = false;                                     // camblk is rebuilt on demand from the gathered cameras
@@ -320,7 +321,8 @@ static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_o
     if (e == hipSuccess) e = row_new.alloc((size_t)n_cam + 1);
     if (e != hipSuccess) return e;
     const unsigned row_blocks = (unsigned)((n_cam + 3) / 4);
-    if (n_cam) hipLaunchKernelGGL(k_keep_row_counts, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, d_keep, n_cam, d_tot);
+    if (n_cam) hipLaunchKernelGGL((k_keep_row_counts<RowSame, KeepByte>), dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, RowSame{},
+                                  KeepByte{d_keep}, d_pt, n_cam, d_tot.ptr);
     scan_short(p->stream, (const uint64_t *)d_tot, n_cam, (uint64_t)0, row_new.ptr, row_new.ptr + n_cam);      // cameras: one workgroup
     e = hipMemcpyAsync(row_ptr_host, row_new, sizeof(uint64_t) * (size_t)(n_cam + 1), hipMemcpyDeviceToHost, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
@@ -330,8 +332,9 @@ static hipError_t compact_rows_on_device(c2b_problem *p, const uint64_t *d_row_o
     e = pt_new.alloc((size_t)*w);
     if (e == hipSuccess) e = uv_new.alloc(2 * (size_t)*w);
     if (e == hipSuccess && n_cam) {
-        hipLaunchKernelGGL(k_keep_row_scatter, dim3(row_blocks), dim3(256), 0, p->stream, d_row_old, (const uint64_t *)row_new, d_keep,
-                           d_pt, reinterpret_cast<const double2 *>(d_uv), n_cam, pt_new, reinterpret_cast<double2 *>(uv_new.ptr));
+        hipLaunchKernelGGL((k_keep_row_scatter<RowSame, KeepByte>), dim3(row_blocks), dim3(256), 0, p->stream, d_row_old,
+                           (const uint64_t *)row_new, RowSame{}, KeepByte{d_keep}, d_pt, reinterpret_cast<const double2 *>(d_uv), n_cam,
+                           pt_new.ptr, reinterpret_cast<double2 *>(uv_new.ptr));
         e = launch_error();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
@@ -1147,6 +1150,7 @@ int c2b_problem_generate_world_points(c2b_problem *p, const float *tri9, int64_t
     free_dense(p);
     drop_rows(p);
     drop_constant(p);
+    entities_replaced(p);
     drop_priors(p);
     drop_lm_state(p);
     p->pts4 = std::move(out);

@@ -74,6 +74,18 @@ struct c2b_problem {
     DevBuf<double> jac_ring;                               // kJacSlots x kJacChunk x 26 doubles
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_done[kJacSlots] = {nullptr, nullptr, nullptr}, ev_free[kJacSlots] = {nullptr, nullptr, nullptr};
+    // identity: serial names the handle for the life of the process (set at create); entity_epoch is raised
+    // wherever the entities are replaced or renumbered (entities_replaced: the rows of the table below whose masks column says X)
+    uint64_t serial = 0, entity_epoch = 0;
+    // c2b_problem_subset / c2b_problem_window: where this problem's entities came from -- the parent's identity and counts at
+    // the extraction, child index -> parent index and the roles (cameras 0 seed / 1 halo, points 0 / 1 shared), on the host and,
+    // for c2b_problem_write_back's scatters, on the device.  Gone as soon as this problem's own entities are replaced.
+    bool has_origin = false;
+    uint64_t origin_serial = 0, origin_epoch = 0;
+    int64_t origin_n_cam = 0, origin_n_pts = 0;
+    std::vector<uint32_t> h_cam_of, h_pt_of;
+    std::vector<uint8_t> h_cam_role, h_pt_role;
+    DevBuf<uint32_t> d_cam_of, d_pt_of;
 };
 
 // Which event drops which cache or handle state.  X: dropped (rebuilt by the next user, or gone), -: stays.  The functions
@@ -95,13 +107,23 @@ struct c2b_problem {
 //   resect_consensus (6)       X            truth      - / X - / X      - / X  -             -           -
 //   merge_points (7)           -            -          - / X - / X      - / X  -             -           -
 //   rematch_observations (8)   -            -          - / X - / X      - / X  -             -           -
+//   subset, window: src        -            - (9)      -     -          -      -             -           -
+//   subset, window: dst (10)   X            X / truth  X     X          X      X             X / carried X
+//   get_origin                 -            -          -     -          -      -             -           -
+//   write_back: parent         X            truth      -     -          -      -             -           -
+//   write_back: child (11)     - / X        - / truth  -     -          -      -             -           -
 // The priors (c2b_problem_set_priors) share the masks' column: kept and dropped with them, by counts of their own.
 // (1) kept when both counts are those the masks were set for.  (2) gathered with the cameras while it is the truth; a merely
 // fresh bal9 (bal9_fresh: to_vec of the current cameras, filled by download_bal / write / apply_step) is dropped.  (3) on
 // entry, so also by a cull that fails later.  (4) one that removes nothing drops nothing.  (5) checkpoint is an apply_step
 // of no step, then the copy.  (6) with C2B_TRI_DROP_OUTLIERS / C2B_RES_DROP_OUTLIERS and something removed: as the filter.  (7) after every round that merged: as the filter.
 // (8) after a call that reassigned or removed something: as the filter.  A new visibility result
-// (pairs_compact, within_distance, dense) replaces the pending one only.
+// (pairs_compact, within_distance, dense) replaces the pending one only.  (9) the source is read, never written.  (10) replaced
+// as an upload replaces it, in the source's camera mode (bal9 gathered while it is the source's truth); the masks and priors are
+// the source's, gathered by the origin lists, with C2B_SUBSET_CARRY (a window: always, OR the roles) and dropped without; the
+// origin (above) is recorded by a window, and by a carrying subset of repeat-free lists.  (11) a state-mode child gets to_vec of
+// its cameras and is in bal mode afterwards; a child in bal mode is only read.
+// An X in the masks column is also where the handle's entity_epoch is raised and its origin dropped (entities_replaced).
 // the cameras moved: every cache of them (apply_step / rollback then make bal9 the truth)
 static void cameras_mutated(c2b_problem *p) { p->bal_valid = false; p->blk_valid = false; p->bal9_fresh = false; }
 
@@ -140,6 +162,19 @@ static bool has_priors(const c2b_problem *p) { return p->pcw || p->piw || p->pxw
 static void drop_lm_state(c2b_problem *p) {
     p->ck_bal9.reset(); p->ck_pts4.reset(); p->lm.reset();
     p->ck_valid = false;
+}
+
+// the origin of a sub-problem: it no longer describes the entities
+static void drop_origin(c2b_problem *p) {
+    p->has_origin = false;
+    p->h_cam_of.clear(); p->h_pt_of.clear(); p->h_cam_role.clear(); p->h_pt_role.clear();
+    p->d_cam_of.reset(); p->d_pt_of.reset();
+}
+
+// the entities were replaced or renumbered: no origin taken FROM this problem fits it any more, and its own origin is gone
+static void entities_replaced(c2b_problem *p) {
+    ++p->entity_epoch;
+    drop_origin(p);
 }
 
 // everything but the constant masks goes: "nothing uploaded"
@@ -183,6 +218,8 @@ int c2b_problem_create(int device, c2b_problem **out) {
     c2b_problem *p = new (std::nothrow) c2b_problem();
     if (!p) return fail(C2B_ERR_OOM, "problem_create: host allocation failed");
     p->device = device;
+    static std::atomic<uint64_t> next_serial{1};
+    p->serial = next_serial.fetch_add(1, std::memory_order_relaxed);
     hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete p; return fail(C2B_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
     *out = p;
@@ -196,6 +233,7 @@ void c2b_problem_destroy(c2b_problem *p) {
     free_buffers(p);
     drop_constant(p);
     drop_priors(p);
+    drop_origin(p);
     for (int k = 0; k < c2b_problem::kJacSlots; ++k) {
         if (p->ev_done[k]) (void)hipEventDestroy(p->ev_done[k]);
         if (p->ev_free[k]) (void)hipEventDestroy(p->ev_free[k]);
@@ -225,6 +263,7 @@ static int new_workspace(DevBuf<char> &ws, int64_t n_obs, hipStream_t st) {
 static int alloc_problem(c2b_problem *p, int64_t n_cam, int64_t n_pts, int64_t n_obs, bool same_entities = false) {
     HIP_TRY(hipSetDevice(p->device));
     free_buffers(p);
+    entities_replaced(p);
     if (!same_entities || n_cam != p->const_n_cam || n_pts != p->const_n_pts) drop_constant(p);
     if (!same_entities || n_cam != p->prior_n_cam || n_pts != p->prior_n_pts) drop_priors(p);
     HIP_TRY(p->cam15.alloc(15 * (size_t)n_cam));
@@ -730,6 +769,7 @@ int c2b_problem_stats(c2b_problem *p, double *stats) {
 }
 
 #include "capi_graph.hpp"        // cull, adopt, filter, the visibility entries, generate_world_points, the dense sweep
+#include "capi_subset.hpp"       // subset, window, get_origin, write_back: a sub-problem cut out on the device and put back
 #include "capi_files.hpp"        // c2b_problem_write / c2b_problem_read: both file forms assembled / taken apart on the device
 
 // ---- the noise functions, alone and for a problem that is ONE SHARD of a larger one ----------

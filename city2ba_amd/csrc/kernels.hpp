@@ -1836,37 +1836,57 @@ __global__ __launch_bounds__(kBlock) void k_rows_from_sorted(const uint32_t *__r
     for (int64_t c = prev + 1; c <= cur && c <= n_cam; ++c) row_ptr[c] = (uint64_t)i;
 }
 
-// ---- stable compaction of a CSR observation list by a keep mask (the occlusion filter's output), on the device ----
-// one wave per camera: kept observations per row ...
-__global__ __launch_bounds__(256) void k_keep_row_counts(const uint64_t *__restrict__ row_ptr, const uint8_t *__restrict__ keep,
-                                                        int64_t n_cam, uint64_t *__restrict__ cam_total) {
+// ---- stable compaction of a CSR observation list, on the device: new row c reads old row src.row(c) and keeps the ----
+// ---- entries that `keep` passes, in row order.  Two policies say which: RowSame / RowVia the row source, KeepByte  ----
+// ---- / KeepMapped (subset_kernels.hpp) the predicate and the point index written.  One wave per row, four rows per ----
+// ---- workgroup; the kept count is the popcount of a ballot over chunks of 64, the fill position the carried count  ----
+// ---- plus the lane's rank in the ballot.                                                                            ----
+struct RowSame {                                              // row c of the new list is row c of the old one
+    __device__ __forceinline__ int64_t row(int64_t c) const { return c; }
+};
+struct KeepByte {                                             // a keep byte per old entry (the filter's mask); the point index stays
+    const uint8_t *__restrict__ keep;
+    __device__ __forceinline__ bool kept(uint64_t i, const uint32_t *) const { return keep[i] != 0; }
+    __device__ __forceinline__ uint32_t index(uint32_t pt) const { return pt; }
+};
+
+// kept observations per row ...
+template <class Row, class Keep>
+__global__ __launch_bounds__(256) void k_keep_row_counts(const uint64_t *__restrict__ row_ptr, Row src, Keep keep,
+                                                        const uint32_t *__restrict__ pt_in, int64_t n_rows,
+                                                        uint64_t *__restrict__ row_total) {
     const int lane = threadIdx.x & 63;
     const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= n_cam) return;
-    const uint64_t b = row_ptr[c], e = row_ptr[c + 1];
-    int count = 0;
-    for (uint64_t i = b + lane; i < e; i += 64) count += keep[i] ? 1 : 0;
-    const double s = wave_sum((double)count);                 // exact: counts are far below 2^53
-    if (lane == 0) cam_total[c] = (uint64_t)s;
+    if (c >= n_rows) return;                                  // wave-uniform
+    const int64_t r = src.row(c);
+    const uint64_t b = row_ptr[r], e = row_ptr[r + 1];
+    uint64_t count = 0;
+    for (uint64_t base = b; base < e; base += 64) {           // wave-uniform trip count
+        const uint64_t i = base + lane;
+        count += (uint64_t)__popcll(__ballot(i < e && keep.kept(i, pt_in)));
+    }
+    if (lane == 0) row_total[c] = count;
 }
 
 // ... and, after the row scan, the kept (point index, uv) pairs moved to their new rows in their old order
+template <class Row, class Keep>
 __global__ __launch_bounds__(256) void k_keep_row_scatter(const uint64_t *__restrict__ row_old, const uint64_t *__restrict__ row_new,
-                                                         const uint8_t *__restrict__ keep, const uint32_t *__restrict__ pt_in,
-                                                         const double2 *__restrict__ uv_in, int64_t n_cam,
+                                                         Row src, Keep keep, const uint32_t *__restrict__ pt_in,
+                                                         const double2 *__restrict__ uv_in, int64_t n_rows,
                                                          uint32_t *__restrict__ pt_out, double2 *__restrict__ uv_out) {
     const int lane = threadIdx.x & 63;
     const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= n_cam) return;
-    const uint64_t b = row_old[c], e = row_old[c + 1];
+    if (c >= n_rows) return;                                  // wave-uniform
+    const int64_t r = src.row(c);
+    const uint64_t b = row_old[r], e = row_old[r + 1];
     uint64_t dst = row_new[c];
     for (uint64_t base = b; base < e; base += 64) {           // wave-uniform trip count
         const uint64_t i = base + lane;
-        const bool k = i < e && keep[i] != 0;
+        const bool k = i < e && keep.kept(i, pt_in);
         const unsigned long long m = __ballot(k);
         if (k) {
             const uint64_t at = dst + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
-            pt_out[at] = pt_in[i];
+            pt_out[at] = keep.index(pt_in[i]);
             uv_out[at] = uv_in[i];
         }
         dst += (uint64_t)__popcll(m);

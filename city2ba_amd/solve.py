@@ -159,3 +159,44 @@ def solve_filtered(ba, max_error, rounds=1, in_front=False, **lm):
     last["loss"] = "squared"
     solves.append(levenberg_marquardt_device(ba, **last))
     return solves, removed
+
+
+def solve_window(ba, cameras, halo=True, **lm):
+    """Local bundle adjustment of one window, on the device: ba.window(cameras, halo), levenberg_marquardt_device(child,
+    **lm), child.write_back(ba), child.close().  The rim of the window is held constant and every residual that depends
+    on a free variable is in the child, so the child's cost reduction is ba's: one step of block-coordinate descent on
+    the full cost.  The child carries ba's masks, priors, loss, preconditioner and inner iterations; **lm is what
+    levenberg_marquardt_device takes (a `constant` or `priors` given there would replace what the window installed, the
+    rim's masks included, and must be sized for the child).  ba is in bal mode afterwards.  Returns the LM summary plus
+    cameras, points, observations (the child's sizes), written = write_back's counts and history = the iterations."""
+    child = ba.window(cameras, halo=halo)
+    try:
+        history, summary = levenberg_marquardt_device(child, **lm)
+        out = dict(summary)
+        out["cameras"], out["points"], out["observations"] = child._sizes()
+        out["written"] = child.write_back(ba)
+        out["history"] = history
+        return out
+    finally:
+        child.close()
+
+
+def solve_windows(ba, size, stride=None, sweeps=1, halo=True, **lm):
+    """solve_window over windows of `size` consecutive camera indices every `stride` (default: size), over all cameras,
+    `sweeps` times.  Returns the per-window summaries in the order solved, each with lo and hi (its cameras lo .. hi - 1)
+    and sweep."""
+    size = int(size)
+    stride = size if stride is None else int(stride)
+    if size < 1 or stride < 1:
+        raise ValueError("solve_windows: size and stride must be at least 1")
+    n_cam = ba.num_cameras()
+    out = []
+    for sweep in range(int(sweeps)):
+        for lo in range(0, n_cam, stride):
+            hi = min(lo + size, n_cam)
+            s = solve_window(ba, range(lo, hi), halo=halo, **lm)
+            s.update(lo=lo, hi=hi, sweep=sweep)
+            out.append(s)
+            if hi == n_cam:
+                break
+    return out

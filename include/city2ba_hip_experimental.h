@@ -712,6 +712,44 @@ int c2b_rematch_rows(const double *camblk, const double *pts4, int64_t n_pts, co
 int c2b_problem_rematch_observations(c2b_problem *p, double radius, double max_error, int min_fits, uint8_t *status_out,
                                      int64_t *n_reassigned, int64_t *n_removed);
 
+/* ---- sub-problems on the device: BAProblem::subset (src/baproblem.rs:394-423) for a caller's selection, a window
+ * of cameras with its rim held fixed, and the write-back of what a solve of the child moved.  Integer kernels and copies only:
+ * the same inputs give the same bits.  Only the selection lists cross PCIe on the way in and the origin lists on the way out.
+ * `dst` is a handle from c2b_problem_create on src's device; its contents are replaced as an upload replaces them, and it is
+ * left as it was on any failure.  The child is in src's camera mode and holds src's bits.  A pending visibility result of src
+ * is not carried; neither are a checkpoint, LM scratch, rows, transpose or solve buffers.
+ * c2b_problem_subset: cameras cam_sel and points pt_sel in the given order, repeats allowed; a repeated point appears twice and
+ *   its observations name its LAST slot; observations of points that were not selected disappear; duplicated (camera, point)
+ *   entries of a row are both kept; empty lists give a child without cameras and / or points.  flags = C2B_SUBSET_CARRY: the child
+ *   takes src's options, loss and scale, preconditioner, inner iterations, and the constant masks and every prior kind src
+ *   holds, gathered by the lists; and, when neither list repeats an index, an origin.  Without the flag the child's handle state
+ *   is a new handle's.  An index out of range: C2B_ERR_INDEX_OUT_OF_RANGE; dst == src, another device, a shard, a NULL list with a
+ *   non-zero count, a count >= 2^31, an unknown flag bit: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_problem_window: S = the cameras with seed[c] != 0 (seed: host, one byte per camera of src; an empty S is refused), P = the
+ *   points with an observation in a row of S.  flags = C2B_WINDOW_HALO: H = the cameras outside S with an observation of a point
+ *   of P; the child's cameras are S and H in ascending index, a seed row whole, a halo row's observations of P in row order, and
+ *   a halo camera's mask word is src's OR C2B_CONST_ALL.  flags = 0: the child's cameras are S, and a point of P with an observation
+ *   outside S is shared: its mask byte is src's OR 1.  The child's points are P in ascending index.  A window always carries the
+ *   handle state and always records an origin.  With the rim so chosen every residual that depends on a free variable of the
+ *   child is in the child.
+ * c2b_problem_get_origin: cam_of [n_cam], pt_of [n_pts] (the parent's index of every camera / point of the child), cam_role
+ *   [n_cam] (0 seed, 1 halo), pt_role [n_pts] (0, 1 shared); any pointer may be NULL.  A problem without an origin:
+ *   C2B_ERR_INVALID_ARGUMENT.  The origin goes when the child's own entities are replaced or renumbered.
+ * c2b_problem_write_back: the child's cameras and points over the parent's, component by component where the child's mask AT THE
+ *   CALL leaves it free: bal9 entries whose mask bit is clear, xyz of points whose byte is clear (the fourth lane of the parent's
+ *   row stays).  Worded as c2b_problem_apply_step: the parent (and a state-mode child) gets to_vec of its cameras first and is in
+ *   bal mode afterwards; the parent's list, rows, transpose, solve buffers, masks, priors, loss and checkpoint stay.
+ *   *n_cam_written = cameras with at least one free component, *n_pts_written = free points (may be NULL).  Refused with nothing
+ *   written (C2B_ERR_INVALID_ARGUMENT): a child without an origin, a parent that is not the handle the origin names or whose
+ *   entities were replaced or renumbered since (upload, read, cull, the generators), child == parent, different devices, a shard. */
+#define C2B_SUBSET_CARRY 1
+#define C2B_WINDOW_HALO 1
+int c2b_problem_subset(c2b_problem *src, const uint32_t *cam_sel, int64_t n_cam_sel, const uint32_t *pt_sel, int64_t n_pt_sel, int flags,
+                       c2b_problem *dst);
+int c2b_problem_window(c2b_problem *src, const uint8_t *seed, int flags, c2b_problem *dst);
+int c2b_problem_get_origin(const c2b_problem *child, uint32_t *cam_of, uint32_t *pt_of, uint8_t *cam_role, uint8_t *pt_role);
+int c2b_problem_write_back(c2b_problem *child, c2b_problem *parent, int64_t *n_cam_written, int64_t *n_pts_written);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */

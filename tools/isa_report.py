@@ -4,6 +4,7 @@ operations, waits and branches (what the software-pipelined kernels are checked 
 and no scratch inside the loop).  Works on the CPU box: hipcc cross-compiles.
 
     python tools/isa_report.py [--filter k_residual_jacobian_l] [--dump <mangled-name-substring>]
+    python tools/isa_report.py --filter subset        (a named group: the kernels of sub-problem extraction and write-back)
 
 Also a module: compile_asm() / kernel_table() / kernel_body() are what tests/test_isa_pins.py asserts on.
 """
@@ -74,20 +75,25 @@ def kernel_body(asm, mangled):
     return [ln.strip() for ln in asm[i:j].split("\n") if ln.strip() and not ln.strip().startswith(";")]
 
 
+# named groups of --filter: the kernels one feature launches, by the substrings of their names
+GROUPS = {"subset": ("k_subset_", "k_window_", "k_scatter_free_", "k_keep_row_", "k_gather_rows")}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--filter", default="", help="only kernels whose demangled name contains this")
+    ap.add_argument("--filter", default="", help="only kernels whose demangled name contains this, or a group: " + ", ".join(sorted(GROUPS)))
     ap.add_argument("--dump", default="", help="print the VM-op / wait skeleton of the first kernel whose name contains this")
     ap.add_argument("--keep", default="", help="directory to keep the temporaries in")
     a = ap.parse_args()
     asm = compile_asm(a.keep)
     rows = kernel_table(asm)
+    wanted = GROUPS.get(a.filter, (a.filter,))
     for r in rows:
-        if a.filter in r["name"]:
+        if any(w in r["name"] for w in wanted):
             v = r["vgpr"]
             waves = 512 // ((v + 7) // 8 * 8) if v else 8
-            print("%-70s vgpr %3d (%d waves/SIMD)  sgpr %3d  lds %6d  scratch %d" % (
-                r["name"][:70], v, min(waves, 8), r["sgpr"], r["lds"], r["scratch"]))
+            print("%-70s vgpr %3d (%d waves/SIMD)  sgpr %3d  lds %6d  scratch %d  spills %d" % (
+                r["name"][:70], v, min(waves, 8), r["sgpr"], r["lds"], r["scratch"], r["vgpr_spill"] + r["sgpr_spill"]))
     if a.dump:
         for r in rows:
             if a.dump in r["name"] or a.dump in r["mangled"]:
