@@ -209,6 +209,14 @@ SIGNATURES = {
     "c2b_problem_resect_consensus": (_int, [_vp, _d, _int, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_merge_points": (_int, [_vp, _d, _d, _int, _vp, C.POINTER(_i64), C.POINTER(_int)]),
     "c2b_problem_rematch_observations": (_int, [_vp, _d, _d, _int, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "c2b_drop_keep_rows": (_int, [_vp, _i64, _i64, _d, _u64, _vp, _vp]),
+    "c2b_mismatch_partner_rows": (_int, [_vp, _i64, _vp, _i64, _d, _u64, _vp, _vp, _vp]),
+    "c2b_select_smallest_keys_rows": (_int, [_vp, _i64, _u64, _int, _int, _i64, _vp, _vp]),
+    "c2b_nearest_points_rows": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "c2b_problem_drop_features": (_int, [_vp, _d, _u64, C.POINTER(_i64)]),
+    "c2b_problem_add_incorrect_correspondences": (_int, [_vp, _d, _u64, C.POINTER(_i64)]),
+    "c2b_problem_split_landmarks": (_int, [_vp, _d, _u64, C.POINTER(_i64)]),
+    "c2b_problem_join_landmarks": (_int, [_vp, _d, _u64, C.POINTER(_i64)]),
     "c2b_problem_subset": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp]),
     "c2b_problem_window": (_int, [_vp, _vp, _int, _vp]),
     "c2b_problem_get_origin": (_int, [_vp, _vp, _vp, _vp, _vp]),

@@ -623,6 +623,36 @@ class BAProblem:
         assert (out["reassigned"], out["removed"]) == (reassigned.value, removed.value)
         return (out, status) if return_status else out
 
+    # ---- index noise in place: a second, counter-based draw scheme next to noise.py's host route ----
+    def _index_noise(self, entry, value, seed):
+        n = C.c_int64()
+        L.check(entry(self._h, float(value), int(seed), C.byref(n)))
+        if n.value:
+            self._refresh_graph()
+        return n.value
+
+    def drop_features(self, keep_fraction, seed=0):
+        """drop_features (src/noise.rs:229-251) in place, on the device: every camera keeps floor(len * keep_fraction) of its
+        observations, those with the smallest (draw, index); the survivors keep their order.  Masks, priors, loss and options
+        stay as across filter_observations.  Returns the number removed."""
+        return self._index_noise(L.lib().c2b_problem_drop_features, keep_fraction, seed)
+
+    def add_incorrect_correspondences(self, mismatch_chance, seed=0):
+        """add_incorrect_correspondences (src/noise.rs:180-226) in place, on the device: the pixels stay, point indices are
+        swapped inside a camera.  Returns the number of observations that swapped (one with itself included)."""
+        return self._index_noise(L.lib().c2b_problem_add_incorrect_correspondences, mismatch_chance, seed)
+
+    def split_landmarks(self, split_fraction, seed=0):
+        """split_landmarks (src/noise.rs:255-291) in place, on the device: floor(split_fraction * n_pts) points are
+        duplicated at the table's end and half of their observations move to the copy.  The point count changes: masks,
+        priors, a checkpoint and an origin are dropped as cull drops them.  Returns the number of points duplicated."""
+        return self._index_noise(L.lib().c2b_problem_split_landmarks, split_fraction, seed)
+
+    def join_landmarks(self, join_fraction, seed=0):
+        """join_landmarks (src/noise.rs:323-378) in place, on the device: floor(join_fraction * n_pts) observations take
+        one of the ten nearest other points of their point.  Returns the number of observations relabelled."""
+        return self._index_noise(L.lib().c2b_problem_join_landmarks, join_fraction, seed)
+
     def _status_pass(self, entry, args, n, names, return_status):
         """entry(handle, *args, status, counts) over n entities: the counts as a dict under `names`, and the status bytes"""
         counts = np.zeros(len(names), dtype=np.int64)

@@ -10,6 +10,8 @@
 //                         --drift-std X --drift-strength X --fixed-drift --drift-angle X
 //                         --sin-strength X --sin-frequency X --mismatch-chance X --drop-features X
 //                         --split-landmarks X --join-landmarks X] [--seed N] [--gpus N | --devices a,b,...]
+//                        [--index-noise host|device]   (extension: with `device` the four index passes run in place on the
+//                                                       resident problem, by counter-based draws: c2b_problem_drop_features, ...)
 //
 //   city2ba generate FILE OUT [--cameras N --intrinsics-start x,y,z --intrinsics-end x,y,z --points N --max-dist X
 //                              --ground X --height X --no-lcc --move-to-origin --path NAME --step-size X] [--seed N]
@@ -339,6 +341,7 @@ struct NoiseOptions {
     bool fixed_drift = false;
     int device = 0;                // the GPU of the unsharded routes
     std::vector<int> devices;      // --gpus N / --devices a,b,...: the sharded route when not empty
+    bool index_on_device = false;  // --index-noise device: the index passes in place on the resident problem (another draw scheme)
     bool reshapes() const { return drop < 1.0 || join > 0.0 || split > 0.0; }
 };
 
@@ -353,6 +356,13 @@ NoiseOptions noise_options(const Args &a) {
     if (o.sin_strength > 0.0) o.sin_frequency = a.f("sin-frequency", 1);
     o.translation_std = a.f("translation-std", 0); o.rotation_std = a.f("rotation-std", 0);
     o.point_std = a.f("point-std", 0); o.observation_std = a.f("observation-std", 0);
+    if (a.has("index-noise")) {
+        const std::string &v = a.opt.at("index-noise");
+        if (v != "host" && v != "device") die("Invalid value for '--index-noise <index-noise>': expected host or device");
+        o.index_on_device = v == "device";
+        if (o.index_on_device && (a.has("gpus") || a.has("devices")))
+            die("--index-noise device runs on one GPU: it cannot be combined with --gpus or --devices (the index passes are not sharded)");
+    }
     if (!a.has("devices") && !a.has("gpus")) {
         o.device = (int)a.i("device", 0);
         return o;
@@ -563,7 +573,7 @@ int run_noise(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {"fixed-drift"},
                          {"rotation-std", "translation-std", "point-std", "observation-std", "drift-std", "drift-strength",
                           "drift-angle", "mismatch-chance", "drop-features", "split-landmarks", "join-landmarks",
-                          "sin-strength", "sin-frequency", "seed", "device", "gpus", "devices"});
+                          "sin-strength", "sin-frequency", "seed", "device", "gpus", "devices", "index-noise"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
     const NoiseOptions o = noise_options(a);                             // every value is converted before the device is touched
     const std::string &in = a.positional[0], &out = a.positional[1];
@@ -584,6 +594,45 @@ int run_noise(int argc, char **argv) {
         print_correspondences(nc, np, no);
         print_final_error(l1, l2);
         timer.mark("errors + drift + noise (device)");
+        close_problem(timer, p, out);
+        return 0;
+    }
+
+    // --index-noise device: the same chain in the reference's order (src/bin/city2ba.rs:288-303, :341) with the four index
+    // passes in place on the resident problem -- the problem is read on the device and never comes down.
+    if (o.index_on_device) {
+        PhaseTimer timer;
+        c2b_problem *p = read_problem(timer, o.device, in);
+        ck(c2b_problem_total_reprojection_errors_l1_l2(p, &l1, &l2));
+        print_initial_error(l1, l2);
+        timer.mark("initial errors (device)");
+        if (o.drop < 1.0) {
+            ck(c2b_problem_drop_features(p, o.drop, o.seed + 2, nullptr));
+            ck(c2b_problem_cull(p, 1));
+            timer.mark("drop_features + cull (device)");
+        }
+        if (o.join > 0.0) {                                              // the split fraction: the reference's quirk at :296
+            ck(c2b_problem_join_landmarks(p, o.split, o.seed + 3, nullptr));
+            ck(c2b_problem_cull(p, 1));
+            timer.mark("join_landmarks + cull (device)");
+        }
+        if (o.split > 0.0) {
+            ck(c2b_problem_split_landmarks(p, o.split, o.seed + 4, nullptr));
+            ck(c2b_problem_cull(p, 1));
+            timer.mark("split_landmarks + cull (device)");
+        }
+        int64_t nc = 0, np = 0, no = 0;
+        ck(c2b_problem_sizes(p, &nc, &np, &no));
+        if (o.reshapes() && (nc == 0 || np == 0)) die("EmptyProblem: nothing remains after culling");
+        ck(perturb(p, nullptr, o, &l1, &l2));
+        timer.mark("drift + noise + errors (device)");
+        if (o.mismatch > 0.0) {                                          // :341, on the noised image positions
+            ck(c2b_problem_add_incorrect_correspondences(p, o.mismatch, o.seed + 5, nullptr));
+            ck(c2b_problem_total_reprojection_errors_l1_l2(p, &l1, &l2));
+            timer.mark("add_incorrect_correspondences + errors (device)");
+        }
+        print_correspondences(nc, np, no);
+        print_final_error(l1, l2);
         close_problem(timer, p, out);
         return 0;
     }
@@ -1256,6 +1305,9 @@ const char *subcommand_help(const std::string &sub) {
                "    --drift-strength <X> --drift-angle <X> --drift-std <X> [--fixed-drift]            drift [0]\n"
                "    --sin-strength <X> [0]  --sin-frequency <X> [1]                                  sine displacement\n"
                "    --mismatch-chance <X> [0]  --drop-features <X> [1]  --split-landmarks <X> [0]  --join-landmarks <X> [0]\n"
+               "    --index-noise <host|device> [host]   where those four passes run: on the host arrays (sequential draws), or in\n"
+               "                              place on the device-resident problem (counter-based draws: another result for a seed;\n"
+               "                              one GPU only)\n"
                "    --seed <N>                every random draw is seeded (default: std::random_device)\n"
                "    --gpus <N> | --devices <a,b,...>   shard the problem over N GPUs of this node (contiguous camera ranges,\n"
                "                              points replicated, statistics and errors through RCCL); the same file for every N up to rounding\n";

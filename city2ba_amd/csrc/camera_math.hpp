@@ -389,7 +389,8 @@ C2B_DEV double abs_pow_k(double x, double norm) {
 
 // ---- Philox4x32-10 + Box-Muller (build-defined draw scheme) -------------
 enum : uint32_t { kStreamDriftCam = 1, kStreamDriftPt = 2, kStreamNoiseCam = 3,
-                  kStreamNoisePt = 4, kStreamNoiseObs = 5 };
+                  kStreamNoisePt = 4, kStreamNoiseObs = 5,
+                  kStreamDrop = 6, kStreamMismatch = 7, kStreamSplit = 8, kStreamJoin = 9 };       // index_noise_kernels.hpp
 
 C2B_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                            uint32_t k1, uint32_t out[4]) {

@@ -46,6 +46,7 @@
 #include "cell_kernels.hpp"
 #include "merge_kernels.hpp"
 #include "rematch_kernels.hpp"
+#include "index_noise_kernels.hpp"
 #include "subset_kernels.hpp"
 #include "text_kernels.hpp"
 #include "comm_rccl.hpp"

@@ -588,8 +588,9 @@ struct PointCells {
     DevBuf<uint32_t> cell_of, cnt, start, sorted, tiles, total;
     DevBuf<unsigned long long> ext;
 };
-template <class Extra>
-static int build_point_cells(hipStream_t st, const char *who, const double4 *pos4, int64_t n_pts, double radius, PointCells &pc, Extra &&extra) {
+// radius_of(stats): the radius from the extent (stats[6..11] as a statistics record holds it; all 0 without a finite point)
+template <class Radius, class Extra>
+static int build_point_cells_by(hipStream_t st, const char *who, const double4 *pos4, int64_t n_pts, Radius &&radius_of, PointCells &pc, Extra &&extra) {
     // the extent of the points -> the cell grid
     const unsigned long long ext0[4] = {~0ull, ~0ull, 0ull, 0ull};
     unsigned long long ext_h[4] = {0, 0, 0, 0};
@@ -605,7 +606,7 @@ static int build_point_cells(hipStream_t st, const char *who, const double4 *pos
         stats[9] = merge_key_value(ext_h[2]); stats[11] = merge_key_value(ext_h[3]);
     }
     int64_t n_cells = 0;
-    int rc = cell_grid_from_stats(stats, radius, who, &pc.g, &n_cells);
+    int rc = cell_grid_from_stats(stats, radius_of((const double *)stats), who, &pc.g, &n_cells);
     if (rc) return rc;
     auto temporaries = [&](auto &&each) {
         each(pc.cell_of, (size_t)n_pts); each(pc.cnt, (size_t)(n_cells + 1)); each(pc.start, (size_t)(n_cells + 1));
@@ -621,6 +622,10 @@ static int build_point_cells(hipStream_t st, const char *who, const double4 *pos
     rc = build_cell_list(st, who, pos4, n_pts, pc.g, n_cells, pc.cell_of, pc.cnt, pc.start, pc.sorted, pc.tiles, pc.total);
     if (rc) (void)hipStreamSynchronize(st);
     return rc;
+}
+template <class Extra>
+static int build_point_cells(hipStream_t st, const char *who, const double4 *pos4, int64_t n_pts, double radius, PointCells &pc, Extra &&extra) {
+    return build_point_cells_by(st, who, pos4, n_pts, [radius](const double *) { return radius; }, pc, extra);
 }
 }  // extern "C++"
 

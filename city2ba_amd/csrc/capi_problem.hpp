@@ -107,6 +107,9 @@ struct c2b_problem {
 //   resect_consensus (6)       X            truth      - / X - / X      - / X  -             -           -
 //   merge_points (7)           -            -          - / X - / X      - / X  -             -           -
 //   rematch_observations (8)   -            -          - / X - / X      - / X  -             -           -
+//   drop_features (4)          -            -          X     X          X      -             -           -
+//   mismatch, join (12)        -            -          - / X - / X      - / X  -             -           -
+//   split_landmarks (13)       -            -          X     X          X      X             X           X
 //   subset, window: src        -            - (9)      -     -          -      -             -           -
 //   subset, window: dst (10)   X            X / truth  X     X          X      X             X / carried X
 //   get_origin                 -            -          -     -          -      -             -           -
@@ -122,7 +125,9 @@ struct c2b_problem {
 // as an upload replaces it, in the source's camera mode (bal9 gathered while it is the source's truth); the masks and priors are
 // the source's, gathered by the origin lists, with C2B_SUBSET_CARRY (a window: always, OR the roles) and dropped without; the
 // origin (above) is recorded by a window, and by a carrying subset of repeat-free lists.  (11) a state-mode child gets to_vec of
-// its cameras and is in bal mode afterwards; a child in bal mode is only read.
+// its cameras and is in bal mode afterwards; a child in bal mode is only read.  (12) add_incorrect_correspondences, join_landmarks
+// (DESIGN 4.18): after a call that changed a label, as the filter.  (13) the point count grows: cull's policy; a call that selects
+// no point drops nothing.
 // An X in the masks column is also where the handle's entity_epoch is raised and its origin dropped (entities_replaced).
 // the cameras moved: every cache of them (apply_step / rollback then make bal9 the truth)
 static void cameras_mutated(c2b_problem *p) { p->bal_valid = false; p->blk_valid = false; p->bal9_fresh = false; }
@@ -770,6 +775,7 @@ int c2b_problem_stats(c2b_problem *p, double *stats) {
 
 #include "capi_graph.hpp"        // cull, adopt, filter, the visibility entries, generate_world_points, the dense sweep
 #include "capi_subset.hpp"       // subset, window, get_origin, write_back: a sub-problem cut out on the device and put back
+#include "capi_index_noise.hpp"  // drop_features, add_incorrect_correspondences, split_landmarks, join_landmarks in place
 #include "capi_files.hpp"        // c2b_problem_write / c2b_problem_read: both file forms assembled / taken apart on the device
 
 // ---- the noise functions, alone and for a problem that is ONE SHARD of a larger one ----------

@@ -1,7 +1,8 @@
 // Host side of noise.rs' index-corruption functions (src/noise.rs:179-378): add_incorrect_correspondences,
 // drop_features, split_landmarks, join_landmarks.  They reshuffle the visibility graph's indices with sequential
 // random draws -- no arithmetic worth a device -- so they run on the CPU over the flat CSR arrays.  The reference
-// draws from thread_rng(); here one std::mt19937_64 per call, seeded by the caller.
+// draws from thread_rng(); here one std::mt19937_64 per call, seeded by the caller.  The device route exists as well --
+// index_noise_kernels.hpp / capi_index_noise.hpp: in place on the resident problem, by counter-based draws of its own.
 #pragma once
 
 #include <algorithm>

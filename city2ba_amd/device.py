@@ -364,6 +364,36 @@ def rematch_rows(camblk, pts4, rows, pt_idx, uv, fits, choice, status, counts, r
     return choice, status, counts
 
 
+def drop_keep_rows(row_ptr, n_obs, keep_fraction, seed, keep):
+    """drop_features' keep bits (c2b_drop_keep_rows): keep [n_obs] uint8 = 1 for the floor(len * keep_fraction)
+    observations of every camera row (row_ptr [n_cam + 1] uint64-valued int64) with the smallest (draw, index)"""
+    L.check(L.lib().c2b_drop_keep_rows(_p(row_ptr), row_ptr.shape[0] - 1, int(n_obs), float(keep_fraction), int(seed), _p(keep), _stream()))
+    return keep
+
+
+def mismatch_partner_rows(row_ptr, uv, mismatch_chance, seed, partner, n_zero_rows):
+    """add_incorrect_correspondences' partner pass (c2b_mismatch_partner_rows): partner [n_obs] int32 = the row-relative index
+    the observation swaps its point with, or -1; n_zero_rows [1] int64 = the rows with a swapping observation whose weights are
+    all zero.  uv [n_obs, 2] float64."""
+    L.check(L.lib().c2b_mismatch_partner_rows(_p(row_ptr), row_ptr.shape[0] - 1, _p(uv), uv.shape[0], float(mismatch_chance), int(seed),
+                                              _p(partner), _p(n_zero_rows), _stream()))
+    return partner, n_zero_rows
+
+
+def select_smallest_keys_rows(n, n_select, select, seed=0, stream=0, slot=0, keys=None):
+    """select [n] uint8 = 1 for the n_select smallest (key, index) (c2b_select_smallest_keys_rows): keys [n] int64 holding
+    uint64 bit patterns, or None for the draws a of (seed; stream, entity = index, slot).  Synchronises the stream."""
+    L.check(L.lib().c2b_select_smallest_keys_rows(_p(keys), int(n), int(seed), int(stream), int(slot), int(n_select), _p(select), _stream()))
+    return select
+
+
+def nearest_points_rows(pts4, query, nearest):
+    """nearest [n_query, 11] int32 = the nearest points of the points query [n_query] (int32-valued uint32) of pts4 [n_pts, 4]
+    by ascending (d2, index), the point itself included; -1 past the table's size (c2b_nearest_points_rows).  Synchronises."""
+    L.check(L.lib().c2b_nearest_points_rows(_p(pts4), pts4.shape[0], _p(query), query.shape[0], _p(nearest), _stream()))
+    return nearest
+
+
 def residual_jacobian_rows(camblk, pts4, rows, pt_idx, uv, r, Jc, Jp, norm=2.0, ws=None, out_sum=None, obs_base=0,
                            n_obs=None):
     """residual + Jacobian (+ sum |r|^norm when ws is given: into out_sum, or into ws for error_sum_finish) of the

@@ -43,7 +43,8 @@ def add_noise_with_errors(bal, translation_std, rotation_std, point_std, observa
     return bal, l1.value, l2.value
 
 
-# ---- index-corruption functions (src/noise.rs:179-378): host-side reshuffles of the visibility graph ------------
+# ---- index-corruption functions (src/noise.rs:179-378): host-side reshuffles of the visibility graph by default (download,
+# host pass, a new problem); with on_device=True the in-place device passes of DESIGN 4.18 ------------
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -58,25 +59,35 @@ def _rebuild(bal, cams, pts, row_ptr, pt_idx, uv):
     return BAProblem.from_visibility(cams, pts, row_ptr, pt_idx, uv, bal._device)
 
 
-def add_incorrect_correspondences(bal, mismatch_chance, seed=0):
-    """add_incorrect_correspondences (src/noise.rs:180-226); returns a new problem"""
+def add_incorrect_correspondences(bal, mismatch_chance, seed=0, on_device=False):
+    """add_incorrect_correspondences (src/noise.rs:180-226); returns a new problem.  on_device=True: in place on `bal` by the
+    counter-based draws of BAProblem.add_incorrect_correspondences (another draw scheme), returns `bal`"""
+    if on_device:
+        bal.add_incorrect_correspondences(mismatch_chance, seed=seed)
+        return bal
     cams, pts, row_ptr, pt_idx, uv = _graph(bal)
     L.check(L.lib().c2b_add_incorrect_correspondences(len(cams), _ptr(row_ptr), _ptr(pt_idx), _ptr(uv),
                                                       float(mismatch_chance), int(seed)))
     return _rebuild(bal, cams, pts, row_ptr, pt_idx, uv)
 
 
-def drop_features(bal, drop_percent, seed=0):
+def drop_features(bal, drop_percent, seed=0, on_device=False):
     """drop_features (src/noise.rs:229-251): `drop_percent` is the fraction of each camera's observations KEPT
-    (`l = len * drop_percent`, :238), as in the reference"""
+    (`l = len * drop_percent`, :238), as in the reference.  on_device=True: in place on `bal` (BAProblem.drop_features)"""
+    if on_device:
+        bal.drop_features(drop_percent, seed=seed)
+        return bal
     cams, pts, row_ptr, pt_idx, uv = _graph(bal)
     L.check(L.lib().c2b_drop_features(len(cams), _ptr(row_ptr), _ptr(pt_idx), _ptr(uv), float(drop_percent), int(seed)))
     n = int(row_ptr[-1])
     return _rebuild(bal, cams, pts, row_ptr, pt_idx[:n].copy(), uv[:n].copy())
 
 
-def split_landmarks(bal, split_percent, seed=0):
-    """split_landmarks (src/noise.rs:255-291)"""
+def split_landmarks(bal, split_percent, seed=0, on_device=False):
+    """split_landmarks (src/noise.rs:255-291).  on_device=True: in place on `bal` (BAProblem.split_landmarks)"""
+    if on_device:
+        bal.split_landmarks(split_percent, seed=seed)
+        return bal
     cams, pts, row_ptr, pt_idx, uv = _graph(bal)
     n_pts = len(pts)
     buf = np.zeros((n_pts + int(max(0.0, split_percent) * n_pts) + 1, 3))
@@ -87,8 +98,11 @@ def split_landmarks(bal, split_percent, seed=0):
     return _rebuild(bal, cams, buf[:n.value].copy(), row_ptr, pt_idx, uv)
 
 
-def join_landmarks(bal, join_percent, seed=0):
-    """join_landmarks (src/noise.rs:326-378)"""
+def join_landmarks(bal, join_percent, seed=0, on_device=False):
+    """join_landmarks (src/noise.rs:326-378).  on_device=True: in place on `bal` (BAProblem.join_landmarks)"""
+    if on_device:
+        bal.join_landmarks(join_percent, seed=seed)
+        return bal
     cams, pts, row_ptr, pt_idx, uv = _graph(bal)
     pts = np.ascontiguousarray(pts, dtype=np.float64)
     L.check(L.lib().c2b_join_landmarks(len(pts), _ptr(pts), len(pt_idx), _ptr(pt_idx), float(join_percent), int(seed)))

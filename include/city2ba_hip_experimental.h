@@ -712,6 +712,64 @@ int c2b_rematch_rows(const double *camblk, const double *pts4, int64_t n_pts, co
 int c2b_problem_rematch_observations(c2b_problem *p, double radius, double max_error, int min_fits, uint8_t *status_out,
                                      int64_t *n_reassigned, int64_t *n_removed);
 
+/* ---- index noise on the device: noise.rs' index-corruption functions -- drop_features (src/noise.rs:229-251),
+ * add_incorrect_correspondences (src/noise.rs:180-226), split_landmarks (src/noise.rs:255-291), join_landmarks
+ * (src/noise.rs:323-378) -- in place on the resident problem.  The host entries of city2ba_hip_host.h (c2b_drop_features, ...)
+ * draw from one sequential std::mt19937_64 and keep their seeded outputs; these are a SECOND draw scheme: every draw is a
+ * Philox4x32-10 block of its own, addressed as the arithmetic noise addresses its normals: counter = (entity lo, entity hi, slot,
+ * stream), key = the seed's halves, a = o1 << 32 | o0, b = o3 << 32 | o2, u(x) = (x >> 11) * 2^-53 in [0, 1).  Streams: 6 drop,
+ * 7 mismatch, 8 split, 9 join.  "Observation index" = the position in the whole camera-major list when the pass starts.  A seed
+ * fixes the result whatever the launch shape.  The rules (tests/_indexnoiseref.py restates them):
+ *   drop      a camera with len observations keeps l = floor(len * keep_fraction), saturating (below 0: none, above len: all):
+ *             those with the l smallest (a, index), a of stream 6, entity = observation index, slot 0.  The kept observations stay
+ *             in their order (the reference leaves them shuffled: the kept SET is distributed as the reference's).
+ *   mismatch  observation i of a row with len > 1 swaps iff u(a) <= mismatch_chance (stream 7, entity = observation index, slot 0).
+ *             Its partner: weights w_k = max_d - d_ik, d_ik = sqrt(dx * dx + dy * dy) unfused, max_d the largest of the row -- so
+ *             w_i = max_d, the reference's zeroed-before-shift quirk (:203-205): the likeliest partner is i itself --; j = the
+ *             first k whose cumulative weight exceeds u(b) * total, else len - 1 (the cumulative sums are a wave's scan: equal to
+ *             a sequential sum to rounding).  partner[i] = j, or -1.  A row with a swapping observation whose total is not
+ *             positive (all positions coincide) is counted.  Then per camera the swaps of pt_idx in ascending i.
+ *   select    the n smallest (key, index) of N entities, key = a of (stream, entity, slot) or a caller's 64-bit keys.
+ *   split     n = min(floor(split_fraction * n_pts), n_pts) points are selected: the n smallest (a, index), stream 8, entity =
+ *             point index, slot 0.  The copy of the r-th selected point in ascending index is row n_pts + r, with the same bits; an
+ *             observation of a selected point moves to the copy iff bit 0 of a (stream 8, entity = observation index, slot 1).
+ *   join      n = floor(join_fraction * n_pts), at most n_obs, observations are selected: the n smallest (a, index), stream 9,
+ *             entity = observation index, slot 0.  The point q of each becomes entry 1 + floor(u(b) * avail) of q's nearest
+ *             list, avail = min(10, n_pts - 1), b of the same draw.  Every lookup reads the table as it was.
+ *   nearest   the up to 11 nearest points of a point q by ascending (d2, index), d2 = (dx * dx + dy * dy) + dz * dz unfused, q
+ *             itself included (it is first unless an exact duplicate with a lower index is).
+ * Level 0, stateless, on `stream`, device arrays:
+ * c2b_drop_keep_rows: keep [n_obs] (one byte) for the rows row_ptr [n_cam + 1].  Asynchronous.
+ * c2b_mismatch_partner_rows: partner [n_obs] (int32: the row-relative j, or -1) and *n_zero_rows (device int64, zeroed first: the
+ *   rows counted).  Asynchronous.  n_obs > 2^31 - 65: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_select_smallest_keys_rows: select [n] (one byte).  keys [n] (device uint64) or NULL: the draws (seed; draw_stream, entity =
+ *   index, slot).  n_select <= 0 selects nothing, >= n everything.  A radix select whose digits are picked on the host: SYNCHRONISES.
+ * c2b_nearest_points_rows: nearest [n_query * 11] (int32, -1 past the table's size) for the point indices query [n_query] into
+ *   pts4 [n_pts] (32-byte rows).  It builds an x / z cell list of about four points per cell and frees it: SYNCHRONISES.  One wave
+ *   per query walks the rings of cells outward and stops once the last wanted d2 <= (r * cell * (1 - 2^-20))^2; a scene that is
+ *   tall and narrow (everything in one x / z cell) is searched by brute force.
+ * Level 1, synchronous, in place; a NaN fraction and a shard are refused with the problem unchanged; the counts may be NULL:
+ * c2b_problem_drop_features: the list compacted as c2b_problem_filter_observations compacts it; cameras, points, masks, priors, loss,
+ *   options and a checkpoint stay, what was derived from the list goes.  cull is the caller's call.
+ * c2b_problem_add_incorrect_correspondences: *n_swaps = the observations that swapped (one with itself included).  A counted row
+ *   fails the call with the host entry's message and leaves the list untouched.  uv, the row lengths and every per-entity state
+ *   stay; what was derived from the list goes, as after c2b_problem_rematch_observations.
+ * c2b_problem_split_landmarks: *n_split = n.  The point table grows, and what has one entry per point is treated as
+ *   c2b_problem_cull treats it when a count changes: the constant masks, the priors, a checkpoint with the LM scratch and an origin
+ *   are dropped.  n = 0 changes and drops nothing.
+ * c2b_problem_join_landmarks: *n_joined = n.  n > 0 with fewer than two points: C2B_ERR_INVALID_ARGUMENT, "No neighbors?!".  Only
+ *   pt_idx changes; what was derived from the list goes. */
+int c2b_drop_keep_rows(const uint64_t *row_ptr, int64_t n_cam, int64_t n_obs, double keep_fraction, uint64_t seed, uint8_t *keep, void *stream);
+int c2b_mismatch_partner_rows(const uint64_t *row_ptr, int64_t n_cam, const double *uv_obs, int64_t n_obs, double mismatch_chance, uint64_t seed,
+                              int32_t *partner, int64_t *n_zero_rows, void *stream);
+int c2b_select_smallest_keys_rows(const uint64_t *keys, int64_t n, uint64_t seed, int draw_stream, int slot, int64_t n_select, uint8_t *select,
+                                  void *stream);
+int c2b_nearest_points_rows(const double *pts4, int64_t n_pts, const uint32_t *query, int64_t n_query, int32_t *nearest, void *stream);
+int c2b_problem_drop_features(c2b_problem *p, double keep_fraction, uint64_t seed, int64_t *n_removed);
+int c2b_problem_add_incorrect_correspondences(c2b_problem *p, double mismatch_chance, uint64_t seed, int64_t *n_swaps);
+int c2b_problem_split_landmarks(c2b_problem *p, double split_fraction, uint64_t seed, int64_t *n_split);
+int c2b_problem_join_landmarks(c2b_problem *p, double join_fraction, uint64_t seed, int64_t *n_joined);
+
 /* ---- sub-problems on the device: BAProblem::subset (src/baproblem.rs:394-423) for a caller's selection, a window
  * of cameras with its rim held fixed, and the write-back of what a solve of the child moved.  Integer kernels and copies only:
  * the same inputs give the same bits.  Only the selection lists cross PCIe on the way in and the origin lists on the way out.
