@@ -1987,7 +1987,10 @@ __global__ void k_cameras_transform(double *__restrict__ cam15, const double *__
 // (src/generate.rs:455-476).  Per kept observation a f32 ray from the camera centre towards the point, tfar =
 // |dir| - 1e-6; occluded iff any triangle is hit with 0 < t <= tfar.  Triangles are staged 256 at a time in LDS and
 // read by broadcast (every lane tests the same triangle).  Embree's own intersector (BVH traversal order, its
-// watertight / SIMD arithmetic) is not reproducible; rays grazing an edge may be classified differently.
+// watertight / SIMD arithmetic) is not reproducible; rays grazing an edge may be classified differently.  Nor is this
+// test watertight at seams: on an edge two triangles share, one triangle's u >= 0 and its neighbour's w >= 0 test the
+// same quantity in another operation order, so a ray within rounding of a shared edge or vertex can miss both and keep a
+// point behind a closed wall (counted per ray family, never on a ray exact geometry decides: DESIGN 3.6).
 namespace c2b {
 
 constexpr int kOccTile = 256;     // triangles per LDS round (9 KB)
@@ -2049,14 +2052,19 @@ constexpr int kBvhEmptyChild = INT32_MIN;
 
 __device__ __forceinline__ bool bvh_box_hit(const float lo[3], const float hi[3], float ox, float oy, float oz, float ix,
                                             float iy, float iz, float tfar, float &tnear) {
-    // fminf / fmaxf drop a NaN operand ((lo - o) * inf with lo == o): that slab then does not constrain
+    // fminf / fmaxf drop a NaN operand ((lo - o) * inf with lo == o): that slab then does not constrain.
+    // The far end has slack: tn and a leaf's th are rounded differently, and a point ON the mesh has th ~ tfar, so a
+    // bare tn <= tfar prunes hits the all-triangles loop finds once the box margin (4 ulps of the largest COORDINATE)
+    // is below an ulp of tfar (a small mesh seen from afar).  Measured over the ray families of tests/_occref.py, on
+    // the pairs the float32 triangle test accepts: worst tn - tfar = +2.0 ulps of tfar (253 of 6349 accepted pairs of
+    // the `far` family pruned).  16 x that is 32 ulps; 1e-5 relative is 84..168 ulps of tfar.  (host_bvh.hpp: the same.)
     const float ax = (lo[0] - ox) * ix, bx = (hi[0] - ox) * ix;
     const float ay = (lo[1] - oy) * iy, by = (hi[1] - oy) * iy;
     const float az = (lo[2] - oz) * iz, bz = (hi[2] - oz) * iz;
     const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
     const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
     tnear = tn;
-    return tn <= tf * 1.00001f + 1e-30f && tf >= 0.0f && tn <= tfar;
+    return tn <= tf * 1.00001f + 1e-30f && tf >= 0.0f && tn <= tfar * 1.00001f;
 }
 
 __global__ __launch_bounds__(kBlock) void k_occlusion_bvh(const double *__restrict__ camblk, const double4 *__restrict__ pts4,

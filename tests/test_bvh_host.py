@@ -140,7 +140,7 @@ def box_hit(lo, hi, o, inv, tfar):
         a, b = (lo - o) * inv, (hi - o) * inv
         tn = np.nanmax(np.fmin(a, b)) if not np.all(np.isnan(np.fmin(a, b))) else -np.inf
         tf = np.nanmin(np.fmax(a, b)) if not np.all(np.isnan(np.fmax(a, b))) else np.inf
-    return tn <= tf * f32(1.00001) + f32(1e-30) and tf >= 0 and tn <= tfar
+    return tn <= tf * f32(1.00001) + f32(1e-30) and tf >= 0 and tn <= tfar * f32(1.00001)
 
 
 def test_python_traversal_equals_all_triangles(lib):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from _occref import occluded_numpy      # the float32 restatement of the kernels' triangle test
 
 pytestmark = pytest.mark.gpu
 
@@ -28,38 +29,6 @@ def c2b():
 def cli():
     import __graft_entry__ as entry
     return entry.build_cli()
-
-
-def occluded_numpy(centers, pts, tri):
-    """float32 rays as embree_rs::Ray::new(center as f32, dir.normalize() as f32), tfar = |dir| as f32 - 1e-6
-    (src/generate.rs:456-464); occluded iff some triangle is hit with 0 < t <= tfar.  Same operation order as the
-    kernel, numpy float32 arithmetic (no fused multiply-add)."""
-    e = pts - centers
-    mag = np.sqrt((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2])
-    inv = 1.0 / mag
-    o = centers.astype(f32)
-    d = (e * inv[:, None]).astype(f32)
-    tfar = mag.astype(f32) - f32(1e-6)
-    occ = np.zeros(len(pts), dtype=bool)
-    with np.errstate(all="ignore"):
-        for q in tri.astype(f32):
-            e1, e2 = q[3:6] - q[0:3], q[6:9] - q[0:3]
-            px = d[:, 1] * e2[2] - d[:, 2] * e2[1]
-            py = d[:, 2] * e2[0] - d[:, 0] * e2[2]
-            pz = d[:, 0] * e2[1] - d[:, 1] * e2[0]
-            det = (e1[0] * px + e1[1] * py) + e1[2] * pz
-            nz = det != 0
-            idet = f32(1.0) / det
-            tx, ty, tz = o[:, 0] - q[0], o[:, 1] - q[1], o[:, 2] - q[2]
-            u = ((tx * px + ty * py) + tz * pz) * idet
-            qx = ty * e1[2] - tz * e1[1]
-            qy = tz * e1[0] - tx * e1[2]
-            qz = tx * e1[1] - ty * e1[0]
-            w = ((d[:, 0] * qx + d[:, 1] * qy) + d[:, 2] * qz) * idet
-            th = ((e2[0] * qx + e2[1] * qy) + e2[2] * qz) * idet
-            hit = nz & ~(u < 0) & ~(u > 1) & ~(w < 0) & ~(u + w > 1) & (th > 0) & (th <= tfar)
-            occ |= hit
-    return occ
 
 
 def scene(seed, n_cam=40, n_pts=700, n_tri=90):
