@@ -162,6 +162,7 @@ SIGNATURES = {
     "c2b_residual_keep_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _d, _int, _vp, _vp]),
     "c2b_triangulate_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "c2b_refine_points_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_refine_cameras_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_triangulate_consensus_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _d, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_resect_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _d, _vp, _vp, _vp, _vp]),
     "c2b_resect_consensus_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _int, _d, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -202,6 +203,7 @@ SIGNATURES = {
     "c2b_problem_filter_observations": (_int, [_vp, _d, _int, C.POINTER(_i64)]),
     "c2b_problem_triangulate_points": (_int, [_vp, _d, _vp, _vp]),
     "c2b_problem_refine_points": (_int, [_vp, _vp, _vp, _vp]),
+    "c2b_problem_refine_cameras": (_int, [_vp, _vp, _vp, _vp]),
     "c2b_problem_set_inner_iterations": (_int, [_vp, _int]),
     "c2b_problem_get_inner_iterations": (_int, [_vp, C.POINTER(_int)]),
     "c2b_problem_triangulate_consensus": (_int, [_vp, _d, _d, _int, _int, _int, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),

@@ -748,6 +748,22 @@ class BAProblem:
         return self._status_pass(L.lib().c2b_problem_resect_cameras, (int(min_points), float(min_gap)), self.num_cameras(),
                                  L.RES_STATUS, return_status)
 
+    def refine_cameras(self, rounds=10, lam=1e-4, function_tol=0.0, gradient_tol=0.0, parameter_tol=0.0, return_status=False):
+        """Per-camera Levenberg-Marquardt on the device (c2b_problem_refine_cameras): every camera's nine
+        parameters are re-minimised against the points as they are, with its own damping (from `lam`) and its own
+        acceptance, for up to `rounds` rounds -- motion-only bundle adjustment in one launch, the dual of refine_points and
+        the follow-up to resect_cameras.  A camera's cost is sum rho(|r|^2) over its observations under the handle's loss
+        plus its centre and intrinsics priors'; parameters constant under set_constant keep their bits; it stops when a
+        tolerance is met (0 disables a test).  A camera is written only when its cost fell; cameras with all nine
+        parameters constant, cameras with neither an observation nor a prior and cameras whose start cost is not finite
+        keep their bits.  Masks, priors, loss, preconditioner and a checkpoint stay; the problem is in bal mode afterwards,
+        as after apply_step.  Returns dict(converged, max_rounds, unobserved, failed, constant, moved): the number of
+        cameras of each status and of cameras written; with return_status also the uint8 status per camera (the dict's
+        order: 0 .. 4)."""
+        opt = L.RefineOptions(int(rounds), 0, float(lam), float(function_tol), float(gradient_tol), float(parameter_tol))
+        return self._status_pass(L.lib().c2b_problem_refine_cameras, (C.cast(C.pointer(opt), C.c_void_p),), self.num_cameras(),
+                                 L.REFINE_COUNTS, return_status)
+
     def resect_cameras_robust(self, max_error, min_inliers=6, min_gap=1e-4, max_hypotheses=64, drop_outliers=False,
                               return_status=False, return_inliers=False):
         """Consensus resection on the device (c2b_problem_resect_consensus): resect_cameras for a list that

@@ -40,10 +40,11 @@
 //   city2ba rematch IN OUT --radius R --max-error X [--min-fits N]
 //                        (extension: wrong point indices put right, the repair of --mismatch-chance and --join-landmarks that
 //                         keeps the observation, c2b_problem_rematch_observations; whoever fits no point is removed)
-//   city2ba refine IN OUT [--rounds N] [--lambda L] [--loss KIND --loss-scale A] [--function-tol T] [--gradient-tol T]
+//   city2ba refine IN OUT [--cameras | --alternate N] [--rounds N] [--lambda L] [--loss KIND --loss-scale A] [--function-tol T] [--gradient-tol T]
 //                         [--parameter-tol T]
 //                        (extension: every point re-minimised by itself with the cameras held, per-point Levenberg-Marquardt,
-//                         c2b_problem_refine_points)
+//                         c2b_problem_refine_points; --cameras: every camera with the points held, c2b_problem_refine_cameras;
+//                         --alternate N: N sweeps of both)
 //
 // `generate` casts its rays by brute force over the triangles instead of through Embree.  Every random draw is
 // seeded (--seed; default: std::random_device) where the reference uses thread_rng().
@@ -1240,10 +1241,22 @@ int run_rematch(int argc, char **argv) {
 
 // `refine`: every point of a .bal / .bbal re-minimised by itself against the cameras as they are, by
 // c2b_problem_refine_points (an extension: per-point Levenberg-Marquardt on the device; cameras and observations are written as
-// they were read).  Every argument is parsed before the device is touched.
+// they were read); with --cameras every camera against the points as they are, by c2b_problem_refine_cameras (the points are
+// written as they were read); with --alternate N, N sweeps of both, cameras first.  Every argument is parsed before the device
+// is touched.
+void print_refined(const char *what, const int64_t counts[6]) {
+    std::printf("refined %lld %s: %lld converged, %lld at the round limit; kept: %lld unobserved, %lld with a cost that is not finite, %lld constant\n",
+                (long long)counts[5], what, (long long)counts[C2B_REFINE_CONVERGED], (long long)counts[C2B_REFINE_MAX_ROUNDS],
+                (long long)counts[C2B_REFINE_UNOBSERVED], (long long)counts[C2B_REFINE_FAILED], (long long)counts[C2B_REFINE_CONSTANT]);
+}
+
 int run_refine(int argc, char **argv) {
-    const Args a = parse(argc, argv, 2, {}, {"rounds", "lambda", "loss", "loss-scale", "function-tol", "gradient-tol", "parameter-tol", "device"});
+    const Args a = parse(argc, argv, 2, {"cameras"},
+                         {"rounds", "lambda", "loss", "loss-scale", "function-tol", "gradient-tol", "parameter-tol", "alternate", "device"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
+    if (a.has("cameras") && a.has("alternate")) die("The argument '--cameras' cannot be used with '--alternate <N>'");
+    const int64_t sweeps = a.i("alternate", 0);
+    if (sweeps > 1000000) die("Invalid value for '--alternate <N>': expected an integer in 0 ... 1000000");
     const int64_t rounds = a.i("rounds", 10);
     if (rounds > 1000000) die("Invalid value for '--rounds <N>': expected an integer in 0 ... 1000000");
     c2b_refine_options opt = {(int32_t)rounds, 0, a.f("lambda", 1e-4), a.f("function-tol", 0.0), a.f("gradient-tol", 0.0), a.f("parameter-tol", 0.0)};
@@ -1260,11 +1273,25 @@ int run_refine(int argc, char **argv) {
     c2b_problem *p = open_problem(timer, device, a.positional[0], nc, np, no);
     ck(c2b_problem_set_loss(p, loss, loss_scale));
     int64_t counts[6] = {0, 0, 0, 0, 0, 0};
-    ck(c2b_problem_refine_points(p, &opt, nullptr, counts));
-    timer.mark("refine_points (device)");
-    std::printf("refined %lld points: %lld converged, %lld at the round limit; kept: %lld unobserved, %lld with a cost that is not finite, %lld constant\n",
-                (long long)counts[5], (long long)counts[C2B_REFINE_CONVERGED], (long long)counts[C2B_REFINE_MAX_ROUNDS],
-                (long long)counts[C2B_REFINE_UNOBSERVED], (long long)counts[C2B_REFINE_FAILED], (long long)counts[C2B_REFINE_CONSTANT]);
+    if (a.has("alternate")) {                                // the last sweep's counts are the ones reported
+        int64_t cam_counts[6] = {0, 0, 0, 0, 0, 0};
+        for (int64_t s = 0; s < sweeps; ++s) {
+            ck(c2b_problem_refine_cameras(p, &opt, nullptr, cam_counts));
+            ck(c2b_problem_refine_points(p, &opt, nullptr, counts));
+        }
+        timer.mark("refine_cameras / refine_points (device)");
+        std::printf("%lld sweeps; the last one:\n", (long long)sweeps);
+        print_refined("cameras", cam_counts);
+        print_refined("points", counts);
+    } else if (a.has("cameras")) {
+        ck(c2b_problem_refine_cameras(p, &opt, nullptr, counts));
+        timer.mark("refine_cameras (device)");
+        print_refined("cameras", counts);
+    } else {
+        ck(c2b_problem_refine_points(p, &opt, nullptr, counts));
+        timer.mark("refine_points (device)");
+        print_refined("points", counts);
+    }
     close_problem(timer, p, a.positional[1]);
     return 0;
 }
@@ -1282,7 +1309,7 @@ void usage() {
                 "    resect            Set the camera poses of a .bal or .bbal from its points and observations.\n"
                 "    merge             Merge the duplicate landmarks of a .bal or .bbal (the repair of noise --split-landmarks).\n"
                 "    rematch           Put the wrong point indices of a .bal or .bbal right (the repair of noise --mismatch-chance).\n"
-                "    refine            Refine every point of a .bal or .bbal by itself, the cameras held (per-point Levenberg-Marquardt).\n",
+                "    refine            Refine every point (or, --cameras, every camera) of a .bal or .bbal by itself, the rest held.\n",
                 c2b_version());
 }
 
@@ -1386,7 +1413,10 @@ const char *subcommand_help(const std::string &sub) {
                "    --lambda <L> [1e-4]       every point's initial damping\n"
                "    --loss <squared|huber|cauchy|soft-l1> [squared]   --loss-scale <A> [1]\n"
                "    --function-tol <T> [0]  --gradient-tol <T> [0]  --parameter-tol <T> [0]   per-point stopping tests (0: off)\n"
-               "                              A point is written only when its cost fell.\n";
+               "                              A point is written only when its cost fell.\n"
+               "    --cameras                 refine every camera by itself instead, the points held (per-camera Levenberg-Marquardt: its own\n"
+               "                              damping and acceptance; --rounds, --lambda and the stopping tests are then per camera)\n"
+               "    --alternate <N>           N sweeps of both: every camera, then every point, with the options above for each\n";
     return nullptr;
 }
 

@@ -39,6 +39,7 @@
 #include "prior_kernels.hpp"
 #include "triangulate_kernels.hpp"
 #include "refine_kernels.hpp"
+#include "refine_cameras_kernels.hpp"
 #include "triangulate_robust_kernels.hpp"
 #include "resect_kernels.hpp"
 #include "resect_robust_kernels.hpp"

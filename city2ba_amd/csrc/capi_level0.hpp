@@ -1729,6 +1729,39 @@ int c2b_resect_rows(double *bal9, const double *pts4, const uint64_t *row_ptr, i
     C2B_API_END("resect_rows")
 }
 
+// ---- per-camera Levenberg-Marquardt (refine_cameras_kernels.hpp) -------------------------------------------
+int c2b_refine_cameras_rows(double *bal9, const double *pts4, int64_t n_cam, const uint64_t *row_ptr, const uint32_t *pt_idx,
+                            const double *uv_obs, int loss_kind, double loss_a2, const double *prior_center, const double *prior_center_w,
+                            const double *prior_intr, const double *prior_intr_w, const c2b_refine_options *opt, const uint16_t *cam_mask,
+                            uint8_t *status, int64_t *counts, void *stream) {
+    C2B_API_BEGIN
+    if (n_cam < 0 || n_cam > (int64_t)0x7fffffff - kRcCams) return fail(C2B_ERR_INVALID_ARGUMENT, "refine_cameras_rows: n_cam out of range");
+    if (const int rc = check_refine_options("refine_cameras_rows", opt)) return rc;
+    if (loss_kind < kLossSquared || loss_kind > kLossSoftL1 || (loss_kind != kLossSquared && (!(loss_a2 > 0.0) || !std::isfinite(loss_a2))))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "refine_cameras_rows: loss kind must be 0..3 and its squared scale finite and > 0");
+    if (!prior_center != !prior_center_w || !prior_intr != !prior_intr_w)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "refine_cameras_rows: prior targets and weights go in pairs (both or neither)");
+    if (!counts || (n_cam && (!bal9 || !row_ptr))) return fail(C2B_ERR_INVALID_ARGUMENT, "refine_cameras_rows: NULL argument");
+    if (!aligned8(bal9) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(row_ptr) || !aligned8(counts) || !aligned8(prior_center) ||
+        !aligned8(prior_center_w) || !aligned8(prior_intr) || !aligned8(prior_intr_w) || (reinterpret_cast<uintptr_t>(pt_idx) & 3) ||
+        (reinterpret_cast<uintptr_t>(cam_mask) & 1))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "refine_cameras_rows: misaligned pointer");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * kRefCounts, st));
+    if (!n_cam) return C2B_OK;
+    auto tol = [](double t) { return t > 0.0 ? t : std::numeric_limits<double>::quiet_NaN(); };        // (RefOptions: 0 = disabled = NaN)
+    const RefOptions o{opt->max_rounds, opt->lambda0, tol(opt->function_tol), tol(opt->gradient_tol), tol(opt->parameter_tol)};
+    with_loss(loss_kind, loss_a2, [&](auto... loss) {
+        hipLaunchKernelGGL((k_refine_cameras<decltype(loss)...>), dim3(blocks_for(n_cam, kRcCams)), dim3(kRcBlock), 0, st, bal9,
+                           reinterpret_cast<const double4 *>(pts4), (int)n_cam, row_ptr, pt_idx, reinterpret_cast<const double2 *>(uv_obs),
+                           prior_center, prior_center_w, prior_intr, prior_intr_w, o, cam_mask, status,
+                           reinterpret_cast<unsigned long long *>(counts), loss...);
+    });
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("refine_cameras_rows")
+}
+
 // ---- consensus resection (resect_robust_kernels.hpp) -------------------------------------------------------
 int c2b_resect_consensus_rows(double *bal9, const double *pts4, const uint64_t *row_ptr, int64_t n_cam, const uint32_t *pt_idx,
                               const double *uv_obs, int64_t n_obs, double max_error, int min_inliers, double min_gap, int max_hypotheses,

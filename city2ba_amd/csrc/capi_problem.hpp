@@ -104,6 +104,7 @@ struct c2b_problem {
 //   refine_points              -            -          -     -          -      -             -           -
 //   triangulate_consensus (6)  -            -          - / X - / X      - / X  -             -           -
 //   resect_cameras             X            truth      -     -          -      -             -           -
+//   refine_cameras             X            truth      -     -          -      -             -           -
 //   resect_consensus (6)       X            truth      - / X - / X      - / X  -             -           -
 //   merge_points (7)           -            -          - / X - / X      - / X  -             -           -
 //   rematch_observations (8)   -            -          - / X - / X      - / X  -             -           -

@@ -810,6 +810,39 @@ int c2b_problem_resect_cameras(c2b_problem *p, int min_points, double min_gap, u
     C2B_API_END("problem_resect_cameras")
 }
 
+// ---- per-camera Levenberg-Marquardt -------------------------------------------------------------------
+// The resident cameras re-minimised one by one against the resident points: c2b_refine_cameras_rows over the row structure, in
+// place on bal9, which is made the truth first and stays the truth exactly as in c2b_problem_resect_cameras, under the handle's
+// loss, camera mask, centre priors and intrinsics priors.  The list, the row structure, the transpose, the solve buffers, the
+// masks, the loss, the preconditioner, the priors and a checkpoint all stay.  Without a single observation a camera has its
+// priors alone: an all-zero row pointer stands in.
+int c2b_problem_refine_cameras(c2b_problem *p, const c2b_refine_options *opt, uint8_t *status, int64_t *counts) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_refine_cameras");
+    if (const int bad = check_refine_options("problem_refine_cameras", opt)) return bad;
+    if (p->shard_n_cam_global >= 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_refine_cameras: a shard is not refined alone");
+    const int64_t nc = p->n_cam;
+    StatusReport rep(kRefCounts);
+    if (!nc) return rep.all_have(kRefUnobserved, 0, status, counts);
+    DevBuf<uint64_t> empty_ptr;
+    int rc = ensure_rows(p);
+    if (rc) return rc;
+    hipStream_t st = p->stream;
+    hipError_t e = rep.alloc(nc);
+    if (e == hipSuccess && !p->n_obs) {
+        e = empty_ptr.alloc((size_t)nc + 1);
+        if (e == hipSuccess) e = hipMemsetAsync(empty_ptr, 0, sizeof(uint64_t) * ((size_t)nc + 1), st);
+    }
+    if (e != hipSuccess) return fail(hip_code(e), "problem_refine_cameras: allocation: %s", hipGetErrorString(e));
+    if ((rc = bal9_edit_begin(p))) return rc;                // state mode: the pass works on to_vec(cam15)
+    rc = c2b_refine_cameras_rows(p->bal9, p->pts4, nc, p->n_obs ? p->rows_ptr.ptr : empty_ptr.ptr, p->pt_idx, p->uv, p->loss_kind,
+                                 p->loss_scale * p->loss_scale, p->pcw ? p->pc0.ptr : nullptr, p->pcw ? p->pcw.ptr : nullptr,
+                                 p->piw ? p->pi0.ptr : nullptr, p->piw ? p->piw.ptr : nullptr, opt, p->cmask, rep.d_status, rep.d_counts, st);
+    rc = bal9_edit_end(p, rc);
+    return rep.read_back("problem_refine_cameras", st, rc, hipSuccess, nc, status, counts);
+    C2B_API_END("problem_refine_cameras")
+}
+
 // ---- Levenberg-Marquardt on the device -----------------------------------------------------------------
 int c2b_problem_checkpoint(c2b_problem *p) {
     C2B_API_BEGIN

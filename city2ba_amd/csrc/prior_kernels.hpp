@@ -32,8 +32,10 @@
 
 namespace c2b {
 
-// r_C and the 3x6 block of one camera from its record; cw == NULL or a zero weight leaves that row 0 (its target unread)
-C2B_DEV void prior_center_rows(const CamRef cam, const double *__restrict__ c0, const double w[3], double r[3], double A[18]) {
+// r_C and the 3x6 block of one camera from its record (anything indexable by record double: the table in place, or an
+// LDS-typed pointer); cw == NULL or a zero weight leaves that row 0 (its target unread)
+template <typename P>
+C2B_DEV void prior_center_rows(const P cam, const double *__restrict__ c0, const double w[3], double r[3], double A[18]) {
     const double t0 = cam[kT], t1 = cam[kT + 1], t2 = cam[kT + 2];
 #pragma unroll
     for (int k = 0; k < 3; ++k) r[k] = w[k] != 0.0 ? w[k] * (cam[kCenter + k] - c0[k]) : 0.0;

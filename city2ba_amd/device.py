@@ -307,6 +307,23 @@ def refine_points_rows(camblk, pts4, prows, uv, status, counts, rounds=10, lam=1
     return status, counts
 
 
+def refine_cameras_rows(bal9, pts4, rows, pt_idx, uv, status, counts, rounds=10, lam=1e-4, function_tol=0.0, gradient_tol=0.0,
+                        parameter_tol=0.0, loss=None, loss_scale=1.0, prior_center=None, prior_center_w=None, prior_intr=None,
+                        prior_intr_w=None, cam_mask=None):
+    """per-camera Levenberg-Marquardt (c2b_refine_cameras_rows): bal9 [n_cam,9] in place, every camera re-minimised
+    by itself over its row of observations (Rows) with the points held; status [n_cam] uint8 (_lib.REFINE_STATUS order) or
+    None, counts [6] int64 (_lib.REFINE_COUNTS: the five statuses, then the cameras written); loss by name with its scale;
+    the centre and intrinsics priors [n_cam,3] (targets and weights, in pairs) and cam_mask [n_cam] uint16 (an OR of
+    C2B_CONST_* bits) or None"""
+    import ctypes as C
+    opt = L.RefineOptions(int(rounds), 0, float(lam), float(function_tol), float(gradient_tol), float(parameter_tol))
+    L.check(L.lib().c2b_refine_cameras_rows(_p(bal9), _p(pts4), rows.n_cam, _p(rows.row_ptr), _p(pt_idx), _p(uv), L.loss_kind(loss),
+                                            float(loss_scale) * float(loss_scale), _p(prior_center), _p(prior_center_w), _p(prior_intr),
+                                            _p(prior_intr_w), C.cast(C.pointer(opt), C.c_void_p), _p(cam_mask), _p(status), _p(counts),
+                                            _stream()))
+    return status, counts
+
+
 def triangulate_consensus_rows(camblk, pts4, prows, uv, status, counts, min_angle, max_error, min_inliers=3, max_hypotheses=64,
                                pt_mask=None, hyp=None, n_inl=None, inlier=None):
     """consensus triangulation (c2b_triangulate_consensus_rows): triangulate_rows over the rays of a point that agree with

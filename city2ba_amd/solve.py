@@ -3,7 +3,8 @@ cameras' Schur complement, on the device) and apply_step, with Nielsen's update 
 robust loss (BAProblem.set_loss), by iteratively reweighted least squares, with chosen camera parameters and points
 held constant (BAProblem.set_constant) and with priors on camera centres, intrinsics and points (BAProblem.set_priors);
 and the usual pipeline around it (solve_filtered): a robust solve, the observations whose residual is still large
-dropped on the device (BAProblem.filter_observations), a last solve without a loss."""
+dropped on the device (BAProblem.filter_observations), a last solve without a loss; and resection-intersection
+alternation (alternate): BAProblem.refine_cameras and refine_points in turn."""
 
 LAMBDA_MIN, LAMBDA_MAX = 1e-20, 1e32                # the damping c2b_problem_solve_step accepts (C2B_STEP_LAMBDA_MIN / _MAX)
 # bits of a camera's constant mask (BAProblem.set_constant; C2B_CONST_*): parameter k of to_vec order is bit k
@@ -137,6 +138,44 @@ def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_t
     summary = dict(iterations=s.iterations, termination=s.termination, reason=L.LM_TERMINATIONS[s.termination],
                    initial_cost=s.initial_cost, final_cost=s.final_cost, lam_next=s.lambda_next)
     return history, summary
+
+
+def alternate(ba, sweeps=10, camera_rounds=5, point_rounds=5, function_tol=0.0, lam=1e-4, loss=None, loss_scale=1.0, constant=None, priors=None):
+    """Resection-intersection alternation on ba in place: per sweep ba.refine_cameras(rounds=camera_rounds, lam=lam), then
+    ba.refine_points(rounds=point_rounds, lam=lam), then the cost -- full bundle adjustment as block-coordinate descent, two
+    launches per sweep, without a Schur complement or a PCG.  Every camera and every point has its own damping
+    and acceptance and never ends a call with a higher cost of its own, so the total cost does not rise.  The cost is the one
+    the LM loops compare: the observations' (ba.robust_cost() under a loss, else the sum of squared residuals), then, with
+    priors in force, + ba.prior_cost().  It stops early after a sweep whose relative decrease, (before - after) / before, is
+    <= function_tol (0 disables the test: every sweep is run, as `city2ba refine --alternate N` runs them).  loss, constant and priors as levenberg_marquardt takes them: set on ba when given
+    (they stay), left as they are when None.
+    The gauge is the caller's business: nothing here fixes the seven degrees of freedom of the whole problem, and alternation
+    drifts along them only slowly, but a comparison against ground truth needs them held -- hold cameras with set_constant
+    (constant=) or tie them down with set_priors (priors=).
+    Returns dict(costs, cameras, points, sweeps): costs = the cost before the first sweep and after every sweep run
+    (sweeps + 1 entries), cameras and points = the status dicts of the last sweep's two calls (None when sweeps is 0)."""
+    if priors is not None:
+        ba.set_priors(**priors)
+    if constant is not None:
+        ba.set_constant(*constant)
+    if loss is not None:
+        ba.set_loss(loss, loss_scale)
+    robust = ba.loss[0] is not None
+    with_priors = any(ba.priors["active"])
+
+    def cost():
+        observed = ba.robust_cost() if robust else ba.total_reprojection_error(2.0) ** 2
+        return observed + ba.prior_cost() if with_priors else observed
+
+    costs = [cost()]
+    cams = pts = None
+    for _ in range(int(sweeps)):
+        cams = ba.refine_cameras(rounds=camera_rounds, lam=lam)
+        pts = ba.refine_points(rounds=point_rounds, lam=lam)
+        costs.append(cost())
+        if function_tol > 0.0 and costs[-2] - costs[-1] <= function_tol * costs[-2]:
+            break
+    return dict(costs=costs, cameras=cams, points=pts, sweeps=len(costs) - 1)
 
 
 def solve_filtered(ba, max_error, rounds=1, in_front=False, **lm):

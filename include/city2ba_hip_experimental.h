@@ -435,6 +435,46 @@ int c2b_problem_refine_points(c2b_problem *p, const c2b_refine_options *opt, uin
 int c2b_problem_set_inner_iterations(c2b_problem *p, int rounds);
 int c2b_problem_get_inner_iterations(c2b_problem *p, int *rounds);
 
+/* ---- per-camera Levenberg-Marquardt: every camera re-minimised by itself, the points held (motion-only bundle adjustment) ----
+ * The dual of c2b_refine_points_rows, with its options, statuses and counts, and its rule set with 9 for 3.  The parameters are
+ * q = bal9[c][0..8] (to_vec order: w0 w1 w2 t0 t1 t2 f k1 k2).  For every walk the camera's record is formed from q as
+ * c2b_camblk_from_bal forms it; a step is q + delta on the free entries, what c2b_problem_apply_step does to bal9.  A walk at q:
+ *   F = sum_o rho(|r_o|^2) + |w_C o (C - C0)|^2 + |w_I o ((f, k1, k2) - I0)|^2     observations, centre prior, intrinsics prior;
+ *   U = sum_o w Jc^T Jc + A^T A (9x9), g = sum_o w Jc^T r + A^T r_prior, w = rho'(|r_o|^2) at q: r and Jc scaled by sqrt(w)
+ *   before the products; A is the prior Jacobian of c2b_prior_cameras_rows.  A prior component of weight 0 never reads its target.
+ *   Then the rows and columns of U and the entries of g of the constant parameters (cam_mask bit k = parameter k) are zeroed;
+ *   F is not masked.  Sixteen lanes own a camera: lane l sums observations b + l, b + l + 16, ... of the camera's row, then a
+ *   fixed xor tree.  At walk 0, U and g are the bits c2b_problem_normal_equations gives for a handle that holds the same bal9.
+ * Round k, per camera, with mu = lambda0 and nu = 2 at the start:
+ *   the gradient test: max |g_i| <= gradient_tol -> converged;
+ *   (U + mu diag(d)) delta = -g by the 9x9 Cholesky of the step's preconditioner, d_i = min(max(U_ii, 1e-6), 1e32); a pivot
+ *     <= 0 or a non-finite delta is a rejection; a constant entry's delta compares == 0;
+ *   the parameter test: |delta| <= parameter_tol (|q| + parameter_tol) -> converged, the step not applied;
+ *   a walk at q + delta gives F', U', g'; model = -(2 g.delta + delta^T U delta); gain = (F - F') / model if model > 0, else -1;
+ *   accepted iff gain > 0, F' < F and F' is finite: q, F, U, g become the trial's, mu *= max(1/3, 1 - (2 gain - 1)^3),
+ *     nu = 2, and the function test: F - F' <= function_tol F -> converged;
+ *   rejected: mu *= nu, nu *= 2.  mu is held in [C2B_STEP_LAMBDA_MIN, C2B_STEP_LAMBDA_MAX].
+ * Status, one byte per camera: C2B_REFINE_CONSTANT all nine mask bits set (nothing of the camera is read);
+ * C2B_REFINE_UNOBSERVED an empty row and no prior weight; C2B_REFINE_FAILED the start cost is not finite; C2B_REFINE_CONVERGED;
+ * C2B_REFINE_MAX_ROUNDS.  bal9[c] is written only if the camera's cost fell strictly, and its constant entries are not
+ * rewritten.  counts [6]: the five statuses, then `moved`.  No float atomics, no scratch memory: a camera's result depends on
+ * its own row, its points and the options alone.  Bad options: C2B_ERR_INVALID_ARGUMENT, as c2b_refine_points_rows.
+ * c2b_refine_cameras_rows: Level 0, stateless, asynchronous on `stream`.  bal9 [n_cam][9] in place; pts4, row_ptr [n_cam + 1],
+ *   pt_idx, uv_obs as c2b_resect_rows takes them (pts4, pt_idx and uv_obs are read only for a non-empty row); loss_a2 is the
+ *   loss's squared scale (ignored for kind 0); the prior arrays (device, [n_cam][3], in pairs) in c2b_prior_cameras_rows'
+ *   layout; the priors, cam_mask and status may be NULL; counts [6] (device int64) is zeroed and then summed by integer atomics.
+ * c2b_problem_refine_cameras: Level 1, synchronous, in c2b_problem_resect_cameras' shape: the row structure (built when absent),
+ *   bal9 made the truth (to_vec of the cameras first in state mode), the pass under the handle's loss, camera mask, centre and
+ *   intrinsics priors, the cameras rebuilt from bal9: the problem is in bal mode afterwards.  The list, the row structure, the
+ *   transpose, the solve buffers, the masks, the loss, the preconditioner, the priors and a checkpoint all stay.  A shard is
+ *   refused.  status (host, [n_cam]) and counts (host, [6]) may be NULL.  With no observation at all every unmasked camera
+ *   without a prior weight is C2B_REFINE_UNOBSERVED, and one with a prior is pulled towards its target. */
+int c2b_refine_cameras_rows(double *bal9, const double *pts4, int64_t n_cam, const uint64_t *row_ptr, const uint32_t *pt_idx,
+                            const double *uv_obs, int loss_kind, double loss_a2, const double *prior_center, const double *prior_center_w,
+                            const double *prior_intr, const double *prior_intr_w, const c2b_refine_options *opt, const c2b_camera_mask *cam_mask,
+                            uint8_t *status, int64_t *counts, void *stream);
+int c2b_problem_refine_cameras(c2b_problem *p, const c2b_refine_options *opt, uint8_t *status, int64_t *counts);
+
 /* ---- consensus triangulation: points from the rays that agree (two-ray hypotheses, inlier mask, refit) ----
  * c2b_triangulate_rows is a least-squares midpoint over every ray of a point: one ray that belongs to another point (a
  * wrong match, a joined landmark) drags it arbitrarily far.  This pass forms candidates from pairs of rays, keeps the
