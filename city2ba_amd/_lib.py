@@ -129,6 +129,9 @@ REMATCH_STATUS = ("fits", "skipped", "reassigned", "removed")
 SUBSET_CARRY = 1           # C2B_SUBSET_CARRY: the child takes the parent's handle state and, for repeat-free lists, an origin
 WINDOW_HALO = 1            # C2B_WINDOW_HALO: halo cameras held constant; 0 = no halo cameras, shared points held constant
 
+# c2b_covisibility_temp_bytes' passes (C2B_COVIS_TEMP_*)
+COVIS_TEMP_GRAPH, COVIS_TEMP_EXPAND = 0, 1
+
 
 # name -> (restype, argtypes).  Kept in one table so tests can check every symbol the header declares.
 SIGNATURES = {
@@ -223,6 +226,13 @@ SIGNATURES = {
     "c2b_problem_window": (_int, [_vp, _vp, _int, _vp]),
     "c2b_problem_get_origin": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "c2b_problem_write_back": (_int, [_vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "c2b_covisibility_temp_bytes": (_i64, [_i64, _int]),
+    "c2b_covisibility_degree_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
+    "c2b_covisibility_fill_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_covisibility_expand_rows": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_problem_covisibility": (_int, [_vp, _int, C.POINTER(_i64)]),
+    "c2b_problem_get_covisibility": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_int), C.POINTER(_i64)]),
+    "c2b_problem_neighbourhood": (_int, [_vp, _vp, _int, _int, _i64, _vp, _vp, _vp, C.POINTER(_i64)]),
     "c2b_problem_set_loss": (_int, [_vp, _int, _d]),
     "c2b_problem_get_loss": (_int, [_vp, C.POINTER(_int), C.POINTER(_d)]),
     "c2b_problem_robust_cost": (_int, [_vp, C.POINTER(_d)]),

@@ -853,6 +853,60 @@ class BAProblem:
             raise
         return child._refresh_graph()
 
+    def covisibility(self, min_shared=1):
+        """The camera covisibility graph of the observation list, built on the device (c2b_problem_covisibility):
+        (nbr_ptr [n_cam + 1] uint64, nbr [n_edges] uint32, shared [n_edges] uint32) as numpy arrays -- per camera the cameras
+        that observe at least min_shared distinct points it observes too, in ascending index, and how many.  Symmetric, no
+        self edge; n_edges counts both directions.  The graph stays in the handle until the list changes or another
+        min_shared is asked for, so neighbourhood() at the same threshold does not rebuild it."""
+        n = C.c_int64()
+        L.check(L.lib().c2b_problem_covisibility(self._h, int(min_shared), C.byref(n)))
+        nbr_ptr = np.zeros(self.num_cameras() + 1, dtype=np.uint64)
+        nbr, shared = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+        L.check(L.lib().c2b_problem_get_covisibility(self._h, _ptr(nbr_ptr), _ptr(nbr) if n.value else None, _ptr(shared) if n.value else None,
+                                                     None, None))
+        return nbr_ptr, nbr, shared
+
+    def covisibility_heavy_cameras(self):
+        """how many cameras of the graph the handle holds took the heavy path (more candidate neighbours than a wave's LDS
+        table has slots), or None without a graph"""
+        n = C.c_int64()
+        if L.lib().c2b_problem_get_covisibility(self._h, None, None, None, None, C.byref(n)):
+            return None
+        return n.value
+
+    def neighbourhood(self, cameras, hops=1, min_shared=1, max_cameras=None, within=None, return_levels=False):
+        """This camera and the cameras that see what it sees (c2b_problem_neighbourhood): a breadth-first search over the
+        covisibility graph at min_shared from `cameras` (an index list or a bool mask [n_cam]), at most `hops` levels beyond
+        them (0: the seeds themselves; None: until nothing new is reached, the seeds' connected components at that
+        threshold), inside `within` (an index list or a bool mask, default all cameras; the seeds must lie in it).  With
+        max_cameras whole levels are taken while they fit and the first level that does not is cut by (shared points with
+        the levels already taken, descending; index, ascending).  Returns the member cameras in ascending index; with
+        return_levels also their levels (int32, 0 for a seed)."""
+        n_cam = self.num_cameras()
+
+        def mask(a, what):
+            a = np.asarray(a)
+            if a.dtype == np.bool_:
+                if a.shape != (n_cam,):
+                    raise ValueError("neighbourhood: a bool mask must have shape (%d,)" % n_cam)
+                return np.ascontiguousarray(a, dtype=np.uint8)
+            idx = np.asarray(a, dtype=np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= n_cam):
+                raise L.City2baError(L.ERR_INDEX_OUT_OF_RANGE, "neighbourhood: %s index out of range" % what)
+            m = np.zeros(n_cam, dtype=np.uint8)
+            m[idx] = 1
+            return m
+
+        seed = mask(cameras, "camera")
+        inside = None if within is None else mask(within, "within")
+        member, level, n = np.zeros(n_cam, dtype=np.uint8), np.zeros(n_cam, dtype=np.int32), C.c_int64()
+        L.check(L.lib().c2b_problem_neighbourhood(self._h, _ptr(seed), -1 if hops is None else int(hops), int(min_shared),
+                                                  0 if max_cameras is None else int(max_cameras), None if inside is None else _ptr(inside),
+                                                  _ptr(member), _ptr(level), C.byref(n)))
+        idx = np.flatnonzero(member)
+        return (idx, level[idx]) if return_levels else idx
+
     def origin(self):
         """where a child of subset(carry=True) / window came from (c2b_problem_get_origin): dict(cam_of [n_cam], pt_of
         [n_pts]: the parent's index of every camera / point; cam_role: 0 seed, 1 halo; pt_role: 1 = shared), or None"""

@@ -24,10 +24,14 @@
 //                         --preconditioner block-jacobi|schur-jacobi --inner-iterations N --fix-intrinsics --fix-first-camera
 //                         --filter-max-error X --filter-rounds N --filter-in-front
 //                         --prior-from FILE [--prior-center-sigma S|SX,SY,SZ] [--prior-intrinsics-sigma SF,SK1,SK2]
-//                         [--prior-point-sigma S [--prior-point-every N]] [--window LO:HI [--no-halo]]]
+//                         [--prior-point-sigma S [--prior-point-every N]] [--window LO:HI [--no-halo]]
+//                         [--window-around C[,C...] [--hops N] [--min-shared K] [--max-cameras M] [--no-halo]]]
 //                        (extension: Levenberg-Marquardt on the device, c2b_problem_levenberg_marquardt; with
 //                         --filter-max-error: N times solve + c2b_problem_filter_observations, then a solve without a loss;
-//                         with --window: cameras LO .. HI-1 alone, c2b_problem_window + c2b_problem_write_back)
+//                         with --window: cameras LO .. HI-1 alone, c2b_problem_window + c2b_problem_write_back;
+//                         with --window-around: the covisibility neighbourhood of the cameras given, c2b_problem_neighbourhood)
+//   city2ba covisibility IN [--min-shared K]   (one line: cameras, undirected edges, maximum degree, isolated cameras of the
+//                         camera covisibility graph, c2b_problem_covisibility)
 //   city2ba triangulate IN OUT [--min-angle DEG] [--max-error X [--min-inliers N] [--max-hypotheses H] [--drop-outliers]]
 //                        (extension: the points from the cameras and observations, c2b_problem_triangulate_points; with
 //                         --max-error: from the rays that agree with each other, c2b_problem_triangulate_consensus)
@@ -936,7 +940,8 @@ int run_solve(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera", "filter-in-front", "no-halo"},
                          {"iterations", "lambda", "pcg-iterations", "pcg-tol", "function-tol", "gradient-tol", "parameter-tol", "loss",
                           "loss-scale", "preconditioner", "inner-iterations", "device", "filter-max-error", "filter-rounds", "prior-from",
-                          "prior-center-sigma", "prior-intrinsics-sigma", "prior-point-sigma", "prior-point-every", "window"});
+                          "prior-center-sigma", "prior-intrinsics-sigma", "prior-point-sigma", "prior-point-every", "window", "window-around", "hops",
+                          "min-shared", "max-cameras"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
     c2b_lm_options opt;
     opt.max_iterations = (int32_t)std::min<int64_t>(a.i("iterations", 10), 1 << 20);
@@ -969,7 +974,36 @@ int run_solve(int argc, char **argv) {
     // camera count here, before a device exists
     const bool window = a.has("window");
     int64_t win_lo = 0, win_hi = 0;
-    if (a.has("no-halo") && !window) die("--no-halo needs --window <LO:HI>");
+    // --window-around C[,C...]: the cameras within --hops edges of the covisibility graph at --min-shared, at most --max-cameras
+    const bool around = a.has("window-around");
+    if (window && around) die("--window <LO:HI> and --window-around <C[,C...]> cannot be used together");
+    if (a.has("no-halo") && !window && !around) die("--no-halo needs --window <LO:HI> or --window-around <C[,C...]>");
+    for (const char *k : {"hops", "min-shared", "max-cameras"})
+        if (a.has(k) && !around) die(std::string("--") + k + " needs --window-around <C[,C...]>");
+    std::vector<int64_t> around_cams;
+    const int64_t hops = a.i("hops", 1), min_shared = a.i("min-shared", 1), max_cameras = a.i("max-cameras", 0);
+    if (around) {
+        const std::string &v = a.opt.at("window-around");
+        const std::string bad = "Invalid value for '--window-around <C[,C...]>': expected camera indices separated by commas";
+        size_t at = 0;
+        while (at <= v.size()) {
+            const size_t comma = std::min(v.find(',', at), v.size());
+            if (comma == at || comma - at > 18) die(bad);
+            for (size_t k = at; k < comma; ++k)
+                if (v[k] < '0' || v[k] > '9') die(bad);
+            around_cams.push_back(std::stoll(v.substr(at, comma - at)));
+            at = comma + 1;
+        }
+        if (hops < 0 || hops > 2147483647) die("Invalid value for '--hops <N>': expected an integer >= 0");
+        if (min_shared < 1 || min_shared > 2147483647) die("Invalid value for '--min-shared <K>': expected an integer >= 1");
+        if (a.has("max-cameras") && max_cameras < (int64_t)around_cams.size())
+            die("Invalid value for '--max-cameras <M>': expected at least the number of cameras given to --window-around");
+        int64_t in_cam = 0, in_pts = 0;
+        peek_counts(a.positional[0], in_cam, in_pts);
+        for (const int64_t c : around_cams)
+            if (c >= in_cam)
+                die("--window-around: " + a.positional[0] + " has " + std::to_string(in_cam) + " cameras, camera " + std::to_string(c) + " was given");
+    }
     if (window) {
         const std::string &v = a.opt.at("window");
         const std::string bad = "Invalid value for '--window <LO:HI>': expected two integers LO:HI with 0 <= LO < HI <= the number of cameras";
@@ -1056,17 +1090,30 @@ int run_solve(int argc, char **argv) {
     }
     // the window: a child of the problem that carries everything set above (the rim's masks on top); it is what is solved
     c2b_problem *whole = p;
-    if (window) {
+    if (window || around) {
         std::vector<uint8_t> seed((size_t)nc + 1, 0);
         for (int64_t c = win_lo; c < win_hi && c < nc; ++c) seed[(size_t)c] = 1;
+        if (around) {
+            std::vector<uint8_t> from((size_t)nc + 1, 0);
+            for (const int64_t c : around_cams)
+                if (c < nc) from[(size_t)c] = 1;
+            int64_t members = 0;
+            ck(c2b_problem_neighbourhood(whole, from.data(), (int)hops, (int)min_shared, max_cameras, nullptr, seed.data(), nullptr, &members));
+            timer.mark("neighbourhood (device)");
+            std::printf("neighbourhood of %lld cameras: %lld hops at %lld shared points: %lld cameras\n", (long long)around_cams.size(), (long long)hops,
+                        (long long)min_shared, (long long)members);
+        }
         c2b_problem *child = nullptr;
         ck(create_problem(device, &child));
         ck(c2b_problem_window(whole, seed.data(), a.has("no-halo") ? 0 : C2B_WINDOW_HALO, child));
         p = child;
         ck(c2b_problem_sizes(p, &nc, &np, &no));
         timer.mark("window (device)");
-        std::printf("window %lld:%lld: %lld cameras, %lld points, %lld observations\n", (long long)win_lo, (long long)win_hi, (long long)nc,
-                    (long long)np, (long long)no);
+        if (window)
+            std::printf("window %lld:%lld: %lld cameras, %lld points, %lld observations\n", (long long)win_lo, (long long)win_hi, (long long)nc,
+                        (long long)np, (long long)no);
+        else
+            std::printf("window: %lld cameras, %lld points, %lld observations\n", (long long)nc, (long long)np, (long long)no);
     }
     std::vector<c2b_lm_iteration> hist((size_t)opt.max_iterations + 1);
     static const char *const why[] = {"iteration limit reached", "function tolerance reached", "gradient tolerance reached",
@@ -1093,7 +1140,7 @@ int run_solve(int argc, char **argv) {
         ck(c2b_problem_set_loss(p, 0, 1.0));
     }
     solve_once();
-    if (window) {                                            // the child's free cameras and points back into the whole problem
+    if (window || around) {                                  // the child's free cameras and points back into the whole problem
         int64_t wc = 0, wp = 0;
         ck(c2b_problem_write_back(p, whole, &wc, &wp));
         c2b_problem_destroy(p);
@@ -1102,6 +1149,32 @@ int run_solve(int argc, char **argv) {
         std::printf("written back: %lld cameras, %lld points\n", (long long)wc, (long long)wp);
     }
     close_problem(timer, p, a.positional[1]);
+    return 0;
+}
+
+// `covisibility IN [--min-shared K]`: the camera covisibility graph's figures, one line
+int run_covisibility(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {}, {"min-shared", "device"});
+    if (a.positional.size() != 1) die("The following required arguments were not provided:\n    <FILE>");
+    const int64_t min_shared = a.i("min-shared", 1);
+    if (min_shared < 1 || min_shared > 2147483647) die("Invalid value for '--min-shared <K>': expected an integer >= 1");
+    PhaseTimer timer;
+    int64_t nc = 0, np = 0, no = 0, edges = 0;
+    c2b_problem *p = open_problem(timer, (int)a.i("device", 0), a.positional[0], nc, np, no);
+    ck(c2b_problem_covisibility(p, (int)min_shared, &edges));
+    std::vector<uint64_t> ptr((size_t)nc + 1, 0);
+    ck(c2b_problem_get_covisibility(p, ptr.data(), nullptr, nullptr, nullptr, nullptr));
+    timer.mark("covisibility (device)");
+    uint64_t max_degree = 0;
+    int64_t isolated = 0;
+    for (int64_t c = 0; c < nc; ++c) {
+        const uint64_t d = ptr[(size_t)c + 1] - ptr[(size_t)c];
+        max_degree = std::max(max_degree, d);
+        isolated += d == 0;
+    }
+    std::printf("covisibility at %lld shared points: %lld cameras, %lld edges, maximum degree %llu, %lld isolated cameras\n", (long long)min_shared,
+                (long long)nc, (long long)(edges / 2), (unsigned long long)max_degree, (long long)isolated);
+    c2b_problem_destroy(p);
     return 0;
 }
 
@@ -1305,6 +1378,7 @@ void usage() {
                 "    generate          Generate a synthetic bundle adjustment problem from a 3D model.\n"
                 "    ply               Convert a .bal or .bbal to a .ply for visualization.\n"
                 "    solve             Bundle-adjust a .bal or .bbal by Levenberg-Marquardt on the device.\n"
+                "    covisibility      Print the figures of the camera covisibility graph of a .bal or .bbal.\n"
                 "    triangulate       Set the points of a .bal or .bbal from its cameras and observations.\n"
                 "    resect            Set the camera poses of a .bal or .bbal from its points and observations.\n"
                 "    merge             Merge the duplicate landmarks of a .bal or .bbal (the repair of noise --split-landmarks).\n"
@@ -1346,6 +1420,10 @@ const char *subcommand_help(const std::string &sub) {
                "    --ground <X> [0]  --height <X> [1]     Poisson placement (without --path)\n"
                "    --move-to-origin   --no-lcc   --exact-lcc (extension)   --seed <N>\n";
     if (sub == "ply") return "city2ba ply <FILE> <OUT.ply>\n";
+    if (sub == "covisibility")
+        return "city2ba covisibility <FILE>\n"
+               "    --min-shared <K> [1]      an edge joins two cameras that observe at least K points in common\n"
+               "    prints the cameras, the edges, the maximum degree and the isolated cameras of that graph, built on the device\n";
     if (sub == "solve")
         return "city2ba solve <FILE> <OUT>\n"
                "    --iterations <N> [10]     --lambda <X> [1e-4]        Levenberg-Marquardt iterations, initial damping\n"
@@ -1362,6 +1440,11 @@ const char *subcommand_help(const std::string &sub) {
                "                              flag applies to the window [off]\n"
                "    --no-halo                 with --window: take no cameras from outside the window; the points also seen from outside\n"
                "                              are held constant instead of the outside cameras that see the window's points\n"
+               "    --window-around <C[,C...]>  the window is cameras C and the cameras that see what they see: those within --hops edges\n"
+               "                              of the covisibility graph (cameras that share at least --min-shared points), at most\n"
+               "                              --max-cameras of them, the nearest levels first and the last level by shared points;\n"
+               "                              not with --window; --no-halo applies\n"
+               "    --hops <N> [1]  --min-shared <K> [1]  --max-cameras <M> [no limit]\n"
                "    --filter-max-error <X>    outlier rejection: solve, drop the observations whose reprojection residual exceeds X,\n"
                "                              then solve again without a loss [off]\n"
                "    --filter-rounds <N> [1]   solve + filter rounds before the last solve\n"
@@ -1440,6 +1523,7 @@ int main(int argc, char **argv) {
     if (sub == "generate") return run_generate(argc, argv);
     if (sub == "ply") return run_ply(argc, argv);
     if (sub == "solve") return run_solve(argc, argv);
+    if (sub == "covisibility") return run_covisibility(argc, argv);
     if (sub == "triangulate") return run_triangulate(argc, argv);
     if (sub == "resect") return run_resect(argc, argv);
     if (sub == "merge") return run_merge(argc, argv);

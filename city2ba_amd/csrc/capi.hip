@@ -49,6 +49,7 @@
 #include "rematch_kernels.hpp"
 #include "index_noise_kernels.hpp"
 #include "subset_kernels.hpp"
+#include "covis_kernels.hpp"
 #include "text_kernels.hpp"
 #include "comm_rccl.hpp"
 

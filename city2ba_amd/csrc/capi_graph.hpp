@@ -1305,3 +1305,153 @@ int c2b_problem_visibility_dense_fetch(c2b_problem *p, uint64_t *pt_idx, double 
     return C2B_OK;
     C2B_API_END("problem_visibility_dense_fetch")
 }
+
+// ---- the camera covisibility graph of the resident list and the search over it -------------------------------
+// The graph at min_shared, built on first use (degree pass, its total, fill pass) into locals and moved in on success, as
+// ensure_transpose does; kept until the list changes (drop_rows) or another threshold is asked for.
+static int ensure_covisibility(c2b_problem *p, int min_shared) {
+    if (p->cv_ptr && p->cv_min_shared == min_shared) return C2B_OK;
+    const int64_t n_cam = p->n_cam;
+    hipStream_t st = p->stream;
+    DevBuf<uint64_t> ptr;
+    DevBuf<uint32_t> nbr, shared;
+    DevBuf<char> temp;
+    DevBuf<int64_t> counts;
+    int64_t h[2] = {0, 0};
+    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{st};      // before the locals are freed
+    HIP_TRY(ptr.alloc((size_t)n_cam + 1));
+    HIP_TRY(counts.alloc(2));
+    HIP_TRY(temp.alloc((size_t)c2b_covisibility_temp_bytes(n_cam, C2B_COVIS_TEMP_GRAPH)));
+    int rc = ensure_rows(p);
+    if (!rc && p->n_obs) rc = ensure_transpose(p);
+    if (!rc) rc = c2b_covisibility_degree_rows(p->rows_ptr, p->pt_idx, p->nt_ptr, p->nt_obs, p->nt_cam, n_cam, p->n_pts, p->n_obs, min_shared, temp, ptr,
+                                               counts, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(h, counts.ptr, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(nbr.alloc((size_t)h[0]));
+    HIP_TRY(shared.alloc((size_t)h[0]));
+    rc = c2b_covisibility_fill_rows(p->rows_ptr, p->pt_idx, p->nt_ptr, p->nt_obs, p->nt_cam, n_cam, p->n_pts, p->n_obs, min_shared, temp, ptr, nbr, shared, st);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    p->cv_ptr = std::move(ptr); p->cv_nbr = std::move(nbr); p->cv_shared = std::move(shared);
+    p->cv_min_shared = min_shared;
+    p->cv_edges = h[0]; p->cv_heavy = h[1];
+    return C2B_OK;
+}
+
+int c2b_problem_covisibility(c2b_problem *p, int min_shared, int64_t *n_edges) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_covisibility: problem is NULL");
+    if (min_shared < 1) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_covisibility: min_shared must be at least 1");
+    NEED_UPLOADED(p, "problem_covisibility");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_covisibility: a shard has no graph of its own (a point's observations span every rank)");
+    if (const int rc = ensure_covisibility(p, min_shared)) return rc;
+    if (n_edges) *n_edges = p->cv_edges;
+    return C2B_OK;
+    C2B_API_END("problem_covisibility")
+}
+
+int c2b_problem_get_covisibility(c2b_problem *p, uint64_t *nbr_ptr, uint32_t *nbr, uint32_t *shared, int *min_shared, int64_t *n_heavy) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_covisibility: problem is NULL");
+    if (!p->cv_ptr) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_covisibility: no graph (c2b_problem_covisibility builds it; a change of the list drops it)");
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t ne = (size_t)p->cv_edges;
+    if (nbr_ptr) HIP_TRY(hipMemcpyAsync(nbr_ptr, p->cv_ptr, sizeof(uint64_t) * ((size_t)p->n_cam + 1), hipMemcpyDeviceToHost, p->stream));
+    if (nbr && ne) HIP_TRY(hipMemcpyAsync(nbr, p->cv_nbr, sizeof(uint32_t) * ne, hipMemcpyDeviceToHost, p->stream));
+    if (shared && ne) HIP_TRY(hipMemcpyAsync(shared, p->cv_shared, sizeof(uint32_t) * ne, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (min_shared) *min_shared = p->cv_min_shared;
+    if (n_heavy) *n_heavy = p->cv_heavy;
+    return C2B_OK;
+    C2B_API_END("problem_get_covisibility")
+}
+
+int c2b_problem_neighbourhood(c2b_problem *p, const uint8_t *seed, int hops, int min_shared, int64_t max_cameras, const uint8_t *within,
+                              uint8_t *member, int32_t *level, int64_t *n) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_neighbourhood: problem is NULL");
+    if (!seed) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_neighbourhood: seed is NULL");
+    if (min_shared < 1) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_neighbourhood: min_shared must be at least 1");
+    NEED_UPLOADED(p, "problem_neighbourhood");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_neighbourhood: a shard has no graph of its own (a point's observations span every rank)");
+    const int64_t n_cam = p->n_cam, cap = max_cameras > 0 ? max_cameras : 0;
+    int64_t n_seed = 0;
+    for (int64_t c = 0; c < n_cam; ++c) {
+        if (!seed[c]) continue;
+        ++n_seed;
+        if (within && !within[c]) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_neighbourhood: seed camera %lld lies outside `within`", (long long)c);
+    }
+    if (!n_seed) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_neighbourhood: no seed camera");
+    if (cap && n_seed > cap)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_neighbourhood: %lld seed cameras, max_cameras %lld", (long long)n_seed, (long long)cap);
+    if (const int rc = ensure_covisibility(p, min_shared)) return rc;
+    hipStream_t st = p->stream;
+    DevBuf<uint8_t> d_seed, d_within, select;
+    DevBuf<int32_t> d_level;
+    DevBuf<uint32_t> front, next, n_next;
+    DevBuf<uint64_t> keys;
+    DevBuf<char> temp;
+    DevArena arena;
+    const size_t nc = (size_t)n_cam;
+    auto temporaries = [&](auto &&each) {
+        each(d_seed, nc); each(d_within, nc); each(select, nc); each(d_level, nc); each(front, nc); each(next, nc); each(n_next, (size_t)1);
+        each(keys, nc); each(temp, (size_t)c2b_covisibility_temp_bytes(n_cam, C2B_COVIS_TEMP_EXPAND));
+    };
+    size_t arena_bytes = 0;
+    temporaries([&](auto &b, size_t k) { arena_bytes += DevArena::room(b, k); });
+    hipError_t e = arena.reserve(arena_bytes);
+    if (e != hipSuccess) return fail(hip_code(e), "problem_neighbourhood: %s", hipGetErrorString(e));
+    temporaries([&](auto &b, size_t k) { arena.carve(b, k); });
+    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{st};      // before the arena is freed
+    const CovisTemp T(temp.ptr, n_cam, false);
+    HIP_TRY(hipMemcpyAsync(d_seed, seed, nc, hipMemcpyHostToDevice, st));
+    if (within) HIP_TRY(hipMemcpyAsync(d_within, within, nc, hipMemcpyHostToDevice, st));
+    const uint8_t *w = within ? d_within.ptr : nullptr;
+    hipLaunchKernelGGL(k_covis_seed_levels, dim3(blocks_for(n_cam, 256)), dim3(256), 0, st, (const uint8_t *)d_seed, n_cam, d_level.ptr);
+    covis_collect_level(st, T, d_level, n_cam, 0, front.ptr, n_next.ptr);
+    LAUNCH_CHECK();
+    int64_t taken = n_seed, n_front = n_seed;
+    for (int h = 0; (hops < 0 || h < hops) && n_front && !(cap && taken == cap) && h < 0x7ffffffe; ++h) {
+        int rc = c2b_covisibility_expand_rows(p->cv_ptr, p->cv_nbr, p->cv_shared, n_cam, min_shared, w, front, n_front, h, d_level, next, n_next, temp, st);
+        if (rc) return rc;
+        uint32_t got = 0;
+        HIP_TRY(hipMemcpyAsync(&got, n_next.ptr, sizeof got, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (!got) break;
+        if (cap && taken + (int64_t)got > cap) {
+            // the level does not fit: its best (score descending, index ascending) fill the remainder and the search ends
+            const int64_t rem = cap - taken;
+            HIP_TRY(hipMemsetAsync(keys, 0xff, sizeof(uint64_t) * nc, st));              // a camera that is no candidate sorts last
+            hipLaunchKernelGGL(k_covis_score, dim3(blocks_for(got, 4)), dim3(256), 0, st, (const uint64_t *)p->cv_ptr, (const uint32_t *)p->cv_nbr,
+                               (const uint32_t *)p->cv_shared, (uint32_t)min_shared, (const uint32_t *)next, (int64_t)got, (int32_t)h,
+                               (const int32_t *)d_level, keys.ptr);
+            LAUNCH_CHECK();
+            if ((rc = c2b_select_smallest_keys_rows(keys, n_cam, 0, 0, 0, rem, select, st))) return rc;
+            hipLaunchKernelGGL(k_covis_unselect, dim3(blocks_for(got, 256)), dim3(256), 0, st, (const uint32_t *)next, (int64_t)got, (const uint8_t *)select,
+                               d_level.ptr);
+            LAUNCH_CHECK();
+            taken = cap;
+            break;
+        }
+        taken += got;
+        n_front = got;
+        std::swap(front, next);
+    }
+    std::vector<int32_t> h_level(nc);
+    if (nc) HIP_TRY(hipMemcpyAsync(h_level.data(), d_level, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int64_t count = 0;
+    for (size_t c = 0; c < nc; ++c) count += h_level[c] >= 0;
+    if (count != taken) return fail(C2B_ERR_HIP, "problem_neighbourhood: %lld cameras reached instead of %lld", (long long)count, (long long)taken);
+    for (size_t c = 0; c < nc; ++c) {
+        if (member) member[c] = h_level[c] >= 0 ? 1 : 0;
+        if (level) level[c] = h_level[c];
+    }
+    if (n) *n = count;
+    return C2B_OK;
+    C2B_API_END("problem_neighbourhood")
+}

@@ -1845,3 +1845,142 @@ int c2b_schur_jacobi_rows(const double *camblk, const double *pts4, const uint64
     return c2b_schur_jacobi_rows_loss(camblk, pts4, row_ptr, n_cam, pt_idx, uv_obs, n_obs, U, V, lambda, M, 0, 1.0, stream);
 }
 
+
+// ---- the camera covisibility graph and the search over it (covis_kernels.hpp) ---------------------------------
+// temp of the three entries, every piece on a 256-byte boundary:
+//   [heavy: n_cam u32] [its scan: n_cam u32] [the heavy cameras: n_cam u32] [degrees: n_cam u64] [scan tiles: u64]
+//   [the number of heavy cameras: u32] [dense counter rows of the heavy path: covis_heavy_groups(n_cam) x n_cam u32]
+// c2b_covisibility_expand_rows uses the first two and the tiles for its flags and their scan: its temp ends before the counter rows.
+static int64_t covis_heavy_groups(int64_t n_cam) {
+    const int64_t g = ((int64_t)64 << 20) / (4 * std::max<int64_t>(n_cam, 1));      // 64 MiB of counter rows
+    return std::min<int64_t>(std::max<int64_t>(g, 1), 256);
+}
+struct CovisTemp {
+    uint32_t *heavy, *hpos, *hlist, *n_heavy, *dense;
+    uint64_t *deg, *tiles;
+    int64_t bytes;
+    CovisTemp(void *temp, int64_t n_cam, bool graph = true) {
+        char *q = reinterpret_cast<char *>(temp);
+        int64_t used = 0;
+        auto carve = [&](int64_t b) { char *at = q ? q + used : nullptr; used += (std::max<int64_t>(b, 16) + 255) & ~(int64_t)255; return at; };
+        heavy = reinterpret_cast<uint32_t *>(carve(4 * n_cam));
+        hpos = reinterpret_cast<uint32_t *>(carve(4 * n_cam));
+        hlist = reinterpret_cast<uint32_t *>(carve(4 * n_cam));
+        deg = reinterpret_cast<uint64_t *>(carve(8 * n_cam));
+        tiles = reinterpret_cast<uint64_t *>(carve(8 * (int64_t)scan_scratch_count(n_cam)));
+        n_heavy = reinterpret_cast<uint32_t *>(carve(4));
+        dense = graph ? reinterpret_cast<uint32_t *>(carve(4 * covis_heavy_groups(n_cam) * n_cam)) : nullptr;
+        bytes = used;
+    }
+};
+int64_t c2b_covisibility_temp_bytes(int64_t n_cam, int pass) { return CovisTemp(nullptr, n_cam < 0 ? 0 : n_cam, pass != C2B_COVIS_TEMP_EXPAND).bytes; }
+
+// short or tiled by the length (scratch: scan_scratch_count(n) elements of Out)
+extern "C++" {
+template <class In, class Out>
+static void covis_scan(hipStream_t st, const In *in, int64_t n, Out *out, Out *total, Out *scratch) {
+    if (n <= kScanTile) scan_short(st, in, n, (Out)0, out, total);
+    else scan_tiled(st, in, n, (Out)0, out, total, scratch);
+}
+}
+
+static int covis_graph_check(const char *who, const uint64_t *row_ptr, const uint32_t *pt_idx, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                             const uint32_t *cam_of, int64_t n_cam, int64_t n_pts, int64_t n_obs, int min_shared, const void *temp,
+                             const void *out_a, const void *out_b, const void *out_c) {
+    if (min_shared < 1) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: min_shared must be at least 1", who);
+    if (n_cam < 0 || n_cam >= (int64_t)1 << 31) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: n_cam out of range", who);
+    if (n_pts < 0 || n_pts > (int64_t)0xffffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: n_pts out of range", who);
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 64) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: n_obs out of range", who);
+    if (!out_a || !out_b || !out_c || !temp || (n_obs && (!row_ptr || !pt_idx || !pt_row_ptr || !obs_of || !cam_of || !n_cam || !n_pts)))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "%s: NULL argument, or observations without cameras or points", who);
+    if (!aligned8(row_ptr) || !aligned8(pt_row_ptr) || !aligned16(temp) || ((reinterpret_cast<uintptr_t>(pt_idx) | reinterpret_cast<uintptr_t>(obs_of) |
+                                                                            reinterpret_cast<uintptr_t>(cam_of)) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "%s: misaligned pointer (row pointers 8 bytes, indices 4, temp 16)", who);
+    return C2B_OK;
+}
+
+int c2b_covisibility_degree_rows(const uint64_t *row_ptr, const uint32_t *pt_idx, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                                 const uint32_t *cam_of, int64_t n_cam, int64_t n_pts, int64_t n_obs, int min_shared, void *temp,
+                                 uint64_t *nbr_ptr, int64_t *counts, void *stream) {
+    C2B_API_BEGIN
+    if (const int rc = covis_graph_check("covisibility_degree_rows", row_ptr, pt_idx, pt_row_ptr, obs_of, cam_of, n_cam, n_pts, n_obs, min_shared, temp,
+                                         nbr_ptr, counts, counts))
+        return rc;
+    if (!aligned8(nbr_ptr) || !aligned8(counts)) return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_degree_rows: misaligned pointer (nbr_ptr, counts: 8 bytes)");
+    hipStream_t st = S(stream);
+    if (!n_obs || !n_cam) {
+        HIP_TRY(hipMemsetAsync(nbr_ptr, 0, sizeof(uint64_t) * (size_t)(n_cam + 1), st));
+        HIP_TRY(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
+        return C2B_OK;
+    }
+    const CovisTemp T(temp, n_cam);
+    const int64_t groups = covis_heavy_groups(n_cam);
+    HIP_TRY(hipMemsetAsync(T.dense, 0, sizeof(uint32_t) * (size_t)(groups * n_cam), st));
+    hipLaunchKernelGGL(k_covis_bound, dim3(blocks_for(n_cam, 4)), dim3(256), 0, st, row_ptr, pt_idx, pt_row_ptr, n_cam, T.heavy);
+    covis_scan(st, (const uint32_t *)T.heavy, n_cam, T.hpos, T.n_heavy, reinterpret_cast<uint32_t *>(T.tiles));
+    hipLaunchKernelGGL(k_covis_compact, dim3(blocks_for(n_cam, 256)), dim3(256), 0, st, (const uint32_t *)T.heavy, (const uint32_t *)T.hpos, n_cam, T.hlist);
+    hipLaunchKernelGGL(k_covis_light<false>, dim3(blocks_for(n_cam, kCvWaves)), dim3(kCvBlock), 0, st, row_ptr, pt_idx, pt_row_ptr, obs_of, cam_of, n_cam,
+                       (uint32_t)min_shared, (const uint32_t *)T.heavy, T.deg, (const uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_covis_heavy<false>, dim3((unsigned)groups), dim3(kCvHeavyBlock), 0, st, row_ptr, pt_idx, pt_row_ptr, obs_of, cam_of, n_cam,
+                       (uint32_t)min_shared, (const uint32_t *)T.hlist, (const uint32_t *)T.n_heavy, T.dense, T.deg, (const uint64_t *)nullptr,
+                       (uint32_t *)nullptr, (uint32_t *)nullptr);
+    covis_scan(st, (const uint64_t *)T.deg, n_cam, nbr_ptr, nbr_ptr + n_cam, T.tiles);          // the row-pointer form
+    hipLaunchKernelGGL(k_covis_counts, dim3(1), dim3(64), 0, st, (const uint64_t *)nbr_ptr, n_cam, (const uint32_t *)T.n_heavy, counts);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("covisibility_degree_rows")
+}
+
+int c2b_covisibility_fill_rows(const uint64_t *row_ptr, const uint32_t *pt_idx, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                               const uint32_t *cam_of, int64_t n_cam, int64_t n_pts, int64_t n_obs, int min_shared, void *temp,
+                               const uint64_t *nbr_ptr, uint32_t *nbr, uint32_t *shared, void *stream) {
+    C2B_API_BEGIN
+    if (const int rc = covis_graph_check("covisibility_fill_rows", row_ptr, pt_idx, pt_row_ptr, obs_of, cam_of, n_cam, n_pts, n_obs, min_shared, temp,
+                                         nbr_ptr, nbr_ptr, nbr_ptr))
+        return rc;
+    if (!aligned8(nbr_ptr) || ((reinterpret_cast<uintptr_t>(nbr) | reinterpret_cast<uintptr_t>(shared)) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_fill_rows: misaligned pointer (nbr_ptr 8 bytes, nbr and shared 4)");
+    if (!n_obs || !n_cam) return C2B_OK;
+    if (!nbr || !shared) return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_fill_rows: NULL output");
+    hipStream_t st = S(stream);
+    const CovisTemp T(temp, n_cam);
+    hipLaunchKernelGGL(k_covis_light<true>, dim3(blocks_for(n_cam, kCvWaves)), dim3(kCvBlock), 0, st, row_ptr, pt_idx, pt_row_ptr, obs_of, cam_of, n_cam,
+                       (uint32_t)min_shared, (const uint32_t *)T.heavy, (uint64_t *)nullptr, nbr_ptr, nbr, shared);
+    hipLaunchKernelGGL(k_covis_heavy<true>, dim3((unsigned)covis_heavy_groups(n_cam)), dim3(kCvHeavyBlock), 0, st, row_ptr, pt_idx, pt_row_ptr, obs_of,
+                       cam_of, n_cam, (uint32_t)min_shared, (const uint32_t *)T.hlist, (const uint32_t *)T.n_heavy, T.dense, (uint64_t *)nullptr, nbr_ptr,
+                       nbr, shared);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("covisibility_fill_rows")
+}
+
+// out[0 .. *n_out) = the cameras of level h in ascending index: flags, their scan, the compaction (unchecked launches)
+static void covis_collect_level(hipStream_t st, const CovisTemp &T, const int32_t *level, int64_t n_cam, int h, uint32_t *out, uint32_t *n_out) {
+    if (n_cam) hipLaunchKernelGGL(k_covis_level_flags, dim3(blocks_for(n_cam, 256)), dim3(256), 0, st, level, n_cam, (int32_t)h, T.heavy);
+    covis_scan(st, (const uint32_t *)T.heavy, n_cam, T.hpos, n_out, reinterpret_cast<uint32_t *>(T.tiles));
+    if (n_cam) hipLaunchKernelGGL(k_covis_compact, dim3(blocks_for(n_cam, 256)), dim3(256), 0, st, (const uint32_t *)T.heavy, (const uint32_t *)T.hpos, n_cam, out);
+}
+
+int c2b_covisibility_expand_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, const uint32_t *shared, int64_t n_cam, int min_shared,
+                                 const uint8_t *within, const uint32_t *frontier, int64_t n_frontier, int hop, int32_t *level, uint32_t *next,
+                                 uint32_t *n_next, void *temp, void *stream) {
+    C2B_API_BEGIN
+    if (min_shared < 1) return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_expand_rows: min_shared must be at least 1");
+    if (n_cam < 0 || n_cam >= (int64_t)1 << 31) return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_expand_rows: n_cam out of range");
+    if (n_frontier < 0 || n_frontier > n_cam) return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_expand_rows: n_frontier out of range");
+    if (hop < 0 || hop == 0x7fffffff) return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_expand_rows: hop out of range");
+    if (!n_next || !temp || (n_cam && (!nbr_ptr || !level || !next)) || (n_frontier && !frontier))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_expand_rows: NULL argument");
+    if (!aligned8(nbr_ptr) || !aligned16(temp) || ((reinterpret_cast<uintptr_t>(nbr) | reinterpret_cast<uintptr_t>(shared) | reinterpret_cast<uintptr_t>(frontier) |
+                                                    reinterpret_cast<uintptr_t>(level) | reinterpret_cast<uintptr_t>(next) | reinterpret_cast<uintptr_t>(n_next)) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "covisibility_expand_rows: misaligned pointer (nbr_ptr 8 bytes, indices and levels 4, temp 16)");
+    hipStream_t st = S(stream);
+    const CovisTemp T(temp, n_cam, false);
+    if (n_frontier)
+        hipLaunchKernelGGL(k_covis_mark, dim3(blocks_for(n_frontier, 4)), dim3(256), 0, st, nbr_ptr, nbr, shared, (uint32_t)min_shared, within, frontier,
+                           n_frontier, (int32_t)(hop + 1), level);
+    covis_collect_level(st, T, level, n_cam, hop + 1, next, n_next);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("covisibility_expand_rows")
+}

@@ -58,6 +58,12 @@ struct c2b_problem {
     // one allocation, sized by the list, dropped with it
     DevBuf<double> sv;
     int64_t sv_doubles = 0;
+    // c2b_problem_covisibility: the camera covisibility graph of the list at threshold cv_min_shared (nbr_ptr
+    // [n_cam + 1], nbr / shared [cv_edges]) and how many cameras took the heavy path; derived from the list, dropped with it
+    DevBuf<uint64_t> cv_ptr;
+    DevBuf<uint32_t> cv_nbr, cv_shared;
+    int cv_min_shared = 0;
+    int64_t cv_edges = 0, cv_heavy = 0;
     // c2b_problem_checkpoint: bal9 and pts4 as they were when it was taken, what c2b_problem_rollback copies
     // back.  Allocated on first use and reused while the counts stay; ck_valid says whether they hold a checkpoint.
     // lm: the scratch of c2b_problem_levenberg_marquardt (its step, the partials and scalars of k_lm_norms /
@@ -89,7 +95,8 @@ struct c2b_problem {
 };
 
 // Which event drops which cache or handle state.  X: dropped (rebuilt by the next user, or gone), -: stays.  The functions
-// below and cameras_mutated are the table's implementation; the list's three caches go together (drop_rows).
+// below and cameras_mutated are the table's implementation; the list's three caches go together (drop_rows), and the
+// covisibility graph (c2b_problem_covisibility) goes with them: wherever the transpose column says X, it is dropped.
 //                              camblk/cen4  bal9       rows  transpose  solve  pending vis.  masks       checkpoint/LM
 //   upload, upload_bal         X            X / truth  X     X          X      X             - / X (1)   X
 //   layout (grid, line)        X            X          X     X          X      X             X           X
@@ -139,12 +146,15 @@ static void free_dense(c2b_problem *p) {
     p->dense_n = 0;
 }
 
-// what is derived from the observation list: row structure, transpose, solve buffers
+// what is derived from the observation list: row structure, transpose, solve buffers, covisibility graph
 static void drop_rows(c2b_problem *p) {
     p->rows_ptr.reset(); p->rows_tiles.reset();
     p->nt_ptr.reset(); p->nt_obs.reset(); p->nt_cam.reset();
     p->sv.reset();
     p->sv_doubles = 0;
+    p->cv_ptr.reset(); p->cv_nbr.reset(); p->cv_shared.reset();
+    p->cv_min_shared = 0;
+    p->cv_edges = p->cv_heavy = 0;
 }
 
 // the masks: nothing is constant any more

@@ -467,6 +467,51 @@ class PointRows:
         temp.record_stream(torch.cuda.current_stream(dev))
 
 
+COVIS_WAVE_SLOTS = 2048     # C2B_COVIS_WAVE_SLOTS: slots of the LDS table a wave counts one camera's neighbours in
+
+
+def _covis_temp(n_cam, which, device):
+    return torch.empty((L.lib().c2b_covisibility_temp_bytes(int(n_cam), which) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def covisibility_rows(rows, pt_idx, prows, min_shared=1, return_counts=False):
+    """the camera covisibility graph of a camera-major list (c2b_covisibility_degree_rows / _fill_rows): rows (Rows),
+    pt_idx [n_obs] int32, prows (PointRows of the same list).  Returns (nbr_ptr [n_cam + 1] int64 holding u64, nbr [n_edges],
+    shared [n_edges] int32 holding u32): per camera its neighbours in ascending index -- the cameras that observe at least
+    min_shared distinct points it observes too -- and the number shared.  With return_counts also the int64 [2] tensor
+    (n_edges, cameras that took the heavy path).  Synchronises the stream once, to size the outputs."""
+    dev = rows.row_ptr.device
+    n_cam = rows.n_cam
+    temp = _covis_temp(n_cam, L.COVIS_TEMP_GRAPH, dev)
+    nbr_ptr = torch.empty(n_cam + 1, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    args = (_p(rows.row_ptr), _p(pt_idx), _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of), n_cam, prows.n_pts, rows.n_obs, int(min_shared), _p(temp))
+    L.check(L.lib().c2b_covisibility_degree_rows(*args, _p(nbr_ptr), _p(counts), _stream()))
+    n_edges = int(counts[0].item())
+    nbr = torch.empty(max(n_edges, 1), dtype=torch.int32, device=dev)             # (never a NULL pointer)
+    shared = torch.empty(max(n_edges, 1), dtype=torch.int32, device=dev)
+    L.check(L.lib().c2b_covisibility_fill_rows(*args, _p(nbr_ptr), _p(nbr), _p(shared), _stream()))
+    temp.record_stream(torch.cuda.current_stream(dev))
+    nbr, shared = nbr[:n_edges], shared[:n_edges]
+    return (nbr_ptr, nbr, shared, counts) if return_counts else (nbr_ptr, nbr, shared)
+
+
+def covisibility_expand_rows(nbr_ptr, nbr, shared, frontier, hop, level, min_shared=1, within=None):
+    """one level of a breadth-first search over a covisibility graph (c2b_covisibility_expand_rows): level [n_cam] int32 in place
+    (-1 = not reached), frontier [n] int32 = the cameras of level `hop`; their neighbours that are not reached, share at least
+    min_shared points and lie inside within [n_cam] uint8 (or None) get level hop + 1.  Returns (next [n_cam] int32, n_next [1]
+    int32): the cameras of level hop + 1 in ascending index and their number."""
+    dev = level.device
+    n_cam = level.shape[0]
+    temp = _covis_temp(n_cam, L.COVIS_TEMP_EXPAND, dev)
+    nxt = torch.empty(max(n_cam, 1), dtype=torch.int32, device=dev)
+    n_next = torch.empty(1, dtype=torch.int32, device=dev)
+    L.check(L.lib().c2b_covisibility_expand_rows(_p(nbr_ptr), _p(nbr), _p(shared), n_cam, int(min_shared), _p(within), _p(frontier), frontier.shape[0],
+                                                 int(hop), _p(level), _p(nxt), _p(n_next), _p(temp), _stream()))
+    temp.record_stream(torch.cuda.current_stream(dev))
+    return nxt[:n_cam], n_next
+
+
 def _loss_args(loss):
     """loss= of the *_rows passes: None, or (name, scale) -- the (kind, scale) of the *_rows_loss entries"""
     if isinstance(loss, str) or not hasattr(loss, "__len__") or len(loss) != 2:

@@ -220,11 +220,49 @@ def solve_window(ba, cameras, halo=True, **lm):
         child.close()
 
 
-def solve_windows(ba, size, stride=None, sweeps=1, halo=True, **lm):
-    """solve_window over windows of `size` consecutive camera indices every `stride` (default: size), over all cameras,
-    `sweeps` times.  Returns the per-window summaries in the order solved, each with lo and hi (its cameras lo .. hi - 1)
-    and sweep."""
+def solve_neighbourhood(ba, cameras, hops=1, min_shared=1, max_cameras=None, halo=True, **lm):
+    """solve_window on a covisibility neighbourhood: the seeds of the window are ba.neighbourhood(cameras, hops, min_shared,
+    max_cameras) -- `cameras` and every camera within `hops` edges of the covisibility graph at min_shared, cut to
+    max_cameras by shared points -- and the rim is the window's as ever.  Returns solve_window's summary plus seeds (the
+    window's cameras, ascending) and levels (their distance from `cameras` in the graph)."""
+    seeds, levels = ba.neighbourhood(cameras, hops=hops, min_shared=min_shared, max_cameras=max_cameras, return_levels=True)
+    out = solve_window(ba, seeds, halo=halo, **lm)
+    out["seeds"], out["levels"] = seeds, levels
+    return out
+
+
+def solve_windows(ba, size, stride=None, sweeps=1, halo=True, by="index", min_shared=1, **lm):
+    """solve_window over windows of `size` cameras, over all cameras, `sweeps` times.
+    by="index": windows of consecutive camera indices every `stride` (default: size).  Returns the per-window summaries in the
+    order solved, each with lo and hi (its cameras lo .. hi - 1) and sweep.
+    by="covisibility": windows grown over the covisibility graph at min_shared, for lists whose index order does not follow
+    the scene.  Per sweep every camera starts as to-do; until none is left, the lowest to-do index is the seed, the window is
+    ba.neighbourhood([seed], hops=None, max_cameras=size, within=the to-do cameras), it is solved and its cameras are done.
+    The windows of a sweep partition the cameras.  `stride` is refused.  Each summary carries seed, seeds (the window's
+    cameras), levels and sweep."""
     size = int(size)
+    if by == "covisibility":
+        if stride is not None:
+            raise ValueError("solve_windows: stride has no meaning with by='covisibility'")
+        if size < 1:
+            raise ValueError("solve_windows: size must be at least 1")
+        import numpy as np
+        n_cam = ba.num_cameras()
+        out = []
+        for sweep in range(int(sweeps)):
+            todo = np.ones(n_cam, dtype=bool)
+            first = 0
+            while first < n_cam:
+                seeds, levels = ba.neighbourhood([first], hops=None, min_shared=min_shared, max_cameras=size, within=todo, return_levels=True)
+                s = solve_window(ba, seeds, halo=halo, **lm)
+                s.update(seed=first, seeds=seeds, levels=levels, sweep=sweep)
+                out.append(s)
+                todo[seeds] = False
+                while first < n_cam and not todo[first]:
+                    first += 1
+        return out
+    if by != "index":
+        raise ValueError("solve_windows: by must be 'index' or 'covisibility', not %r" % (by,))
     stride = size if stride is None else int(stride)
     if size < 1 or stride < 1:
         raise ValueError("solve_windows: size and stride must be at least 1")

@@ -848,6 +848,64 @@ int c2b_problem_window(c2b_problem *src, const uint8_t *seed, int flags, c2b_pro
 int c2b_problem_get_origin(const c2b_problem *child, uint32_t *cam_of, uint32_t *pt_of, uint8_t *cam_role, uint8_t *pt_role);
 int c2b_problem_write_back(c2b_problem *child, c2b_problem *parent, int64_t *n_cam_written, int64_t *n_pts_written);
 
+/* ---- the camera covisibility graph on the device and the search over it ----
+ * Cameras are nodes.  shared(c, c'), c != c', = the number of DISTINCT points with at least one observation in row c and at
+ * least one in row c': a duplicated (camera, point) entry counts once per camera pair.  The graph at a threshold min_shared >= 1
+ * is a symmetric CSR: nbr_ptr [n_cam + 1] (uint64), nbr [n_edges] (uint32: the neighbours of a camera in ASCENDING index, never
+ * the camera itself), shared [n_edges] (uint32), holding exactly the pairs with shared >= min_shared; n_edges counts directed
+ * entries, twice the undirected number.  It is the sparsity pattern of the reduced camera system.  Integers only: the same list
+ * gives the same bytes on every call, whatever the launch shape.  No float atomics, no scratch memory.
+ * Level 0, stateless, asynchronous on `stream`, device arrays: row_ptr [n_cam + 1] / pt_idx [n_obs] the camera-major list,
+ * pt_row_ptr / obs_of / cam_of its transpose as c2b_normal_transpose writes it (stable: a track ascends in camera index).
+ * One wave per camera counts (other camera -> shared) in a table of C2B_COVIS_WAVE_SLOTS slots in LDS; a camera whose bound --
+ * the sum over its row of (track length - 1) -- exceeds the table takes the heavy path (a workgroup and a dense counter row in
+ * temp) with exactly the same result: no camera is truncated, whatever its degree.
+ * c2b_covisibility_temp_bytes: the size of `temp` (16-byte aligned) for n_cam cameras: pass = C2B_COVIS_TEMP_GRAPH for the degree
+ *   and fill passes (ONE temp, handed from the first to the second untouched), C2B_COVIS_TEMP_EXPAND for the expansion step.
+ * c2b_covisibility_degree_rows: nbr_ptr [n_cam + 1] (the scanned degrees; nbr_ptr[n_cam] = n_edges) and counts [2] (device int64:
+ *   n_edges, then the cameras that took the heavy path).  The caller reads counts[0] and allocates nbr and shared.
+ * c2b_covisibility_fill_rows: nbr and shared [n_edges] for the nbr_ptr, temp and min_shared of the degree pass.
+ *   Both: n_obs = 0 or n_cam = 0 gives an all-zero nbr_ptr and launches nothing else.  min_shared < 1, n_cam >= 2^31,
+ *   n_obs > 2^31 - 65, a NULL or misaligned pointer: C2B_ERR_INVALID_ARGUMENT before any device work.
+ * c2b_covisibility_expand_rows: one level of a breadth-first search.  level [n_cam] (int32, -1 = not reached); frontier
+ *   [n_frontier] = cameras of level hop.  Every neighbour q of a frontier camera with level[q] < 0, shared >= min_shared (applied
+ *   to the stored counts, so a graph built at a lower threshold serves) and within[q] != 0 (within: one byte per camera, or NULL)
+ *   gets level hop + 1; next [n_cam] takes the cameras of level hop + 1 in ascending index and *n_next (device uint32) their
+ *   number.  Refusals as above.
+ * Level 1, synchronous, on the resident problem; a shard is refused:
+ * c2b_problem_covisibility: builds the graph at min_shared and keeps it in the handle with its threshold; a call with the
+ *   threshold it holds returns at once, another threshold rebuilds.  It is derived from the list: whatever drops the transpose
+ *   (the table under c2b_problem in capi_problem.hpp) drops it; apply_step, the arithmetic noise and the refine passes keep it.
+ *   *n_edges (may be NULL) = the directed entries.
+ * c2b_problem_get_covisibility: the graph the handle holds to host buffers nbr_ptr [n_cam + 1], nbr, shared [n_edges]; its
+ *   threshold and the number of cameras that took the heavy path; any pointer may be NULL.  No graph: C2B_ERR_INVALID_ARGUMENT.
+ * c2b_problem_neighbourhood: seed (host, one byte per camera; an empty set is refused, as c2b_problem_window refuses it), within
+ *   (host, one byte per camera, or NULL; a seed outside it is refused).  Level 0 is the seeds; level h + 1 is every camera not
+ *   reached yet, inside `within`, with an edge of the graph at min_shared to a camera of level h; at most `hops` levels beyond
+ *   the seeds (hops = 0 returns the seeds, hops < 0: until nothing new is reached -- the seeds' connected components).
+ *   max_cameras <= 0: no cap.  With a cap (fewer than the seeds: refused) whole levels are taken while they fit; the first level
+ *   that does not fit is ranked by (score descending, index ascending), score = the sum of shared over the candidate's edges
+ *   into the levels already taken, saturating at 2^32 - 1, its best fill the remainder (c2b_select_smallest_keys_rows' radix
+ *   select), and the search ends.  member [n_cam] (host bytes), level [n_cam] (host int32, -1 = not reached), *n = the members;
+ *   each may be NULL.  Nothing is written on a refusal. */
+#define C2B_COVIS_WAVE_SLOTS 2048
+#define C2B_COVIS_TEMP_GRAPH 0
+#define C2B_COVIS_TEMP_EXPAND 1
+int64_t c2b_covisibility_temp_bytes(int64_t n_cam, int pass);
+int c2b_covisibility_degree_rows(const uint64_t *row_ptr, const uint32_t *pt_idx, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                                 const uint32_t *cam_of, int64_t n_cam, int64_t n_pts, int64_t n_obs, int min_shared, void *temp,
+                                 uint64_t *nbr_ptr, int64_t *counts, void *stream);
+int c2b_covisibility_fill_rows(const uint64_t *row_ptr, const uint32_t *pt_idx, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                               const uint32_t *cam_of, int64_t n_cam, int64_t n_pts, int64_t n_obs, int min_shared, void *temp,
+                               const uint64_t *nbr_ptr, uint32_t *nbr, uint32_t *shared, void *stream);
+int c2b_covisibility_expand_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, const uint32_t *shared, int64_t n_cam, int min_shared,
+                                 const uint8_t *within, const uint32_t *frontier, int64_t n_frontier, int hop, int32_t *level, uint32_t *next,
+                                 uint32_t *n_next, void *temp, void *stream);
+int c2b_problem_covisibility(c2b_problem *p, int min_shared, int64_t *n_edges);
+int c2b_problem_get_covisibility(c2b_problem *p, uint64_t *nbr_ptr, uint32_t *nbr, uint32_t *shared, int *min_shared, int64_t *n_heavy);
+int c2b_problem_neighbourhood(c2b_problem *p, const uint8_t *seed, int hops, int min_shared, int64_t max_cameras, const uint8_t *within,
+                              uint8_t *member, int32_t *level, int64_t *n);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
