@@ -89,6 +89,32 @@ class LmSummary(C.Structure):
                 ("lambda_next", C.c_double)]
 
 
+class Similarity(C.Structure):
+    """c2b_similarity (include/city2ba_hip_experimental.h): y = scale * rotation x + translation, rotation row-major"""
+    _fields_ = [("scale", C.c_double), ("rotation", C.c_double * 9), ("translation", C.c_double * 3)]
+
+
+class AlignOptions(C.Structure):
+    """c2b_align_options"""
+    _fields_ = [("on", C.c_int32), ("scale", C.c_int32), ("rounds", C.c_int32), ("reserved", C.c_int32), ("max_dist", C.c_double),
+                ("use_cam", C.c_void_p), ("use_pt", C.c_void_p)]
+
+
+class AlignStat(C.Structure):
+    """c2b_align_stat"""
+    _fields_ = [("n", C.c_int64), ("argmax", C.c_int64), ("sum_sq", C.c_double), ("sum", C.c_double), ("max", C.c_double)]
+
+
+class AlignSummary(C.Structure):
+    """c2b_align_summary"""
+    _fields_ = [("status", C.c_int32), ("rounds", C.c_int32), ("cameras", AlignStat), ("camera_rotations", AlignStat), ("points", AlignStat)]
+
+
+# c2b_align_options.on (C2B_ALIGN_CAMERAS / _POINTS / _BOTH) and c2b_align_summary.status (C2B_ALIGN_OK / _TOO_FEW / _DEGENERATE)
+ALIGN_ON = {"cameras": 1, "points": 2, "both": 3}
+ALIGN_OK, ALIGN_TOO_FEW, ALIGN_DEGENERATE = range(3)
+ALIGN_STATUS = ("ok", "too_few", "degenerate")
+
 # c2b_lm_summary.termination
 LM_TERMINATIONS = {0: "max_iterations", 1: "function_tolerance", 2: "gradient_tolerance", 3: "parameter_tolerance", 4: "not_finite"}
 
@@ -380,6 +406,17 @@ SIGNATURES = {
     "c2b_problem_add_noise": (_int, [_vp, _d, _d, _d, _d, _u64]),
     "c2b_problem_add_sin_noise": (_int, [_vp, _vp, _vp, _d, _d]),
     "c2b_problem_set_shard": (_int, [_vp, _i64, _i64, _i64]),
+    "c2b_align_options_init": (None, [_vp]),
+    "c2b_similarity_from_moments": (_int, [_i64, _vp, _vp, _d, _d, _vp, _int, _vp, C.POINTER(_int)]),
+    "c2b_align_finish_moments": (_int, [_vp, _vp, C.POINTER(_d), _vp, _vp, C.POINTER(_d), C.POINTER(_d), _vp]),
+    "c2b_align_launch_shape": (_int, [C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
+    "c2b_align_means_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "c2b_align_moments_rows": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "c2b_align_errors_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_align_rotation_errors_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_similarity_apply": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "c2b_problem_align": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_problem_transform": (_int, [_vp, _vp]),
     "c2b_problem_stats_sharded": (_int, [_vp, _vp, _vp]),
     "c2b_problem_add_drift_sharded": (_int, [_vp, _vp, _d, _d, _d, _vp, _u64]),
     "c2b_problem_add_noise_sharded": (_int, [_vp, _vp, _d, _d, _d, _d, _u64]),
@@ -444,6 +481,45 @@ def lib():
 def check(status):
     if status != OK:
         raise City2baError(status, lib().c2b_last_error().decode("utf-8", "replace"))
+
+
+def similarity(scale, rotation, translation):
+    """a c2b_similarity from a scale, a [3, 3] rotation and a [3] translation"""
+    import numpy as np
+    T = Similarity()
+    T.scale = float(scale)
+    T.rotation[:] = [float(v) for v in np.asarray(rotation, dtype=np.float64).reshape(9)]
+    T.translation[:] = [float(v) for v in np.asarray(translation, dtype=np.float64).reshape(3)]
+    return T
+
+
+def similarity_from_moments(n, mean_x, mean_y, var_x, var_y, cov, scale=True):
+    """c2b_similarity_from_moments (host arithmetic, no device): Umeyama's closed form from the centred moments.
+    Returns (status, scale, rotation [3, 3], translation [3]); on a failure the identity."""
+    import numpy as np
+    mx, my, cv = (np.ascontiguousarray(a, dtype=np.float64).reshape(k) for a, k in ((mean_x, 3), (mean_y, 3), (cov, 9)))
+    T, st = Similarity(), _int(-1)
+    check(lib().c2b_similarity_from_moments(int(n), mx.ctypes.data_as(_vp), my.ctypes.data_as(_vp), float(var_x), float(var_y),
+                                            cv.ctypes.data_as(_vp), int(bool(scale)), C.byref(T), C.byref(st)))
+    return st.value, T.scale, np.array(T.rotation[:]).reshape(3, 3), np.array(T.translation[:])
+
+
+def align_finish_moments(means7, moments23):
+    """c2b_align_finish_moments (host arithmetic): what the two device passes leave -> dict(n, mean_x, mean_y, var_x, var_y, cov [3, 3])"""
+    import numpy as np
+    a, b = np.ascontiguousarray(means7, dtype=np.float64).reshape(7), np.ascontiguousarray(moments23, dtype=np.float64).reshape(23)
+    n, vx, vy = _d(), _d(), _d()
+    mx, my, cov = np.empty(3), np.empty(3), np.empty(9)
+    check(lib().c2b_align_finish_moments(a.ctypes.data_as(_vp), b.ctypes.data_as(_vp), C.byref(n), mx.ctypes.data_as(_vp), my.ctypes.data_as(_vp),
+                                         C.byref(vx), C.byref(vy), cov.ctypes.data_as(_vp)))
+    return dict(n=n.value, mean_x=mx, mean_y=my, var_x=vx.value, var_y=vy.value, cov=cov.reshape(3, 3))
+
+
+def align_launch_shape():
+    """(threads per workgroup, most workgroups, entities per thread and trip) of the alignment passes"""
+    a, b, c = _int(), _int(), _int()
+    check(lib().c2b_align_launch_shape(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
 
 
 def device_count():

@@ -927,6 +927,62 @@ class BAProblem:
         L.check(L.lib().c2b_problem_write_back(self._h, parent._h, C.byref(a), C.byref(b)))
         return dict(cameras=a.value, points=b.value)
 
+    # ---- against ground truth: similarity alignment ---------------------------------
+    def align(self, ref, on="cameras", scale=True, use_cameras=None, use_points=None, max_dist=None, rounds=5, return_errors=False,
+              return_inliers=False):
+        """c2b_problem_align: the similarity (s, R, t) that takes this problem onto `ref` (same counts, index i of one corresponds to
+        index i of the other) in the least-squares sense, Umeyama's closed form over the camera centres, the points or both
+        (`on`), and the errors that remain.  use_cameras / use_points: byte masks, None = all on.  max_dist: after a fit only the
+        correspondences within it stay on and the fit is repeated, until the set repeats or after `rounds` re-fits -- trimming from
+        the least-squares start, not a consensus search: gross outliers can empty the set, which is reported (status "too_few").
+        Neither problem is modified.  Returns dict(status, scale, rotation [3, 3], translation [3], rounds, cameras=dict(n, rmse, mean,
+        max, argmax, rot_rmse_deg, rot_mean_deg, rot_max_deg, rot_argmax), points=dict(n, rmse, mean, max, argmax)); with return_errors
+        also camera_errors, camera_rotation_errors (radians), point_errors (every entity, masked off or not); with return_inliers
+        camera_inliers, point_inliers.  A first fit that fails ("too_few", "degenerate") returns the identity and empty summaries."""
+        if on not in L.ALIGN_ON:
+            raise ValueError("on must be 'cameras', 'points' or 'both', not %r" % (on,))
+        nc, np_, _ = self._sizes()
+        o = L.AlignOptions()
+        L.lib().c2b_align_options_init(C.byref(o))
+        o.on, o.scale, o.rounds = L.ALIGN_ON[on], int(bool(scale)), int(rounds) if max_dist is not None else 0
+        o.max_dist = float(max_dist) if max_dist is not None else 0.0
+        masks = []
+        for name, m, n in (("use_cam", use_cameras, nc), ("use_pt", use_points, np_)):
+            if m is not None:
+                m = np.ascontiguousarray(np.asarray(m) != 0, dtype=np.uint8)
+                if m.shape != (n,):
+                    raise L.City2baError(L.ERR_INVALID_ARGUMENT, "align: a mask must have one entry per entity")
+                masks.append(m)
+                setattr(o, name, m.ctypes.data)
+        T, S = L.Similarity(), L.AlignSummary()
+        ce, re_, pe = (np.zeros(n) if return_errors else None for n in (nc, nc, np_))
+        ci, pi = (np.zeros(n, dtype=np.uint8) if return_inliers else None for n in (nc, np_))
+        L.check(L.lib().c2b_problem_align(self._h, ref._h, C.byref(o), C.byref(T), C.byref(S), _ptr(ce), _ptr(re_), _ptr(pe), _ptr(ci), _ptr(pi)))
+
+        def stat(s, scale_=1.0):
+            n = s.n
+            return dict(n=n, rmse=scale_ * float(np.sqrt(s.sum_sq / n)) if n else 0.0, mean=scale_ * s.sum / n if n else 0.0,
+                        max=scale_ * s.max if n else 0.0, argmax=s.argmax)
+        cams, rot = stat(S.cameras), stat(S.camera_rotations, 180.0 / np.pi)
+        cams.update(rot_rmse_deg=rot["rmse"], rot_mean_deg=rot["mean"], rot_max_deg=rot["max"], rot_argmax=rot["argmax"])
+        out = dict(status=L.ALIGN_STATUS[S.status], scale=T.scale, rotation=np.array(T.rotation[:]).reshape(3, 3),
+                   translation=np.array(T.translation[:]), rounds=S.rounds, cameras=cams, points=stat(S.points))
+        if return_errors:
+            out.update(camera_errors=ce, camera_rotation_errors=re_, point_errors=pe)
+        if return_inliers:
+            out.update(camera_inliers=ci, point_inliers=pi)
+        return out
+
+    def transform(self, scale, rotation, translation):
+        """c2b_problem_transform: the whole problem moved by a similarity, in place: every point X <- s R X + t, every camera the
+        rotation R_c R^T and the centre s R c + t; intrinsics stay, and so does every projection.  The problem is in state mode
+        afterwards; rows, transpose, solve buffers, covisibility graph, masks, loss and a checkpoint stay.  Priors hold positions
+        in the OLD frame and are left as they are: set them again after a transform.  Refused: a non-finite entry, scale <= 0, a
+        rotation that is not orthonormal to 1e-9 or has det < 0."""
+        T = L.similarity(scale, rotation, translation)
+        L.check(L.lib().c2b_problem_transform(self._h, C.byref(T)))
+        return self
+
     def _refresh_graph(self):
         """host mirrors of the graph (row_ptr, pt_idx) after a device-side change"""
         n_cam, _, n_obs = self._sizes()

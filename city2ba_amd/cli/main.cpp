@@ -32,6 +32,9 @@
 //                         with --window-around: the covisibility neighbourhood of the cameras given, c2b_problem_neighbourhood)
 //   city2ba covisibility IN [--min-shared K]   (one line: cameras, undirected edges, maximum degree, isolated cameras of the
 //                         camera covisibility graph, c2b_problem_covisibility)
+//   city2ba compare EST REF [--on cameras|points|both] [--no-scale] [--max-dist D [--rounds N]] [--apply OUT]
+//                        (one JSON line: the similarity that takes EST onto REF, the status and the camera and point errors that
+//                         remain, c2b_problem_align; --apply: EST moved into REF's frame, c2b_problem_transform)
 //   city2ba triangulate IN OUT [--min-angle DEG] [--max-error X [--min-inliers N] [--max-hypotheses H] [--drop-outliers]]
 //                        (extension: the points from the cameras and observations, c2b_problem_triangulate_points; with
 //                         --max-error: from the rays that agree with each other, c2b_problem_triangulate_consensus)
@@ -1178,6 +1181,57 @@ int run_covisibility(int argc, char **argv) {
     return 0;
 }
 
+// `compare EST REF`: how close EST came to REF -- the same cameras and points under the same indices -- after the best similarity
+// between their frames (c2b_problem_align): ONE JSON line with the transform, the status and the two summaries.
+// --apply OUT writes EST moved into REF's frame.  Every argument is parsed before the device is touched.  (Priors are a handle's
+// state and no file carries them, so there is none here for the transform to leave behind.)
+int run_compare(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {"no-scale"}, {"on", "max-dist", "rounds", "apply", "device"});
+    if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <EST> <REF>");
+    const std::string on = a.has("on") ? a.opt.at("on") : "cameras";
+    if (on != "cameras" && on != "points" && on != "both") die("Invalid value for '--on <KIND>': expected cameras, points or both");
+    const double max_dist = a.f("max-dist", 0.0);
+    if (a.has("max-dist") && !(max_dist > 0.0 && std::isfinite(max_dist))) die("Invalid value for '--max-dist <D>': expected a finite number > 0");
+    const int64_t rounds = a.i("rounds", 5);
+    if (rounds < 1 || rounds > 2147483647) die("Invalid value for '--rounds <N>': expected an integer >= 1");
+    if (a.has("rounds") && !a.has("max-dist")) die("--rounds needs --max-dist <D>");
+    PhaseTimer timer;
+    const int device = (int)a.i("device", 0);
+    c2b_problem *est = read_problem(timer, device, a.positional[0]), *ref = read_problem(timer, device, a.positional[1]);
+    c2b_align_options o;
+    c2b_align_options_init(&o);
+    o.on = on == "cameras" ? C2B_ALIGN_CAMERAS : (on == "points" ? C2B_ALIGN_POINTS : C2B_ALIGN_BOTH);
+    o.scale = a.has("no-scale") ? 0 : 1;
+    o.max_dist = max_dist;
+    o.rounds = a.has("max-dist") ? (int)rounds : 0;
+    c2b_similarity T;
+    c2b_align_summary S;
+    ck(c2b_problem_align(est, ref, &o, &T, &S, nullptr, nullptr, nullptr, nullptr, nullptr));
+    timer.mark("align (device)");
+    static const char *const status[] = {"ok", "too_few", "degenerate"};
+    auto stat = [](const c2b_align_stat &s, double unit) {
+        char buf[256];
+        const double n = (double)s.n;
+        std::snprintf(buf, sizeof buf, "{\"n\": %lld, \"rmse\": %.17g, \"mean\": %.17g, \"max\": %.17g, \"argmax\": %lld}", (long long)s.n,
+                      s.n ? unit * std::sqrt(s.sum_sq / n) : 0.0, s.n ? unit * s.sum / n : 0.0, s.n ? unit * s.max : 0.0, (long long)s.argmax);
+        return std::string(buf);
+    };
+    std::printf("{\"status\": \"%s\", \"rounds\": %d, \"scale\": %.17g, \"rotation\": [[%.17g, %.17g, %.17g], [%.17g, %.17g, %.17g], [%.17g, %.17g, %.17g]], "
+                "\"translation\": [%.17g, %.17g, %.17g], \"cameras\": %s, \"camera_rotations_deg\": %s, \"points\": %s}\n",
+                status[S.status], S.rounds, T.scale, T.rotation[0], T.rotation[1], T.rotation[2], T.rotation[3], T.rotation[4], T.rotation[5], T.rotation[6],
+                T.rotation[7], T.rotation[8], T.translation[0], T.translation[1], T.translation[2], stat(S.cameras, 1.0).c_str(),
+                stat(S.camera_rotations, 180.0 / 3.14159265358979323846).c_str(), stat(S.points, 1.0).c_str());
+    c2b_problem_destroy(ref);
+    if (a.has("apply")) {
+        ck(c2b_problem_transform(est, &T));
+        timer.mark("transform (device)");
+        close_problem(timer, est, a.opt.at("apply"));
+    } else {
+        c2b_problem_destroy(est);
+    }
+    return 0;
+}
+
 // The consensus flags `triangulate` and `resect` share, parsed and cross-checked: --min-inliers is at least `least`, `dflt`
 // when absent.
 struct Consensus { bool on, drop_outliers; double max_error; int min_inliers, max_hypotheses; };
@@ -1379,6 +1433,7 @@ void usage() {
                 "    ply               Convert a .bal or .bbal to a .ply for visualization.\n"
                 "    solve             Bundle-adjust a .bal or .bbal by Levenberg-Marquardt on the device.\n"
                 "    covisibility      Print the figures of the camera covisibility graph of a .bal or .bbal.\n"
+                "    compare           Align a .bal or .bbal to its ground truth by a similarity and print the errors that remain.\n"
                 "    triangulate       Set the points of a .bal or .bbal from its cameras and observations.\n"
                 "    resect            Set the camera poses of a .bal or .bbal from its points and observations.\n"
                 "    merge             Merge the duplicate landmarks of a .bal or .bbal (the repair of noise --split-landmarks).\n"
@@ -1424,6 +1479,16 @@ const char *subcommand_help(const std::string &sub) {
         return "city2ba covisibility <FILE>\n"
                "    --min-shared <K> [1]      an edge joins two cameras that observe at least K points in common\n"
                "    prints the cameras, the edges, the maximum degree and the isolated cameras of that graph, built on the device\n";
+    if (sub == "compare")
+        return "city2ba compare <EST> <REF>\n"
+               "    --on <cameras|points|both> [cameras]   what the similarity is fitted to: camera centres, points, or both pooled\n"
+               "    --no-scale                the scale is held at 1\n"
+               "    --max-dist <D>            trimming: after a fit only correspondences within D (in REF's frame) stay, and the fit is repeated\n"
+               "    --rounds <N> [5]          ... at most N times (needs --max-dist); trimming starts from the least-squares fit, it is no\n"
+               "                              consensus search: gross outliers can empty the set (status too_few)\n"
+               "    --apply <OUT>             write EST moved into REF's frame\n"
+               "    prints one JSON line: status, rounds, scale, rotation (row-major), translation, and per kind n, rmse, mean, max, argmax\n"
+               "    (cameras: centre distance; camera_rotations_deg: angle to REF's rotation; points: distance), after the alignment\n";
     if (sub == "solve")
         return "city2ba solve <FILE> <OUT>\n"
                "    --iterations <N> [10]     --lambda <X> [1e-4]        Levenberg-Marquardt iterations, initial damping\n"
@@ -1524,6 +1589,7 @@ int main(int argc, char **argv) {
     if (sub == "ply") return run_ply(argc, argv);
     if (sub == "solve") return run_solve(argc, argv);
     if (sub == "covisibility") return run_covisibility(argc, argv);
+    if (sub == "compare") return run_compare(argc, argv);
     if (sub == "triangulate") return run_triangulate(argc, argv);
     if (sub == "resect") return run_resect(argc, argv);
     if (sub == "merge") return run_merge(argc, argv);

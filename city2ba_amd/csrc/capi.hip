@@ -5,6 +5,7 @@
 //   capi_problem.hpp   Level 1: a BAProblem resident on one device (host buffers in / out, synchronous), *_sharded forms;
 //                      it includes capi_solve.hpp (constant parameters ... Levenberg-Marquardt), capi_graph.hpp (cull, adopt,
 //                      filter, visibility, generate_world_points) and capi_files.hpp (.bal / .bbal) where their text sat
+//   capi_align.hpp     similarity alignment against ground truth: host arithmetic, Level 0 and Level 1
 #include "../../include/city2ba_hip.h"
 #include "../../include/city2ba_hip_host.h"
 #include "../../include/city2ba_hip_experimental.h"
@@ -33,6 +34,7 @@
 #include "host_generate.hpp"
 #include "host_noise.hpp"
 #include "host_synthetic.hpp"
+#include "host_align.hpp"
 #include "kernels.hpp"
 #include "normal_kernels.hpp"
 #include "schur_kernels.hpp"
@@ -50,6 +52,7 @@
 #include "index_noise_kernels.hpp"
 #include "subset_kernels.hpp"
 #include "covis_kernels.hpp"
+#include "align_kernels.hpp"
 #include "text_kernels.hpp"
 #include "comm_rccl.hpp"
 
@@ -395,6 +398,16 @@ int stats_impl(const Src &src, int64_t n, void *workspace, double *stats, hipStr
     return C2B_OK;
 }
 
+// the per-entity errors of an alignment and their summary (align_kernels.hpp), position or rotation by the functor
+template <typename Err>
+int align_errors_launch(const Err &f, int64_t n, const uint8_t *base, const uint8_t *use, double max_dist, double *err, uint8_t *next,
+                               void *workspace, double *summary7, hipStream_t st) {
+    hipLaunchKernelGGL((k_align_errors<Err>), dim3(stats_grid(n, kAlignBlock, kAlignGrid)), dim3(kAlignBlock), 0, st, f, n, base, use, max_dist, err, next,
+                       reinterpret_cast<double *>(workspace), ws_ticket(workspace), summary7);
+    LAUNCH_CHECK();
+    return C2B_OK;
+}
+
 template <typename T>
 int drift_impl(const char *who, T *cam15, int64_t n_cam, T *pts4, int64_t n_pts, const double *origin,
                const double *stats_norm, double strength, double angle_strength, double std, double dx, double dy,
@@ -501,5 +514,6 @@ int64_t c2b_workspace_bytes(int64_t n_obs) {
 #include "capi_level0.hpp"
 #include "capi_host_rows.hpp"
 #include "capi_problem.hpp"
+#include "capi_align.hpp"
 
 }  // extern "C"

@@ -107,6 +107,7 @@ struct c2b_problem {
 //   generate_world_points      -            -          X     X          X      X             X           X
 //   apply_step, rollback (5)   X            truth      -     -          -      -             -           -
 //   noise (drift, noise, sin)  X            X          -     -          -      -             -           -
+//   transform (14)             X            X          -     -          -      -             -           -
 //   triangulate_points         -            -          -     -          -      -             -           -
 //   refine_points              -            -          -     -          -      -             -           -
 //   triangulate_consensus (6)  -            -          - / X - / X      - / X  -             -           -
@@ -135,7 +136,8 @@ struct c2b_problem {
 // origin (above) is recorded by a window, and by a carrying subset of repeat-free lists.  (11) a state-mode child gets to_vec of
 // its cameras and is in bal mode afterwards; a child in bal mode is only read.  (12) add_incorrect_correspondences, join_landmarks
 // (DESIGN 4.18): after a call that changed a label, as the filter.  (13) the point count grows: cull's policy; a call that selects
-// no point drops nothing.
+// no point drops nothing.  (14) c2b_problem_transform (capi_align.hpp): a similarity of the whole problem, the noise row; the
+// priors hold positions in the old frame and are left as they are.  c2b_problem_align writes neither problem (it may build camblk / cen4).
 // An X in the masks column is also where the handle's entity_epoch is raised and its origin dropped (entities_replaced).
 // the cameras moved: every cache of them (apply_step / rollback then make bal9 the truth)
 static void cameras_mutated(c2b_problem *p) { p->bal_valid = false; p->blk_valid = false; p->bal9_fresh = false; }

@@ -799,6 +799,61 @@ def stats(camblk, pts4, ws, out=None, centers=None):
     return out
 
 
+# ---- similarity alignment, Level 0: x = the estimate's tables, y = the reference's, 32-byte rows [n, 4] ----
+def _align_tables(x, y, use, kind):
+    if x is None:
+        return None, None, None, 0
+    for t in (x, y):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 4 and t.shape == x.shape, kind
+    if use is not None:
+        assert use.is_cuda and use.is_contiguous() and use.dtype == torch.uint8 and use.shape[0] == x.shape[0], kind + " mask"
+    return _p(x), _p(y), _p(use), x.shape[0]
+
+
+def align_means_rows(ws, x_cam=None, y_cam=None, use_cam=None, x_pts=None, y_pts=None, use_pt=None, out=None):
+    """c2b_align_means_rows: out [7] = count, sum x, sum y over the on-correspondences of the pooled tables (a kind may be None)"""
+    xc, yc, uc, nc = _align_tables(x_cam, y_cam, use_cam, "cameras")
+    xp, yp, up, np_ = _align_tables(x_pts, y_pts, use_pt, "points")
+    out = out if out is not None else torch.empty(7, dtype=torch.float64, device=ws.device)
+    L.check(L.lib().c2b_align_means_rows(xc, yc, uc, nc, xp, yp, up, np_, _p(ws), _p(out), _stream()))
+    return out
+
+
+def align_moments_rows(ws, means, x_cam=None, y_cam=None, use_cam=None, x_pts=None, y_pts=None, use_pt=None, out=None):
+    """c2b_align_moments_rows: out [23] = the eleven moments about the pivot means[1:] / means[0], the six residual sums, the pivot
+    (L.align_finish_moments moves them onto the mean)"""
+    xc, yc, uc, nc = _align_tables(x_cam, y_cam, use_cam, "cameras")
+    xp, yp, up, np_ = _align_tables(x_pts, y_pts, use_pt, "points")
+    out = out if out is not None else torch.empty(23, dtype=torch.float64, device=ws.device)
+    L.check(L.lib().c2b_align_moments_rows(xc, yc, uc, nc, xp, yp, up, np_, _p(means), _p(ws), _p(out), _stream()))
+    return out
+
+
+def align_errors_rows(ws, x, y, sim, base=None, use=None, max_dist=0.0, err=None, next_=None, out=None):
+    """c2b_align_errors_rows: err [n] = |s R x + t - y| (may be None), next_ [n] = base && err <= max_dist (may be None),
+    out [7] = count, sum e^2, sum e, max, argmax over `use`, bytes of next_ that differ from use, size of next_.  sim = L.similarity(...)"""
+    px, py, _, n = _align_tables(x, y, None, "tables")
+    out = out if out is not None else torch.empty(7, dtype=torch.float64, device=ws.device)
+    L.check(L.lib().c2b_align_errors_rows(px, py, n, C.byref(sim), _p(base), _p(use), float(max_dist), _p(err), _p(next_), _p(ws), _p(out), _stream()))
+    return out
+
+
+def align_rotation_errors_rows(ws, x_cam15, y_cam15, sim, use=None, err=None, out=None):
+    """c2b_align_rotation_errors_rows: err [n] = the angle between R_c R^T and the reference's R_c, out [7] as align_errors_rows"""
+    _chk(x_cam15, torch.float64, "x_cam15")
+    _chk(y_cam15, torch.float64, "y_cam15")
+    assert x_cam15.shape == y_cam15.shape and x_cam15.shape[1] == 15
+    out = out if out is not None else torch.empty(7, dtype=torch.float64, device=ws.device)
+    L.check(L.lib().c2b_align_rotation_errors_rows(_p(x_cam15), _p(y_cam15), x_cam15.shape[0], C.byref(sim), _p(use), _p(err), _p(ws), _p(out), _stream()))
+    return out
+
+
+def similarity_apply(cam15, pts4, sim):
+    """c2b_similarity_apply: cam15 [n, 15] and pts4 [n, 4] moved in place (either may be None)"""
+    L.check(L.lib().c2b_similarity_apply(_p(cam15), cam15.shape[0] if cam15 is not None else 0, _p(pts4), pts4.shape[0] if pts4 is not None else 0,
+                                         C.byref(sim), _stream()))
+
+
 def stats_partial_pass1(camblk, cam_base, n_cam_global, pts4_slice, pt_base, n_entities_global, ws, part=None, centers=None):
     """this shard's share of the statistics (c2b_stats_partial_pass1); pts4_slice = the rows of the point table this
     rank reduces"""

@@ -277,3 +277,11 @@ def solve_windows(ba, size, stride=None, sweeps=1, halo=True, by="index", min_sh
             if hi == n_cam:
                 break
     return out
+
+
+def compare(ba, ref, **align):
+    """How close ba came to the truth `ref` (same counts, corresponding indices): ba.align(ref, **align) -- the best similarity
+    between the two frames, which the seven gauge freedoms leave open, and the camera and point errors that remain after it.
+    Both problems are left untouched.  The keywords are BAProblem.align's (on, scale, use_cameras, use_points, max_dist, rounds,
+    return_errors, return_inliers); returns its dict."""
+    return ba.align(ref, **align)

@@ -906,6 +906,98 @@ int c2b_problem_get_covisibility(c2b_problem *p, uint64_t *nbr_ptr, uint32_t *nb
 int c2b_problem_neighbourhood(c2b_problem *p, const uint8_t *seed, int hops, int min_shared, int64_t max_cameras, const uint8_t *within,
                               uint8_t *member, int32_t *level, int64_t *n);
 
+/* ---- a problem compared against ground truth: similarity alignment on the device ----
+ * Build-defined (the reference has nothing like it).  Two problems on one device, the estimate p and the reference ref, with equal
+ * n_cam and n_pts; index i of one corresponds to index i of the other.
+ * 1. Correspondences.  `on` is C2B_ALIGN_CAMERAS, C2B_ALIGN_POINTS or both OR-ed.  A camera contributes its centre, a point its
+ *    position: x_i from p, y_i from ref.  Optional byte masks use_cam [n_cam], use_pt [n_pts] switch correspondences off (NULL: all
+ *    on).  With both kinds the two sets are pooled and every correspondence has weight 1.
+ * 2. Fit.  (s, R, t) minimising sum |s R x_i + t - y_i|^2 in Umeyama's closed form: means mu_x, mu_y; var_x = sum |x - mu_x|^2 / n,
+ *    var_y, cov = sum (y - mu_y)(x - mu_x)^T / n; cov = U D V^T; R = U diag(1, 1, det(U V^T)) V^T; s = tr(D diag(1, 1, det(U V^T))) / var_x,
+ *    or 1 when `scale` is off; t = mu_y - s R mu_x.  The moments are centred: a first pass sums the coordinates, a second sums the
+ *    moments about the rounded mean together with the residual sums, and the host moves them onto the mean itself.  Raw sums
+ *    xx^T - n mu mu^T are never formed.
+ * 3. Status.  C2B_ALIGN_OK; C2B_ALIGN_TOO_FEW: fewer than 3 correspondences; C2B_ALIGN_DEGENERATE: var_x = 0, or the second singular
+ *    value of cov is at most 1e-12 times the first (collinear: the rotation is not determined).  On either failure of the FIRST fit the
+ *    transform returned is the identity and nothing else is written.  A planar cloud (rank 2) is not degenerate: the det correction
+ *    picks the proper rotation.
+ * 4. Errors after alignment.  Per camera e_c = |s R c + t - c_ref| and, with the aligned rotation R_c' = R_c R^T,
+ *    theta_c = 2 asin(min(1, |R_c' - R_c_ref|_F / (2 sqrt 2))) in radians (the chord keeps a small angle, which acos((tr - 1) / 2) does
+ *    not); per point e_p = |s R X + t - X_ref|.  Summaries per kind over the correspondences that are on: count, sum e^2, sum e, max and
+ *    the lowest index attaining it (-1 with nothing on); the rotation errors likewise, over the cameras that are on.  A masked-off
+ *    entity still gets its per-entity error; it is left out of the fit and the summaries only.  A kind that is not in `on` is
+ *    summarised over the caller's mask of that kind.
+ * 5. Trimming (max_dist > 0 and rounds >= 1; otherwise one fit).  After a fit a correspondence stays on only if it is on in the
+ *    caller's mask and its aligned distance, in the reference's frame, is <= max_dist; the fit is repeated on that set, until the set
+ *    repeats or after `rounds` re-fits.  A set below 3 (or a degenerate one) ends the loop with that status and the last good
+ *    transform; the inlier masks and the summaries are then those of the set that failed.  Otherwise the inlier masks are the set the
+ *    returned transform was fitted on, and the summaries run over it: a call with rounds = 0 and those masks as use_* returns the same
+ *    bits.  This is trimming from the least-squares start, NOT a consensus search: gross outliers pull the first fit away and can empty
+ *    the set, which is reported (TOO_FEW), not hidden.
+ * 6. c2b_problem_transform: every point X <- s R X + t; every camera gets the rotation R_c R^T and the centre s R c + t
+ *    (t_c <- -R_c' (s R c + t)); f, k1, k2 stay.  Projections are invariant (R_c' (X' - c') = s R_c (X - c), and the projection
+ *    divides by depth).  Caches as after the arithmetic noise: the camera table, the centre table and bal9 are dropped (the problem
+ *    is in state mode afterwards); rows, transpose, solve buffers, the covisibility graph, masks, loss, preconditioner and a
+ *    checkpoint stay.  Priors hold positions in the OLD frame and are left as they are: re-set them after a transform.
+ *    Refused: a non-finite entry, s <= 0, |R^T R - I|_F > 1e-9, det R < 0.
+ * 7. Deterministic: no float atomics; workgroup partials are folded in a fixed order; two calls give the same bits.
+ * c2b_similarity.rotation is row-major.  Host arithmetic (no device): c2b_similarity_from_moments (rule 2 and 3; var_y is not used by
+ *   the closed form and only has to be >= 0), c2b_align_finish_moments (means [7] and moments [23] as the two passes leave them ->
+ *   n, the means, var_x, var_y, cov), c2b_align_launch_shape (threads per workgroup, most workgroups, entities per thread and trip).
+ * Level 0, stateless, asynchronous on `stream`, device pointers; tables are 32-byte rows [n][4] (16-byte aligned), cam15 tables
+ *   [n][15]; a kind with a zero count may pass NULL tables; workspace as for c2b_stats (one launch at a time).  A NULL or misaligned
+ *   pointer or a negative count: C2B_ERR_INVALID_ARGUMENT before any device work.
+ *   _means_rows: means [7] = count, sum x, sum y.  _moments_rows: moments [23] = sum |x - m_x|^2, sum |y - m_y|^2, the nine of
+ *   sum (y - m_y)(x - m_x)^T row-major, sum (x - m_x), sum (y - m_y), and the pivot m_x, m_y = sums / count it read from `means`.
+ *   _errors_rows: err [n] (may be NULL); base / use (may be NULL: all on): the caller's mask and the set summarised; next (may be
+ *   NULL): base && e <= max_dist (max_dist <= 0: base), it must not be `use`; summary [7] = count, sum e^2, sum e, max, argmax, bytes of
+ *   next that differ from use, size of next.  _rotation_errors_rows: the same over two cam15 tables, the error being theta.
+ *   c2b_similarity_apply: cam15 and pts4 in place (either may be NULL with a zero count).
+ * Level 1, synchronous; neither problem is modified by c2b_problem_align (derived caches may be built).  use_cam / use_pt / the
+ *   outputs are host arrays, every output may be NULL: cam_err, cam_rot_err [n_cam], pt_err [n_pts], cam_inlier [n_cam], pt_inlier
+ *   [n_pts].  Both entries refuse a shard, different devices, different sizes, nothing uploaded: C2B_ERR_INVALID_ARGUMENT, nothing written. */
+#define C2B_ALIGN_CAMERAS 1
+#define C2B_ALIGN_POINTS 2
+#define C2B_ALIGN_BOTH 3
+#define C2B_ALIGN_OK 0
+#define C2B_ALIGN_TOO_FEW 1
+#define C2B_ALIGN_DEGENERATE 2
+typedef struct {
+    double scale, rotation[9], translation[3];
+} c2b_similarity;
+typedef struct {
+    int32_t on, scale, rounds, reserved;      /* C2B_ALIGN_*; 0 / 1; re-fits at most (0: one fit); 0 */
+    double max_dist;                          /* <= 0: no trimming */
+    const uint8_t *use_cam, *use_pt;          /* host, may be NULL */
+} c2b_align_options;
+typedef struct {
+    int64_t n, argmax;
+    double sum_sq, sum, max;
+} c2b_align_stat;
+typedef struct {
+    int32_t status, rounds;                   /* C2B_ALIGN_*; re-fits done */
+    c2b_align_stat cameras, camera_rotations, points;
+} c2b_align_summary;
+void c2b_align_options_init(c2b_align_options *opt);
+int c2b_similarity_from_moments(int64_t n, const double mean_x[3], const double mean_y[3], double var_x, double var_y, const double cov9[9],
+                                int scale, c2b_similarity *sim, int *status);
+int c2b_align_finish_moments(const double means7[7], const double moments23[23], double *n, double mean_x[3], double mean_y[3],
+                             double *var_x, double *var_y, double cov9[9]);
+int c2b_align_launch_shape(int *threads_per_workgroup, int *max_workgroups, int *entities_per_trip);
+int c2b_align_means_rows(const double *x_cam4, const double *y_cam4, const uint8_t *use_cam, int64_t n_cam, const double *x_pts4,
+                         const double *y_pts4, const uint8_t *use_pt, int64_t n_pts, void *workspace, double *means7, void *stream);
+int c2b_align_moments_rows(const double *x_cam4, const double *y_cam4, const uint8_t *use_cam, int64_t n_cam, const double *x_pts4,
+                           const double *y_pts4, const uint8_t *use_pt, int64_t n_pts, const double *means7, void *workspace,
+                           double *moments23, void *stream);
+int c2b_align_errors_rows(const double *x4, const double *y4, int64_t n, const c2b_similarity *sim, const uint8_t *base, const uint8_t *use,
+                          double max_dist, double *err, uint8_t *next, void *workspace, double *summary7, void *stream);
+int c2b_align_rotation_errors_rows(const double *x_cam15, const double *y_cam15, int64_t n, const c2b_similarity *sim, const uint8_t *use,
+                                   double *err, void *workspace, double *summary7, void *stream);
+int c2b_similarity_apply(double *cam15, int64_t n_cam, double *pts4, int64_t n_pts, const c2b_similarity *sim, void *stream);
+int c2b_problem_align(c2b_problem *p, c2b_problem *ref, const c2b_align_options *opt, c2b_similarity *sim, c2b_align_summary *summary,
+                      double *cam_err, double *cam_rot_err, double *pt_err, uint8_t *cam_inlier, uint8_t *pt_inlier);
+int c2b_problem_transform(c2b_problem *p, const c2b_similarity *sim);
+
 /* ---- f32 extension (BASELINE.json configs[4]).  The reference has NO f32 compute path:
  * these run the same kernels over a float state -- cam15 / pts4 stored as float -- with the draws and
  * the statistics kept in f64; results track the f64 path to f32 accuracy (tested at an f32 tolerance). */
