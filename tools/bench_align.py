@@ -7,14 +7,11 @@ a warm-up, with the spread (min .. max).  Prints one JSON line.
     python tools/bench_align.py [--blocks 128] [--repeats 20] [--out profiles/align_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-PEAK = 8.0e12
 
 
 def main():
@@ -27,6 +24,7 @@ def main():
     entry.build()
     import numpy as np
     import torch
+    import benchkit as B
     import city2ba_amd as c2b
     from city2ba_amd import _lib as L, device as D, noise as N
 
@@ -40,19 +38,13 @@ def main():
     N.add_noise(est, 1e-2, 1e-3, 1e-2, 0.0, seed=2)
     nc, np_, _ = truth._sizes()
 
-    def spread(v):
-        v = np.asarray(v) * 1e6
-        return dict(median_us=round(float(np.median(v)), 2), min_us=round(float(v.min()), 2), max_us=round(float(v.max()), 2))
+    def spread(us):
+        return dict(median_us=round(B.median(us), 2), min_us=round(min(us), 2), max_us=round(max(us), 2))
 
     def wall(fn):
         for _ in range(5):
             fn()
-        out = []
-        for _ in range(a.repeats):
-            t = time.perf_counter()
-            fn()
-            out.append(time.perf_counter() - t)
-        return spread(out)
+        return spread([B.wall_s(fn)[0] * 1e6 for _ in range(a.repeats)])
     c, s_ = np.cos(0.3), np.sin(0.3)
     Rb = np.array([[c, -s_, 0.0], [s_, c, 0.0], [0.0, 0.0, 1.0]])
     est.transform(1.5, Rb, [10.0, -5.0, 2.0])                  # another frame: what the alignment has to undo
@@ -89,29 +81,14 @@ def main():
     }
     timed = {}
     for name, (fn, nbytes) in passes.items():
-        for _ in range(5):
-            fn()
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ts.append(e0.elapsed_time(e1) * 1e-3)
-        timed[name] = dict(spread(ts), bytes=int(nbytes))
-        timed[name]["fraction_of_8TBs"] = round(nbytes / (timed[name]["median_us"] * 1e-6) / PEAK, 3)
+        timed[name] = dict(spread(B.each_us(fn, a.repeats, 5)), bytes=int(nbytes))
+        timed[name]["fraction_of_8TBs"] = round(B.frac_of_peak(nbytes, timed[name]["median_us"]), 3)
     for name in timed:
         timed[name]["ratio_to_stats"] = round(timed[name]["median_us"] / timed["stats"]["median_us"], 2)
     result = dict(bench="align", blocks=a.blocks, n_cam=nc, n_pts=np_, repeats=a.repeats, status=res["status"], scale=res["scale"],
                   camera_rmse=res["cameras"]["rmse"], point_rmse=res["points"]["rmse"], align_both_wall=t_align, align_both_trim3_wall=t_trim,
                   transform_wall=t_transform, passes=timed)
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -19,7 +19,6 @@ Prints one JSON line.
     python tools/bench_covisibility.py [--blocks 128] [--repeats 7] [--out profiles/covisibility_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -43,23 +42,16 @@ def main():
     import ctypes as C
     import numpy as np
     import torch
-    from city2ba_amd import _lib as L, device as D, synthetic as S
+    import benchkit                                          # (B is the incidence matrix of the host comparator here)
+    from city2ba_amd import _lib as L, device as D
     lib = L.lib()
     ms = a.min_shared
 
     def median_ms(samples):
-        return round(float(np.median(samples)), 4), [round(float(min(samples)), 4), round(float(max(samples)), 4)]
+        return round(benchkit.median(samples), 4), benchkit.spread(samples, 4)
 
     def wall(fn):
-        out = []
-        for k in range(a.repeats + 1):                        # the first call is the warm-up
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            if k:
-                out.append((time.perf_counter() - t0) * 1e3)
-        return median_ms(out)
+        return median_ms(benchkit.wall_ms(fn, a.repeats, 1))
 
     def figures(ba, with_host):
         n_cam, n_pts, n_obs = ba._sizes()
@@ -79,17 +71,16 @@ def main():
         both, spread = wall(build)
         rec["problem_covisibility_two_thresholds_ms"] = both
         rec["problem_covisibility_two_thresholds_spread_ms"] = spread
-        # the two passes alone, by events, on the exported list
-        ex = ba.export_device()
-        rows = D.Rows(ex["row_ptr"], n_obs=n_obs)
-        prows = D.PointRows(rows, ex["pt_idx"], n_pts)
-        dev = ex["row_ptr"].device
+        # the two passes alone, on the exported list, by three events in a chain: the fill pass follows the degree pass at once, as
+        # in the Level-1 call
+        lv = benchkit.level0(ba, point_rows=True)
+        rows, prows, dev = lv.rows, lv.prows, lv.pt_idx.device
         temp = D._covis_temp(n_cam, L.COVIS_TEMP_GRAPH, dev)
         d_ptr = torch.empty(n_cam + 1, dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
         d_nbr = torch.empty(max(len(nbr), 1), dtype=torch.int32, device=dev)
         d_shared = torch.empty(max(len(nbr), 1), dtype=torch.int32, device=dev)
-        args = (D._p(rows.row_ptr), D._p(ex["pt_idx"]), D._p(prows.pt_row_ptr), D._p(prows.obs_of), D._p(prows.cam_of), n_cam, n_pts, n_obs, ms, D._p(temp))
+        args = (D._p(rows.row_ptr), D._p(lv.pt_idx), D._p(prows.pt_row_ptr), D._p(prows.obs_of), D._p(prows.cam_of), n_cam, n_pts, n_obs, ms, D._p(temp))
         t_deg, t_fill = [], []
         for k in range(a.repeats + 1):
             e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -105,7 +96,7 @@ def main():
         assert int(counts[0].item()) == len(nbr) and np.array_equal(d_nbr.cpu().numpy()[:len(nbr)].view(np.uint32), nbr)
         rec["degree_pass_ms"], rec["degree_pass_spread_ms"] = median_ms(t_deg)
         rec["fill_pass_ms"], rec["fill_pass_spread_ms"] = median_ms(t_fill)
-        del ex, rows, prows, temp, d_ptr, d_nbr, d_shared
+        del lv, rows, prows, temp, d_ptr, d_nbr, d_shared
         if with_host:
             import scipy.sparse as sp
             t0 = time.perf_counter()
@@ -154,7 +145,7 @@ def main():
         return dict(windows=windows, child_cameras=int(cams), child_observations=int(obs), halo_ratio=round(cams / max(n_cam, 1), 3),
                     observation_ratio=round(obs / max(ba.num_observations(), 1), 3))
 
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    ba = benchkit.bench_grid(a.blocks)
     n_cam, n_pts, _ = ba._sizes()
     result = dict(bench="covisibility", blocks=a.blocks, repeats=a.repeats, grid=figures(ba, not a.no_host))
     perm = np.random.default_rng(a.seed).permutation(n_cam)
@@ -163,11 +154,7 @@ def main():
     result["permuted"] = figures(shuffled, False)
     result["permuted_sweep"] = dict(size=a.size, index=sweep(shuffled, "index"), covisibility=sweep(shuffled, "covisibility"))
     shuffled.close()
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    benchkit.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -7,10 +7,8 @@ the new list needs.  Both routes must leave the same lists.  Prints one JSON lin
     python tools/bench_filter.py [--blocks 128] [--repeats 3] [--out profiles/filter_observations_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,10 +25,11 @@ def main():
     import __graft_entry__ as entry
     entry.build()
     import numpy as np
+    import benchkit as B
     import city2ba_amd as c2b
-    from city2ba_amd import noise as N, synthetic as S
+    from city2ba_amd import noise as N
 
-    g = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    g = B.bench_grid(a.blocks)
     N.add_noise(g, 0.0, 0.0, 0.0, a.sigma, seed=3)
     bad = N.add_incorrect_correspondences(g, a.mismatch, seed=1)
     g.close()
@@ -43,11 +42,6 @@ def main():
         ba = c2b.BAProblem.from_visibility(*start, device=0)
         ba.solve_step(1e-2)                                  # the caches a filter has to drop exist
         return ba
-
-    def timed(fn):
-        t = time.perf_counter()
-        out = fn()
-        return time.perf_counter() - t, out
 
     def host_route(ba):
         proj, uv = ba.project().reshape(-1, 2), ba.observations().reshape(-1, 2)
@@ -65,26 +59,22 @@ def main():
     same, removed = True, 0
     for _ in range(a.repeats):
         ba = fresh()
-        dt, removed = timed(lambda: ba.filter_observations(max_error))
+        dt, removed = B.wall_s(lambda: ba.filter_observations(max_error))
         t["device"].append(dt)
-        t["step_after_device"].append(timed(lambda: ba.solve_step(1e-2))[0])
+        t["step_after_device"].append(B.wall_s(lambda: ba.solve_step(1e-2))[0])
         src = fresh()
-        dt, twin = timed(lambda: host_route(src))
+        dt, twin = B.wall_s(lambda: host_route(src))
         t["host"].append(dt)
-        t["step_after_host"].append(timed(lambda: twin.solve_step(1e-2))[0])
+        t["step_after_host"].append(B.wall_s(lambda: twin.solve_step(1e-2))[0])
         same = same and ba.row_ptr.tobytes() == twin.row_ptr.tobytes() and ba.pt_idx.tobytes() == twin.pt_idx.tobytes() and \
             ba.observations().tobytes() == twin.observations().tobytes()
         for p in (ba, src, twin):
             p.close()
-    med = {k: round(float(np.median(v)) * 1e3, 3) for k, v in t.items()}
+    med = {k: round(B.median(v) * 1e3, 3) for k, v in t.items()}
     result = dict(bench="filter_observations", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2], removed=int(removed),
                   max_error=max_error, filter_ms=dict(device=med["device"], host_round_trip=med["host"]),
                   step_after_ms=dict(device=med["step_after_device"], host_round_trip=med["step_after_host"]), same_lists=bool(same))
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,6 @@ The median over `--repeats` is reported.  Prints one JSON line.
     python tools/bench_index_noise.py [--blocks 128] [--repeats 3] [--seed 5] [--dir /tmp] [--out profiles/index_noise_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import re
 import subprocess
@@ -40,7 +39,7 @@ def main():
     entry.build()
     cli = entry.build_cli()
     import ctypes as C
-    import numpy as np
+    import benchkit as B
     import city2ba_amd as c2b
     from city2ba_amd import _lib as L, noise as N
 
@@ -62,23 +61,20 @@ def main():
         ba.total_reprojection_error(2.0)                         # the cameras' records and the row structure exist, as in a pipeline
         for k, (name, f, value) in enumerate(passes):
             n = C.c_int64()
-            t0 = time.perf_counter()
-            L.check(f(ba._h, value, a.seed + 2 + k, C.byref(n)))
-            t_dev[name].append((time.perf_counter() - t0) * 1e3)
+            t_dev[name].append(B.wall_s(lambda: L.check(f(ba._h, value, a.seed + 2 + k, C.byref(n))))[0] * 1e3)
             counts[name] = int(n.value)
         ba.close()
         ba = c2b.BAProblem.from_file(src)
         ba.total_reprojection_error(2.0)
         for k, (name, _, value) in enumerate(passes):
-            t0 = time.perf_counter()
-            nxt = getattr(N, name)(ba, value, seed=a.seed + 2 + k)
-            t_host[name].append((time.perf_counter() - t0) * 1e3)
+            dt, nxt = B.wall_s(lambda: getattr(N, name)(ba, value, seed=a.seed + 2 + k))
+            t_host[name].append(dt * 1e3)
             ba.close()
             ba = nxt
         ba.close()
 
     # ---- the command line, end to end -------------------------------------------------------------------------------------------
-    def run(route):
+    def run(route):                                              # (a child process from start to exit: no device work of this one to wait for)
         t0 = time.perf_counter()
         r = subprocess.run([cli, "noise", src, out] + CHAIN + ["--seed", str(a.seed), "--index-noise", route], capture_output=True, text=True,
                            timeout=1200, env=dict(os.environ, C2B_TIMING="1"))
@@ -96,20 +92,16 @@ def main():
             dt, phases[route], reports[route] = run(route)
             t_cli[route].append(dt)
 
-    med = lambda v: float(np.median(v))                          # noqa: E731
+    med = B.median
     result = dict(bench="index_noise", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2], repeats=a.repeats, seed=a.seed,
                   file_bytes=os.path.getsize(src), counts=counts,
                   pass_ms=dict(device={k: round(med(v), 2) for k, v in t_dev.items()}, host_route={k: round(med(v), 2) for k, v in t_host.items()}),
                   cli_chain=" ".join(CHAIN),
                   cli_s=dict(device=round(med(t_cli["device"]), 3), host=round(med(t_cli["host"]), 3)),
-                  cli_spread_s={k: [round(min(v), 3), round(max(v), 3)] for k, v in t_cli.items()},
+                  cli_spread_s={k: B.spread(v, 3) for k, v in t_cli.items()},
                   cli_phases_ms=phases, cli_report=reports,
                   device_route_is_faster=bool(med(t_cli["device"]) < med(t_cli["host"])))
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
     tmp.cleanup()
 
 

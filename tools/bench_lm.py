@@ -8,10 +8,8 @@ structure, the transpose and the solve buffers; the rollback keeps them).  Print
     python tools/bench_lm.py [--blocks 128] [--iterations 10] [--out profiles/lm_loop_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,11 +25,11 @@ def main():
     a = ap.parse_args()
     import __graft_entry__ as entry
     entry.build()
-    import numpy as np
+    import benchkit as B
     import city2ba_amd as c2b
-    from city2ba_amd import noise as N, solve, synthetic as S
+    from city2ba_amd import noise as N, solve
 
-    g = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    g = B.bench_grid(a.blocks)
     N.add_noise(g, 0.0, 0.0, 1e-2, 1e-3, seed=3)
     start = (g.cameras_bal(), g.points(), g.row_ptr.copy(), g.pt_idx.copy(), g.observations())
     sizes = g._sizes()
@@ -40,20 +38,15 @@ def main():
     def fresh():
         return c2b.BAProblem.from_bal(*start, device=0)
 
-    def timed(fn):
-        t = time.perf_counter()
-        out = fn()
-        return time.perf_counter() - t, out
-
     warm = fresh()                                           # the first solve of a process pays for the kernels' load
     solve.levenberg_marquardt_device(warm, 1, lam=a.lam)
     warm.close()
     ba = fresh()
-    t_py, hp = timed(lambda: solve.levenberg_marquardt(ba, a.iterations, lam=a.lam))
+    t_py, hp = B.wall_s(lambda: solve.levenberg_marquardt(ba, a.iterations, lam=a.lam))
     end_py = (ba.cameras_bal(), ba.points())
     ba.close()
     ba = fresh()
-    t_dev, (hd, summary) = timed(lambda: solve.levenberg_marquardt_device(ba, a.iterations, lam=a.lam))
+    t_dev, (hd, summary) = B.wall_s(lambda: solve.levenberg_marquardt_device(ba, a.iterations, lam=a.lam))
     same = end_py[0].tobytes() == ba.cameras_bal().tobytes() and end_py[1].tobytes() == ba.points().tobytes() and \
         [e["error"] for e in hp] == [e["error"] for e in hd]
 
@@ -66,13 +59,13 @@ def main():
     for _ in range(a.repeats):
         ba.checkpoint()
         ba.apply_step(dc, dp)
-        rej["rollback"].append(timed(ba.rollback)[0])
-        rej["step_after_rollback"].append(timed(lambda: ba.solve_step(lam, out=(dc, dp)))[0])
+        rej["rollback"].append(B.wall_s(ba.rollback)[0])
+        rej["step_after_rollback"].append(B.wall_s(lambda: ba.solve_step(lam, out=(dc, dp)))[0])
         ba.apply_step(dc, dp)
-        rej["upload"].append(timed(lambda: ba._upload(bal9, True, pts, row_ptr, pt_idx, uv))[0])
-        rej["step_after_upload"].append(timed(lambda: ba.solve_step(lam, out=(dc, dp)))[0])
+        rej["upload"].append(B.wall_s(lambda: ba._upload(bal9, True, pts, row_ptr, pt_idx, uv))[0])
+        rej["step_after_upload"].append(B.wall_s(lambda: ba.solve_step(lam, out=(dc, dp)))[0])
     ba.close()
-    med = {k: float(np.median(v)) * 1e3 for k, v in rej.items()}
+    med = {k: B.median(v) * 1e3 for k, v in rej.items()}
     n = max(len(hd), 1)
     result = dict(bench="lm_loop", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2], iterations=len(hd),
                   accepted=sum(e["accepted"] for e in hd), pcg_iterations=sum(e["pcg_iterations"] for e in hd),
@@ -83,11 +76,7 @@ def main():
                                     step_after_upload=round(med["step_after_upload"], 2),
                                     step_after_rollback=round(med["step_after_rollback"], 2)),
                   cost=[summary["initial_cost"], summary["final_cost"]])
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -9,10 +9,8 @@ round after a merge pays.  The median over `--repeats` is reported.  Prints one 
                                 [--out profiles/merge_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,49 +29,35 @@ def main():
     a = ap.parse_args()
     import __graft_entry__ as entry
     entry.build()
-    import numpy as np
     import torch
+    import benchkit as B
     import city2ba_amd as c2b
-    from city2ba_amd import _lib as L, device as D, noise as N, synthetic as S
+    from city2ba_amd import _lib as L, device as D, noise as N
 
     dev = torch.device("cuda", 0)
-    whole = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    whole = B.bench_grid(a.blocks)
     n_before = whole._sizes()[1]
     ba = N.split_landmarks(whole, a.split, seed=a.seed)          # a new problem: the list is rewritten on the host
     whole.close()
     sizes = ba._sizes()
     host = (ba.cameras(), ba.points(), ba.row_ptr.copy(), ba.pt_idx.copy(), ba.observations().reshape(-1, 2).copy())
-    ex = ba.export_device()
-    camblk = D.cameras_prepare_state(ex["cam15"])
-    rows = D.Rows(ex["row_ptr"], ex["n_obs"])
-    prows = D.PointRows(rows, ex["pt_idx"], sizes[1])
+    lv = B.level0(ba, point_rows=True)
     partner = torch.zeros(sizes[1], dtype=torch.int32, device=dev)
     status = torch.zeros(sizes[1], dtype=torch.uint8, device=dev)
     counts = torch.zeros(4, dtype=torch.int64, device=dev)
-    torch.cuda.synchronize()
 
     def partner_pass():
-        t0 = time.perf_counter()
-        D.merge_partner_rows(camblk, ex["pts4"], prows, ex["uv"], partner, status, counts, a.radius, a.max_error)
-        return (time.perf_counter() - t0) * 1e6
+        return B.wall_s(lambda: D.merge_partner_rows(lv.camblk, lv.pts4, lv.prows, lv.uv, partner, status, counts, a.radius, a.max_error))[0] * 1e6
 
     def transpose():
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        D.PointRows(rows, ex["pt_idx"], sizes[1])
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) * 1e3
+        return B.each_us(lambda: D.PointRows(lv.rows, lv.pt_idx, sizes[1]), 1, 0)[0]
 
     def whole_call():
         fresh = c2b.BAProblem.from_visibility(*host, device=0)
         fresh.total_reprojection_error(2.0)                      # the cameras' records and the row structure exist, as in a pipeline
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fresh.merge_points(a.radius, a.max_error, rounds=a.rounds)
-        dt = (time.perf_counter() - t0) * 1e6
+        dt, out = B.wall_s(lambda: fresh.merge_points(a.radius, a.max_error, rounds=a.rounds))
         fresh.close()
-        return dt, out
+        return dt * 1e6, out
 
     partner_pass(), transpose()                                  # warm-up
     t = dict(partner=[], transpose=[], call=[])
@@ -84,20 +68,16 @@ def main():
         dt, out = whole_call()
         t["call"].append(dt)
     got = dict(zip(L.MERGE_STATUS, (int(v) for v in counts.cpu().numpy())))
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    med = {k: B.median(v) for k, v in t.items()}
     result = dict(bench="merge_points", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_pts_before_split=n_before, n_obs=sizes[2],
                   split=a.split, radius=a.radius, max_error=a.max_error, rounds=a.rounds, first_round_status=got, merged=out["merged"],
                   rounds_run=out["rounds"], repeats=a.repeats,
                   time_us=dict(merge_partner_rows=round(med["partner"], 1), merge_points_call=round(med["call"], 1),
                                normal_transpose=round(med["transpose"], 1)),
-                  spread_us={k: [round(min(v), 1), round(max(v), 1)] for k, v in
+                  spread_us={k: B.spread(v, 1) for k, v in
                              (("merge_partner_rows", t["partner"]), ("merge_points_call", t["call"]), ("normal_transpose", t["transpose"]))})
     ba.close()
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,6 @@ Algorithmic bytes (each input read once, each output written once):
   point pass:  n_obs x (4 obs_of + 4 cam_of + 16 uv) + n_pts x (8 pt_row_ptr + 32 point + 72 V + 24 gp) + n_cam x 192
 """
 import argparse
-import json
 import os
 import sys
 
@@ -29,6 +28,7 @@ def main():
     entry.build()
     import torch
     import bench
+    import benchkit as B
     from city2ba_amd import device as D
     dev = torch.device("cuda", 0)
     sh = bench.build_shard(argparse.Namespace(blocks=a.blocks), 0, 1, dev)
@@ -51,35 +51,21 @@ def main():
         "points": lambda: D.normal_points_rows(camblk, pts4, pr[0], uv, V, gp),
         "step": lambda: D.residual_jacobian_rows(camblk, pts4, rows, pi, uv, r, Jc, Jp, 2.0, ws, s),
     }
-    us = {}
-    for name, fn in runs.items():
-        for _ in range(a.warmup):
-            fn()
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3)
-        times.sort()
-        us[name] = {"median_us": round(times[len(times) // 2], 1), "min_us": round(times[0], 1)}
+    us = {name: B.us_record(B.each_us(fn, a.reps, a.warmup)) for name, fn in runs.items()}
     bytes_c = n * 20 + n_pts * 32 + n_cam * (8 + 192 + 648 + 72)
     bytes_p = n * 24 + n_pts * (8 + 32 + 72 + 24) + n_cam * 192
     both = us["cameras"]["median_us"] + us["points"]["median_us"]
     out = {
         "blocks": a.blocks, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts,
         "transpose": us["transpose"],
-        "cameras": dict(us["cameras"], algorithmic_bytes=bytes_c, frac_of_8TBs=round(bytes_c / (us["cameras"]["median_us"] * 1e-6) / 8e12, 4)),
-        "points": dict(us["points"], algorithmic_bytes=bytes_p, frac_of_8TBs=round(bytes_p / (us["points"]["median_us"] * 1e-6) / 8e12, 4)),
+        "cameras": dict(us["cameras"], algorithmic_bytes=bytes_c, frac_of_8TBs=round(B.frac_of_peak(bytes_c, us["cameras"]["median_us"]), 4)),
+        "points": dict(us["points"], algorithmic_bytes=bytes_p, frac_of_8TBs=round(B.frac_of_peak(bytes_p, us["points"]["median_us"]), 4)),
         "both_passes_us": round(both, 1),
-        "both_frac_of_8TBs": round((bytes_c + bytes_p) / (both * 1e-6) / 8e12, 4),
+        "both_frac_of_8TBs": round(B.frac_of_peak(bytes_c + bytes_p, both), 4),
         "step_us": us["step"],
         "both_over_step": round(both / us["step"]["median_us"], 3),
     }
-    print(json.dumps(out))
+    B.emit(out)
 
 
 if __name__ == "__main__":

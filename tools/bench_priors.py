@@ -16,18 +16,11 @@ print one JSON line:
     python tools/bench_priors.py [--blocks 128] [--reps 5] [--warmup 1] [--rounds 3] [--sigma 0.3] [--out FILE]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def _median(xs):
-    xs = sorted(xs)
-    return xs[len(xs) // 2]
 
 
 def main():
@@ -48,42 +41,21 @@ def main():
     entry.build()
     import numpy as np
     import torch
+    import benchkit as B
     from city2ba_amd import device as D
     from city2ba_amd import noise as N
     from city2ba_amd import solve as LM
-    from city2ba_amd import synthetic as S
     dev = torch.device("cuda", 0)
     lam = 1e-4
     f64 = dict(dtype=torch.float64, device=dev)
 
     def grid():
-        ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, cull=False, mirror=False)   # bench.py's instance
+        ba = B.bench_grid(a.blocks, cull=False, mirror=False)    # bench.py's instance
         N.add_noise(ba, 0.0, 0.0, 0.0, 1e-3, seed=20243)
         return ba
 
     def events(fn):
-        for _ in range(a.warmup + 2):
-            fn()
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(max(a.reps, 10)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3)
-        return {"median_us": round(_median(times), 1), "min_us": round(min(times), 1)}
-
-    def wall(fn):
-        for _ in range(a.warmup):
-            fn()
-        times = []
-        for _ in range(a.reps):
-            t0 = time.perf_counter()
-            fn()
-            times.append((time.perf_counter() - t0) * 1e3)
-        return {"median_ms": round(_median(times), 3), "min_ms": round(min(times), 3)}
+        return B.us_record(B.each_us(fn, max(a.reps, 10), a.warmup + 2))
 
     ba = grid()
     n_cam, n_pts, n = ba._sizes()
@@ -96,9 +68,8 @@ def main():
                  points=pts + 1e-3, point_weights=xw)
 
     # ---- the three launches, Level 0 ----------------------------------------------------------------------------------
-    ex = ba.export_device()
-    camblk = D.cameras_prepare_state(ex["cam15"])
-    pts4 = ex["pts4"]
+    lv = B.level0(ba)
+    camblk, pts4 = lv.camblk, lv.pts4
     U, gc = torch.zeros((n_cam, 9, 9), **f64), torch.zeros((n_cam, 9), **f64)
     V, gp = torch.zeros((n_pts, 3, 3), **f64), torch.zeros((n_pts, 3), **f64)
     dc, dp = torch.randn((n_cam, 9), **f64) * 1e-3, torch.randn((n_pts, 3), **f64) * 1e-3
@@ -111,10 +82,10 @@ def main():
     us_m = events(lambda: D.prior_model_rows(camblk, pts4, dc, dp, sums, c0, cw, i0, iw, x0, xwd))
     bytes_c = n_cam * (256 + 48 + 48 + 2 * 39 * 8 + 2 * 72)          # record, two pairs, 39 entries of U and gc read and written
     bytes_p = n_pts * 24 + (n_pts // 100 + 1) * (32 + 24 + 48 + 48)    # every point's weights; point, target, V's diagonal and gp of every 100th
-    launches = {"prior_cameras": dict(us_c, algorithmic_bytes=bytes_c, frac_of_8TBs=round(bytes_c / (us_c["median_us"] * 1e-6) / 8e12, 4)),
+    launches = {"prior_cameras": dict(us_c, algorithmic_bytes=bytes_c, frac_of_8TBs=round(B.frac_of_peak(bytes_c, us_c["median_us"]), 4)),
                 "prior_points": dict(us_p, algorithmic_bytes=bytes_p), "prior_model": us_m,
                 "three_launches_us": round(us_c["median_us"] + us_p["median_us"] + us_m["median_us"], 1)}
-    del U, gc, V, gp, c0, cw, i0, iw, x0, xwd, camblk, ex, pts4
+    del U, gc, V, gp, c0, cw, i0, iw, x0, xwd, camblk, lv, pts4
     torch.cuda.empty_cache()
 
     # ---- solve_step with 0 iterations, interleaved ------------------------------------------------------------------------
@@ -128,12 +99,13 @@ def main():
                 ba.set_priors(camera_center_weights=0.0, intrinsics_weights=0.0, point_weights=0.0)
             else:
                 ba.set_priors(**every)
-            rounds[how].append(wall(lambda: ba.solve_step(lam, max_iters=0, rel_tol=0.0, out=(out_c, out_p)))["median_ms"])
+            times = B.wall_ms(lambda: ba.solve_step(lam, max_iters=0, rel_tol=0.0, out=(out_c, out_p)), a.reps, a.warmup)
+            rounds[how].append(round(B.upper_median(times), 3))
     none = rounds["none"]
-    solve0 = {k: {"per_round_ms": v, "median_ms": round(_median(v), 3)} for k, v in rounds.items()}
+    solve0 = {k: {"per_round_ms": v, "median_ms": round(B.upper_median(v), 3)} for k, v in rounds.items()}
     solve0["no_prior_spread_ms"] = round(max(none) - min(none), 3)
-    solve0["zero_weights_minus_none_ms"] = round(_median(rounds["zero_weights"]) - _median(none), 3)
-    solve0["in_force_minus_none_ms"] = round(_median(rounds["in_force"]) - _median(none), 3)
+    solve0["zero_weights_minus_none_ms"] = round(B.upper_median(rounds["zero_weights"]) - B.upper_median(none), 3)
+    solve0["in_force_minus_none_ms"] = round(B.upper_median(rounds["in_force"]) - B.upper_median(none), 3)
     ba.close()
     del out_c, out_p, dc, dp
     torch.cuda.empty_cache()
@@ -150,12 +122,9 @@ def main():
             ba.set_preconditioner(kind)
             if tied:
                 ba.set_priors(camera_centers=clean, camera_center_weights=1.0 / a.sigma)
-            t0 = time.perf_counter()
-            info = ba.solve_step(lam, max_iters=a.tol_max_iters, rel_tol=1e-6)[2]
-            pcg_ms = (time.perf_counter() - t0) * 1e3
-            t0 = time.perf_counter()
-            h, s = LM.levenberg_marquardt_device(ba, a.lm_iterations, lam=lam, max_iters=100, rel_tol=1e-6)
-            lm_ms = (time.perf_counter() - t0) * 1e3
+            pcg_s, (_, _, info) = B.wall_s(lambda: ba.solve_step(lam, max_iters=a.tol_max_iters, rel_tol=1e-6))
+            lm_s, (h, s) = B.wall_s(lambda: LM.levenberg_marquardt_device(ba, a.lm_iterations, lam=lam, max_iters=100, rel_tol=1e-6))
+            pcg_ms, lm_ms = pcg_s * 1e3, lm_s * 1e3
             g = [e["gradient_max"] for e in h]
             reached = next((k for k, v in enumerate(g) if v <= a.gradient_drop * g[0]), None)
             drifted["%s %s" % (kind, "centre priors" if tied else "no priors")] = {
@@ -167,12 +136,7 @@ def main():
             ba.close()
     out = {"blocks": a.blocks, "n_obs": n, "n_cam": n_cam, "n_pts": n_pts, "lambda": lam, "sigma": a.sigma, "drift": list(a.drift),
            "gradient_drop": a.gradient_drop, "launches": launches, "solve_0_iterations": solve0, "drifted": drifted}
-    text = json.dumps(out)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
+    B.emit(out, a.out)
 
 
 if __name__ == "__main__":

@@ -15,10 +15,8 @@ Prints one JSON line.
     python tools/bench_refine.py [--blocks 128] [--repeats 7] [--out profiles/refine_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,21 +35,18 @@ def main():
     a = ap.parse_args()
     import __graft_entry__ as entry
     entry.build()
-    import numpy as np
     import torch
+    import benchkit as B
     import city2ba_amd as c2b
-    from city2ba_amd import _lib as L, device as D, noise as N, solve, synthetic as S
+    from city2ba_amd import _lib as L, device as D, noise as N, solve
 
     dev = torch.device("cuda", 0)
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    ba = B.bench_grid(a.blocks)
     N.add_noise(ba, 0.0, 0.0, a.point_std, a.sigma, seed=3)
     sizes = ba._sizes()
     lm_start = (ba.cameras_bal(), ba.points(), ba.row_ptr.copy(), ba.pt_idx.copy(), ba.observations())
-    ex = ba.export_device()
-    camblk = D.cameras_prepare_state(ex["cam15"])
-    rows = D.Rows(ex["row_ptr"], ex["n_obs"])
-    prows = D.PointRows(rows, ex["pt_idx"], sizes[1])
-    start, uv = ex["pts4"].clone(), ex["uv"]
+    lv = B.level0(ba, point_rows=True)
+    camblk, prows, start, uv = lv.camblk, lv.prows, lv.pts4, lv.uv
     pts4 = start.clone()
     status = torch.zeros(sizes[1], dtype=torch.uint8, device=dev)
     counts = torch.zeros(6, dtype=torch.int64, device=dev)
@@ -59,14 +54,7 @@ def main():
     gp = torch.empty((sizes[1], 3), dtype=torch.float64, device=dev)
 
     def window(fn):
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(a.launches):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / a.launches        # microseconds per launch
+        return B.window_us(fn, a.launches)
 
     def refine(rounds):
         def fn():
@@ -84,7 +72,7 @@ def main():
             t[k].append(window(fn))
             if k.startswith("refine"):
                 got[k] = dict(zip(L.REFINE_COUNTS, (int(v) for v in counts.cpu().numpy())))
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    med = {k: B.median(v) for k, v in t.items()}
     kernel = {"normal_points_rows": round(med["normal_points_rows"], 2), "points_copy": round(med["copy"], 2)}
     passes = {}
     for r in (1, 5, 10):
@@ -99,10 +87,7 @@ def main():
 
     def run(n_inner, iterations):
         g = fresh()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        h, s = solve.levenberg_marquardt_device(g, iterations, lam=a.lam, inner_iterations=n_inner)
-        dt = time.perf_counter() - t0
+        dt, (h, s) = B.wall_s(lambda: solve.levenberg_marquardt_device(g, iterations, lam=a.lam, inner_iterations=n_inner))
         g.close()
         return dt, h, s
     run(2, 1)                                                # the first solve of a process pays for the kernels' load
@@ -116,21 +101,17 @@ def main():
         reach = next((k + 1 for k, c in enumerate(after) if c <= target), None)
         t_reach = None
         if reach is not None:
-            t_reach = float(np.median([run(n_inner, reach)[0] for _ in range(3)]))
+            t_reach = B.median([run(n_inner, reach)[0] for _ in range(3)])
         lm["inner_%d" % n_inner] = dict(wall_s=round(dt, 4), accepted="".join("A" if e["accepted"] else "R" for e in h), initial_cost=s["initial_cost"],
                                         cost_after_iteration=after, final_cost=s["final_cost"], iterations_to_plain_final_cost=reach,
                                         wall_s_to_plain_final_cost=None if t_reach is None else round(t_reach, 4),
                                         pcg_iterations=[e["pcg_iterations"] for e in h])
     result = dict(bench="refine_points", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2], lam=a.lam, point_std=a.point_std,
                   counts=got, launches_per_window=a.launches, windows=a.repeats, kernel_us=kernel,
-                  spread_us={k: [round(min(v), 2), round(max(v), 2)] for k, v in t.items()},
+                  spread_us={k: B.spread(v, 2) for k, v in t.items()},
                   point_passes=passes, expected_point_passes={"refine_rounds_%d" % r: r + 1 for r in (1, 5, 10)},
                   lm_iterations=a.iterations, lm=lm)
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,6 @@ launch starts from the noisy cameras.  Prints one JSON line.
     python tools/bench_refine_cameras.py [--blocks 128] [--repeats 7] [--out profiles/refine_cameras_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -34,19 +33,18 @@ def main():
     a = ap.parse_args()
     import __graft_entry__ as entry
     entry.build()
-    import numpy as np
     import torch
-    from city2ba_amd import _lib as L, device as D, noise as N, synthetic as S
+    import benchkit as B
+    from city2ba_amd import _lib as L, device as D, noise as N
 
     dev = torch.device("cuda", 0)
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    ba = B.bench_grid(a.blocks)
     N.add_noise(ba, a.translation_std, a.rotation_std, 0.0, a.sigma, seed=3)
     sizes = ba._sizes()
     start = torch.from_numpy(ba.cameras_bal()).to(dev)
-    ex = ba.export_device()
-    camblk = D.cameras_prepare_bal(start)
-    rows = D.Rows(ex["row_ptr"], ex["n_obs"])
-    pts4, pt_idx, uv = ex["pts4"], ex["pt_idx"], ex["uv"]
+    lv = B.level0(ba)
+    rows, pts4, pt_idx, uv = lv.rows, lv.pts4, lv.pt_idx, lv.uv
+    camblk = D.cameras_prepare_bal(start)                    # the table of the cameras the refinement starts from, as it reads them
     bal9 = start.clone()
     status = torch.zeros(sizes[0], dtype=torch.uint8, device=dev)
     counts = torch.zeros(6, dtype=torch.int64, device=dev)
@@ -54,14 +52,7 @@ def main():
     gc = torch.empty((sizes[0], 9), dtype=torch.float64, device=dev)
 
     def window(fn):
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(a.launches):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / a.launches        # microseconds per launch
+        return B.window_us(fn, a.launches)
 
     def refine(rounds):
         def fn():
@@ -79,7 +70,7 @@ def main():
             t[k].append(window(fn))
             if k.startswith("refine"):
                 got[k] = dict(zip(L.REFINE_COUNTS, (int(v) for v in counts.cpu().numpy())))
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    med = {k: B.median(v) for k, v in t.items()}
     kernel = {"normal_cameras_rows": round(med["normal_cameras_rows"], 2), "bal9_copy": round(med["copy"], 2)}
     passes = {}
     for r in (1, 5, 10):
@@ -94,13 +85,9 @@ def main():
                     fixed_part_of_a_launch=round(passes["refine_rounds_1"] - per_round, 3))
     result = dict(bench="refine_cameras", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2], lam=a.lam,
                   translation_std=a.translation_std, rotation_std=a.rotation_std, counts=got, launches_per_window=a.launches, windows=a.repeats,
-                  kernel_us=kernel, spread_us={k: [round(min(v), 2), round(max(v), 2)] for k, v in t.items()}, camera_passes=passes,
+                  kernel_us=kernel, spread_us={k: B.spread(v, 2) for k, v in t.items()}, camera_passes=passes,
                   expected_camera_passes={"refine_rounds_%d" % r: r + 1 for r in (1, 5, 10)}, marginal_in_camera_passes=marginal)
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

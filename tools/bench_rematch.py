@@ -11,10 +11,8 @@ process.  --radius 0 takes the 90th percentile of the distance to the tenth near
                                   [--repeats 5] [--out profiles/rematch_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,11 +34,12 @@ def main():
     entry.build()
     import numpy as np
     import torch
+    import benchkit as B
     import city2ba_amd as c2b
-    from city2ba_amd import _lib as L, device as D, noise as N, synthetic as S
+    from city2ba_amd import _lib as L, device as D, noise as N
 
     dev = torch.device("cuda", 0)
-    whole = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    whole = B.bench_grid(a.blocks)
     true_idx = whole.pt_idx.copy()
     joined = N.join_landmarks(whole, a.join, seed=a.seed)        # new problems: the list is rewritten on the host
     whole.close()
@@ -49,16 +48,14 @@ def main():
     sizes = ba._sizes()
     wrong = ba.pt_idx != true_idx
     host = (ba.cameras(), ba.points(), ba.row_ptr.copy(), ba.pt_idx.copy(), ba.observations().reshape(-1, 2).copy())
-    ex = ba.export_device()
+    lv = B.level0(ba, point_rows=True)
+    camblk, rows, prows, pts4, pt_idx, uv = lv.camblk, lv.rows, lv.prows, lv.pts4, lv.pt_idx, lv.uv
     radius = a.radius
     if radius <= 0.0:
         pick = torch.from_numpy(np.random.default_rng(a.seed).choice(sizes[1], size=min(2000, sizes[1]), replace=False)).to(dev)
-        xyz = ex["pts4"][:, :3]
+        xyz = pts4[:, :3]
         tenth = torch.cat([torch.cdist(xyz[pick[k:k + 250]], xyz).kthvalue(min(11, sizes[1]), dim=1).values for k in range(0, len(pick), 250)])
         radius = float(torch.quantile(tenth, 0.9).item())       # (the nearest of all is the point itself)
-    camblk = D.cameras_prepare_state(ex["cam15"])
-    rows = D.Rows(ex["row_ptr"], ex["n_obs"])
-    prows = D.PointRows(rows, ex["pt_idx"], sizes[1])
     fits = torch.zeros(sizes[2], dtype=torch.uint8, device=dev)
     choice = torch.zeros(sizes[2], dtype=torch.int32, device=dev)
     status = torch.zeros(sizes[2], dtype=torch.uint8, device=dev)
@@ -66,31 +63,24 @@ def main():
     partner = torch.zeros(sizes[1], dtype=torch.int32, device=dev)
     pstatus = torch.zeros(sizes[1], dtype=torch.uint8, device=dev)
     pcounts = torch.zeros(4, dtype=torch.int64, device=dev)
-    D.residual_keep_rows(camblk, ex["pts4"], rows, ex["pt_idx"], ex["uv"], a.max_error, fits, in_front=True)
+    D.residual_keep_rows(camblk, pts4, rows, pt_idx, uv, a.max_error, fits, in_front=True)
     # rule 2 with the pieces Level 0 exposes: the fitting observations per point
-    nfit = torch.zeros(sizes[1], dtype=torch.int64, device=dev).index_add_(0, ex["pt_idx"].long(), fits.long())
-    trusted = ((nfit >= a.min_fits) & torch.isfinite(ex["pts4"][:, :3]).all(dim=1)).to(torch.uint8)
-    torch.cuda.synchronize()
+    nfit = torch.zeros(sizes[1], dtype=torch.int64, device=dev).index_add_(0, pt_idx.long(), fits.long())
+    trusted = ((nfit >= a.min_fits) & torch.isfinite(pts4[:, :3]).all(dim=1)).to(torch.uint8)
 
     def choose_pass():
-        t0 = time.perf_counter()
-        D.rematch_rows(camblk, ex["pts4"], rows, ex["pt_idx"], ex["uv"], fits, choice, status, counts, radius, a.max_error, pt_trusted=trusted)
-        return (time.perf_counter() - t0) * 1e6
+        return B.wall_s(lambda: D.rematch_rows(camblk, pts4, rows, pt_idx, uv, fits, choice, status, counts, radius, a.max_error,
+                                               pt_trusted=trusted))[0] * 1e6
 
     def partner_pass():
-        t0 = time.perf_counter()
-        D.merge_partner_rows(camblk, ex["pts4"], prows, ex["uv"], partner, pstatus, pcounts, radius, a.max_error)
-        return (time.perf_counter() - t0) * 1e6
+        return B.wall_s(lambda: D.merge_partner_rows(camblk, pts4, prows, uv, partner, pstatus, pcounts, radius, a.max_error))[0] * 1e6
 
     def whole_call():
         fresh = c2b.BAProblem.from_visibility(*host, device=0)
         fresh.total_reprojection_error(2.0)                      # the cameras' records and the row structure exist, as in a pipeline
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fresh.rematch_observations(radius, a.max_error, min_fits=a.min_fits)
-        dt = (time.perf_counter() - t0) * 1e6
+        dt, out = B.wall_s(lambda: fresh.rematch_observations(radius, a.max_error, min_fits=a.min_fits))
         fresh.close()
-        return dt, out
+        return dt * 1e6, out
 
     choose_pass(), partner_pass()                                # warm-up
     t = dict(choose=[], partner=[], call=[])
@@ -103,19 +93,15 @@ def main():
     got = dict(zip(L.REMATCH_STATUS, (int(v) for v in counts.cpu().numpy())))
     st, ch = status.cpu().numpy(), choice.cpu().numpy()
     back = int(((st == L.REMATCH_REASSIGNED) & (ch == true_idx.astype(np.int64))).sum())
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    med = {k: B.median(v) for k, v in t.items()}
     names = (("rematch_rows", "choose"), ("rematch_observations_call", "call"), ("merge_partner_rows", "partner"))
     result = dict(bench="rematch_observations", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2], join=a.join, mismatch=a.mismatch,
                   wrong_labels=int(wrong.sum()), radius=round(radius, 6), max_error=a.max_error, min_fits=a.min_fits, level0_status=got,
                   level1_status=out, reassigned_to_truth=back, right_observations_changed=int((~wrong & (st >= L.REMATCH_REASSIGNED)).sum()),
                   repeats=a.repeats, time_us={k: round(med[v], 1) for k, v in names},
-                  spread_us={k: [round(min(t[v]), 1), round(max(t[v]), 1)] for k, v in names})
+                  spread_us={k: B.spread(t[v], 1) for k, v in names})
     ba.close()
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

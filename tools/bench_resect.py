@@ -9,7 +9,6 @@ Prints one JSON line.
     python tools/bench_resect.py [--blocks 128] [--repeats 7] [--out profiles/resect_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -31,18 +30,16 @@ def main():
     a = ap.parse_args()
     import __graft_entry__ as entry
     entry.build()
-    import numpy as np
     import torch
-    from city2ba_amd import _lib as L, device as D, noise as N, synthetic as S
+    import benchkit as B
+    from city2ba_amd import _lib as L, device as D, noise as N
 
     dev = torch.device("cuda", 0)
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    ba = B.bench_grid(a.blocks)
     N.add_noise(ba, a.translation_std, a.rotation_std, 0.0, a.sigma, seed=3)
     sizes = ba._sizes()
-    ex = ba.export_device()
-    camblk = D.cameras_prepare_state(ex["cam15"])
-    rows = D.Rows(ex["row_ptr"], ex["n_obs"])
-    pts4, pt_idx, uv = ex["pts4"], ex["pt_idx"], ex["uv"]
+    lv = B.level0(ba)
+    camblk, rows, pts4, pt_idx, uv = lv.camblk, lv.rows, lv.pts4, lv.pt_idx, lv.uv
     start = torch.from_numpy(ba.cameras_bal()).to(dev)
     bal9 = start.clone()
     status = torch.zeros(sizes[0], dtype=torch.uint8, device=dev)
@@ -51,15 +48,7 @@ def main():
     gc = torch.empty((sizes[0], 9), dtype=torch.float64, device=dev)
 
     def window(fn):
-        bal9.copy_(start)
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(a.launches):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / a.launches        # microseconds per launch
+        return B.window_us(fn, a.launches, before=lambda: bal9.copy_(start))
 
     res = lambda: D.resect_rows(bal9, pts4, rows, pt_idx, uv, status, counts, a.min_points, a.min_gap)
     nrm = lambda: D.normal_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, gc)
@@ -70,19 +59,14 @@ def main():
         t["res"].append(window(res))
         t["nrm"].append(window(nrm))
     got = dict(zip(L.RES_STATUS, (int(v) for v in counts.cpu().numpy())))
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    med = {k: B.median(v) for k, v in t.items()}
     result = dict(bench="resect_cameras", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2], min_points=a.min_points,
                   min_gap=a.min_gap, counts=got, launches_per_window=a.launches, windows=a.repeats,
                   kernel_us=dict(resect_rows=round(med["res"], 2), normal_cameras_rows=round(med["nrm"], 2)),
-                  spread_us=dict(resect_rows=[round(min(t["res"]), 2), round(max(t["res"]), 2)],
-                                 normal_cameras_rows=[round(min(t["nrm"]), 2), round(max(t["nrm"]), 2)]),
+                  spread_us=dict(resect_rows=B.spread(t["res"], 2), normal_cameras_rows=B.spread(t["nrm"], 2)),
                   ratio_resect_over_normal_cameras=round(med["res"] / med["nrm"], 4))
     ba.close()
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,6 @@ work does not depend on where the cameras are.  Prints one JSON line.
                                         [--out profiles/resect_robust_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -36,20 +35,19 @@ def main():
     a = ap.parse_args()
     import __graft_entry__ as entry
     entry.build()
-    import numpy as np
     import torch
-    from city2ba_amd import _lib as L, device as D, noise as N, synthetic as S
+    import benchkit as B
+    from city2ba_amd import _lib as L, device as D, noise as N
 
     dev = torch.device("cuda", 0)
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    ba = B.bench_grid(a.blocks)
     N.add_noise(ba, a.translation_std, a.rotation_std, 0.0, a.sigma, seed=3)
     clean = ba
     ba = N.add_incorrect_correspondences(clean, a.mismatch, seed=4)     # a new problem: the list is rewritten on the host
     clean.close()
     sizes = ba._sizes()
-    ex = ba.export_device()
-    rows = D.Rows(ex["row_ptr"], ex["n_obs"])
-    pts4, pt_idx, uv = ex["pts4"], ex["pt_idx"], ex["uv"]
+    lv = B.level0(ba)
+    rows, pts4, pt_idx, uv = lv.rows, lv.pts4, lv.pt_idx, lv.uv
     start = torch.from_numpy(ba.cameras_bal()).to(dev)
     bal9 = start.clone()
     status = torch.zeros(sizes[0], dtype=torch.uint8, device=dev)
@@ -60,15 +58,7 @@ def main():
     counts_plain = torch.zeros(5, dtype=torch.int64, device=dev)
 
     def window(fn):
-        bal9.copy_(start)
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(a.launches):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / a.launches        # microseconds per launch
+        return B.window_us(fn, a.launches, before=lambda: bal9.copy_(start))
 
     rob = lambda: D.resect_consensus_rows(bal9, pts4, rows, pt_idx, uv, status, counts, a.max_error, a.min_inliers, a.min_gap, a.max_hypotheses,
                                           hyp=hyp, n_inl=n_inl, inlier=inlier)
@@ -94,7 +84,7 @@ def main():
     got = dict(zip(L.RES_CONSENSUS_STATUS, (int(v) for v in counts.cpu().numpy())))
     got_plain = dict(zip(L.RES_STATUS, (int(v) for v in counts_plain.cpu().numpy())))
     outliers = int((inlier[:sizes[2]] == 0).sum().item())
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    med = {k: B.median(v) for k, v in t.items()}
     result = dict(bench="resect_cameras_robust", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2],
                   mean_row=round(sizes[2] / max(sizes[0], 1), 3), mismatch=a.mismatch, max_error=a.max_error, min_inliers=a.min_inliers,
                   min_gap=a.min_gap, max_hypotheses=a.max_hypotheses, counts=got, outliers=outliers, counts_plain=got_plain,
@@ -102,17 +92,12 @@ def main():
                   counts_filtered=got_fit, n_obs_filtered=rows_f.n_obs,
                   kernel_us=dict(resect_consensus_rows=round(med["rob"], 2), resect_rows=round(med["res"], 2),
                                  resect_rows_filtered=round(med["fit"], 2)),
-                  spread_us=dict(resect_consensus_rows=[round(min(t["rob"]), 2), round(max(t["rob"]), 2)],
-                                 resect_rows=[round(min(t["res"]), 2), round(max(t["res"]), 2)],
-                                 resect_rows_filtered=[round(min(t["fit"]), 2), round(max(t["fit"]), 2)]),
+                  spread_us=dict(resect_consensus_rows=B.spread(t["rob"], 2), resect_rows=B.spread(t["res"], 2),
+                                 resect_rows_filtered=B.spread(t["fit"], 2)),
                   ratio_consensus_over_resect=round(med["rob"] / med["res"], 4),
                   refit_share_of_consensus=round(med["fit"] / med["rob"], 4))
     ba.close()
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -29,18 +29,11 @@ Algorithmic bytes (each input read once, each output written once):
   camera pass: n_obs x (4 pt_idx + 16 uv) + n_pts x (32 point + 24 t) + n_cam x (8 row_ptr + 192 record + 648 U + 72 x + 72 y)
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def _median(xs):
-    xs = sorted(xs)
-    return xs[len(xs) // 2]
 
 
 def main():
@@ -60,22 +53,19 @@ def main():
     import __graft_entry__ as entry
     entry.build()
     import torch
+    import benchkit as B
     from city2ba_amd import device as D
     from city2ba_amd import noise as N
-    from city2ba_amd import synthetic as S
     dev = torch.device("cuda", 0)
     lam = 1e-4
 
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, cull=False, mirror=False)   # bench.py's instance
+    ba = B.bench_grid(a.blocks, cull=False, mirror=False)    # bench.py's instance
     N.add_noise(ba, 0.0, 0.0, 0.0, 1e-3, seed=20243)
-    n_cam, n_pts, n = ba._sizes()
 
     # Level 0 over the same state
-    ex = ba.export_device()
-    camblk = D.cameras_prepare_state(ex["cam15"])
-    pts4, pi, uv = ex["pts4"], ex["pt_idx"], ex["uv"]
-    rows = D.Rows(ex["row_ptr"], n)
-    prows = D.PointRows(rows, pi, n_pts)
+    lv = B.level0(ba, point_rows=True)
+    n_cam, n_pts, n = lv.n_cam, lv.n_pts, lv.n_obs
+    camblk, rows, prows, pts4, pi, uv = lv.camblk, lv.rows, lv.prows, lv.pts4, lv.pt_idx, lv.uv
     f64 = dict(dtype=torch.float64, device=dev)
     U, gc = torch.empty((n_cam, 9, 9), **f64), torch.empty((n_cam, 9), **f64)
     V, gp = torch.empty((n_pts, 3, 3), **f64), torch.empty((n_pts, 3), **f64)
@@ -85,41 +75,24 @@ def main():
     t, y = torch.empty((n_pts, 3), **f64), torch.empty((n_cam, 9), **f64)
 
     def events(fn):
-        for _ in range(a.warmup + 2):
-            fn()
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(max(a.reps, 10)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3)
-        return {"median_us": round(_median(times), 1), "min_us": round(min(times), 1)}
+        return B.us_record(B.each_us(fn, max(a.reps, 10), a.warmup + 2))
 
     def wall(fn):
-        for _ in range(a.warmup):
-            fn()
-        times = []
-        for _ in range(a.reps):
-            t0 = time.perf_counter()
-            fn()
-            times.append((time.perf_counter() - t0) * 1e3)
-        return {"median_ms": round(_median(times), 3), "min_ms": round(min(times), 3)}
+        times = B.wall_ms(fn, a.reps, a.warmup)
+        return {"median_ms": round(B.upper_median(times), 3), "min_ms": round(min(times), 3)}
 
     us_p = events(lambda: D.schur_points_rows(camblk, pts4, prows, uv, V, lam, x, None, t, loss=loss))
     us_c = events(lambda: D.schur_cameras_rows(camblk, pts4, rows, pi, uv, U, lam, x, t, y, loss=loss))
     bytes_p = n * 24 + n_pts * (8 + 32 + 72 + 24) + n_cam * (192 + 72)
     bytes_c = n * 20 + n_pts * (32 + 24) + n_cam * (8 + 192 + 648 + 72 + 72)
-    frac = lambda b, us: round(b / (us * 1e-6) / 8e12, 4)
+    frac = lambda b, us: round(B.frac_of_peak(b, us), 4)
     sj = a.preconditioner == "schur_jacobi"
     if sj:                                                   # the pass that forms M, alone
         M = torch.empty((n_cam, 9, 9), **f64)
         us_m = events(lambda: D.schur_jacobi_blocks(camblk, pts4, rows, pi, uv, U, V, lam, M, loss=loss))
         bytes_m = n * 20 + n_pts * (32 + 72) + n_cam * (8 + 192 + 72 + 648)      # + U's diagonal (its lines), M written once
         del M
-    del U, gc, V, gp, t, y, x, prows, rows, camblk, ex
+    del U, gc, V, gp, t, y, x, prows, rows, camblk, lv
     torch.cuda.empty_cache()
 
     dc, dp = torch.empty((n_cam, 9), **f64), torch.empty((n_pts, 3), **f64)
@@ -172,7 +145,7 @@ def main():
         "info_25": info[25],
     }
     ba.close()
-    print(json.dumps(out))
+    B.emit(out)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,6 @@ points are restored between windows, so every triangulation launch starts from t
     python tools/bench_triangulate.py [--blocks 128] [--repeats 7] [--out profiles/triangulate_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -30,17 +29,15 @@ def main():
     entry.build()
     import numpy as np
     import torch
-    from city2ba_amd import _lib as L, device as D, noise as N, synthetic as S
+    import benchkit as B
+    from city2ba_amd import _lib as L, device as D, noise as N
 
     dev = torch.device("cuda", 0)
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    ba = B.bench_grid(a.blocks)
     N.add_noise(ba, 0.0, 0.0, a.point_std, a.sigma, seed=3)
     sizes = ba._sizes()
-    ex = ba.export_device()
-    camblk = D.cameras_prepare_state(ex["cam15"])
-    rows = D.Rows(ex["row_ptr"], ex["n_obs"])
-    prows = D.PointRows(rows, ex["pt_idx"], sizes[1])
-    start, uv = ex["pts4"].clone(), ex["uv"]
+    lv = B.level0(ba, point_rows=True)
+    camblk, prows, start, uv = lv.camblk, lv.prows, lv.pts4, lv.uv
     pts4 = start.clone()
     status = torch.zeros(sizes[1], dtype=torch.uint8, device=dev)
     counts = torch.zeros(5, dtype=torch.int64, device=dev)
@@ -49,15 +46,7 @@ def main():
     angle = float(np.deg2rad(a.min_angle))
 
     def window(fn):
-        pts4.copy_(start)
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(a.launches):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / a.launches        # microseconds per launch
+        return B.window_us(fn, a.launches, before=lambda: pts4.copy_(start))
 
     # (the first launch of a window moves the points; the later ones walk the same rows from the triangulated points: the
     # pass reads no point, so its work does not depend on where the points are)
@@ -70,19 +59,14 @@ def main():
         t["tri"].append(window(tri))
         t["nrm"].append(window(nrm))
     got = dict(zip(L.TRI_STATUS, (int(v) for v in counts.cpu().numpy())))
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    med = {k: B.median(v) for k, v in t.items()}
     result = dict(bench="triangulate_points", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2], min_angle_deg=a.min_angle,
                   counts=got, launches_per_window=a.launches, windows=a.repeats,
                   kernel_us=dict(triangulate_rows=round(med["tri"], 2), normal_points_rows=round(med["nrm"], 2)),
-                  spread_us=dict(triangulate_rows=[round(min(t["tri"]), 2), round(max(t["tri"]), 2)],
-                                 normal_points_rows=[round(min(t["nrm"]), 2), round(max(t["nrm"]), 2)]),
+                  spread_us=dict(triangulate_rows=B.spread(t["tri"], 2), normal_points_rows=B.spread(t["nrm"], 2)),
                   ratio_triangulate_over_normal_points=round(med["tri"] / med["nrm"], 4))
     ba.close()
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

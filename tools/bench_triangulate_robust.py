@@ -10,7 +10,6 @@ Neither pass reads a point, so its work does not depend on where the points are.
                                              [--out profiles/triangulate_robust_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -36,20 +35,18 @@ def main():
     entry.build()
     import numpy as np
     import torch
-    from city2ba_amd import _lib as L, device as D, noise as N, synthetic as S
+    import benchkit as B
+    from city2ba_amd import _lib as L, device as D, noise as N
 
     dev = torch.device("cuda", 0)
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    ba = B.bench_grid(a.blocks)
     N.add_noise(ba, 0.0, 0.0, a.point_std, a.sigma, seed=3)
     clean = ba
     ba = N.add_incorrect_correspondences(clean, a.mismatch, seed=4)     # a new problem: the list is rewritten on the host
     clean.close()
     sizes = ba._sizes()
-    ex = ba.export_device()
-    camblk = D.cameras_prepare_state(ex["cam15"])
-    rows = D.Rows(ex["row_ptr"], ex["n_obs"])
-    prows = D.PointRows(rows, ex["pt_idx"], sizes[1])
-    start, uv = ex["pts4"].clone(), ex["uv"]
+    lv = B.level0(ba, point_rows=True)
+    camblk, prows, start, uv = lv.camblk, lv.prows, lv.pts4, lv.uv
     pts4 = start.clone()
     status = torch.zeros(sizes[1], dtype=torch.uint8, device=dev)
     hyp = torch.zeros(sizes[1], dtype=torch.int32, device=dev)
@@ -60,15 +57,7 @@ def main():
     angle = float(np.deg2rad(a.min_angle))
 
     def window(fn):
-        pts4.copy_(start)
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(a.launches):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / a.launches        # microseconds per launch
+        return B.window_us(fn, a.launches, before=lambda: pts4.copy_(start))
 
     rob = lambda: D.triangulate_consensus_rows(camblk, pts4, prows, uv, status, counts, angle, a.max_error, a.min_inliers, a.max_hypotheses,
                                                hyp=hyp, n_inl=n_inl, inlier=inlier)
@@ -83,21 +72,16 @@ def main():
     got = dict(zip(L.TRI_CONSENSUS_STATUS, (int(v) for v in counts.cpu().numpy())))
     got_plain = dict(zip(L.TRI_STATUS, (int(v) for v in counts_plain.cpu().numpy())))
     outliers = int((inlier[:sizes[2]] == 0).sum().item())
-    med = {k: float(np.median(v)) for k, v in t.items()}
+    med = {k: B.median(v) for k, v in t.items()}
     result = dict(bench="triangulate_points_robust", blocks=a.blocks, n_cam=sizes[0], n_pts=sizes[1], n_obs=sizes[2],
                   mean_row=round(sizes[2] / max(sizes[1], 1), 3), mismatch=a.mismatch, min_angle_deg=a.min_angle, max_error=a.max_error,
                   min_inliers=a.min_inliers, max_hypotheses=a.max_hypotheses, counts=got, outliers=outliers, counts_plain=got_plain,
                   launches_per_window=a.launches, windows=a.repeats,
                   kernel_us=dict(triangulate_consensus_rows=round(med["rob"], 2), triangulate_rows=round(med["tri"], 2)),
-                  spread_us=dict(triangulate_consensus_rows=[round(min(t["rob"]), 2), round(max(t["rob"]), 2)],
-                                 triangulate_rows=[round(min(t["tri"]), 2), round(max(t["tri"]), 2)]),
+                  spread_us=dict(triangulate_consensus_rows=B.spread(t["rob"], 2), triangulate_rows=B.spread(t["tri"], 2)),
                   ratio_consensus_over_triangulate=round(med["rob"] / med["tri"], 4))
     ba.close()
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -14,14 +14,11 @@ Prints one JSON line.
     python tools/bench_window.py [--blocks 128] [--repeats 7] [--out profiles/window_bench_blocks128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-HBM_BYTES_PER_S = 8.0e12        # the MI355X's HBM3E peak; a streaming copy reaches about 6.3e12 of it
 
 
 def host_subset(c2b, np, ba, ci, pi):
@@ -55,11 +52,11 @@ def main():
     import __graft_entry__ as entry
     entry.build()
     import numpy as np
-    import torch
+    import benchkit as B
     import city2ba_amd as c2b
-    from city2ba_amd import noise as N, solve, synthetic as S
+    from city2ba_amd import noise as N, solve
 
-    ba = S.synthetic_grid(10, 10, a.blocks, 20.0, 1.0, 1.0, 1.0, 10.0, False, cull=True)
+    ba = B.bench_grid(a.blocks)
     N.add_noise(ba, 0.0, 0.0, a.point_std, a.sigma, seed=3)
     n_cam, n_pts, n_obs = ba._sizes()
     start = (ba.cameras_bal(), ba.points(), ba.row_ptr.copy(), ba.pt_idx.copy(), ba.observations())
@@ -67,14 +64,10 @@ def main():
     def wall(fn, repeats):
         out = []
         for _ in range(repeats):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            r = fn()
-            torch.cuda.synchronize()
-            out.append(time.perf_counter() - t0)
-            if r is not None:
-                r.close()
-        return float(np.median(out)), [round(min(out) * 1e3, 3), round(max(out) * 1e3, 3)]
+            dt, child = B.wall_s(fn)
+            out.append(dt)
+            child.close()
+        return B.median(out), B.spread([dt * 1e3 for dt in out], 3)
 
     extraction = {}
     for seeds in (1024, 16384):
@@ -92,8 +85,8 @@ def main():
             # (12 + 4 + 16 bytes in, 4 + 4 + 16 out per observation); the entities are gathered (15 + 9 and 4 doubles, in and out)
             floor_bytes = 2 * 8 * n_obs + no * (32 + 24) + nc * 2 * 8 * 24 + npt * 2 * 8 * 4
             rec = dict(seed_cameras=seeds, halo=halo, cameras=nc, points=npt, observations=no, wall_ms=round(t * 1e3, 3), spread_ms=spread,
-                       floor_bytes=floor_bytes, floor_ms_at_hbm_peak=round(floor_bytes / HBM_BYTES_PER_S * 1e3, 4),
-                       time_over_floor=round(t / (floor_bytes / HBM_BYTES_PER_S), 1))
+                       floor_bytes=floor_bytes, floor_ms_at_hbm_peak=round(floor_bytes / B.HBM_PEAK_BYTES_PER_S * 1e3, 4),
+                       time_over_floor=round(t / (floor_bytes / B.HBM_PEAK_BYTES_PER_S), 1))
             if halo:
                 th, spread_h = wall(lambda: host_subset(c2b, np, ba, origin["cam_of"].astype(np.int64), origin["pt_of"].astype(np.int64)), 3)
                 rec["host_subset_wall_ms"] = round(th * 1e3, 1)
@@ -111,17 +104,11 @@ def main():
     g.close()
     g = fresh()
     c0 = cost(g)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    _, s = solve.levenberg_marquardt_device(g, a.iterations)
-    t_full = time.perf_counter() - t0
+    t_full, (_, s) = B.wall_s(lambda: solve.levenberg_marquardt_device(g, a.iterations))
     c_full = cost(g)
     g.close()
     g = fresh()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    sweep = solve.solve_windows(g, a.size, sweeps=1, halo=True, iterations=a.iterations)
-    t_sweep = time.perf_counter() - t0
+    t_sweep, sweep = B.wall_s(lambda: solve.solve_windows(g, a.size, sweeps=1, halo=True, iterations=a.iterations))
     c_sweep = cost(g)
     g.close()
     result = dict(bench="window", blocks=a.blocks, n_cam=n_cam, n_pts=n_pts, n_obs=n_obs, repeats=a.repeats, extraction=extraction,
@@ -129,11 +116,7 @@ def main():
                   full_lm=dict(wall_s=round(t_full, 4), cost=c_full, iterations=s["iterations"]),
                   window_sweep=dict(size=a.size, windows=len(sweep), wall_s=round(t_sweep, 4), cost=c_sweep,
                                     child_cameras=[w["cameras"] for w in sweep], child_observations=[w["observations"] for w in sweep]))
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    B.emit(result, a.out)
 
 
 if __name__ == "__main__":
