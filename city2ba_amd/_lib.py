@@ -58,6 +58,21 @@ def precond_kind(name):
         raise ValueError("preconditioner must be 'block_jacobi' or 'schur_jacobi', not %r" % (name,))
 
 
+# how the step applies the Schur complement (c2b_problem_set_schur): name -> kind
+SCHUR_KINDS = {"implicit": 0, "explicit": 1}
+SCHUR_NAMES = {0: "implicit", 1: "explicit"}
+
+
+def schur_kind(name):
+    """the C ABI's kind of a Schur complement given by name (or the kind itself)"""
+    if isinstance(name, int) and not isinstance(name, bool):
+        return name
+    try:
+        return SCHUR_KINDS[name]
+    except (KeyError, TypeError):
+        raise ValueError("schur must be 'implicit' or 'explicit', not %r" % (name,))
+
+
 class StepInfo(C.Structure):
     """c2b_step_info (include/city2ba_hip_experimental.h)"""
     _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("rel_residual", C.c_double), ("sum_sq", C.c_double),
@@ -269,6 +284,15 @@ SIGNATURES = {
     "c2b_problem_set_preconditioner": (_int, [_vp, _int]),
     "c2b_problem_get_preconditioner": (_int, [_vp, C.POINTER(_int)]),
     "c2b_problem_preconditioner_fallbacks": (_int, [_vp, C.POINTER(_i64)]),
+    "c2b_problem_set_schur": (_int, [_vp, _int]),
+    "c2b_problem_get_schur": (_int, [_vp, C.POINTER(_int)]),
+    "c2b_problem_schur_bytes": (_int, [_vp, C.POINTER(_i64)]),
+    "c2b_problem_schur_complement": (_int, [_vp, _d, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "c2b_problem_get_schur_pattern": (_int, [_vp, _vp, _vp]),
+    "c2b_schur_y_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _d, _vp, _vp]),
+    "c2b_schur_y_rows_loss": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _d, _vp, _int, _d, _vp]),
+    "c2b_schur_blocks_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_schur_spmv_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_problem_set_constant": (_int, [_vp, _vp, _vp]),
     "c2b_problem_get_constant": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "c2b_problem_set_priors": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

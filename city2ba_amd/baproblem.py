@@ -323,6 +323,56 @@ class BAProblem:
         L.check(L.lib().c2b_problem_preconditioner_fallbacks(self._h, C.byref(n)))
         return n.value
 
+    def set_schur(self, kind):
+        """How solve_step applies the reduced camera system S (c2b_problem_set_schur): "implicit", two passes over
+        the observations per PCG iteration and S never formed (the default), or "explicit", S formed once per step in
+        block-CSR on the covisibility pattern and one product with the stored blocks per iteration -- an iteration then
+        costs edges, not observations, at the price of the build and of schur_bytes() of device memory.  It changes the
+        arithmetic of the iteration, not what the step converges to.  The setting belongs to the handle: uploads and culls
+        keep it, window() and subset(carry=True) carry it.  If the blocks cannot be allocated solve_step raises with the
+        bytes in the message; there is no fallback, and the handle stays usable under "implicit"."""
+        L.check(L.lib().c2b_problem_set_schur(self._h, L.schur_kind(kind)))
+
+    def schur(self):
+        """the name of the setting in force: "implicit" or "explicit" """
+        k = C.c_int()
+        L.check(L.lib().c2b_problem_get_schur(self._h, C.byref(k)))
+        return L.SCHUR_NAMES[k.value]
+
+    def schur_bytes(self):
+        """device bytes the explicit setting adds to the solve buffers, 648 (n_edges + n_cam) + 216 n_obs
+        (c2b_problem_schur_bytes); builds the pattern"""
+        n = C.c_int64()
+        L.check(L.lib().c2b_problem_schur_bytes(self._h, C.byref(n)))
+        return n.value
+
+    def schur_complement(self, lam):
+        """The reduced camera system at damping lam, built on the device (c2b_problem_schur_complement) under the handle's loss,
+        masks and priors, whatever set_schur says: (nbr_ptr [n_cam + 1] uint64, nbr [n_edges] uint32, S_diag [n_cam, 9, 9],
+        S_off [n_edges, 9, 9], b [n_cam, 9]) as numpy arrays.  Row c of S holds S_diag[c] on the diagonal and S_off[e] in block
+        column nbr[e] for e in [nbr_ptr[c], nbr_ptr[c + 1]): the covisibility graph at min_shared = 1, both triangles stored,
+        S_off of (c', c) the transpose of (c, c') bit for bit.  S dc = b is the system solve_step solves.  The call needs
+        schur_bytes() of device memory besides the arrays it returns; under "implicit" that is freed again before it returns."""
+        import torch
+        nc = self.num_cameras()
+        nbr_ptr = np.zeros(nc + 1, dtype=np.uint64)
+        L.check(L.lib().c2b_problem_get_schur_pattern(self._h, _ptr(nbr_ptr), None))
+        ne = int(nbr_ptr[-1])
+        nbr = np.zeros(ne, dtype=np.uint32)
+        if ne:
+            L.check(L.lib().c2b_problem_get_schur_pattern(self._h, None, _ptr(nbr)))
+        dev = torch.device("cuda", self._device)
+        f64 = dict(dtype=torch.float64, device=dev)
+        Sd, So, b = torch.empty((nc, 9, 9), **f64), torch.empty((ne, 9, 9), **f64), torch.empty((nc, 9), **f64)
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a.numel() else None
+        n = C.c_int64()
+        torch.cuda.current_stream(dev).synchronize()
+        # (an empty tensor has no address: a problem without cameras passes a dummy the library never writes through)
+        dummy = torch.empty(1, **f64)
+        L.check(L.lib().c2b_problem_schur_complement(self._h, float(lam), ptr(Sd) or ptr(dummy), ptr(So), ptr(b) or ptr(dummy), C.byref(n)))
+        assert n.value == ne
+        return nbr_ptr, nbr, Sd.cpu().numpy(), So.cpu().numpy(), b.cpu().numpy()
+
     def set_constant(self, cameras=None, points=None):
         """Hold camera parameters and points constant in normal_equations / solve_step / apply_step
         (c2b_problem_set_constant).  cameras: uint16 [n_cam], bit k set = parameter k constant, k in to_vec order

@@ -52,6 +52,7 @@
 #include "index_noise_kernels.hpp"
 #include "subset_kernels.hpp"
 #include "covis_kernels.hpp"
+#include "schur_explicit_kernels.hpp"
 #include "align_kernels.hpp"
 #include "text_kernels.hpp"
 #include "comm_rccl.hpp"

@@ -1307,33 +1307,14 @@ int c2b_problem_visibility_dense_fetch(c2b_problem *p, uint64_t *pt_idx, double 
 }
 
 // ---- the camera covisibility graph of the resident list and the search over it -------------------------------
-// The graph at min_shared, built on first use (degree pass, its total, fill pass) into locals and moved in on success, as
-// ensure_transpose does; kept until the list changes (drop_rows) or another threshold is asked for.
+// The graph at min_shared, built on first use (covisibility_build, capi_solve.hpp, which the solver's own pattern shares) into
+// locals and moved in on success, as ensure_transpose does; kept until the list changes (drop_rows) or another threshold is asked for.
 static int ensure_covisibility(c2b_problem *p, int min_shared) {
     if (p->cv_ptr && p->cv_min_shared == min_shared) return C2B_OK;
-    const int64_t n_cam = p->n_cam;
-    hipStream_t st = p->stream;
     DevBuf<uint64_t> ptr;
     DevBuf<uint32_t> nbr, shared;
-    DevBuf<char> temp;
-    DevBuf<int64_t> counts;
     int64_t h[2] = {0, 0};
-    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{st};      // before the locals are freed
-    HIP_TRY(ptr.alloc((size_t)n_cam + 1));
-    HIP_TRY(counts.alloc(2));
-    HIP_TRY(temp.alloc((size_t)c2b_covisibility_temp_bytes(n_cam, C2B_COVIS_TEMP_GRAPH)));
-    int rc = ensure_rows(p);
-    if (!rc && p->n_obs) rc = ensure_transpose(p);
-    if (!rc) rc = c2b_covisibility_degree_rows(p->rows_ptr, p->pt_idx, p->nt_ptr, p->nt_obs, p->nt_cam, n_cam, p->n_pts, p->n_obs, min_shared, temp, ptr,
-                                               counts, st);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(h, counts.ptr, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(nbr.alloc((size_t)h[0]));
-    HIP_TRY(shared.alloc((size_t)h[0]));
-    rc = c2b_covisibility_fill_rows(p->rows_ptr, p->pt_idx, p->nt_ptr, p->nt_obs, p->nt_cam, n_cam, p->n_pts, p->n_obs, min_shared, temp, ptr, nbr, shared, st);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
+    if (const int rc = covisibility_build(p, min_shared, ptr, nbr, shared, h)) return rc;
     p->cv_ptr = std::move(ptr); p->cv_nbr = std::move(nbr); p->cv_shared = std::move(shared);
     p->cv_min_shared = min_shared;
     p->cv_edges = h[0]; p->cv_heavy = h[1];

@@ -1984,3 +1984,96 @@ int c2b_covisibility_expand_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, c
     return C2B_OK;
     C2B_API_END("covisibility_expand_rows")
 }
+
+// ---- the explicit Schur complement (schur_explicit_kernels.hpp) ----------------------------------------------
+// one launcher per pass, asynchronous and unchecked like those of the solver's observation passes above
+static void launch_schur_y(hipStream_t st, const double *camblk, const double *pts4, const uint32_t *cam_idx, const uint32_t *pt_idx,
+                           const double *uv_obs, int64_t n_obs, const double *V, double lambda, double *Y, int kind, double scale) {
+    with_loss(kind, scale * scale, [&](auto... loss) {
+        hipLaunchKernelGGL(k_schur_y<decltype(loss)...>, dim3(blocks_for(n_obs, kSchurBlock)), dim3(kSchurBlock), 0, st, camblk, as4(pts4), cam_idx,
+                           pt_idx, as2(uv_obs), n_obs, V, lambda, Y, loss...);
+    });
+}
+
+// S_off written and the duplicated pairs' cross terms added to S_diag: the light rows a wave each, then the heavy rows
+static void launch_schur_blocks(hipStream_t st, const uint64_t *row_ptr, const uint32_t *pt_idx, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                                const uint32_t *cam_of, int64_t n_cam, const uint64_t *nbr_ptr, const uint32_t *nbr, const double *Y, double *S_diag,
+                                double *S_off) {
+    hipLaunchKernelGGL(k_schur_blocks_light, dim3((unsigned)n_cam), dim3(64), 0, st, row_ptr, pt_idx, pt_row_ptr, obs_of, cam_of, nbr_ptr, nbr, Y, S_diag,
+                       S_off);
+    hipLaunchKernelGGL(k_schur_blocks_heavy, dim3((unsigned)std::min<int64_t>(n_cam, kSxHeavyGrid)), dim3(kSxHeavyWaves * 64), 0, st, row_ptr, pt_idx,
+                       pt_row_ptr, obs_of, cam_of, nbr_ptr, nbr, n_cam, Y, S_diag, S_off);
+}
+
+// grid of k_schur_spmv (one wave per camera) and the partials its DOT instance leaves
+static unsigned schur_spmv_grid(int64_t n_cam) { return blocks_for(n_cam, kSxSpmvWaves); }
+static int64_t schur_spmv_parts(int64_t n_cam) { return (int64_t)schur_spmv_grid(n_cam) * kSxSpmvWaves; }
+
+static void launch_schur_spmv(hipStream_t st, const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_cam, const double *S_diag, const double *S_off,
+                              const double *x, double *y, double *part) {
+    const dim3 grid(schur_spmv_grid(n_cam)), block(kSxSpmvWaves * 64);
+    if (part) hipLaunchKernelGGL(k_schur_spmv<true>, grid, block, 0, st, nbr_ptr, nbr, n_cam, S_diag, S_off, x, y, part);
+    else hipLaunchKernelGGL(k_schur_spmv<false>, grid, block, 0, st, nbr_ptr, nbr, n_cam, S_diag, S_off, x, y, part);
+}
+
+int c2b_schur_y_rows_loss(const double *camblk, const double *pts4, const uint32_t *cam_idx, const uint32_t *pt_idx, const double *uv_obs,
+                          int64_t n_obs, const double *V, double lambda, double *Y, int kind, double scale, void *stream) {
+    C2B_API_BEGIN
+    NEED_LOSS(kind, scale, "schur_y_rows_loss");
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 64) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_y_rows: n_obs out of range");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_y_rows: lambda must lie in [1e-20, 1e32]");
+    if (n_obs && (!camblk || !pts4 || !cam_idx || !pt_idx || !uv_obs || !V || !Y)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_y_rows: NULL argument");
+    if (!aligned16(camblk) || !aligned16(pts4) || !aligned16(uv_obs) || !aligned8(V) || !aligned8(Y) ||
+        ((reinterpret_cast<uintptr_t>(cam_idx) | reinterpret_cast<uintptr_t>(pt_idx)) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_y_rows: misaligned pointer");
+    if (!n_obs) return C2B_OK;
+    launch_schur_y(S(stream), camblk, pts4, cam_idx, pt_idx, uv_obs, n_obs, V, lambda, Y, kind, scale);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("schur_y_rows_loss")
+}
+
+int c2b_schur_y_rows(const double *camblk, const double *pts4, const uint32_t *cam_idx, const uint32_t *pt_idx, const double *uv_obs,
+                     int64_t n_obs, const double *V, double lambda, double *Y, void *stream) {
+    return c2b_schur_y_rows_loss(camblk, pts4, cam_idx, pt_idx, uv_obs, n_obs, V, lambda, Y, 0, 1.0, stream);
+}
+
+// the pattern's pointers and count, as both entries below take them
+static int schur_pattern_check(const char *who, const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_cam) {
+    if (n_cam < 0 || n_cam >= (int64_t)1 << 31) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: n_cam out of range", who);
+    if (n_cam && !nbr_ptr) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: NULL argument (nbr_ptr)", who);
+    if (!aligned8(nbr_ptr) || (reinterpret_cast<uintptr_t>(nbr) & 3)) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: misaligned pointer (nbr_ptr 8 bytes, nbr 4)", who);
+    return C2B_OK;
+}
+
+int c2b_schur_blocks_rows(const uint64_t *row_ptr, const uint32_t *pt_idx, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                          const uint32_t *cam_of, int64_t n_cam, int64_t n_obs, const uint64_t *nbr_ptr, const uint32_t *nbr,
+                          const double *Y, double *S_diag, double *S_off, void *stream) {
+    C2B_API_BEGIN
+    if (const int rc = schur_pattern_check("schur_blocks_rows", nbr_ptr, nbr, n_cam)) return rc;
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff - 64) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_blocks_rows: n_obs out of range");
+    if ((n_cam && (!row_ptr || !S_diag)) || (n_obs && (!pt_idx || !pt_row_ptr || !obs_of || !cam_of || !Y || !n_cam)))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_blocks_rows: NULL argument, or observations without cameras");
+    if (!aligned8(row_ptr) || !aligned8(pt_row_ptr) || !aligned8(Y) || !aligned8(S_diag) || !aligned8(S_off) ||
+        ((reinterpret_cast<uintptr_t>(pt_idx) | reinterpret_cast<uintptr_t>(obs_of) | reinterpret_cast<uintptr_t>(cam_of)) & 3))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_blocks_rows: misaligned pointer (row pointers and doubles 8 bytes, indices 4)");
+    if (!n_cam || !n_obs) return C2B_OK;                     // no observation: no edge and no duplicated pair
+    launch_schur_blocks(S(stream), row_ptr, pt_idx, pt_row_ptr, obs_of, cam_of, n_cam, nbr_ptr, nbr, Y, S_diag, S_off);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("schur_blocks_rows")
+}
+
+int c2b_schur_spmv_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_cam, const double *S_diag, const double *S_off,
+                        const double *x, double *y, double *part, void *stream) {
+    C2B_API_BEGIN
+    if (const int rc = schur_pattern_check("schur_spmv_rows", nbr_ptr, nbr, n_cam)) return rc;
+    if (n_cam && (!S_diag || !x || !y)) return fail(C2B_ERR_INVALID_ARGUMENT, "schur_spmv_rows: NULL argument");
+    if (!aligned8(S_diag) || !aligned8(S_off) || !aligned8(x) || !aligned8(y) || !aligned8(part))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "schur_spmv_rows: misaligned pointer");
+    if (!n_cam) return C2B_OK;
+    launch_schur_spmv(S(stream), nbr_ptr, nbr, n_cam, S_diag, S_off, x, y, part);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("schur_spmv_rows")
+}

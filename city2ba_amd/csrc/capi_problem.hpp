@@ -29,6 +29,9 @@ struct c2b_problem {
     // 1 Schur-Jacobi), the handle's too; and how many cameras' Schur-Jacobi factors fell back in the last solve
     int precond_kind = 0;
     int64_t precond_fallbacks = 0;
+    // c2b_problem_set_schur: how c2b_problem_solve_step applies S (0 implicit, never formed; 1 explicit, block-CSR
+    // on the covisibility pattern), the handle's too
+    int schur_kind = 0;
     // c2b_problem_set_constant: the camera parameters (bit k of a camera's word, to_vec order) and the points
     // (0 / 1) that normal_equations / solve_step / apply_step hold constant; the handle's, kept while both counts stay
     // what they were set for (const_n_cam, const_n_pts).  A kind with nothing set has no array: no launch changes for it.
@@ -64,6 +67,11 @@ struct c2b_problem {
     DevBuf<uint32_t> cv_nbr, cv_shared;
     int cv_min_shared = 0;
     int64_t cv_edges = 0, cv_heavy = 0;
+    // the sparsity pattern of the explicit S: the solver's OWN copy of the graph at threshold 1 (sp_ptr [n_cam + 1],
+    // sp_nbr [sp_edges]), so that a covisibility call at another threshold does not disturb it; derived from the list, dropped with it
+    DevBuf<uint64_t> sp_ptr;
+    DevBuf<uint32_t> sp_nbr;
+    int64_t sp_edges = 0;
     // c2b_problem_checkpoint: bal9 and pts4 as they were when it was taken, what c2b_problem_rollback copies
     // back.  Allocated on first use and reused while the counts stay; ck_valid says whether they hold a checkpoint.
     // lm: the scratch of c2b_problem_levenberg_marquardt (its step, the partials and scalars of k_lm_norms /
@@ -96,34 +104,35 @@ struct c2b_problem {
 
 // Which event drops which cache or handle state.  X: dropped (rebuilt by the next user, or gone), -: stays.  The functions
 // below and cameras_mutated are the table's implementation; the list's three caches go together (drop_rows), and the
-// covisibility graph (c2b_problem_covisibility) goes with them: wherever the transpose column says X, it is dropped.
-//                              camblk/cen4  bal9       rows  transpose  solve  pending vis.  masks       checkpoint/LM
-//   upload, upload_bal         X            X / truth  X     X          X      X             - / X (1)   X
-//   layout (grid, line)        X            X          X     X          X      X             X           X
-//   read (.bal, .bbal)         X            truth      X     X          X      X             X           X
-//   cull                       X            - (2)      X     X          X      X (3)         X           X
-//   adopt_visibility           -            -          X     X          X      X (spent)     -           -
-//   filter (4)                 -            -          X     X          X      -             -           -
-//   generate_world_points      -            -          X     X          X      X             X           X
-//   apply_step, rollback (5)   X            truth      -     -          -      -             -           -
-//   noise (drift, noise, sin)  X            X          -     -          -      -             -           -
-//   transform (14)             X            X          -     -          -      -             -           -
-//   triangulate_points         -            -          -     -          -      -             -           -
-//   refine_points              -            -          -     -          -      -             -           -
-//   triangulate_consensus (6)  -            -          - / X - / X      - / X  -             -           -
-//   resect_cameras             X            truth      -     -          -      -             -           -
-//   refine_cameras             X            truth      -     -          -      -             -           -
-//   resect_consensus (6)       X            truth      - / X - / X      - / X  -             -           -
-//   merge_points (7)           -            -          - / X - / X      - / X  -             -           -
-//   rematch_observations (8)   -            -          - / X - / X      - / X  -             -           -
-//   drop_features (4)          -            -          X     X          X      -             -           -
-//   mismatch, join (12)        -            -          - / X - / X      - / X  -             -           -
-//   split_landmarks (13)       -            -          X     X          X      X             X           X
-//   subset, window: src        -            - (9)      -     -          -      -             -           -
-//   subset, window: dst (10)   X            X / truth  X     X          X      X             X / carried X
-//   get_origin                 -            -          -     -          -      -             -           -
-//   write_back: parent         X            truth      -     -          -      -             -           -
-//   write_back: child (11)     - / X        - / truth  -     -          -      -             -           -
+// covisibility graph (c2b_problem_covisibility) goes with them: wherever the transpose column says X, it is dropped.  "S pattern" is the
+// solver's own copy of the graph at threshold 1: it goes in drop_rows too, with the blocks it addresses.
+//                              camblk/cen4  bal9       rows  transpose  solve  S pattern  pending vis.  masks       checkpoint/LM
+//   upload, upload_bal         X            X / truth  X     X          X      X          X             - / X (1)   X
+//   layout (grid, line)        X            X          X     X          X      X          X             X           X
+//   read (.bal, .bbal)         X            truth      X     X          X      X          X             X           X
+//   cull                       X            - (2)      X     X          X      X          X (3)         X           X
+//   adopt_visibility           -            -          X     X          X      X          X (spent)     -           -
+//   filter (4)                 -            -          X     X          X      X          -             -           -
+//   generate_world_points      -            -          X     X          X      X          X             X           X
+//   apply_step, rollback (5)   X            truth      -     -          -      -          -             -           -
+//   noise (drift, noise, sin)  X            X          -     -          -      -          -             -           -
+//   transform (14)             X            X          -     -          -      -          -             -           -
+//   triangulate_points         -            -          -     -          -      -          -             -           -
+//   refine_points              -            -          -     -          -      -          -             -           -
+//   triangulate_consensus (6)  -            -          - / X - / X      - / X  - / X      -             -           -
+//   resect_cameras             X            truth      -     -          -      -          -             -           -
+//   refine_cameras             X            truth      -     -          -      -          -             -           -
+//   resect_consensus (6)       X            truth      - / X - / X      - / X  - / X      -             -           -
+//   merge_points (7)           -            -          - / X - / X      - / X  - / X      -             -           -
+//   rematch_observations (8)   -            -          - / X - / X      - / X  - / X      -             -           -
+//   drop_features (4)          -            -          X     X          X      X          -             -           -
+//   mismatch, join (12)        -            -          - / X - / X      - / X  - / X      -             -           -
+//   split_landmarks (13)       -            -          X     X          X      X          X             X           X
+//   subset, window: src        -            - (9)      -     -          -      -          -             -           -
+//   subset, window: dst (10)   X            X / truth  X     X          X      X          X             X / carried X
+//   get_origin                 -            -          -     -          -      -          -             -           -
+//   write_back: parent         X            truth      -     -          -      -          -             -           -
+//   write_back: child (11)     - / X        - / truth  -     -          -      -          -             -           -
 // The priors (c2b_problem_set_priors) share the masks' column: kept and dropped with them, by counts of their own.
 // (1) kept when both counts are those the masks were set for.  (2) gathered with the cameras while it is the truth; a merely
 // fresh bal9 (bal9_fresh: to_vec of the current cameras, filled by download_bal / write / apply_step) is dropped.  (3) on
@@ -148,7 +157,7 @@ static void free_dense(c2b_problem *p) {
     p->dense_n = 0;
 }
 
-// what is derived from the observation list: row structure, transpose, solve buffers, covisibility graph
+// what is derived from the observation list: row structure, transpose, solve buffers, covisibility graph, the pattern of S
 static void drop_rows(c2b_problem *p) {
     p->rows_ptr.reset(); p->rows_tiles.reset();
     p->nt_ptr.reset(); p->nt_obs.reset(); p->nt_cam.reset();
@@ -157,6 +166,8 @@ static void drop_rows(c2b_problem *p) {
     p->cv_ptr.reset(); p->cv_nbr.reset(); p->cv_shared.reset();
     p->cv_min_shared = 0;
     p->cv_edges = p->cv_heavy = 0;
+    p->sp_ptr.reset(); p->sp_nbr.reset();
+    p->sp_edges = 0;
 }
 
 // the masks: nothing is constant any more

@@ -319,6 +319,25 @@ int c2b_problem_preconditioner_fallbacks(const c2b_problem *p, int64_t *n) {
     C2B_API_END("problem_preconditioner_fallbacks")
 }
 
+// ---- how the step applies S ---------------------------------------------------------------------------------
+int c2b_problem_set_schur(c2b_problem *p, int kind) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_schur: problem is NULL");
+    if (kind != C2B_SCHUR_IMPLICIT && kind != C2B_SCHUR_EXPLICIT)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_schur: kind must be 0 (implicit) or 1 (explicit), not %d", kind);
+    p->schur_kind = kind;
+    return C2B_OK;
+    C2B_API_END("problem_set_schur")
+}
+
+int c2b_problem_get_schur(const c2b_problem *p, int *kind) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_schur: problem is NULL");
+    if (kind) *kind = p->schur_kind;
+    return C2B_OK;
+    C2B_API_END("problem_get_schur")
+}
+
 // sum over the observations of rho(s) (weighted_sq: of w s) under the problem's loss into out[0] (device), asynchronous;
 // one partial per workgroup of 256 observations: the workspace holds one per 4 tiles of 64 (block_part_slots)
 static int robust_sum(c2b_problem *p, bool weighted_sq, double *out) {
@@ -410,20 +429,28 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
 // ---- damped Gauss-Newton step (schur_kernels.hpp) ------------------------------------------------------------------
 // c2b_problem::sv, carved: U [n_cam][81], gc [n_cam][9], V [n_pts][9], gp [n_pts][3], Lf [n_cam][45], t [n_pts][3],
 // r / z / p / q [n_cam][9], two partial arrays [n_part], the device scalars [kScSlots]; under the Schur-Jacobi
-// preconditioner its blocks M [n_cam][81] after them (the rest lies where it lies without)
+// preconditioner its blocks M [n_cam][81] after them (the rest lies where it lies without); under the explicit Schur
+// complement its blocks Sd [n_cam][81], So [sp_edges][81] and Y [n_obs][27] after those, and the partial arrays
+// also cover k_schur_spmv's grid.  With neither option nothing moves.
 struct SolveBufs {
-    double *U, *gc, *V, *gp, *Lf, *t, *r, *z, *pv, *q, *pa, *pb, *sc, *M;
+    double *U, *gc, *V, *gp, *Lf, *t, *r, *z, *pv, *q, *pa, *pb, *sc, *M, *Sd, *So, *Y;
     int64_t n_part;
 };
 
+static bool schur_explicit(const c2b_problem *p) { return p->schur_kind == C2B_SCHUR_EXPLICIT; }
+
 static int64_t solve_parts(const c2b_problem *p) {
     const int64_t a = (int64_t)schur_cameras_grid(p->n_cam) * (kNormBlock / 64);
-    return std::max<int64_t>({a, (int64_t)blocks_for(p->n_cam, kSchurBlock), (int64_t)blocks_for(p->n_obs, kSchurBlock), 1});
+    const int64_t e = schur_explicit(p) ? schur_spmv_parts(p->n_cam) : 0;
+    return std::max<int64_t>({a, e, (int64_t)blocks_for(p->n_cam, kSchurBlock), (int64_t)blocks_for(p->n_obs, kSchurBlock), 1});
 }
+
+// the doubles the explicit Schur complement adds: its blocks and Y (the pattern is built before this is asked)
+static int64_t schur_explicit_doubles(const c2b_problem *p) { return 81 * (p->n_cam + p->sp_edges) + 27 * p->n_obs; }
 
 static int64_t solve_doubles(const c2b_problem *p) {
     return p->n_cam * (81 + 9 + kCholPacked + 4 * 9) + p->n_pts * (9 + 3 + 3) + 2 * solve_parts(p) + kScSlots +
-           (p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? 81 * p->n_cam : 0);
+           (p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? 81 * p->n_cam : 0) + (schur_explicit(p) ? schur_explicit_doubles(p) : 0);
 }
 
 static SolveBufs solve_bufs(c2b_problem *p) {
@@ -436,6 +463,10 @@ static SolveBufs solve_bufs(c2b_problem *p) {
     b.n_part = solve_parts(p);
     b.pa = take(b.n_part); b.pb = take(b.n_part); b.sc = take(kScSlots);
     b.M = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? take(81 * nc) : nullptr;
+    const bool ex = schur_explicit(p);
+    b.Sd = ex ? take(81 * nc) : nullptr;
+    b.So = ex ? take(81 * p->sp_edges) : nullptr;
+    b.Y = ex ? take(27 * p->n_obs) : nullptr;
     return b;
 }
 
@@ -444,8 +475,60 @@ static int ensure_solver(c2b_problem *p) {
     if (p->sv && p->sv_doubles >= n) return C2B_OK;
     p->sv_doubles = 0;
     const hipError_t e = p->sv.alloc((size_t)n);                  // (the smaller one is freed first)
+    if (e != hipSuccess && schur_explicit(p))                    // no fallback: the caller sets C2B_SCHUR_IMPLICIT, the handle is usable
+        return fail(hip_code(e), "problem_solve_step: allocation of %lld bytes for the explicit Schur complement (%lld of them its blocks and Y): %s",
+                    (long long)(8 * n), (long long)(8 * schur_explicit_doubles(p)), hipGetErrorString(e));
     if (e != hipSuccess) return fail(hip_code(e), "problem_solve_step: allocation: %s", hipGetErrorString(e));
     p->sv_doubles = n;
+    return C2B_OK;
+}
+
+// The covisibility graph of the resident list at min_shared into the caller's buffers (degree pass, its total, fill pass):
+// counts[0] = the directed edges, counts[1] = the cameras that took the heavy path.  Synchronous.
+static int covisibility_build(c2b_problem *p, int min_shared, DevBuf<uint64_t> &ptr, DevBuf<uint32_t> &nbr, DevBuf<uint32_t> &shared, int64_t counts_out[2]) {
+    const int64_t n_cam = p->n_cam;
+    hipStream_t st = p->stream;
+    DevBuf<char> temp;
+    DevBuf<int64_t> counts;
+    counts_out[0] = counts_out[1] = 0;
+    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{st};      // before the locals are freed
+    HIP_TRY(ptr.alloc((size_t)n_cam + 1));
+    HIP_TRY(counts.alloc(2));
+    HIP_TRY(temp.alloc((size_t)c2b_covisibility_temp_bytes(n_cam, C2B_COVIS_TEMP_GRAPH)));
+    int rc = ensure_rows(p);
+    if (!rc && p->n_obs) rc = ensure_transpose(p);
+    if (!rc) rc = c2b_covisibility_degree_rows(p->rows_ptr, p->pt_idx, p->nt_ptr, p->nt_obs, p->nt_cam, n_cam, p->n_pts, p->n_obs, min_shared, temp, ptr,
+                                               counts, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(counts_out, counts.ptr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(nbr.alloc((size_t)counts_out[0]));
+    HIP_TRY(shared.alloc((size_t)counts_out[0]));
+    rc = c2b_covisibility_fill_rows(p->rows_ptr, p->pt_idx, p->nt_ptr, p->nt_obs, p->nt_cam, n_cam, p->n_pts, p->n_obs, min_shared, temp, ptr, nbr, shared, st);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return C2B_OK;
+}
+
+// The pattern of the explicit S: the graph at threshold 1, the solver's own.  Copied from the cached graph when
+// that is at threshold 1, built by the same passes otherwise; kept until the list changes (drop_rows).
+static int ensure_schur_pattern(c2b_problem *p) {
+    if (p->sp_ptr) return C2B_OK;
+    DevBuf<uint64_t> ptr;
+    DevBuf<uint32_t> nbr, shared;
+    int64_t h[2] = {0, 0};
+    if (p->cv_ptr && p->cv_min_shared == 1) {
+        h[0] = p->cv_edges;
+        HIP_TRY(ptr.alloc((size_t)p->n_cam + 1));
+        HIP_TRY(nbr.alloc((size_t)h[0]));
+        HIP_TRY(hipMemcpyAsync(ptr, p->cv_ptr, sizeof(uint64_t) * ((size_t)p->n_cam + 1), hipMemcpyDeviceToDevice, p->stream));
+        if (h[0]) HIP_TRY(hipMemcpyAsync(nbr, p->cv_nbr, sizeof(uint32_t) * (size_t)h[0], hipMemcpyDeviceToDevice, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    } else if (const int rc = covisibility_build(p, 1, ptr, nbr, shared, h)) {
+        return rc;
+    }
+    p->sp_ptr = std::move(ptr); p->sp_nbr = std::move(nbr);
+    p->sp_edges = h[0];
     return C2B_OK;
 }
 
@@ -486,6 +569,40 @@ static int step_preconditioner(c2b_problem *p, const SolveBufs &B, double lambda
     return C2B_OK;
 }
 
+// The set-up under the explicit Schur complement, in place of step_preconditioner: S into B.Sd / B.So on the
+// handle's pattern, then -- want_factors -- the same preconditioner's factors.  V comes in as step_preconditioner's Schur-Jacobi
+// branch takes it (the constant points' at kConstPointV: their Y is 0) and leaves as it leaves there.
+//   Sd = M of k_schur_jacobi (it does not cancel at small lambda), the priors and the constant zeros as they follow M; M is a
+//   copy of it at that point, its definition unchanged; then k_schur_blocks adds the cross terms of duplicated pairs, which
+//   are S's and not M's, and the constant zeros follow once more, now also on the off-diagonal blocks.
+static int schur_explicit_setup(c2b_problem *p, const SolveBufs &B, double lambda, bool want_factors) {
+    hipStream_t st = p->stream;
+    const int64_t nc = p->n_cam;
+    const unsigned nbc = blocks_for(nc, kSchurBlock);
+    launch_schur_jacobi(st, p->camblk, p->pts4, p->rows_ptr, nc, p->pt_idx, p->uv, B.U, B.V, lambda, B.Sd, p->loss_kind, p->loss_scale);
+    int rc = stack_cameras(p, B.Sd, nullptr, lambda * 1e-6, false);
+    if (rc) return rc;
+    if (B.M && want_factors) HIP_TRY(hipMemcpyAsync(B.M, B.Sd, sizeof(double) * 81 * (size_t)nc, hipMemcpyDeviceToDevice, st));
+    launch_schur_y(st, p->camblk, p->pts4, p->cam_idx, p->pt_idx, p->uv, p->n_obs, B.V, lambda, B.Y, p->loss_kind, p->loss_scale);
+    if ((rc = constant_points(p, B.V, 0.0, nullptr))) return rc;
+    launch_schur_blocks(st, p->rows_ptr, p->pt_idx, p->nt_ptr, p->nt_obs, p->nt_cam, nc, p->sp_ptr, p->sp_nbr, B.Y, B.Sd, B.So);
+    if (p->cmask) {
+        if ((rc = constant_cameras(p, B.Sd, lambda * 1e-6, nullptr))) return rc;
+        hipLaunchKernelGGL(k_const_offdiag, dim3(blocks_for(nc, 4)), dim3(256), 0, st, (const uint64_t *)p->sp_ptr, (const uint32_t *)p->sp_nbr, nc,
+                           (const uint16_t *)p->cmask, B.So);
+    }
+    LAUNCH_CHECK();
+    if (!want_factors) return C2B_OK;
+    if (!B.M) {
+        hipLaunchKernelGGL(k_schur_factor, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.U, lambda, B.Lf);
+        return C2B_OK;
+    }
+    hipLaunchKernelGGL(k_schur_factor_blocks, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.M, (const double *)B.U, lambda,
+                       B.Lf, B.pa);
+    fold_sum(st, B.pa, (int)nbc, B.sc + kScFallback);
+    return C2B_OK;
+}
+
 // PCG on the reduced system from x = 0 (x is dc), its right-hand side b in B.r: the iterations run, the status (0 converged,
 // 1 max_iters reached, 2 a breakdown or a non-finite number), |b|^2 and the last |r|.  One read-back per iteration.
 struct PcgResult {
@@ -515,8 +632,14 @@ static int schur_pcg(c2b_problem *p, const SolveBufs &B, double lambda, int max_
         while (it < max_iters) {
             const int cur = (it & 1) ? kScRz1 : kScRz0, nxt = (it & 1) ? kScRz0 : kScRz1;
             // q = S p and the p.q partials (p's constant entries are 0: they need no correction)
-            if ((rc = schur_apply(p, B, lambda, B.pv, nullptr, B.t, false, nullptr, B.q, B.pa))) return rc;
-            fold_sum(st, B.pa, (int)(schur_cameras_grid(nc) * (kNormBlock / 64)), B.sc + kScPq);
+            // (explicit: one product with the stored blocks, whose constant rows are 0 already)
+            if (B.So) {
+                launch_schur_spmv(st, p->sp_ptr, p->sp_nbr, nc, B.Sd, B.So, B.pv, B.q, B.pa);
+                fold_sum(st, B.pa, (int)schur_spmv_parts(nc), B.sc + kScPq);
+            } else {
+                if ((rc = schur_apply(p, B, lambda, B.pv, nullptr, B.t, false, nullptr, B.q, B.pa))) return rc;
+                fold_sum(st, B.pa, (int)(schur_cameras_grid(nc) * (kNormBlock / 64)), B.sc + kScPq);
+            }
             hipLaunchKernelGGL(k_pcg_update<false>, dim3(nbc), dim3(kSchurBlock), 0, st, nc, (const double *)B.Lf, (const double *)B.sc,
                                cur, dc, B.r, B.pv, (const double *)B.q, B.z, B.pa, B.pb);
             fold_sum(st, B.pa, (int)nbc, B.sc + kScRr);
@@ -591,6 +714,8 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     int rc = ensure_camblk(p);
     if (!rc) rc = ensure_rows(p);
     if (!rc) rc = ensure_transpose(p);
+    const bool ex = schur_explicit(p);
+    if (!rc && ex) rc = ensure_schur_pattern(p);
     if (!rc) rc = ensure_solver(p);
     if (rc) return rc;
     const SolveBufs B = solve_bufs(p);
@@ -598,8 +723,8 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     // from here on, and so is the damping's diagonal.  The constant points' V: see step_preconditioner
     PcgResult pcg{0, 1, 0.0, 0.0};
     rc = assemble_cameras(p, B.U, B.gc, 0.0, false);
-    if (!rc) rc = assemble_points(p, B.V, B.gp, B.M ? kConstPointV : 0.0, false);
-    if (!rc) rc = step_preconditioner(p, B, lambda);
+    if (!rc) rc = assemble_points(p, B.V, B.gp, B.M || ex ? kConstPointV : 0.0, false);
+    if (!rc) rc = ex ? schur_explicit_setup(p, B, lambda, true) : step_preconditioner(p, B, lambda);
     if (!rc) rc = schur_apply(p, B, lambda, nullptr, B.gp, B.t, false, B.gc, B.r, nullptr);      // b = -gc + W V_l^-1 gp into r
     if (!rc) rc = schur_pcg(p, B, lambda, max_iters, rel_tol, dc, &pcg);
     if (!rc) rc = step_model(p, B, lambda, dc, dp, &out.sum_sq, &out.model_decrease);
@@ -619,6 +744,86 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     if (info) *info = out;
     return C2B_OK;
     C2B_API_END("problem_solve_step")
+}
+
+// ---- the reduced camera system as a product ------------------------------------------------------------------
+int c2b_problem_schur_bytes(c2b_problem *p, int64_t *bytes) {
+    C2B_API_BEGIN
+    if (!p || !bytes) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_bytes: NULL argument");
+    NEED_UPLOADED(p, "problem_schur_bytes");
+    if (p->shard_n_cam_global >= 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_bytes: a shard cannot be solved alone");
+    if (const int rc = ensure_schur_pattern(p)) return rc;
+    *bytes = 8 * schur_explicit_doubles(p);
+    return C2B_OK;
+    C2B_API_END("problem_schur_bytes")
+}
+
+int c2b_problem_get_schur_pattern(c2b_problem *p, uint64_t *nbr_ptr, uint32_t *nbr) {
+    C2B_API_BEGIN
+    NEED_UPLOADED(p, "problem_get_schur_pattern");
+    if (p->shard_n_cam_global >= 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_schur_pattern: a shard cannot be solved alone");
+    if (const int rc = ensure_schur_pattern(p)) return rc;
+    const size_t ne = (size_t)p->sp_edges;
+    if (nbr_ptr) HIP_TRY(hipMemcpyAsync(nbr_ptr, p->sp_ptr, sizeof(uint64_t) * ((size_t)p->n_cam + 1), hipMemcpyDeviceToHost, p->stream));
+    if (nbr && ne) HIP_TRY(hipMemcpyAsync(nbr, p->sp_nbr, sizeof(uint32_t) * ne, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return C2B_OK;
+    C2B_API_END("problem_get_schur_pattern")
+}
+
+int c2b_problem_schur_complement(c2b_problem *p, double lambda, double *S_diag, double *S_off, double *b, int64_t *n_edges) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_complement: problem is NULL");
+    if (!S_diag || !b || !n_edges) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_complement: NULL argument (S_diag, b, n_edges)");
+    if (!aligned8(S_diag) || !aligned8(S_off) || !aligned8(b)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_complement: misaligned pointer");
+    if (!good_lambda(lambda)) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_complement: lambda must lie in [1e-20, 1e32]");
+    NEED_UPLOADED(p, "problem_schur_complement");
+    if (p->shard_n_cam_global >= 0)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_complement: a shard has no reduced system of its own (the point-side sums span every rank)");
+    const int64_t nc = p->n_cam, no = p->n_obs;
+    hipStream_t st = p->stream;
+    if (!no && has_priors(p))
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_complement: priors without a single observation are not solved (DESIGN 4.13)");
+    int rc = ensure_schur_pattern(p);
+    if (rc) return rc;
+    if (p->sp_edges && !S_off) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_schur_complement: S_off is NULL and the pattern has %lld edges", (long long)p->sp_edges);
+    *n_edges = p->sp_edges;
+    if (!no) {                                               // no observation: U = 0, its damped diagonal alone; b = 0
+        std::vector<double> h(81 * (size_t)nc, 0.0);
+        for (int64_t c = 0; c < nc; ++c)
+            for (int k = 0; k < 9; ++k) h[(size_t)c * 81 + k * 10] = lambda * 1e-6;
+        if (nc) HIP_TRY(hipMemcpyAsync(S_diag, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
+        if (nc) HIP_TRY(hipMemsetAsync(b, 0, sizeof(double) * 9 * (size_t)nc, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return C2B_OK;
+    }
+    rc = ensure_camblk(p);
+    if (!rc) rc = ensure_rows(p);
+    if (!rc) rc = ensure_transpose(p);
+    if (rc) return rc;
+    // the buffers in the explicit layout, whatever the handle's setting is (it is put back at once).  Under an implicit handle
+    // they are freed again before returning: S and Y are gigabytes at scale, and an implicit solve has no use for them
+    const int keep = p->schur_kind;
+    p->schur_kind = C2B_SCHUR_EXPLICIT;
+    rc = ensure_solver(p);
+    const SolveBufs B = solve_bufs(p);
+    p->schur_kind = keep;
+    if (rc) return rc;
+    rc = assemble_cameras(p, B.U, B.gc, 0.0, false);
+    if (!rc) rc = assemble_points(p, B.V, B.gp, kConstPointV, false);
+    if (!rc) rc = schur_explicit_setup(p, B, lambda, false);
+    if (!rc) rc = schur_apply(p, B, lambda, nullptr, B.gp, B.t, false, B.gc, B.r, nullptr);      // b, as the step forms it
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(S_diag, B.Sd, sizeof(double) * 81 * (size_t)nc, hipMemcpyDeviceToDevice, st));
+    if (p->sp_edges) HIP_TRY(hipMemcpyAsync(S_off, B.So, sizeof(double) * 81 * (size_t)p->sp_edges, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b, B.r, sizeof(double) * 9 * (size_t)nc, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (keep != C2B_SCHUR_EXPLICIT) {                        // (the next solve allocates its own, smaller, buffers)
+        p->sv.reset();
+        p->sv_doubles = 0;
+    }
+    return C2B_OK;
+    C2B_API_END("problem_schur_complement")
 }
 
 // ---- bal9 made the truth (the apply_step / rollback / resect rows of the table above cameras_mutated) -------------------

@@ -59,6 +59,7 @@ void adopt_problem(c2b_problem *dst, c2b_problem &t, const c2b_problem *src, Chi
         dst->loss_kind = src->loss_kind; dst->loss_scale = src->loss_scale;
         dst->inner_rounds = src->inner_rounds;
         dst->precond_kind = src->precond_kind;
+        dst->schur_kind = src->schur_kind;
         dst->precond_fallbacks = 0;
     }
     if (L.origin) {

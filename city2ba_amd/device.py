@@ -583,6 +583,39 @@ def schur_cameras_rows(camblk, pts4, rows, pt_idx, uv, U, lam, x, t, y, loss=Non
     return y
 
 
+SCHUR_LDS_BLOCKS = 32       # C2B_SCHUR_LDS_BLOCKS: a row of at most this many neighbours accumulates its blocks of S in LDS
+
+
+def schur_y_rows(camblk, pts4, cam_idx, pt_idx, uv, V, lam, Y, loss=None):
+    """per observation Y [n_obs,3,9] = L^-1 Jp^T Jc with V_l = L L^T of the observation's point (c2b_schur_y_rows):
+    cam_idx [n_obs] int32 (expand_rows), V as normal_points_rows filled it; W_o V_l^-1 W_o'^T = Y_o^T Y_o' for two
+    observations of one point.  loss as in normal_cameras_rows"""
+    n_obs = pt_idx.shape[0]
+    if loss is not None:
+        L.check(L.lib().c2b_schur_y_rows_loss(_p(camblk), _p(pts4), _p(cam_idx), _p(pt_idx), _p(uv), n_obs, _p(V), float(lam), _p(Y),
+                                              *_loss_args(loss), _stream()))
+        return Y
+    L.check(L.lib().c2b_schur_y_rows(_p(camblk), _p(pts4), _p(cam_idx), _p(pt_idx), _p(uv), n_obs, _p(V), float(lam), _p(Y), _stream()))
+    return Y
+
+
+def schur_blocks_rows(rows, pt_idx, prows, nbr_ptr, nbr, Y, S_diag, S_off):
+    """the blocks of the explicit Schur complement on the pattern (nbr_ptr, nbr) = covisibility_rows(rows, pt_idx, prows, 1)
+    (c2b_schur_blocks_rows): S_off [n_edges,9,9] written, both (c, c') and its transpose at (c', c); the cross terms of
+    duplicated (camera, point) pairs added to S_diag [n_cam,9,9], which holds schur_jacobi_blocks' M on entry and S's
+    diagonal blocks on exit"""
+    L.check(L.lib().c2b_schur_blocks_rows(_p(rows.row_ptr), _p(pt_idx), _p(prows.pt_row_ptr), _p(prows.obs_of), _p(prows.cam_of), rows.n_cam,
+                                          rows.n_obs, _p(nbr_ptr), _p(nbr), _p(Y), _p(S_diag), _p(S_off), _stream()))
+    return S_diag, S_off
+
+
+def schur_spmv_rows(nbr_ptr, nbr, S_diag, S_off, x, y, part=None):
+    """y [n_cam,9] = S x with the stored blocks (c2b_schur_spmv_rows); part [4 ceil(n_cam / 4)], when given, takes x.y as one
+    partial per wave"""
+    L.check(L.lib().c2b_schur_spmv_rows(_p(nbr_ptr), _p(nbr), S_diag.shape[0], _p(S_diag), _p(S_off), _p(x), _p(y), _p(part), _stream()))
+    return y
+
+
 def _prior_pair(target, w, n, name):
     """a (target, weights) pair of a prior: both None, or both [n, 3] float64 on the device"""
     if (target is None) != (w is None):

@@ -18,7 +18,7 @@ def _clamp(lam):
 
 
 def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0, preconditioner=None, constant=None,
-                        priors=None, inner_iterations=None):
+                        priors=None, inner_iterations=None, schur=None):
     """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
     sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
     and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit); lam is held
@@ -43,7 +43,12 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     is.  With n > 0 in force, after a step is applied and before its cost is taken, every point is re-minimised against the
     moved cameras by ba.refine_points(rounds=n) (Ceres' inner iterations with the points as the inner block).
     The cost compared is the one after the refinement, so the gain ratio may exceed 1; a rejected step restores the points
-    as before."""
+    as before.
+    schur = "implicit" | "explicit" (BAProblem.set_schur, which this calls: it stays on ba); None leaves ba's setting as it is.
+    Explicit forms the reduced camera system once per step and iterates on the stored blocks: the steps converge
+    to the same solution."""
+    if schur is not None:
+        ba.set_schur(schur)
     if inner_iterations is not None:
         ba.set_inner_iterations(inner_iterations)
     n_inner = ba.inner_iterations()
@@ -94,7 +99,7 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
 
 def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, function_tol=0.0, gradient_tol=0.0,
                                parameter_tol=0.0, loss=None, loss_scale=1.0, preconditioner=None, constant=None, priors=None,
-                               inner_iterations=None):
+                               inner_iterations=None, schur=None):
     """levenberg_marquardt's loop inside the library (c2b_problem_levenberg_marquardt): the same steps, the same damping
     and the same numbers, with a device-side checkpoint and rollback where the loop above downloads and uploads, and with
     stopping tests.  Returns (history, summary).
@@ -109,10 +114,13 @@ def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_t
     is the last accepted one).  A tolerance of 0 disables its test: with all three at 0 this is levenberg_marquardt,
     iteration for iteration.  loss, preconditioner, constant and priors as there: with priors in force every cost is the
     observations' cost + the priors', and the gradient test reads the gradient of the stacked system.
-    inner_iterations as there: set on the handle when given, left as it is when None; the library's loop honours the handle's."""
+    inner_iterations and schur as there: set on the handle when given, left as they are when None; the library's loop honours
+    the handle's."""
     import ctypes as C
 
     from . import _lib as L
+    if schur is not None:
+        ba.set_schur(schur)
     if priors is not None:
         ba.set_priors(**priors)
     if constant is not None:

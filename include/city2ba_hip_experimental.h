@@ -906,6 +906,64 @@ int c2b_problem_get_covisibility(c2b_problem *p, uint64_t *nbr_ptr, uint32_t *nb
 int c2b_problem_neighbourhood(c2b_problem *p, const uint8_t *seed, int hops, int min_shared, int64_t max_cameras, const uint8_t *within,
                               uint8_t *member, int32_t *level, int64_t *n);
 
+/* ---- the explicit Schur complement on the covisibility pattern ----
+ * c2b_problem_solve_step solves S dc = b, S = U_l - W V_l^-1 W^T, without forming S.  With C2B_SCHUR_EXPLICIT it forms S once per
+ * call in block-CSR and runs the same PCG on the stored blocks; the step it converges to is the same.  Notation as above: U, V, gc, gp
+ * are the stacked system's (priors in, constant rows and columns zeroed), W_o = w_o Jc_o^T Jp_o with w_o the loss's weight, U_l and
+ * V_l are damped by the clamp rule.
+ * Pattern: the covisibility graph above at min_shared = 1, plus the diagonal: nbr_ptr [n_cam + 1] (uint64), nbr [n_edges] (uint32,
+ *   ascending, no self edge).  The handle keeps its OWN copy (built by the Level-0 covisibility passes, or copied from the cached graph
+ *   when that is at threshold 1), so c2b_problem_covisibility at another threshold does not disturb it; it is derived from the list
+ *   and dropped with the rows, the transpose and the solve buffers.
+ * Off-diagonal block of edge e = (c, c'), 81 doubles row-major at S_off[e]:
+ *   S_e = - sum_{p seen by both} (sum_{o in (c,p)} W_o) V_l,p^-1 (sum_{o' in (c',p)} W_o')^T     (duplicated pairs: the inner sums).
+ * Diagonal block at S_diag[c]:  S_cc = U_l,c - sum_p (sum_{o in (c,p)} W_o) V_l,p^-1 (sum_{o in (c,p)} W_o)^T -- S's own diagonal,
+ *   the cross terms of a duplicated pair included (so not the Schur-Jacobi M_c when a pair repeats; M_c itself does not change).
+ * Storage is full: (c, c') and (c', c) are both stored and S_off[(c', c)] == S_off[(c, c')]^T bit for bit.
+ * Constants: the constant rows and columns of every block are 0, a constant diagonal entry is lambda 1e-6, a constant point
+ *   contributes nothing; every constant entry of dc and every dp row of a constant point compares == 0.0 as before.
+ * Deterministic: no float atomics; a block's terms are added in ascending observation of the lower camera's row, then ascending
+ *   position in the point's track; the product adds a row's blocks in ascending edge order in a fixed tree.
+ * _set_schur / _get_schur: the handle's state like the preconditioner (default C2B_SCHUR_IMPLICIT): it survives uploads, reads
+ *   and culls and is carried by subset / window under C2B_SUBSET_CARRY.  Another kind: C2B_ERR_INVALID_ARGUMENT.  With
+ *   C2B_SCHUR_IMPLICIT c2b_problem_solve_step launches exactly what it launched before this entry existed, bit for bit.  With
+ *   C2B_SCHUR_EXPLICIT the set-up builds the pattern if absent, Y_o = L_p^-1 Jp_o^T Jc_o per observation (V_l,p = L L^T; 216 bytes
+ *   each, in the solve buffers), the blocks, and q = S p of every iteration is one product with them; b and the back-substitution
+ *   stay the implicit passes; both preconditioners work unchanged.  If the buffers cannot be allocated the call returns
+ *   C2B_ERR_OOM with the bytes in the message and the handle stays usable (set C2B_SCHUR_IMPLICIT): there is no silent fallback.
+ * _schur_bytes: the bytes the explicit solve adds to the solve buffers, 648 (n_edges + n_cam) + 216 n_obs; builds the pattern.
+ * _schur_complement: S and b = -gc + W V_l^-1 gp at lambda into the caller's DEVICE arrays S_diag [n_cam][81], S_off [n_edges][81],
+ *   b [n_cam][9] (8-byte aligned; S_off may be NULL when there is no edge), *n_edges = the directed entries; under either setting,
+ *   which it leaves as it is.  It needs the explicit solve's buffers (c2b_problem_schur_bytes) for the duration of the call: under
+ *   C2B_SCHUR_EXPLICIT they are the handle's and stay, under C2B_SCHUR_IMPLICIT they are freed before it returns.  NULL p / S_diag / b / n_edges, a misaligned pointer or a lambda outside the step's range:
+ *   C2B_ERR_INVALID_ARGUMENT before any device work.  A shard is refused.  Without observations S = lambda 1e-6 I and b = 0.
+ * _get_schur_pattern: the pattern to HOST arrays nbr_ptr [n_cam + 1], nbr [n_edges] (either may be NULL); builds it if absent.
+ * Level 0, stateless, asynchronous on `stream`, device arrays, 8-byte aligned doubles and row pointers, 4-byte indices; a NULL or
+ * misaligned pointer or a count out of range: C2B_ERR_INVALID_ARGUMENT before any device work:
+ * _schur_y_rows(_loss): Y [n_obs][3][9] from the inputs of c2b_schur_points_rows, cam_idx [n_obs] (c2b_expand_rows) and V.
+ * _schur_blocks_rows: S_off [n_edges][81] written, and the cross terms of duplicated pairs ADDED to S_diag [n_cam][81] (which holds
+ *   M of c2b_schur_jacobi_rows on entry), from Y, the list, its transpose and the pattern -- which must be the covisibility graph
+ *   of that list at min_shared 1: a pair it does not hold is skipped.  Rows of more than C2B_SCHUR_LDS_BLOCKS neighbours take the
+ *   heavy path with the same result.
+ * _schur_spmv_rows: y [n_cam][9] = S x; part (may be NULL) takes x.y as 4 ceil(n_cam / 4) partials, one per wave. */
+#define C2B_SCHUR_IMPLICIT 0
+#define C2B_SCHUR_EXPLICIT 1
+#define C2B_SCHUR_LDS_BLOCKS 32
+int c2b_problem_set_schur(c2b_problem *p, int kind);
+int c2b_problem_get_schur(const c2b_problem *p, int *kind);
+int c2b_problem_schur_bytes(c2b_problem *p, int64_t *bytes);
+int c2b_problem_schur_complement(c2b_problem *p, double lambda, double *S_diag, double *S_off, double *b, int64_t *n_edges);
+int c2b_problem_get_schur_pattern(c2b_problem *p, uint64_t *nbr_ptr, uint32_t *nbr);
+int c2b_schur_y_rows(const double *camblk, const double *pts4, const uint32_t *cam_idx, const uint32_t *pt_idx, const double *uv_obs,
+                     int64_t n_obs, const double *V, double lambda, double *Y, void *stream);
+int c2b_schur_y_rows_loss(const double *camblk, const double *pts4, const uint32_t *cam_idx, const uint32_t *pt_idx, const double *uv_obs,
+                          int64_t n_obs, const double *V, double lambda, double *Y, int kind, double scale, void *stream);
+int c2b_schur_blocks_rows(const uint64_t *row_ptr, const uint32_t *pt_idx, const uint64_t *pt_row_ptr, const uint32_t *obs_of,
+                          const uint32_t *cam_of, int64_t n_cam, int64_t n_obs, const uint64_t *nbr_ptr, const uint32_t *nbr,
+                          const double *Y, double *S_diag, double *S_off, void *stream);
+int c2b_schur_spmv_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_cam, const double *S_diag, const double *S_off,
+                        const double *x, double *y, double *part, void *stream);
+
 /* ---- a problem compared against ground truth: similarity alignment on the device ----
  * Build-defined (the reference has nothing like it).  Two problems on one device, the estimate p and the reference ref, with equal
  * n_cam and n_pts; index i of one corresponds to index i of the other.

@@ -5,7 +5,8 @@ and no scratch inside the loop).  Works on the CPU box: hipcc cross-compiles.
 
     python tools/isa_report.py [--filter k_residual_jacobian_l] [--dump <mangled-name-substring>]
     python tools/isa_report.py --filter subset        (a named group: the kernels of sub-problem extraction and write-back;
-                                                       align: those of the similarity alignment)
+                                                       align: those of the similarity alignment; schur_explicit: those of
+                                                       the explicit Schur complement)
 
 Also a module: compile_asm() / kernel_table() / kernel_body() are what tests/test_isa_pins.py asserts on.
 """
@@ -78,7 +79,8 @@ def kernel_body(asm, mangled):
 
 # named groups of --filter: the kernels one feature launches, by the substrings of their names
 GROUPS = {"subset": ("k_subset_", "k_window_", "k_scatter_free_", "k_keep_row_", "k_gather_rows"),
-          "align": ("k_align_", "k_similarity_apply_")}
+          "align": ("k_align_", "k_similarity_apply_"),
+          "schur_explicit": ("k_schur_y", "k_schur_blocks_", "k_schur_spmv", "k_const_offdiag")}
 
 
 def main():
