@@ -73,6 +73,22 @@ def schur_kind(name):
         raise ValueError("schur must be 'implicit' or 'explicit', not %r" % (name,))
 
 
+# how the step solves the reduced camera system (c2b_problem_set_linear_solver): name -> kind
+LINEAR_KINDS = {"pcg": 0, "cholesky": 1}
+LINEAR_NAMES = {0: "pcg", 1: "cholesky"}
+DENSE_MAX_CAMERAS = 4096    # C2B_DENSE_MAX_CAMERAS: the direct solve refuses more cameras than this
+
+
+def linear_kind(name):
+    """the C ABI's kind of a linear solver given by name (or the kind itself)"""
+    if isinstance(name, int) and not isinstance(name, bool):
+        return name
+    try:
+        return LINEAR_KINDS[name]
+    except (KeyError, TypeError):
+        raise ValueError("linear_solver must be 'pcg' or 'cholesky', not %r" % (name,))
+
+
 class StepInfo(C.Structure):
     """c2b_step_info (include/city2ba_hip_experimental.h)"""
     _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("rel_residual", C.c_double), ("sum_sq", C.c_double),
@@ -293,6 +309,12 @@ SIGNATURES = {
     "c2b_schur_y_rows_loss": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _d, _vp, _int, _d, _vp]),
     "c2b_schur_blocks_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c2b_schur_spmv_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c2b_problem_set_linear_solver": (_int, [_vp, _int]),
+    "c2b_problem_get_linear_solver": (_int, [_vp, C.POINTER(_int)]),
+    "c2b_problem_linear_solver_bytes": (_int, [_vp, C.POINTER(_i64)]),
+    "c2b_dense_scatter_rows": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "c2b_dense_cholesky": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "c2b_dense_cholesky_solve": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "c2b_problem_set_constant": (_int, [_vp, _vp, _vp]),
     "c2b_problem_get_constant": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "c2b_problem_set_priors": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -346,6 +346,31 @@ class BAProblem:
         L.check(L.lib().c2b_problem_schur_bytes(self._h, C.byref(n)))
         return n.value
 
+    def set_linear_solver(self, kind):
+        """How solve_step solves the reduced camera system S dc = b (c2b_problem_set_linear_solver): "pcg", the
+        preconditioned conjugate gradients (the default), or "cholesky": S formed as the explicit setting forms it whatever
+        set_schur says, scattered into a dense lower triangle, factored by a blocked Cholesky on the device and solved by two
+        substitutions -- the exact step, 0 iterations, no max_iters or rel_tol to choose, at linear_solver_bytes() of device
+        memory; for the few hundred cameras of a window, not for a whole city (at most 4096 cameras).  A factor that fails
+        (a pivot not finite or <= 0) gives status 2 and a zero step, which the LM loops answer by raising the damping.  The
+        setting belongs to the handle: uploads and culls keep it, window() and subset(carry=True) carry it.  If the buffers
+        cannot be allocated solve_step raises with the bytes in the message; there is no fallback, and the handle stays
+        usable under "pcg"."""
+        L.check(L.lib().c2b_problem_set_linear_solver(self._h, L.linear_kind(kind)))
+
+    def linear_solver(self):
+        """the name of the linear solver in force: "pcg" or "cholesky" """
+        k = C.c_int()
+        L.check(L.lib().c2b_problem_get_linear_solver(self._h, C.byref(k)))
+        return L.LINEAR_NAMES[k.value]
+
+    def linear_solver_bytes(self):
+        """device bytes the "cholesky" setting adds to the solve buffers: schur_bytes() + 8 (Np^2 + 2 Np), Np = 64 ceil(9 n_cam / 64)
+        (c2b_problem_linear_solver_bytes); builds the pattern; refused above 4096 cameras"""
+        n = C.c_int64()
+        L.check(L.lib().c2b_problem_linear_solver_bytes(self._h, C.byref(n)))
+        return n.value
+
     def schur_complement(self, lam):
         """The reduced camera system at damping lam, built on the device (c2b_problem_schur_complement) under the handle's loss,
         masks and priors, whatever set_schur says: (nbr_ptr [n_cam + 1] uint64, nbr [n_edges] uint32, S_diag [n_cam, 9, 9],

@@ -22,6 +22,7 @@
 //   city2ba solve IN OUT [--iterations N --lambda X --pcg-iterations N --pcg-tol X --function-tol X --gradient-tol X
 //                         --parameter-tol X --loss squared|huber|cauchy|soft-l1 --loss-scale X
 //                         --preconditioner block-jacobi|schur-jacobi --schur implicit|explicit --inner-iterations N
+//                         --linear-solver pcg|cholesky
 //                         --fix-intrinsics --fix-first-camera
 //                         --filter-max-error X --filter-rounds N --filter-in-front
 //                         --prior-from FILE [--prior-center-sigma S|SX,SY,SZ] [--prior-intrinsics-sigma SF,SK1,SK2]
@@ -943,7 +944,7 @@ static int loss_kind_of(const Args &a) {
 int run_solve(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {"fix-intrinsics", "fix-first-camera", "filter-in-front", "no-halo"},
                          {"iterations", "lambda", "pcg-iterations", "pcg-tol", "function-tol", "gradient-tol", "parameter-tol", "loss",
-                          "loss-scale", "preconditioner", "schur", "inner-iterations", "device", "filter-max-error", "filter-rounds", "prior-from",
+                          "loss-scale", "preconditioner", "schur", "linear-solver", "inner-iterations", "device", "filter-max-error", "filter-rounds", "prior-from",
                           "prior-center-sigma", "prior-intrinsics-sigma", "prior-point-sigma", "prior-point-every", "window", "window-around", "hops",
                           "min-shared", "max-cameras"});
     if (a.positional.size() != 2) die("The following required arguments were not provided:\n    <FILE> <OUT>");
@@ -978,6 +979,13 @@ int run_solve(int argc, char **argv) {
         if (v == "implicit") schur = C2B_SCHUR_IMPLICIT;
         else if (v == "explicit") schur = C2B_SCHUR_EXPLICIT;
         else die("Invalid value for '--schur <implicit|explicit>': expected implicit or explicit");
+    }
+    int linear = C2B_LINEAR_PCG;
+    if (a.has("linear-solver")) {
+        const std::string &v = a.opt.at("linear-solver");
+        if (v == "pcg") linear = C2B_LINEAR_PCG;
+        else if (v == "cholesky") linear = C2B_LINEAR_CHOLESKY;
+        else die("Invalid value for '--linear-solver <pcg|cholesky>': expected pcg or cholesky");
     }
     const int64_t inner_iterations = a.i("inner-iterations", 0);
     if (inner_iterations > 1000) die("Invalid value for '--inner-iterations <N>': expected an integer in 0 ... 1000");
@@ -1066,6 +1074,7 @@ int run_solve(int argc, char **argv) {
     ck(c2b_problem_set_loss(p, loss, loss_scale));
     ck(c2b_problem_set_preconditioner(p, precond));
     ck(c2b_problem_set_schur(p, schur));
+    ck(c2b_problem_set_linear_solver(p, linear));
     ck(c2b_problem_set_inner_iterations(p, (int)inner_iterations));
     if (prior) {                                             // the targets: FILE's centres, intrinsics and points, as a problem holds them
         c2b_problem *q = nullptr;
@@ -1507,6 +1516,8 @@ const char *subcommand_help(const std::string &sub) {
                "    --preconditioner <block-jacobi|schur-jacobi> [block-jacobi]\n"
                "    --schur <implicit|explicit> [implicit]   explicit: the reduced camera system is formed once per step on the\n"
                "                              covisibility pattern and the conjugate gradients run on the stored blocks\n"
+               "    --linear-solver <pcg|cholesky> [pcg]   cholesky: the reduced camera system is formed, factored densely on the\n"
+               "                              device and solved exactly, without conjugate gradients (at most 4096 cameras)\n"
                "    --inner-iterations <N> [0] after every step, N rounds of per-point refinement of the points against the moved cameras,\n"
                "                              before the step's cost is taken (0: off)\n"
                "    --fix-intrinsics          hold f, k1, k2 of every camera constant\n"

@@ -53,6 +53,7 @@
 #include "subset_kernels.hpp"
 #include "covis_kernels.hpp"
 #include "schur_explicit_kernels.hpp"
+#include "dense_kernels.hpp"
 #include "align_kernels.hpp"
 #include "text_kernels.hpp"
 #include "comm_rccl.hpp"

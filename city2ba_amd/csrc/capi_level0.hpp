@@ -2077,3 +2077,89 @@ int c2b_schur_spmv_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_
     return C2B_OK;
     C2B_API_END("schur_spmv_rows")
 }
+
+// ---- the dense Cholesky of the reduced system (dense_kernels.hpp) ---------------------------------------------
+static int64_t dense_padded(int64_t n) { return (n + kDnTile - 1) / kDnTile * kDnTile; }
+
+// S's lower triangle and the padding rows into A; one wave per camera and per padding row
+static void launch_dense_scatter(hipStream_t st, const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_cam, const double *S_diag, const double *S_off,
+                                 double *A, int64_t ld) {
+    const int64_t waves = n_cam + (dense_padded(9 * n_cam) - 9 * n_cam);
+    hipLaunchKernelGGL(k_dense_scatter, dim3(blocks_for(waves, kDnScatterWaves)), dim3(kDnScatterWaves * 64), 0, st, nbr_ptr, nbr, n_cam, S_diag, S_off, A,
+                       ld);
+}
+
+// A = L L^T in place over np = 64 T rows: per panel the tile, the tiles below it, the trailing lower tile pairs (the last
+// panel has neither of the two, and an empty grid is not launched)
+static void launch_dense_cholesky(hipStream_t st, double *A, int64_t np, int64_t ld, int *info) {
+    const int64_t T = np / kDnTile;
+    for (int64_t k = 0; k < T; ++k) {
+        const int64_t k0 = k * kDnTile, m = T - k - 1;
+        hipLaunchKernelGGL(k_chol_panel, dim3(1), dim3(kDnBlock), 0, st, A, ld, k0, info);
+        if (!m) break;
+        hipLaunchKernelGGL(k_chol_trsm, dim3((unsigned)m), dim3(kDnTile), 0, st, A, ld, k0);
+        hipLaunchKernelGGL(k_chol_syrk, dim3((unsigned)(m * (m + 1) / 2)), dim3(kDnBlock), 0, st, A, ld, k0);
+    }
+}
+
+// x <- L^-T L^-1 x over np = 64 T rows: forward, then backward with L^T
+static void launch_dense_solve(hipStream_t st, const double *A, int64_t np, int64_t ld, double *x) {
+    const int64_t T = np / kDnTile;
+    for (int64_t k = 0; k < T; ++k) {
+        hipLaunchKernelGGL(k_chol_solve_tile<false>, dim3(1), dim3(kDnTile), 0, st, A, ld, k * kDnTile, x);
+        if (T - k - 1) hipLaunchKernelGGL(k_chol_solve_update<false>, dim3((unsigned)(T - k - 1)), dim3(kDnBlock), 0, st, A, ld, k * kDnTile, x);
+    }
+    for (int64_t k = T - 1; k >= 0; --k) {
+        hipLaunchKernelGGL(k_chol_solve_tile<true>, dim3(1), dim3(kDnTile), 0, st, A, ld, k * kDnTile, x);
+        if (k) hipLaunchKernelGGL(k_chol_solve_update<true>, dim3((unsigned)k), dim3(kDnBlock), 0, st, A, ld, k * kDnTile, x);
+    }
+}
+
+// n and ld as both entries below take them: n rows are the matrix, the rows up to 64 ceil(n / 64) its padding
+static int dense_shape_check(const char *who, int64_t n, int64_t ld) {
+    if (n < 0 || ld < 0 || ld > (int64_t)9 * C2B_DENSE_MAX_CAMERAS) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: n or ld out of range (ld at most %d)", who, 9 * C2B_DENSE_MAX_CAMERAS);
+    if (ld % kDnTile) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: ld must be a multiple of 64, not %lld", who, (long long)ld);
+    if (n > ld) return fail(C2B_ERR_INVALID_ARGUMENT, "%s: n = %lld exceeds ld = %lld", who, (long long)n, (long long)ld);
+    return C2B_OK;
+}
+
+int c2b_dense_scatter_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_cam, const double *S_diag, const double *S_off, double *A,
+                           int64_t ld, void *stream) {
+    C2B_API_BEGIN
+    if (const int rc = schur_pattern_check("dense_scatter_rows", nbr_ptr, nbr, n_cam)) return rc;
+    if (n_cam > C2B_DENSE_MAX_CAMERAS) return fail(C2B_ERR_INVALID_ARGUMENT, "dense_scatter_rows: %lld cameras exceed C2B_DENSE_MAX_CAMERAS = %d", (long long)n_cam, C2B_DENSE_MAX_CAMERAS);
+    if (const int rc = dense_shape_check("dense_scatter_rows", 9 * n_cam, ld)) return rc;
+    if (n_cam && (!S_diag || !A)) return fail(C2B_ERR_INVALID_ARGUMENT, "dense_scatter_rows: NULL argument");
+    if (!aligned8(S_diag) || !aligned8(S_off) || !aligned8(A)) return fail(C2B_ERR_INVALID_ARGUMENT, "dense_scatter_rows: misaligned pointer");
+    if (!n_cam) return C2B_OK;
+    launch_dense_scatter(S(stream), nbr_ptr, nbr, n_cam, S_diag, S_off, A, ld);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("dense_scatter_rows")
+}
+
+int c2b_dense_cholesky(double *A, int64_t n, int64_t ld, int32_t *info, void *stream) {
+    C2B_API_BEGIN
+    if (const int rc = dense_shape_check("dense_cholesky", n, ld)) return rc;
+    if (!info || (n && !A)) return fail(C2B_ERR_INVALID_ARGUMENT, "dense_cholesky: NULL argument");
+    if (!aligned8(A) || (reinterpret_cast<uintptr_t>(info) & 3)) return fail(C2B_ERR_INVALID_ARGUMENT, "dense_cholesky: misaligned pointer (A 8 bytes, info 4)");
+    hipStream_t st = S(stream);
+    HIP_TRY(hipMemsetAsync(info, 0, sizeof(int32_t), st));
+    if (!n) return C2B_OK;
+    launch_dense_cholesky(st, A, dense_padded(n), ld, info);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("dense_cholesky")
+}
+
+int c2b_dense_cholesky_solve(const double *A, int64_t n, int64_t ld, double *x, void *stream) {
+    C2B_API_BEGIN
+    if (const int rc = dense_shape_check("dense_cholesky_solve", n, ld)) return rc;
+    if (n && (!A || !x)) return fail(C2B_ERR_INVALID_ARGUMENT, "dense_cholesky_solve: NULL argument");
+    if (!aligned8(A) || !aligned8(x)) return fail(C2B_ERR_INVALID_ARGUMENT, "dense_cholesky_solve: misaligned pointer");
+    if (!n) return C2B_OK;
+    launch_dense_solve(S(stream), A, dense_padded(n), ld, x);
+    LAUNCH_CHECK();
+    return C2B_OK;
+    C2B_API_END("dense_cholesky_solve")
+}

@@ -32,6 +32,11 @@ struct c2b_problem {
     // c2b_problem_set_schur: how c2b_problem_solve_step applies S (0 implicit, never formed; 1 explicit, block-CSR
     // on the covisibility pattern), the handle's too
     int schur_kind = 0;
+    // c2b_problem_set_linear_solver: how c2b_problem_solve_step solves S dc = b (0 PCG; 1 dense Cholesky of the
+    // explicit S), the handle's too; and the device word the factorisation reports a failed pivot in (allocated with the first
+    // direct solve)
+    int linear_kind = 0;
+    DevBuf<int32_t> dense_info;
     // c2b_problem_set_constant: the camera parameters (bit k of a camera's word, to_vec order) and the points
     // (0 / 1) that normal_equations / solve_step / apply_step hold constant; the handle's, kept while both counts stay
     // what they were set for (const_n_cam, const_n_pts).  A kind with nothing set has no array: no launch changes for it.

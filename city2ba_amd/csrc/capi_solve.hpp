@@ -338,6 +338,25 @@ int c2b_problem_get_schur(const c2b_problem *p, int *kind) {
     C2B_API_END("problem_get_schur")
 }
 
+// ---- how the step solves S dc = b -----------------------------------------------------------------------------
+int c2b_problem_set_linear_solver(c2b_problem *p, int kind) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_linear_solver: problem is NULL");
+    if (kind != C2B_LINEAR_PCG && kind != C2B_LINEAR_CHOLESKY)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_set_linear_solver: kind must be 0 (pcg) or 1 (cholesky), not %d", kind);
+    p->linear_kind = kind;
+    return C2B_OK;
+    C2B_API_END("problem_set_linear_solver")
+}
+
+int c2b_problem_get_linear_solver(const c2b_problem *p, int *kind) {
+    C2B_API_BEGIN
+    if (!p) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_get_linear_solver: problem is NULL");
+    if (kind) *kind = p->linear_kind;
+    return C2B_OK;
+    C2B_API_END("problem_get_linear_solver")
+}
+
 // sum over the observations of rho(s) (weighted_sq: of w s) under the problem's loss into out[0] (device), asynchronous;
 // one partial per workgroup of 256 observations: the workspace holds one per 4 tiles of 64 (block_part_slots)
 static int robust_sum(c2b_problem *p, bool weighted_sq, double *out) {
@@ -431,17 +450,26 @@ int c2b_problem_normal_equations(c2b_problem *p, double *U, double *gc, double *
 // r / z / p / q [n_cam][9], two partial arrays [n_part], the device scalars [kScSlots]; under the Schur-Jacobi
 // preconditioner its blocks M [n_cam][81] after them (the rest lies where it lies without); under the explicit Schur
 // complement its blocks Sd [n_cam][81], So [sp_edges][81] and Y [n_obs][27] after those, and the partial arrays
-// also cover k_schur_spmv's grid.  With neither option nothing moves.
+// also cover k_schur_spmv's grid; under the direct solve those whatever `schur` says, and after Y the dense image
+// A [Np][Np] and two vectors [Np], Np = 64 ceil(9 n_cam / 64).  With none of the options nothing moves.
 struct SolveBufs {
-    double *U, *gc, *V, *gp, *Lf, *t, *r, *z, *pv, *q, *pa, *pb, *sc, *M, *Sd, *So, *Y;
+    double *U, *gc, *V, *gp, *Lf, *t, *r, *z, *pv, *q, *pa, *pb, *sc, *M, *Sd, *So, *Y, *A, *dx, *dw;
     int64_t n_part;
 };
 
 static bool schur_explicit(const c2b_problem *p) { return p->schur_kind == C2B_SCHUR_EXPLICIT; }
+static bool linear_cholesky(const c2b_problem *p) { return p->linear_kind == C2B_LINEAR_CHOLESKY; }
+// the solve buffers hold S's blocks and Y
+static bool explicit_bufs(const c2b_problem *p) { return schur_explicit(p) || linear_cholesky(p); }
+// the doubles the direct solve adds behind them: the dense image and its two vectors
+static int64_t dense_doubles(const c2b_problem *p) {
+    const int64_t np = dense_padded(9 * p->n_cam);
+    return np * np + 2 * np;
+}
 
 static int64_t solve_parts(const c2b_problem *p) {
     const int64_t a = (int64_t)schur_cameras_grid(p->n_cam) * (kNormBlock / 64);
-    const int64_t e = schur_explicit(p) ? schur_spmv_parts(p->n_cam) : 0;
+    const int64_t e = explicit_bufs(p) ? schur_spmv_parts(p->n_cam) : 0;
     return std::max<int64_t>({a, e, (int64_t)blocks_for(p->n_cam, kSchurBlock), (int64_t)blocks_for(p->n_obs, kSchurBlock), 1});
 }
 
@@ -450,7 +478,8 @@ static int64_t schur_explicit_doubles(const c2b_problem *p) { return 81 * (p->n_
 
 static int64_t solve_doubles(const c2b_problem *p) {
     return p->n_cam * (81 + 9 + kCholPacked + 4 * 9) + p->n_pts * (9 + 3 + 3) + 2 * solve_parts(p) + kScSlots +
-           (p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? 81 * p->n_cam : 0) + (schur_explicit(p) ? schur_explicit_doubles(p) : 0);
+           (p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? 81 * p->n_cam : 0) + (explicit_bufs(p) ? schur_explicit_doubles(p) : 0) +
+           (linear_cholesky(p) ? dense_doubles(p) : 0);
 }
 
 static SolveBufs solve_bufs(c2b_problem *p) {
@@ -463,10 +492,14 @@ static SolveBufs solve_bufs(c2b_problem *p) {
     b.n_part = solve_parts(p);
     b.pa = take(b.n_part); b.pb = take(b.n_part); b.sc = take(kScSlots);
     b.M = p->precond_kind == C2B_PRECOND_SCHUR_JACOBI ? take(81 * nc) : nullptr;
-    const bool ex = schur_explicit(p);
+    const bool ex = explicit_bufs(p), dn = linear_cholesky(p);
+    const int64_t dnp = dense_padded(9 * nc);
     b.Sd = ex ? take(81 * nc) : nullptr;
     b.So = ex ? take(81 * p->sp_edges) : nullptr;
     b.Y = ex ? take(27 * p->n_obs) : nullptr;
+    b.A = dn ? take(dnp * dnp) : nullptr;
+    b.dx = dn ? take(dnp) : nullptr;
+    b.dw = dn ? take(dnp) : nullptr;
     return b;
 }
 
@@ -475,6 +508,9 @@ static int ensure_solver(c2b_problem *p) {
     if (p->sv && p->sv_doubles >= n) return C2B_OK;
     p->sv_doubles = 0;
     const hipError_t e = p->sv.alloc((size_t)n);                  // (the smaller one is freed first)
+    if (e != hipSuccess && linear_cholesky(p))                   // no fallback: the caller sets C2B_LINEAR_PCG, the handle is usable
+        return fail(hip_code(e), "problem_solve_step: allocation of %lld bytes for the direct solve (%lld of them the explicit blocks, Y and the dense image): %s",
+                    (long long)(8 * n), (long long)(8 * (schur_explicit_doubles(p) + dense_doubles(p))), hipGetErrorString(e));
     if (e != hipSuccess && schur_explicit(p))                    // no fallback: the caller sets C2B_SCHUR_IMPLICIT, the handle is usable
         return fail(hip_code(e), "problem_solve_step: allocation of %lld bytes for the explicit Schur complement (%lld of them its blocks and Y): %s",
                     (long long)(8 * n), (long long)(8 * schur_explicit_doubles(p)), hipGetErrorString(e));
@@ -662,6 +698,34 @@ static int schur_pcg(c2b_problem *p, const SolveBufs &B, double lambda, int max_
     return C2B_OK;
 }
 
+// The direct solve of the reduced system, in place of schur_pcg: S's lower triangle into the dense image, its
+// Cholesky factor, the two substitutions on b (in B.r) into dc, then the true residual from one product with the stored blocks.
+// res: 0 iterations; status 0, or 2 when a pivot was not finite or not > 0 (dc is then garbage: the caller zeroes the step).
+static int dense_solve(c2b_problem *p, const SolveBufs &B, double *dc, PcgResult *res) {
+    hipStream_t st = p->stream;
+    const int64_t nc = p->n_cam, n = 9 * nc, np = dense_padded(n);
+    const unsigned nb = blocks_for(n, kSchurBlock);
+    if (!p->dense_info) HIP_TRY(p->dense_info.alloc(1));
+    launch_dense_scatter(st, p->sp_ptr, p->sp_nbr, nc, B.Sd, B.So, B.A, np);
+    HIP_TRY(hipMemsetAsync(p->dense_info, 0, sizeof(int32_t), st));
+    launch_dense_cholesky(st, B.A, np, np, p->dense_info);
+    HIP_TRY(hipMemsetAsync(B.dx, 0, sizeof(double) * (size_t)np, st));
+    HIP_TRY(hipMemcpyAsync(B.dx, B.r, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    launch_dense_solve(st, B.A, np, np, B.dx);
+    HIP_TRY(hipMemcpyAsync(dc, B.dx, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    launch_schur_spmv(st, p->sp_ptr, p->sp_nbr, nc, B.Sd, B.So, dc, B.dw, nullptr);
+    hipLaunchKernelGGL(k_dense_residual, dim3(nb), dim3(kSchurBlock), 0, st, n, (const double *)B.r, (const double *)B.dw, B.pa, B.pb);
+    fold_sum(st, B.pa, (int)nb, B.sc + kScRz0);
+    fold_sum(st, B.pb, (int)nb, B.sc + kScRr);
+    HIP_TRY(launch_error());
+    int32_t bad = 0;
+    double h[kScSlots];
+    HIP_TRY(hipMemcpyAsync(&bad, p->dense_info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (const int rc = scalars_to_host(st, B.sc, kScRz1 + 1, h)) return rc;
+    *res = PcgResult{0, bad ? 2 : 0, h[kScRr], std::sqrt(h[kScRz0])};
+    return C2B_OK;
+}
+
 // dp = -V_l^-1 (gp + W^T dc); then |r|^2 and the model decrease from J, per observation, and the priors' share of the two
 // sums beside k_schur_model's; the step's last read-back, which also brings the Schur-Jacobi fallbacks' count
 static int step_model(c2b_problem *p, const SolveBufs &B, double lambda, const double *dc, double *dp, double *sum_sq, double *model) {
@@ -681,8 +745,9 @@ static int step_model(c2b_problem *p, const SolveBufs &B, double lambda, const d
         HIP_TRY(hipMemcpyAsync(hpr, P.sc + kPrSumSq, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(launch_error());
-    if ((rc = scalars_to_host(st, B.sc, B.M ? kScFallback + 1 : kScModel + 1, h))) return rc;
-    if (B.M) p->precond_fallbacks = (int64_t)h[kScFallback];
+    const bool fb = B.M && !linear_cholesky(p);                      // (the direct solve builds no preconditioner)
+    if ((rc = scalars_to_host(st, B.sc, fb ? kScFallback + 1 : kScModel + 1, h))) return rc;
+    if (fb) p->precond_fallbacks = (int64_t)h[kScFallback];
     *sum_sq = pri ? h[kScSumSq] + hpr[0] : h[kScSumSq];
     *model = pri ? h[kScModel] + hpr[1] : h[kScModel];
     return C2B_OK;
@@ -714,8 +779,11 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     int rc = ensure_camblk(p);
     if (!rc) rc = ensure_rows(p);
     if (!rc) rc = ensure_transpose(p);
-    const bool ex = schur_explicit(p);
-    if (!rc && ex) rc = ensure_schur_pattern(p);
+    const bool dn = linear_cholesky(p), ex = schur_explicit(p) && !dn;
+    if (dn && nc > C2B_DENSE_MAX_CAMERAS)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_solve_step: %lld cameras exceed C2B_DENSE_MAX_CAMERAS = %d of the direct solve (set C2B_LINEAR_PCG)",
+                    (long long)nc, C2B_DENSE_MAX_CAMERAS);
+    if (!rc && (ex || dn)) rc = ensure_schur_pattern(p);
     if (!rc) rc = ensure_solver(p);
     if (rc) return rc;
     const SolveBufs B = solve_bufs(p);
@@ -723,16 +791,16 @@ int c2b_problem_solve_step(c2b_problem *p, double lambda, int max_iters, double 
     // from here on, and so is the damping's diagonal.  The constant points' V: see step_preconditioner
     PcgResult pcg{0, 1, 0.0, 0.0};
     rc = assemble_cameras(p, B.U, B.gc, 0.0, false);
-    if (!rc) rc = assemble_points(p, B.V, B.gp, B.M || ex ? kConstPointV : 0.0, false);
-    if (!rc) rc = ex ? schur_explicit_setup(p, B, lambda, true) : step_preconditioner(p, B, lambda);
+    if (!rc) rc = assemble_points(p, B.V, B.gp, B.M || ex || dn ? kConstPointV : 0.0, false);
+    if (!rc) rc = dn ? schur_explicit_setup(p, B, lambda, false) : ex ? schur_explicit_setup(p, B, lambda, true) : step_preconditioner(p, B, lambda);
     if (!rc) rc = schur_apply(p, B, lambda, nullptr, B.gp, B.t, false, B.gc, B.r, nullptr);      // b = -gc + W V_l^-1 gp into r
-    if (!rc) rc = schur_pcg(p, B, lambda, max_iters, rel_tol, dc, &pcg);
+    if (!rc) rc = dn ? dense_solve(p, B, dc, &pcg) : schur_pcg(p, B, lambda, max_iters, rel_tol, dc, &pcg);
     if (!rc) rc = step_model(p, B, lambda, dc, dp, &out.sum_sq, &out.model_decrease);
     if (rc) return rc;
     out.iterations = pcg.iterations;
     out.status = pcg.status;
     out.rel_residual = pcg.bb == 0.0 ? 0.0 : pcg.rnorm / std::sqrt(pcg.bb);
-    if (!std::isfinite(out.sum_sq) || !std::isfinite(out.model_decrease) || !std::isfinite(out.rel_residual)) {
+    if (!std::isfinite(out.sum_sq) || !std::isfinite(out.model_decrease) || !std::isfinite(out.rel_residual) || (dn && pcg.status == 2)) {
         // a factorisation failed (a pivot <= 0 at the damping's low end) and a NaN reached the step: no step at all
         HIP_TRY(hipMemsetAsync(dc, 0, sizeof(double) * 9 * (size_t)nc, st));
         if (np) HIP_TRY(hipMemsetAsync(dp, 0, sizeof(double) * 3 * (size_t)np, st));
@@ -756,6 +824,20 @@ int c2b_problem_schur_bytes(c2b_problem *p, int64_t *bytes) {
     *bytes = 8 * schur_explicit_doubles(p);
     return C2B_OK;
     C2B_API_END("problem_schur_bytes")
+}
+
+int c2b_problem_linear_solver_bytes(c2b_problem *p, int64_t *bytes) {
+    C2B_API_BEGIN
+    if (!p || !bytes) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_linear_solver_bytes: NULL argument");
+    NEED_UPLOADED(p, "problem_linear_solver_bytes");
+    if (p->shard_n_cam_global >= 0) return fail(C2B_ERR_INVALID_ARGUMENT, "problem_linear_solver_bytes: a shard cannot be solved alone");
+    if (p->n_cam > C2B_DENSE_MAX_CAMERAS)
+        return fail(C2B_ERR_INVALID_ARGUMENT, "problem_linear_solver_bytes: %lld cameras exceed C2B_DENSE_MAX_CAMERAS = %d of the direct solve",
+                    (long long)p->n_cam, C2B_DENSE_MAX_CAMERAS);
+    if (const int rc = ensure_schur_pattern(p)) return rc;
+    *bytes = 8 * (schur_explicit_doubles(p) + dense_doubles(p));
+    return C2B_OK;
+    C2B_API_END("problem_linear_solver_bytes")
 }
 
 int c2b_problem_get_schur_pattern(c2b_problem *p, uint64_t *nbr_ptr, uint32_t *nbr) {

@@ -60,6 +60,7 @@ void adopt_problem(c2b_problem *dst, c2b_problem &t, const c2b_problem *src, Chi
         dst->inner_rounds = src->inner_rounds;
         dst->precond_kind = src->precond_kind;
         dst->schur_kind = src->schur_kind;
+        dst->linear_kind = src->linear_kind;
         dst->precond_fallbacks = 0;
     }
     if (L.origin) {

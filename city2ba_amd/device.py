@@ -616,6 +616,31 @@ def schur_spmv_rows(nbr_ptr, nbr, S_diag, S_off, x, y, part=None):
     return y
 
 
+DENSE_MAX_CAMERAS = 4096    # C2B_DENSE_MAX_CAMERAS: the dense image's leading dimension is at most 9 times this
+
+
+def dense_scatter_rows(nbr_ptr, nbr, S_diag, S_off, A):
+    """the lower triangle of S = (S_diag [n_cam,9,9], S_off [n_edges,9,9] on the pattern nbr_ptr, nbr) into the dense image
+    A [Np, ld] (c2b_dense_scatter_rows), Np = 64 ceil(9 n_cam / 64) <= ld = A.shape[1], ld a multiple of 64: zeros
+    elsewhere in the lower triangle, the padding rows i >= 9 n_cam rows of the identity; the upper triangle is not written"""
+    L.check(L.lib().c2b_dense_scatter_rows(_p(nbr_ptr), _p(nbr), S_diag.shape[0], _p(S_diag), _p(S_off), _p(A), A.shape[1], _stream()))
+    return A
+
+
+def dense_cholesky(A, n, info):
+    """A [Np, ld] = L L^T in place on the lower triangle (c2b_dense_cholesky): n rows are the matrix, the rows up to
+    Np = 64 ceil(n / 64) padding rows of the identity; info [1] int32 takes 0, or the 1-based index of the first pivot that was
+    not finite or not > 0 (the factor is then meaningless)"""
+    L.check(L.lib().c2b_dense_cholesky(_p(A), int(n), A.shape[1], _p(info), _stream()))
+    return A
+
+
+def dense_cholesky_solve(A, n, x):
+    """x [Np] <- L^-T L^-1 x with the factor dense_cholesky left in A (c2b_dense_cholesky_solve); x's padding entries must be finite"""
+    L.check(L.lib().c2b_dense_cholesky_solve(_p(A), int(n), A.shape[1], _p(x), _stream()))
+    return x
+
+
 def _prior_pair(target, w, n, name):
     """a (target, weights) pair of a prior: both None, or both [n, 3] float64 on the device"""
     if (target is None) != (w is None):

@@ -18,7 +18,7 @@ def _clamp(lam):
 
 
 def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, loss=None, loss_scale=1.0, preconditioner=None, constant=None,
-                        priors=None, inner_iterations=None, schur=None):
+                        priors=None, inner_iterations=None, schur=None, linear_solver=None):
     """`iterations` LM iterations on ba in place.  An iteration solves the damped step, applies it and keeps it when the
     sum of squared residuals falls: gain ratio rho = (e0 - e1) / model_decrease, then lam *= max(1/3, 1 - (2 rho - 1)^3)
     and nu = 2 (accepted), or lam *= nu and nu *= 2 (rejected; cameras and points are restored bit for bit); lam is held
@@ -46,9 +46,14 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
     as before.
     schur = "implicit" | "explicit" (BAProblem.set_schur, which this calls: it stays on ba); None leaves ba's setting as it is.
     Explicit forms the reduced camera system once per step and iterates on the stored blocks: the steps converge
-    to the same solution."""
+    to the same solution.
+    linear_solver = "pcg" | "cholesky" (BAProblem.set_linear_solver, which this calls: it stays on ba, as schur does); None leaves
+    ba's setting as it is.  Under "cholesky" every step is the exact solution of the damped system by a dense factorisation
+    (DESIGN 4.23): 'pcg_iterations' is 0 in every entry, and max_iters and rel_tol are checked and not used."""
     if schur is not None:
         ba.set_schur(schur)
+    if linear_solver is not None:
+        ba.set_linear_solver(linear_solver)
     if inner_iterations is not None:
         ba.set_inner_iterations(inner_iterations)
     n_inner = ba.inner_iterations()
@@ -99,7 +104,7 @@ def levenberg_marquardt(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6
 
 def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_tol=1e-6, function_tol=0.0, gradient_tol=0.0,
                                parameter_tol=0.0, loss=None, loss_scale=1.0, preconditioner=None, constant=None, priors=None,
-                               inner_iterations=None, schur=None):
+                               inner_iterations=None, schur=None, linear_solver=None):
     """levenberg_marquardt's loop inside the library (c2b_problem_levenberg_marquardt): the same steps, the same damping
     and the same numbers, with a device-side checkpoint and rollback where the loop above downloads and uploads, and with
     stopping tests.  Returns (history, summary).
@@ -115,12 +120,14 @@ def levenberg_marquardt_device(ba, iterations=10, lam=1e-4, max_iters=100, rel_t
     iteration for iteration.  loss, preconditioner, constant and priors as there: with priors in force every cost is the
     observations' cost + the priors', and the gradient test reads the gradient of the stacked system.
     inner_iterations and schur as there: set on the handle when given, left as they are when None; the library's loop honours
-    the handle's."""
+    the handle's.  linear_solver as there too."""
     import ctypes as C
 
     from . import _lib as L
     if schur is not None:
         ba.set_schur(schur)
+    if linear_solver is not None:
+        ba.set_linear_solver(linear_solver)
     if priors is not None:
         ba.set_priors(**priors)
     if constant is not None:

@@ -95,7 +95,7 @@
  *     remove_singletons, add_incorrect_correspondences, drop_features, split_landmarks, join_landmarks, bal_read,
  *     bal_sizes, bal_copy, bal_close, bal_write, bal_read_as, bal_write_as, format_f64, parse_f64, ply_write,
  *     bvh_build, bvh_sizes, bvh_copy, bvh_free
- *   city2ba_hip_experimental.h: diagnostics, calibration, f32 extension (107):
+ *   city2ba_hip_experimental.h: diagnostics, calibration, f32 extension (113):
  *     workspace_selfcheck, comm_backend, jacobian_tiles_per_wave, jacobian_launch_shape, jacobian_outputs_log,
  *     jacobian_outputs_set_store_rate, calib_store_pattern, calib_copy, normal_transpose_temp_bytes, normal_transpose,
  *     normal_cameras_rows, normal_points_rows, schur_points_rows, schur_cameras_rows, problem_solve_step,
@@ -115,12 +115,13 @@
  *     problem_write_back, covisibility_temp_bytes, covisibility_degree_rows, covisibility_fill_rows,
  *     covisibility_expand_rows, problem_covisibility, problem_get_covisibility, problem_neighbourhood,
  *     problem_set_schur, problem_get_schur, problem_schur_bytes, problem_schur_complement, problem_get_schur_pattern,
- *     schur_y_rows, schur_y_rows_loss, schur_blocks_rows, schur_spmv_rows, align_options_init,
- *     similarity_from_moments, align_finish_moments, align_launch_shape, align_means_rows, align_moments_rows,
- *     align_errors_rows, align_rotation_errors_rows, similarity_apply, problem_align, problem_transform,
- *     convert_f64_to_f32, convert_f32_to_f64, stats_f32, add_drift_f32, add_drift_normalized_f32,
- *     add_noise_entities_f32, add_sin_noise_f32
- *   (269 entry points in all; names above without their c2b_ prefix)
+ *     schur_y_rows, schur_y_rows_loss, schur_blocks_rows, schur_spmv_rows, problem_set_linear_solver,
+ *     problem_get_linear_solver, problem_linear_solver_bytes, dense_scatter_rows, dense_cholesky,
+ *     dense_cholesky_solve, align_options_init, similarity_from_moments, align_finish_moments, align_launch_shape,
+ *     align_means_rows, align_moments_rows, align_errors_rows, align_rotation_errors_rows, similarity_apply,
+ *     problem_align, problem_transform, convert_f64_to_f32, convert_f32_to_f64, stats_f32, add_drift_f32,
+ *     add_drift_normalized_f32, add_noise_entities_f32, add_sin_noise_f32
+ *   (275 entry points in all; names above without their c2b_ prefix)
  * ---- end of index ----
  *
  * Every function returns C2B_OK or a negative status; c2b_last_error() gives the text.

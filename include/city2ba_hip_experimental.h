@@ -964,6 +964,54 @@ int c2b_schur_blocks_rows(const uint64_t *row_ptr, const uint32_t *pt_idx, const
 int c2b_schur_spmv_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_cam, const double *S_diag, const double *S_off,
                         const double *x, double *y, double *part, void *stream);
 
+/* ---- the direct solve of the reduced camera system: dense Cholesky on the device ----
+ * A second linear solver for c2b_problem_solve_step, chosen per handle: C2B_LINEAR_PCG (the default) or C2B_LINEAR_CHOLESKY, under
+ * which the step forms S as the explicit path does, scatters it into a dense lower triangle, factors it by a blocked Cholesky,
+ * solves by two triangular substitutions and back-substitutes dp as before.  There is no PCG and no preconditioner.
+ * Setting.  _set_linear_solver / _get_linear_solver: the handle's state like the preconditioner: it survives uploads, reads and
+ *   culls and is carried by subset / window under C2B_SUBSET_CARRY.  It is NOT a value of c2b_problem_set_schur, which keeps its two.
+ *   Another kind: C2B_ERR_INVALID_ARGUMENT.  Under C2B_LINEAR_PCG every entry launches exactly what it launched before this entry
+ *   existed, bit for bit, whatever `schur` is.
+ * Set-up under C2B_LINEAR_CHOLESKY: the explicit set-up whatever `schur` says (`schur` is left alone, as c2b_problem_schur_complement
+ *   leaves it): the pattern if absent, S into S_diag / S_off without the preconditioner's factors, b by the implicit pass as before.
+ *   The preconditioner setting is ignored and c2b_problem_preconditioner_fallbacks is 0.
+ * Dense image.  N = 9 n_cam, Np = 64 ceil(N / 64).  A is row-major with leading dimension Np.  Only the lower triangle, diagonal
+ *   included, is meaningful: the upper triangle is never read and is unspecified afterwards.  The padding rows i >= N hold 1 on the
+ *   diagonal and 0 elsewhere.  A and two Np vectors are carved from the solve buffers after Y, present only under
+ *   C2B_LINEAR_CHOLESKY.  _linear_solver_bytes: what the direct solve adds to the solve buffers,
+ *   8 (schur_explicit_doubles + Np^2 + 2 Np) with schur_explicit_doubles = c2b_problem_schur_bytes / 8; builds the pattern.
+ *   C2B_DENSE_MAX_CAMERAS (Np = 36 864, 10.9 GB) is a condition, not a tuning result: above it c2b_problem_solve_step and
+ *   _linear_solver_bytes return C2B_ERR_INVALID_ARGUMENT naming the cap.  A failed allocation returns C2B_ERR_OOM with the bytes in
+ *   the message and the handle stays usable under C2B_LINEAR_PCG: there is no silent fallback.  A shard is refused as before.
+ * Constants and empty cameras need nothing special: a constant entry's row and column of S are exactly 0 with lambda 1e-6 on the
+ *   diagonal, an empty camera's block is lambda 1e-6 I, b is exactly 0 there, and the substitutions return exactly +0.0 in those
+ *   entries of dc.
+ * Result.  info.iterations is 0.  info.status is 0 when every pivot was finite and > 0; otherwise 2 with dc = dp = 0, rel_residual 1
+ *   and model_decrease 0 (the rule for a step without a factor: the LM loops raise lambda).  info.rel_residual is the true
+ *   |b - S dc| / |b| from one product with the stored blocks (0 when b = 0).  max_iters and rel_tol are validated as before and
+ *   otherwise unused.  sum_sq and model_decrease are the unchanged model pass's.  Deterministic: every entry has one owner and a
+ *   fixed summation order, no float atomics: the same problem and arguments give the same bits.
+ * Level 0, stateless, asynchronous on `stream`, device pointers, doubles and nbr_ptr 8-byte aligned, nbr and info 4; a NULL or
+ * misaligned pointer, an ld that is no multiple of 64 or exceeds 9 C2B_DENSE_MAX_CAMERAS, n > ld: C2B_ERR_INVALID_ARGUMENT before any
+ * device work:
+ * _dense_scatter_rows: the lower triangle of S (the blocks of a camera's neighbours c' < c of the ascending pattern, and S_cc) into
+ *   A [64 ceil(9 n_cam / 64)][ld], zeros elsewhere in it, and the padding rows.
+ * _dense_cholesky: A [64 ceil(n / 64)][ld] = L L^T in place, lower triangle; n need not be a multiple of 64, ld must be; the rows
+ *   from n to the next multiple of 64 must be padding rows as above and stay so.  info (device int32) is set to 0, then to the
+ *   1-based index of the FIRST pivot that is not finite or not > 0; the factorisation goes on with a pivot of 1 there (a numerical
+ *   status, never a fault: no address depends on matrix data) and what it leaves is then meaningless.
+ * _dense_cholesky_solve: x [64 ceil(n / 64)] holds b on entry (its padding entries finite, e.g. 0) and L^-T L^-1 b on return. */
+#define C2B_LINEAR_PCG 0
+#define C2B_LINEAR_CHOLESKY 1
+#define C2B_DENSE_MAX_CAMERAS 4096
+int c2b_problem_set_linear_solver(c2b_problem *p, int kind);
+int c2b_problem_get_linear_solver(const c2b_problem *p, int *kind);
+int c2b_problem_linear_solver_bytes(c2b_problem *p, int64_t *bytes);
+int c2b_dense_scatter_rows(const uint64_t *nbr_ptr, const uint32_t *nbr, int64_t n_cam, const double *S_diag, const double *S_off,
+                           double *A, int64_t ld, void *stream);
+int c2b_dense_cholesky(double *A, int64_t n, int64_t ld, int32_t *info, void *stream);
+int c2b_dense_cholesky_solve(const double *A, int64_t n, int64_t ld, double *x, void *stream);
+
 /* ---- a problem compared against ground truth: similarity alignment on the device ----
  * Build-defined (the reference has nothing like it).  Two problems on one device, the estimate p and the reference ref, with equal
  * n_cam and n_pts; index i of one corresponds to index i of the other.
